@@ -2,11 +2,23 @@
 """Headline benchmark: DDPM-1000 triplane samples/sec at a 128^2 latent (BASELINE.json configs[1]:
 128-ch UNet, (H,W,D)=(128,128,128), batch 1 per GPU), through the public sampling API.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 --config selects the BASELINE.json workload (default c2 = configs[1], the one the metric is quoted on; c3 = configs[2]'s per-GPU
-share: DDIM-100, batch 8 per GPU; c5 = configs[4]: the (256,256,128) retarget, DDPM-1000) — each line carries its own roofline.
+share: DDIM-100, batch 8 per GPU; c5 = configs[4]: the (256,256,128) retarget, DDPM-1000) — with --full each line carries its own
+roofline.
+
+A plain run measures the headline only: set-up, pre-warm + warm-up, the K timed steps, the line.  --full adds everything else the
+line can carry, each measured as before: the roofline (HIP events on every --profile-every-th timed step, a short untimed pass for the
+1x1 / rank-1 launches, gfx clock and power from amdsmi, HBM traffic from two rocprofv3 --pmc children), `chains2`, the c4
+`side_stream_overlap` trace child, and at N = 1 for c2 the CPU and PyTorch-ROCm eager baselines.  Without --full the options of
+those legs (--profile-every, --traffic, --overlap, --chains, --no-*-baseline) have no effect.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the timed path returned in its last step as DIR/<name>.npy (float32):
+`sample` and `pred_xstart` of the sampling loop's step dict, or for c4 the flat `params`, their `ema` and the step's `grad`.  An
+array of more than DUMP_SAMPLE elements is cut to a fixed seeded sample of its flattened elements (the same indices in every run).
+Weights, x_T and every random draw are seeded, so the same arguments give the same inputs from run to run.
 
 A "step" is one iteration of GaussianDiffusion.p_sample_loop_progressive (the loop src/sample.py drives) for one sample per
 GPU: UNet forward + fused sampler update + the step's noise draw (device generator, as the reference does on a GPU).  value = samples/s over all ranks
@@ -37,6 +49,8 @@ PREWARM = 150
 PEAK_FP32_MFMA_TFLOPS = 157.3     # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, = fp32 vector peak (at the 2400 MHz data-sheet clock)
 PEAK_CLOCK_MHZ = 2400.0
 TRAFFIC_PROFILE = "profiles/r05_pmc_traffic.json"
+DUMP_SAMPLE = 4 << 20                # --dump-outputs: elements kept of a larger array (16 MiB in float32)
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs: all files together
 # BASELINE.json workloads a single GPU can run (per-GPU share of the multi-GPU ones): name -> (hwd, batch per GPU, sampler,
 # timestep_respacing, steps per sample, metric, workload text)
 CONFIGS = {
@@ -208,6 +222,25 @@ def cpu_baseline_c_oracle(budget_s=25.0):
 
 def s3d_switches():
     return {k: v for k, v in sorted(os.environ.items()) if k.startswith("S3D_")}
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: {name: tensor} -> d/<name>.npy in float32; a larger array than DUMP_SAMPLE elements keeps the same seeded
+    sample of its flattened elements in every run (sorted indices, numpy Generator seed 0)."""
+    import numpy as np
+    out = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_SAMPLE:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        out[name] = np.ascontiguousarray(a, dtype=np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    print(f"bench.py: wrote {', '.join(f'{k}{list(a.shape)}' for k, a in out.items())} to {d}", file=sys.stderr, flush=True)
 
 
 # ------------------------------------------------------------------------------------------------ launcher
@@ -471,7 +504,9 @@ def worker(args):
         sync = lambda: None
         dev = torch.device("cpu")
         prof = None
+        outputs = None                                                 # (nothing is computed: --dump-outputs writes nothing)
     else:
+        import numpy as np
         from sin3dm_amd import _lib, testing as T
         from sin3dm_amd.diffusion.script_util import create_gaussian_diffusion
         from sin3dm_amd.diffusion.unet_triplane import TriplaneUNetModelSmall
@@ -484,7 +519,7 @@ def worker(args):
         torch.cuda.set_device(local)
         dev = torch.device(f"cuda:{local}")
         ident = device_identity(local)
-        if rank == 0:
+        if rank == 0 and args.full:
             clock = ClockSampler(ident.get("pci_bus_id"))            # (a child process; it is sampling by the time the model is built)
         if dist_on:
             if world == 1:                                            # --force-dist: a local rendezvous of one
@@ -498,7 +533,8 @@ def worker(args):
         kw = dict(H=H, W=W, D=D)
         from sin3dm_amd import parallel
         torch.manual_seed(parallel.sample_seed(1000, rank))          # rank r's first sample is sample index r (parallel.shard_indices): ONE seed convention
-        state = {"x": None}
+        np.random.seed(parallel.sample_seed(1000, rank))             # (c4's timestep sampler draws from numpy: the same inputs in every run)
+        state = {"x": None, "out": None}
         if sampler_kind == "train":
             # TrainLoop.run_step (src/diffusion/train_util.py:163-247) on one fixed synthetic batch, as tools/bench_train.py drives it
             from sin3dm_amd.diffusion.train_util import TrainLoop
@@ -516,6 +552,9 @@ def worker(args):
             def step():
                 tl.run_step(batch, dict(kw)); tl.step += 1
                 state["x"] = model.flat_parameters
+
+            def outputs():          # what a caller of run_step holds after it: the updated weights, their EMA, the step's gradient
+                return {"params": model.flat_parameters, "ema": tl.opt.ema[0], "grad": tl._grad}
         else:
             model.to(dev).eval()
             diffusion = create_gaussian_diffusion(steps=T_STEPS, noise_schedule="linear", predict_xstart=True, timestep_respacing=respacing)
@@ -526,9 +565,13 @@ def worker(args):
                 while True:
                     for out in loop(model, (BATCH, 12, H + D, W + D), model_kwargs=kw):
                         state["x"] = out["sample"]
+                        state["out"] = out
                         yield
             gen = sampler()
             step = lambda: next(gen)
+
+            def outputs():          # the step dict the loop yielded last
+                return {k: v for k, v in state["out"].items() if v is not None}
         sync = torch.cuda.synchronize
 
     def barrier():
@@ -555,6 +598,8 @@ def worker(args):
         sync()
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and outputs is not None and rank == 0:
+            dump_outputs(args.dump_outputs, outputs())
     if not args.dry_run:
         prof = model.profile_read()
         # the 1x1 and rank-1 launches (informational fields of the line) in a short pass of their own, outside the timed region
@@ -720,10 +765,17 @@ def main():
     ap.add_argument("--chains", type=int, default=2, help="also report the c2 workload as this many independent chains in flight (field `chains2`; 0/1 = off)")
     ap.add_argument("--force-dist", action="store_true", help="create the RCCL process group even at --gpus 1: barrier / all-reduce / gather "
                     "(and --config c4's parameter broadcast + gradient all-reduce) execute at world size 1")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: roofline, chains2, side_stream_overlap, "
+                    "CPU / eager baselines (off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the timed path's last-step outputs as DIR/<name>.npy (float32)")
     ap.add_argument("--dry-run", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--dry-run-fail-early", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if not args.full:                                                     # a plain run: the headline only (module docstring)
+        args.no_cpu_baseline = args.no_eager_baseline = True
+        args.traffic = args.overlap = "off"
+        args.chains = args.profile_every = 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_workers(args, sys.argv[1:])
     if args.traffic == "auto" and args.gpus == 1 and not args.dry_run and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not s3d_switches():

@@ -1,6 +1,7 @@
 """GPU: bench.py's real (not dry-run) worker for the scored config and for the training config, a few steps each: the JSON line
-keeps the driver's contract, the roofline is measured from the library's own HIP events, and nothing under oracle/ is touched
-when the CPU baseline is switched off."""
+keeps the driver's contract, the roofline is measured from the library's own HIP events (--full), and nothing under oracle/ is
+touched when the CPU baseline is switched off; a plain run carries the headline only, and --dump-outputs writes the last step's
+outputs, the same in every run."""
 import json
 import os
 import subprocess
@@ -12,9 +13,9 @@ pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _line(*extra):
+def _line(*extra, full=True):
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "4", "--warmup", "1", "--prewarm", "4",
-                        "--profile-every", "1", "--no-cpu-baseline", "--traffic", "off", *extra],
+                        "--profile-every", "1", "--no-cpu-baseline", "--traffic", "off", *(("--full",) if full else ()), *extra],
                        cwd=REPO, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -67,3 +68,24 @@ def test_eager_gpu_baseline_leg():
     assert b["unit"] == "samples/s" and b["kind"] == "port" and b["value"] > 0
     assert "default" in b["modes"] and set(b["modes"]) <= {"default", "benchmark"} and all(m["steps"] >= 5 and m["ms_per_step"] > 0 for m in b["modes"].values())
     assert abs(b["value"] - 1.0 / (1000 * b["ms_per_step"] * 1e-3)) < 1e-3 * b["value"]
+
+
+def test_plain_run_is_the_headline_only_and_dumps_the_same_outputs(tmp_path):
+    """Without --full the line keeps its headline fields and carries no roofline, chains, overlap or baseline; --dump-outputs
+    writes the last timed step's sample / pred_xstart (float32, the loop's shapes), and a second run with the same arguments
+    draws the same inputs: the same bits.  c4 writes the flat weights, their EMA and the step's gradient (cut to the seeded sample)."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = _line("--config", "c2", "--dump-outputs", str(tmp_path / f"c2_{k}"), full=False)
+        assert d["steps"] == 4 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+        assert d["roofline"] is None and d["chains2"] is None and d["side_stream_overlap"] is None and "cpu_baseline" not in d
+        runs.append({n: np.load(tmp_path / f"c2_{k}" / f"{n}.npy") for n in ("sample", "pred_xstart")})
+    for n, a in runs[0].items():
+        assert a.dtype == np.float32 and a.shape == (1, 12, 256, 256) and np.isfinite(a).all(), n
+        assert np.array_equal(a, runs[1][n]), n
+    d = _line("--config", "c4", "--dump-outputs", str(tmp_path / "c4"), full=False)
+    assert d["roofline"] is None and d["side_stream_overlap"] is None
+    for n in ("params", "ema", "grad"):
+        a = np.load(tmp_path / "c4" / f"{n}.npy")
+        assert a.dtype == np.float32 and a.ndim == 1 and 0 < a.size <= 4 << 20 and np.isfinite(a).all(), n

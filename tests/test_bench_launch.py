@@ -195,3 +195,22 @@ def test_ranks_die_with_a_killed_launcher(tmp_path):
     while any(_alive(pid) for pid in pids) and time.time() - t0 < 10:
         time.sleep(0.1)
     assert not any(_alive(pid) for pid in pids), "ranks outlived a SIGKILLed launcher"
+
+
+def test_dump_outputs_files(tmp_path):
+    """bench.dump_outputs: float32 .npy per name; an array above DUMP_SAMPLE elements keeps the same seeded sample in every call."""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = torch.arange(bench.DUMP_SAMPLE + 1000, dtype=torch.float64)
+    small = torch.ones(3, 4, dtype=torch.float16)
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), {"big": big, "small": small})
+    a, b = np.load(tmp_path / "0" / "big.npy"), np.load(tmp_path / "1" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_SAMPLE,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and np.array_equal(a, np.round(a))          # sorted, distinct elements of the original
+    s = np.load(tmp_path / "0" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (3, 4) and np.all(s == 1)

@@ -31,7 +31,7 @@ if [ -n "$UB" ]; then
 fi
 : > $OUT/${TAG}_bench.txt
 for rep in $(seq $REPS); do for SET in "$@"; do
-  env $SET timeout 900 python bench.py --config $CONFIG --steps $STEPS --warmup 5 --no-cpu-baseline --traffic off --overlap off --chains 0 > $OUT/tmp_ab.json 2> $OUT/tmp_ab.err
+  env $SET timeout 900 python bench.py --full --config $CONFIG --steps $STEPS --warmup 5 --no-cpu-baseline --traffic off --overlap off --chains 0 > $OUT/tmp_ab.json 2> $OUT/tmp_ab.err
   python3 - "$OUT/tmp_ab.json" "$CONFIG" "$SET" <<'PY' | tee -a $OUT/${TAG}_bench.txt
 import json, sys
 try:

@@ -8,7 +8,7 @@ timeout 1200 python -m pytest tests/test_hip_parity.py tests/test_hip_edge_cases
 tail -5 $OUT/${TAG}_pytest.log
 i=0
 for SET in "$@"; do
-  env $SET timeout 600 python bench.py --steps 300 --warmup 5 --no-cpu-baseline > $OUT/${TAG}_bench_$i.json 2> $OUT/${TAG}_bench_$i.err
+  env $SET timeout 600 python bench.py --full --steps 300 --warmup 5 --no-cpu-baseline > $OUT/${TAG}_bench_$i.json 2> $OUT/${TAG}_bench_$i.err
   python3 - "$OUT/${TAG}_bench_$i.json" "$SET" <<'PY'
 import json, sys
 try:

@@ -39,15 +39,15 @@ cd $ROOT
 # 4. the headline line (bench.py measures roofline.traffic itself with two rocprofv3 --pmc children; the committed
 #    profiles/<round>_pmc_traffic.json is only its fallback)
 cp $OUT/${R}_pmc_traffic.json profiles/${R}_pmc_traffic.json
-python3 bench.py 2>/dev/null | tail -1 > $OUT/${R}_bench.json
-python3 bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/${R}_bench_driver_flags.json
+python3 bench.py --full 2>/dev/null | tail -1 > $OUT/${R}_bench.json
+python3 bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/${R}_bench_driver_flags.json
 # 5. the other BASELINE configs through bench.py (each line with its own roofline), the small ones through tools/bench_configs.py,
 #    training, decode
-{ for C in c3 c5 c4; do python3 bench.py --config $C --steps 200 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1; done
+{ for C in c3 c5 c4; do python3 bench.py --full --config $C --steps 200 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1; done
   python3 tools/bench_configs.py "C1 " 2>/dev/null | grep "^{"; python3 tools/bench_configs.py "64-ch" 2>/dev/null | grep "^{"; } > $OUT/${R}_other_configs.txt
 { echo "## default (weight gradients on the backward pass's side stream)"; python3 tools/bench_train.py --steps 100 --warmup 10 2>/dev/null | grep "^{"; python3 tools/bench_ae_train.py 2>/dev/null | grep "^{";
   echo "## S3D_BWD_SIDE=0 (everything in line: round 4's launch structure)"; S3D_BWD_SIDE=0 python3 tools/bench_train.py --steps 100 --warmup 10 2>/dev/null | grep "^{"; S3D_BWD_SIDE=0 python3 tools/bench_ae_train.py 2>/dev/null | grep "^{";
-  echo "## bench.py --config c4, S3D_BWD_SIDE=0: the 3x3 weight-gradient kernel alone (roofline.wgrad3x3)"; S3D_BWD_SIDE=0 python3 bench.py --config c4 --steps 200 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1; } > $OUT/${R}_train_step.txt
+  echo "## bench.py --config c4, S3D_BWD_SIDE=0: the 3x3 weight-gradient kernel alone (roofline.wgrad3x3)"; S3D_BWD_SIDE=0 python3 bench.py --full --config c4 --steps 200 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1; } > $OUT/${R}_train_step.txt
 { python3 tools/bench_decode.py 2>/dev/null | grep -v amdgpu.ids; python3 tools/bench_decode.py --reso 512 --hwd 256 256 128 --aabb-scale 2 2 1 2>/dev/null | grep -v amdgpu.ids;
   python3 tools/bench_config5.py 2>/dev/null | grep "^{"; python3 tools/bench_end_to_end.py 2>/dev/null | grep "^{"; } > $OUT/${R}_decode_and_isosurface.txt
 # 6. the 3x3 kernels alone (steady state), with phase stamps and one / two / three blocks per CU; clock + power under them
