@@ -337,7 +337,10 @@ typedef struct {
     int32_t sdf_loss;            /* 0 = l1, 1 = weightedl1 (default) */
     int32_t tex_loss;            /* 0 = l1 (default), 1 = l2, 2 = huber(delta 0.1) */
     float sdf_threshold;         /* truncation of the sdf samples */
-    float tex_threshold_ratio;   /* texture loss on points with |sdf| < sdf_threshold * ratio (0.999) */
+    float tex_threshold_ratio;   /* texture loss on points with |sdf| < sdf_threshold * ratio (0.999), the product taken
+                                  * in float on the two float fields.  The reference rounds the double product once to
+                                  * float; the Python binding (encoding/model.py:ae_loss_cfg) matches it by passing that
+                                  * rounded product as sdf_threshold with a ratio of 1.0. */
     float tex_weight;            /* 1.0 */
 } s3d_ae_loss_cfg;
 

@@ -173,20 +173,25 @@ def ae_plane_block(sd, prefix, fm):
     return out
 
 
-def _mlp(sd, prefix, x, n_hidden_layers=4):
-    """DecoderMLPSkipConcat, src/encoding/blocks.py:65-91."""
+def _mlp(sd, prefix, x, n_hidden_layers=4, taps=None):
+    """DecoderMLPSkipConcat, src/encoding/blocks.py:65-91.  taps: a list that receives every hidden pre-activation."""
     n = n_hidden_layers // 2
+
+    def relu(z):
+        if taps is not None:
+            taps.append(z)
+        return F.relu(z)
     h = x
     for i in range(n + 1):
-        h = F.relu(F.linear(h, sd[f"{prefix}.first_layers.{2 * i}.weight"], sd[f"{prefix}.first_layers.{2 * i}.bias"]))
+        h = relu(F.linear(h, sd[f"{prefix}.first_layers.{2 * i}.weight"], sd[f"{prefix}.first_layers.{2 * i}.bias"]))
     h = torch.cat([x, h], dim=-1)
     for i in range(n):
-        h = F.relu(F.linear(h, sd[f"{prefix}.second_layers.{2 * i}.weight"], sd[f"{prefix}.second_layers.{2 * i}.bias"]))
+        h = relu(F.linear(h, sd[f"{prefix}.second_layers.{2 * i}.weight"], sd[f"{prefix}.second_layers.{2 * i}.bias"]))
     return F.linear(h, sd[f"{prefix}.second_layers.{2 * n}.weight"], sd[f"{prefix}.second_layers.{2 * n}.bias"])
 
 
-def ae_decode(sd, pts, fm, aabb, geo_dim=4):
-    """AutoEncoderGroupSkip.decode, src/encoding/networks.py:192-220."""
+def ae_decode(sd, pts, fm, aabb, geo_dim=4, taps=None):
+    """AutoEncoderGroupSkip.decode, src/encoding/networks.py:192-220.  taps: as in _mlp, for both MLPs ([N, hidden] each)."""
     x = 2 * (pts - aabb[:3]) / (aabb[3:] - aabb[:3]) - 1
 
     def sample(plane, xy):
@@ -198,18 +203,37 @@ def ae_decode(sd, pts, fm, aabb, geo_dim=4):
     tex = ae_plane_block(sd, "tex_convs", [f[:, geo_dim:] for f in fm])
     h_geo = sum(sample(geo[i], x[..., coords[i]]) for i in range(3))
     h_tex = sum(sample(tex[i], x[..., coords[i]]) for i in range(3))
-    return torch.cat([_mlp(sd, "geo_decoder", h_geo), _mlp(sd, "tex_decoder", h_tex).sigmoid()], dim=1)
+    return torch.cat([_mlp(sd, "geo_decoder", h_geo, taps=taps), _mlp(sd, "tex_decoder", h_tex, taps=taps).sigmoid()], dim=1)
 
 
-def ae_losses(pred, sdf, tex, sdf_threshold, tex_threshold_ratio=0.999, tex_weight=1.0):
-    """ShapeAutoEncoder._forward_batch, src/encoding/model.py:186-237 (weightedl1 sdf loss, l1 texture loss on the
-    points within the truncation band)."""
+def ae_losses(pred, sdf, tex, sdf_threshold, tex_threshold_ratio=0.999, tex_weight=1.0, sdf_loss="weightedl1", tex_loss="l1",
+              sdf_renorm=False):
+    """ShapeAutoEncoder._forward_batch for data_type "sdftex", src/encoding/model.py:186-225: sdf loss `l1` | `weightedl1`
+    over all rows; texture loss `l1` | `l2` (mse) | `huber` (delta 0.1), times tex_weight, over the rows whose |sdf| lies in
+    the band sdf_threshold * ratio (1.0 * ratio with sdf_renorm, where the sdf samples are already divided by the threshold).
+    The band test is the reference's: a float32 sdf tensor against a Python float, i.e. |sdf| < fl32(thr * ratio) with
+    the product taken in double.  It is made on the float32 sdf even when the rest runs in float64 (sdf promoted from
+    float32 converts back exactly), so a float64 port selects the rows the reference selects."""
     ps = pred[..., :1]
-    weight = 1 + 0.5 * torch.sign(sdf) * torch.sign(sdf - ps)
-    sdf_loss = ((ps - sdf).abs() * weight).mean()
-    mask = sdf.squeeze(1).abs() < sdf_threshold * tex_threshold_ratio
-    tex_loss = F.l1_loss(pred[..., 1:][mask], tex[mask]) * tex_weight
-    return {"sdf_loss": sdf_loss, "tex_loss": tex_loss}
+    if sdf_loss == "l1":
+        l_sdf = F.l1_loss(ps, sdf)
+    elif sdf_loss == "weightedl1":
+        weight = 1 + 0.5 * torch.sign(sdf) * torch.sign(sdf - ps)
+        l_sdf = ((ps - sdf).abs() * weight).mean()
+    else:
+        raise ValueError(f"sdf_loss {sdf_loss!r}")
+    band = (1.0 if sdf_renorm else float(sdf_threshold)) * float(tex_threshold_ratio)
+    mask = sdf.squeeze(1).float().abs() < band
+    pt, gt = pred[..., 1:][mask], tex[mask]
+    if tex_loss == "l1":
+        l_tex = F.l1_loss(pt, gt)
+    elif tex_loss == "l2":
+        l_tex = F.mse_loss(pt, gt)
+    elif tex_loss == "huber":
+        l_tex = F.huber_loss(pt, gt, delta=0.1)
+    else:
+        raise ValueError(f"tex_loss {tex_loss!r}")
+    return {"sdf_loss": l_sdf, "tex_loss": l_tex * tex_weight}
 
 
 def ae_param_groups(names):

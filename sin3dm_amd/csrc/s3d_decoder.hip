@@ -486,8 +486,11 @@ static int run_decode(s3d_decoder* d, const float* pts, long long N, const float
     if (upt == 2 && hidt == 8) return launch_decode<2, 8>(a, st);
     if (upt == 1 && hidt == 1) return launch_decode<1, 1>(a, st);
     if (upt == 1 && hidt == 8) return launch_decode<1, 8>(a, st);
+    if (upt == 1 && hidt == 2) return launch_decode<1, 2>(a, st);
+    if (upt == 3 && hidt == 4) return launch_decode<3, 4>(a, st);
     set_error("decoder: feat_channel_up=%d / mlp_hidden_channels=%d has no compiled kernel (supported after padding to 32: "
-              "up<=64 with hidden 256, or up<=32 with hidden 32)", d->cfg.feat_channel_up, d->cfg.mlp_hidden_channels);
+              "up<=64 with hidden 256, up<=32 with hidden 32 or 64, up 96 with hidden 128)", d->cfg.feat_channel_up,
+              d->cfg.mlp_hidden_channels);
     return S3D_ERR_UNSUPPORTED;
 }
 

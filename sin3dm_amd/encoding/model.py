@@ -18,6 +18,16 @@ _SDF_LOSS = {"l1": 0, "weightedl1": 1}
 _TEX_LOSS = {"l1": 0, "l2": 1, "huber": 2}
 
 
+def ae_loss_cfg(sdf_loss, tex_loss, sdf_threshold, tex_threshold_ratio=0.999, tex_weight=1.0, sdf_renorm=False):
+    """The s3d_ae_loss_cfg of _forward_batch (reference :186-225) from the CLI's loss names.  The reference's texture band is
+    `gt_sdf.abs() < sdf_threshold * tex_threshold_ratio`: a float32 tensor against a Python float, so the bound is the
+    double product rounded once to float32.  The library multiplies its two float fields, which would round each factor
+    first (one ulp lower or higher for about a quarter of thresholds), so the product is formed here in double and passed
+    as the threshold with a ratio of exactly 1.0."""
+    band = (1.0 if sdf_renorm else float(sdf_threshold)) * float(tex_threshold_ratio)
+    return _lib.AeLossCfg(_SDF_LOSS[sdf_loss], _TEX_LOSS[tex_loss], band, 1.0, tex_weight)
+
+
 class FlatGroupAdamW:
     """torch.optim.AdamW over the auto-encoder's two parameter groups (geo: lr*split, tex: lr; betas 0.9/0.999, eps 1e-8,
     weight_decay 0.01 = torch's default, which the reference inherits at model.py:131-137) followed by ExponentialLR,
@@ -191,8 +201,8 @@ class ShapeAutoEncoder:
                 "tex": torch.cat([self.tex_grid[gi], self.tex_near_surf[si]], dim=0)}
 
     def _loss_cfg(self):
-        band = 1.0 if self.sdf_renorm else self.sdf_threshold
-        return _lib.AeLossCfg(_SDF_LOSS[self.sdf_loss_type], _TEX_LOSS[self.tex_loss_type], band, self.tex_threshold_ratio, self.tex_weight)
+        return ae_loss_cfg(self.sdf_loss_type, self.tex_loss_type, self.sdf_threshold, self.tex_threshold_ratio, self.tex_weight,
+                           bool(self.sdf_renorm))
 
     def _set_optimizer(self, lr, min_lr_ratio=0.01):
         """AdamW with the geo group at lr*lr_split + ExponentialLR reaching min_lr_ratio after n_iters (reference :129-139)."""

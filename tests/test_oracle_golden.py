@@ -350,3 +350,84 @@ def test_torch_port_ae_training(oracle):
     assert skip == {"geo_convs.in_layers.0.bias", "tex_convs.in_layers.0.bias", "geo_encoder.bias", "tex_encoder.bias"}  # feed an InstanceNorm
     wp = digest_errors({k: (sd[k].detach() - init[k]).numpy() for k in sd}, g, "steps.dparam", skip)
     assert wp["norm"] < 2e-3 and wp["proj"] < 1e-2, wp
+
+
+def _np_ae_losses(pred, sdf, tex, band, sdf_loss, tex_loss, tex_weight):
+    """_forward_batch's losses restated in float64 numpy from their definitions, on an explicit float32 band."""
+    p, g, c = (np.asarray(a, np.float64) for a in (pred, sdf, tex))
+    r = p[:, :1] - g
+    w = 1 + 0.5 * np.sign(g) * np.sign(-r) if sdf_loss == "weightedl1" else 1.0
+    l_sdf = float(np.mean(np.abs(r) * w))
+    m = np.abs(np.asarray(sdf, np.float32)[:, 0]) < np.float32(band)
+    d = p[m, 1:] - c[m]
+    per = {"l1": np.abs(d), "l2": d * d, "huber": np.where(np.abs(d) < 0.1, 0.5 * d * d, 0.1 * (np.abs(d) - 0.05))}[tex_loss]
+    return l_sdf, float(np.mean(per)) * tex_weight, m
+
+
+@pytest.mark.parametrize("sdf_loss", ["l1", "weightedl1"])
+@pytest.mark.parametrize("tex_loss", ["l1", "l2", "huber"])
+@pytest.mark.parametrize("thr,ratio,tw,renorm", [(0.05, 0.999, 1.0, False), (0.03, 0.5, 0.37, False), (0.05, 0.9, 1.0, True)])
+def test_torch_port_ae_loss_modes(oracle, sdf_loss, tex_loss, thr, ratio, tw, renorm):
+    """Every sdf x tex loss of _forward_batch (src/encoding/model.py:186-225), tex_weight, the ratio and the sdf_renorm band
+    (1.0 * ratio) on a float32 batch whose texture residuals straddle the huber cut-off; the float64 port (inputs promoted)
+    gives the same losses and selects the same rows."""
+    import torch
+    import torch_port as tp
+    rng = np.random.Generator(np.random.PCG64(77))
+    N, TC = 500, 3
+    scale = 1.0 / thr if renorm else 1.0
+    sdf = (np.clip(rng.normal(0, 0.6 * thr, size=(N, 1)), -thr, thr) * scale).astype(np.float32)
+    pred = np.concatenate([sdf + rng.normal(0, 0.02 * scale, size=(N, 1)), rng.uniform(0.05, 0.95, size=(N, TC))], 1).astype(np.float32)
+    tex = np.clip(pred[:, 1:] + rng.uniform(-0.2, 0.2, size=(N, TC)), 0, 1).astype(np.float32)
+    band = (1.0 if renorm else thr) * ratio
+    l_sdf, l_tex, m = _np_ae_losses(pred, sdf, tex, band, sdf_loss, tex_loss, tw)
+    assert 0.2 * N < m.sum() < N                                       # a partial band
+    d = np.abs(pred[m, 1:] - tex[m])
+    assert (d < 0.05).any() and ((d > 0.05) & (d < 0.1)).any() and (d > 0.1).any()
+    for dt in (torch.float32, torch.float64):
+        p, s, c = (torch.from_numpy(a).to(dt) for a in (pred, sdf, tex))
+        out = tp.ae_losses(p, s, c, thr, ratio, tw, sdf_loss=sdf_loss, tex_loss=tex_loss, sdf_renorm=renorm)
+        tol = 1e-6 if dt == torch.float32 else 1e-12
+        assert abs(float(out["sdf_loss"]) - l_sdf) < tol * l_sdf, (dt, float(out["sdf_loss"]), l_sdf)
+        assert abs(float(out["tex_loss"]) - l_tex) < tol * l_tex, (dt, float(out["tex_loss"]), l_tex)
+    # the reference's own expressions on the float32 tensors
+    p, s, c = (torch.from_numpy(a) for a in (pred, sdf, tex))
+    mask = s.squeeze(1).abs() < (1.0 if renorm else thr) * ratio
+    assert np.array_equal(mask.numpy(), m)
+    ref = {"l1": torch.nn.functional.l1_loss, "l2": torch.nn.functional.mse_loss,
+           "huber": lambda a, b: torch.nn.functional.huber_loss(a, b, delta=0.1)}[tex_loss](p[..., 1:][mask], c[mask]) * tw
+    assert abs(float(ref) - l_tex) < 1e-6 * l_tex
+
+
+@pytest.mark.parametrize("thr,ratio,renorm", [(0.03, 0.9, False), (0.15, 0.999, False), (0.07, 0.75, False), (0.05, 0.999, False),
+                                              (0.03, 0.9, True)])
+def test_torch_port_ae_band_boundary(oracle, thr, ratio, renorm):
+    """Rows with |sdf| exactly at the float32 band fl32(thr * ratio) (product in double, as a float32 tensor compared with a
+    Python float rounds it) and one ulp either side, with both signs.  (0.03, 0.9): rounding each factor to float first
+    gives a bound one ulp lower; (0.15, 0.999): one ulp higher, and the band lies below the double product, so comparing a
+    float64 sdf in double would also take the row at the band.  The port must select what the float32 comparison selects,
+    in float32 and in float64."""
+    import torch
+    import torch_port as tp
+    f = np.float32
+    prod = (1.0 if renorm else thr) * ratio
+    b = f(prod)
+    vals = np.asarray([np.nextafter(b, f(0)), b, np.nextafter(b, f(1)), f(f(1.0 if renorm else thr) * f(ratio))], f)
+    sdf = np.concatenate([vals, -vals, np.asarray([0.0, 0.5 * b], f)])[:, None]
+    N = len(sdf)
+    expect = np.abs(sdf[:, 0]) < b
+    assert list(expect[:3]) == [True, False, False]
+    if (thr, ratio) == (0.15, 0.999):
+        assert float(b) < prod and vals[3] > b                           # double compare and factor-wise rounding both take b
+    # distinct residuals: the l1 mean identifies the selected set
+    pred = np.zeros((N, 4), f)
+    pred[:, 0] = sdf[:, 0]
+    pred[:, 1:] = 0.5
+    tex = (0.5 + np.ldexp(1.0, -np.arange(1, N + 1))[:, None] * np.asarray([1.0, 2.0, 3.0])).astype(f)
+    _, l_tex, m = _np_ae_losses(pred, sdf, tex, b, "l1", "l1", 1.0)
+    assert np.array_equal(m, expect)
+    ref_mask = torch.from_numpy(sdf).squeeze(1).abs() < prod         # the reference's expression
+    assert np.array_equal(ref_mask.numpy(), expect)
+    for dt in (torch.float32, torch.float64):
+        out = tp.ae_losses(*(torch.from_numpy(a).to(dt) for a in (pred, sdf, tex)), thr, ratio, sdf_renorm=renorm)
+        assert abs(float(out["tex_loss"]) - l_tex) < 1e-6 * l_tex, (dt, float(out["tex_loss"]), l_tex)
