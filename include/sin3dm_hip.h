@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define S3D_ABI_VERSION 4
+#define S3D_ABI_VERSION 5
 #define S3D_API __attribute__((visibility("default")))
 
 typedef enum {
@@ -40,18 +40,16 @@ S3D_API int s3d_abi_version(void);
 
 /* Process-wide options: which of several kernel forms the library launches.  Every form is parity-tested (tests/test_hip_parity.py,
  * test_hip_train.py run the golden vectors under each); "bit-identical" forms differ in launch shape only.  name: with or without
- * the "S3D_" prefix; value: a decimal integer ("naive" / anything else for CONV_IMPL), "" or NULL = back to the library's own choice.
- * Until s3d_set_option is called for an option, the environment variable S3D_<NAME> (read once, at the option's first use) supplies
- * its value — the way earlier rounds selected forms; the call is the documented way.  Options are read at every launch; set them
- * before creating handles: a training handle's repack plan (s3d_unet_train_attach) keeps only the weight images of the forms
- * selected THEN current.
- *   WINO          24 (default) mixed Winograd F(2x4,3x3) | 4, 2: F(2x2) | 0: direct MFMA convolution          (rounding differs)
+ * the "S3D_" prefix; value: WINO 0, 4 or 24, CONV_IMPL "naive" / any other string, every other option 0 or 1; "" or NULL = back
+ * to the library's own choice; any other value is rejected (S3D_ERR_INVALID).  Until s3d_set_option is called for an option,
+ * the environment variable S3D_<NAME> (read once, at the option's first use) supplies its value — the way earlier rounds selected
+ * forms; a value the option does not take leaves it unset there.  The call is the documented way.  Options are read at every
+ * launch; set them before creating handles: a training handle's repack plan (s3d_unet_train_attach) keeps only the weight images
+ * of the forms selected THEN current.
+ *   WINO          24 (default) mixed Winograd F(2x4,3x3) | 4: F(2x2) | 0: direct MFMA convolution             (rounding differs)
  *   WINO24W       unset: by launch size | 0 never | 1 always the 64-output-channel block                    (bit-identical)
- *   WINO24G       1: the mixed Winograd kernel with its halo staged by LDS-DMA and persistent blocks (default: off — measured on
- *                 par with or behind the register-staged kernels, profiles/r06_wino_glds.txt)                (bit-identical)
  *   VCAT          0: materialise upsample + concat in the output blocks (default: virtual concat)            (rounding differs)
- *   WGRAD_WINO    0: direct 3x3 weight gradient (rounding differs) | default (1): Winograd F(2x2) | 2: the same with the operands of
- *                 half regions double-buffered by LDS-DMA (measured slower, profiles/r06_wgrad.txt)         (1, 2: bit-identical)
+ *   WGRAD_WINO    0: direct 3x3 weight gradient | default (1): Winograd F(2x2)                               (rounding differs)
  *   RANK1_SLICES  0: one K slice of the rollout tables (default: two from 256 channels)                      (rounding differs)
  *   RANK1_BATCH   0: k_rank1, one sample per block (default: k_rank1b / two-sample blocks)                   (bit-identical)
  *   CONV_IMPL     "naive": one-thread-per-output reference kernels (tests)                                   (rounding differs)

@@ -90,31 +90,16 @@ int upload(DevBuf& dst, const void* host, size_t bytes);
 // S3D_<NAME> (read once, at the first query of that option); before that the default (kOptUnset for the choices the library
 // makes by launch size).  Queries are a table read: cheap enough for every launch.
 enum Opt { OPT_WINO = 0, OPT_WINO24W, OPT_VCAT, OPT_WGRAD_WINO, OPT_RANK1_SLICES, OPT_RANK1_BATCH, OPT_CONV_IMPL, OPT_CONV1X1_T,
-           OPT_GN_FUSED, OPT_BWD_SIDE, OPT_GNB_FUSED, OPT_WINO24G, OPT_EDGE_SIGNAL, OPT_COUNT };
+           OPT_GN_FUSED, OPT_BWD_SIDE, OPT_GNB_FUSED, OPT_EDGE_SIGNAL, OPT_COUNT };
+// their names (s3d_set_option; S3D_<name> in the environment), in enum order
+constexpr const char* kOptNames[] = {"WINO", "WINO24W", "VCAT", "WGRAD_WINO", "RANK1_SLICES", "RANK1_BATCH", "CONV_IMPL", "CONV1X1_T",
+                                     "GN_FUSED", "BWD_SIDE", "GNB_FUSED", "EDGE_SIGNAL"};
+static_assert(sizeof kOptNames / sizeof kOptNames[0] == OPT_COUNT, "one name per option");
 constexpr int kOptUnset = -1;
 int opt(Opt o);                       // kOptUnset when neither set nor in the environment
 inline bool opt_on(Opt o) { return opt(o) != 0; }      // switches that default to on: anything but an explicit 0
 // compute units of the CURRENT device (cached per device index: one process may drive several)
 int device_cus();
-
-// ------------------------------------------------------------------ LDS-DMA (device code only)
-#if defined(__HIPCC__)
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-// One 1-KB LDS-DMA piece: lane l's 16 bytes at buffer offset voff + soff land at LDS byte lds_addr + 16 l (lds_addr wave-uniform);
-// an out-of-range offset (bit 31) lands as ZEROS, exec-masked lanes write nothing (tools/glds_probe.hip).
-// M0 (the destination base) belongs to the compiler: saved and restored inside the statement.  Nothing here is visible to hipcc's
-// s_waitcnt bookkeeping: the caller retires the piece with its own s_waitcnt vmcnt + a barrier before any lane reads it.
-__device__ __forceinline__ void lds_dma16(unsigned lds_addr, unsigned voff, i32x4 rsrc, unsigned soff) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-// buffer descriptor of `bytes` bytes at p (raw dword addressing, out-of-range reads return 0)
-__device__ __forceinline__ i32x4 lds_dma_desc(const void* p, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)p;
-    return i32x4{int(unsigned(a)), int(unsigned(a >> 32) & 0xFFFF), int(bytes), 0x00020000};
-}
-#endif
 
 // ------------------------------------------------------------------ plane geometry
 // The three planes of a triplane: xy[H,W], xz[H,D], yz[W,D]  (src/utils/triplane_util.py:20-25)
@@ -274,7 +259,7 @@ void wino_gn_parts(const Geo& g, int nparts[3]);
 size_t pack_wino_weights(std::vector<float>& stage, const float* W, int cout, int ctot, int cin);
 int launch_conv_wino(ConvArgs& a, hipStream_t st);
 double wino_exec_fraction();
-// mixed Winograd F(2x4,3x3) (s3d_wino24.hip): the default 3x3 kernel of the inference forward (S3D_WINO=4 / 2 / 0 select the others)
+// mixed Winograd F(2x4,3x3) (s3d_wino24.hip): the default 3x3 kernel of the inference forward (S3D_WINO=4 / 0 select the others)
 bool conv_use_wino24();
 bool conv_wino24_channels(int cin, int cout);       // the mixed kernel takes every 3x3 launch of these widths
 size_t wino24_packed_floats(int cout, int cin);
@@ -284,7 +269,6 @@ size_t pack_wino24s_weights(std::vector<float>& stage, const float* W, int cout,
 int launch_conv_wino24s(ConvArgs& a, hipStream_t st);
 int launch_conv_wino24_narrow(ConvArgs& a, hipStream_t st);     // k_conv_wino24s, whatever the launch size
 int launch_conv_wino24_wide(ConvArgs& a, hipStream_t st);       // k_conv_wino24w (cout % 64 == 0)
-int launch_conv_wino24_glds(ConvArgs& a, hipStream_t st);       // k_conv_wino24g: halo by LDS-DMA, persistent blocks (S3D_WINO24G=1)
 
 // GroupNorm-apply (+FiLM) + SiLU, writing y and (optionally) row/col partial sums of y for the rollout means.
 struct ActArgs {

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void k_conv_mfma(ConvArgs args) {
     float* const Bbase = smem + 2 * CFG::A_ELEMS;
 
     // workgroup i runs on XCD i % 8: contiguous logical ranges per XCD keep a tile's column blocks and its halo
-    // neighbours in one L2 (see k_conv_wino2)
+    // neighbours in one L2
     int bid = blockIdx.x;
     if (args.xcd_swizzle) {
         const int chunk = int(gridDim.x) >> 3;

@@ -33,18 +33,24 @@ int upload(DevBuf& dst, const void* host, size_t bytes) {
 }
 
 // ---- options
-struct OptDef { const char* name; bool is_impl; };
-static const OptDef kOpts[OPT_COUNT] = {{"WINO", false}, {"WINO24W", false}, {"VCAT", false}, {"WGRAD_WINO", false}, {"RANK1_SLICES", false},
-                                        {"RANK1_BATCH", false}, {"CONV_IMPL", true}, {"CONV1X1_T", false}, {"GN_FUSED", false}, {"BWD_SIDE", false}, {"GNB_FUSED", false}, {"WINO24G", false}, {"EDGE_SIGNAL", false}};
 static std::atomic<int> g_opt[OPT_COUNT];
 static std::atomic<int> g_opt_state[OPT_COUNT];          // 0: not looked at yet, 1: resolved (environment or unset), 2: set through the ABI
-static int parse_opt(int o, const char* v) { return kOpts[o].is_impl ? (strcmp(v, "naive") == 0 ? 1 : 0) : atoi(v); }
+// The value a string selects, or kOptUnset when the option does not take it: CONV_IMPL "naive" -> 1, any other string -> 0;
+// WINO 0 / 4 / 24; every other option 0 / 1.
+static int parse_opt(int o, const char* v) {
+    if (o == OPT_CONV_IMPL) return strcmp(v, "naive") == 0 ? 1 : 0;
+    char* end = nullptr;
+    const long n = strtol(v, &end, 10);
+    if (end == v || *end) return kOptUnset;
+    return (o == OPT_WINO ? n == 0 || n == 4 || n == 24 : n == 0 || n == 1) ? int(n) : kOptUnset;
+}
+static const char* opt_values(int o) { return o == OPT_WINO ? "0, 4 or 24" : "0 or 1"; }     // (for messages)
 int opt(Opt o) {
     if (g_opt_state[o].load(std::memory_order_acquire) == 0) {
-        const std::string env = std::string("S3D_") + kOpts[o].name;
+        const std::string env = std::string("S3D_") + kOptNames[o];
         const char* e = getenv(env.c_str());
         int expect = 0;
-        const int v = e ? parse_opt(o, e) : kOptUnset;
+        const int v = e ? parse_opt(o, e) : kOptUnset;      // (a value the option does not take: unset)
         // (a concurrent s3d_set_option wins: its state is 2)
         if (g_opt_state[o].compare_exchange_strong(expect, -1, std::memory_order_acq_rel)) {
             g_opt[o].store(v, std::memory_order_relaxed);
@@ -56,7 +62,7 @@ int opt(Opt o) {
 static int find_opt(const char* name) {
     if (!name) return -1;
     if (strncmp(name, "S3D_", 4) == 0) name += 4;
-    for (int o = 0; o < OPT_COUNT; ++o) if (strcmp(name, kOpts[o].name) == 0) return o;
+    for (int o = 0; o < OPT_COUNT; ++o) if (strcmp(name, kOptNames[o]) == 0) return o;
     return -1;
 }
 int device_cus() {
@@ -79,7 +85,10 @@ int s3d_set_option(const char* name, const char* value) {
     using namespace s3d;
     const int o = find_opt(name);
     S3D_CHECK(o >= 0, S3D_ERR_INVALID, "set_option: unknown option '%s'", name ? name : "(null)");
-    g_opt[o].store(value && *value ? parse_opt(o, value) : kOptUnset, std::memory_order_relaxed);
+    const bool given = value && *value;
+    const int v = given ? parse_opt(o, value) : kOptUnset;
+    S3D_CHECK(!given || v != kOptUnset, S3D_ERR_INVALID, "set_option: %s takes %s, not '%s'", kOptNames[o], opt_values(o), value);
+    g_opt[o].store(v, std::memory_order_relaxed);
     g_opt_state[o].store(2, std::memory_order_release);
     return 0;
 }

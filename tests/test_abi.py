@@ -126,16 +126,18 @@ def test_host_mapped_timesteps_equal_the_tensor_path(orig, respacing):
         assert seen["ts"].host_values == (float(via_tensor[i]),) * 2
 
 
-def test_options_through_the_abi_and_environment_fallback():
+def test_options_take_only_their_values_through_the_abi_and_environment():
     """s3d_set_option / s3d_get_option: the documented way to select kernel forms (the S3D_* environment variables are only the
-    fallback until the first call for an option); unknown names are rejected with a message."""
+    fallback until the first call for an option); unknown names and values an option does not take are rejected with a message,
+    and an environment variable holding such a value leaves the option unset."""
     import subprocess
     import sys
     code = ("import os, sys\n"
             f"sys.path.insert(0, {REPO!r})\n"
-            "os.environ['S3D_WINO'] = '4'; os.environ['S3D_CONV_IMPL'] = 'naive'\n"
+            "os.environ['S3D_WINO'] = '4'; os.environ['S3D_CONV_IMPL'] = 'naive'; os.environ['S3D_VCAT'] = '2'\n"
             "from sin3dm_amd import _lib\n"
             "assert _lib.get_option('WINO') == 4 and _lib.get_option('S3D_CONV_IMPL') == 1        # environment, read at first use\n"
+            "assert _lib.get_option('VCAT') is None                                               # a value VCAT does not take\n"
             "assert _lib.get_option('WINO24W') is None and _lib.get_option('BWD_SIDE') is None     # unset: the library chooses\n"
             "_lib.set_option('S3D_WINO', 24); _lib.set_option('WINO24W', '1'); _lib.set_option('CONV_IMPL', 'mfma')\n"
             "assert _lib.get_option('WINO') == 24 and _lib.get_option('WINO24W') == 1 and _lib.get_option('CONV_IMPL') == 0\n"
@@ -148,11 +150,24 @@ def test_options_through_the_abi_and_environment_fallback():
             "    raise SystemExit('accepted an unknown option')\n"
             "except AssertionError as e:\n"
             "    assert 'NO_SUCH_OPTION' in str(e)\n"
+            "for name, value in (('WINO24G', 1), ('WINO', 2), ('WGRAD_WINO', 2)):                  # removed forms\n"
+            "    try:\n"
+            "        _lib.set_option(name, value)\n"
+            "        raise SystemExit(f'accepted {name}={value}')\n"
+            "    except AssertionError as e:\n"
+            "        assert name in str(e), e\n"
+            "assert _lib.get_option('WINO') == 24 and _lib.get_option('WGRAD_WINO') is None       # (a rejected call changes nothing)\n"
             "print('ok')\n")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120,
-                       env={k: v for k, v in os.environ.items() if not k.startswith("S3D_")})
+    env = {k: v for k, v in os.environ.items() if not k.startswith("S3D_")}
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
+    code = (f"import sys; sys.path.insert(0, {REPO!r})\n"
+            "from sin3dm_amd import _lib\n"
+            "assert _lib.get_option('WINO') is None                 # S3D_WINO=2 (the removed two-wave form): the library's default\n"
+            "print('ok')\n")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, env=dict(env, S3D_WINO="2"))
     assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
     names = re.findall(r"^ \*   ([A-Z][A-Z0-9_]+)  ", open(os.path.join(REPO, "include", "sin3dm_hip.h")).read(), flags=re.M)
-    assert len(names) == 13                                  # every documented option exists
+    assert len(names) == 12                                  # every documented option exists
     for n in names:
         _lib.get_option(n)

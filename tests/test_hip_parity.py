@@ -102,11 +102,11 @@ def test_unet_forward_golden(tag, mc, raw, ssn, cm):
     assert np.all(y[..., H:, W:] == 0)
 
 
-@pytest.mark.parametrize("variant", ["24w", "4", "2", "0", "novcat", "gnsplit", "1x1t", "naive"])
+@pytest.mark.parametrize("variant", ["24w", "4", "0", "novcat", "gnsplit", "1x1t", "naive"])
 def test_unet_forward_golden_other_conv_kernels(variant):
     """Every 3x3 kernel on the golden planes (24w: S3D_WINO24W=1, the 64-output-channel block k_conv_wino24w of the mixed Winograd
     F(2x4,3x3) kernel forced onto every launch whose widths allow it — by default it only takes launches of several rounds of
-    blocks; 4 / 2: F(2x2) with one / two frequency rows per wave; 0: direct MFMA convolution) against the same golden vectors,
+    blocks; 4: F(2x2), k_conv_wino4; 0: direct MFMA convolution) against the same golden vectors,
     leaf convolutions and ragged shapes included; novcat: S3D_VCAT=0, the upsample + concat materialised instead of the virtual
     concat of Fwd::resblock_cat; gnsplit: S3D_GN_FUSED=0, every GroupNorm statistic from a launch of its own (k_gn_finalize_as) instead of
     being added inside k_gn_act / the output head; 1x1t: S3D_CONV1X1_T=1, the transposed-accumulator epilogue of the 1x1 convolutions (16-byte
@@ -156,16 +156,13 @@ def _r1_forward(mc, B, hwd, seed, rank1_name=False):
     return ys[0].cpu().numpy(), model.profile_kernel(0)
 
 
-@pytest.mark.parametrize("switch,value,other,default", [("S3D_WINO24W", "1", "k_conv_wino24w", "k_conv_wino24s"),
-                                                        ("S3D_WINO24G", "1", "k_conv_wino24g", "k_conv_wino24")])
+@pytest.mark.parametrize("switch,value,other,default", [("S3D_WINO24W", "1", "k_conv_wino24w", "k_conv_wino24s")])
 def test_switched_conv_forms_are_bit_identical_and_reported(tmp_path, switch, value, other, default):
     """The two blockings of the mixed Winograd 3x3 kernel (TriplaneConv, unet_triplane.py:27-58) do the same arithmetic in the
     same order: k_conv_wino24w (8x16 pixels x 64 output channels per block, two n32 sub-blocks sharing one halo + input transform;
     S3D_WINO24W=1 forces it onto every launch whose cout is a multiple of 64) against k_conv_wino24s (x 32; S3D_WINO24W=0), each
     in its own process (the switch is read once).  Whole-UNet outputs are bit-identical — the convolution outputs AND the
-    GroupNorm partial sums their epilogues leave — repeated calls agree, and the library reports which kernel ran.
-    S3D_WINO24G=1: the LDS-DMA form (k_conv_wino24g: halo by buffer_load ... lds into a swizzled unpadded ring, persistent blocks when a
-    launch has more tiles than co-resident blocks — the last two cases) against the library's default choice, same bar."""
+    GroupNorm partial sums their epilogues leave — repeated calls agree, and the library reports which kernel ran."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 

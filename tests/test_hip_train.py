@@ -173,6 +173,27 @@ def test_fast_path_equals_autograd_and_is_repeatable():
     assert torch.allclose(p.grad, 2 * m.split_flat(g1)["input_blocks.0.0.in_layers.2.conv_xy.weight"], rtol=1e-6, atol=0)
 
 
+@pytest.mark.parametrize("mc,hwd,B,ssn", [(64, (48, 64, 40), 3, True), (32, (9, 13, 7), 2, True), (32, (9, 13, 7), 2, False),
+                                          (32, (20, 28, 12), 2, True)])
+def test_fast_path_is_repeatable_on_wide_and_ragged_shapes(mc, hwd, B, ssn):
+    """The default training step twice on the same inputs: the same flat gradient bits, all finite — a 64-channel model at batch 3,
+    ragged planes, and the 32-channel model's 96-channel layers (three 32-channel tiles of the 3x3 weight gradient)."""
+    import torch
+    diffusion = _diffusion()
+    dev = torch.device("cuda:0")
+    H, W, D = hwd
+    x0 = torch.from_numpy(T.synthetic_noise((B, 12, H + D, W + D), 440)).clamp(-1, 1).to(dev)
+    noise = torch.from_numpy(T.synthetic_noise((B, 12, H + D, W + D), 441)).to(dev)
+    t = torch.tensor([700, 3, 250][:B], device=dev)
+    w = torch.tensor([1.0, 0.5, 2.0][:B], device=dev)
+    kw = dict(H=H, W=W, D=D)
+    m = _model(mc, ssn=ssn)
+    _, g1 = diffusion.training_losses_and_grads(m, x0, t, w, kw, noise=noise)
+    g1 = g1.clone()
+    _, g2 = diffusion.training_losses_and_grads(m, x0, t, w, kw, noise=noise)
+    assert torch.isfinite(g1).all() and torch.equal(g1, g2)
+
+
 @pytest.mark.parametrize("wd_tag", ["wd0", "wd01"])
 def test_optimizer_steps(wd_tag):
     """Three TrainLoop.run_step iterations (AdamW -> EMA -> linear anneal) with the fused flat optimizer."""
@@ -617,39 +638,6 @@ def test_groupnorm_backward_sums_from_the_dgrad_epilogue_agree_with_the_read_pas
         assert not torch.equal(out[None][1], out[0][1]) or mc == 0          # (another summation order: not the same bits)
 
 
-def test_lds_dma_conv_form_gives_the_same_gradient_bits():
-    """S3D_WINO24G = 1: every mixed-Winograd launch of the training step — forward, input gradient, and the input gradient with the
-    GroupNorm-backward epilogue (k_conv_wino24g_gnb) — takes the LDS-DMA / persistent form (TriplaneConv forward and transpose,
-    src/diffusion/unet_triplane.py:27-58).  Same products and sums in the same order: losses and the whole flat gradient are the
-    same bits as with the default kernels, and the library names the kernel that ran."""
-    import torch
-    from sin3dm_amd import _lib
-    diffusion = _diffusion()
-    dev = torch.device("cuda:0")
-    for mc, (H, W, D), B, ssn in ((64, (48, 64, 40), 3, True), (32, (9, 13, 7), 2, False)):
-        x0 = torch.from_numpy(T.synthetic_noise((B, 12, H + D, W + D), 430)).clamp(-1, 1).to(dev)
-        noise = torch.from_numpy(T.synthetic_noise((B, 12, H + D, W + D), 431)).to(dev)
-        t = torch.tensor([700, 3, 250][:B], device=dev)
-        w = torch.tensor([1.0, 0.5, 2.0][:B], device=dev)
-        kw = dict(H=H, W=W, D=D)
-        out = {}
-        try:
-            for mode in (None, 1):
-                _lib.set_option("WINO24G", mode)
-                m = _model(mc, ssn=ssn)
-                m.profile(1, classes=1)
-                terms, g = diffusion.training_losses_and_grads(m, x0, t, w, kw, noise=noise)
-                g = g.clone()
-                _, g2 = diffusion.training_losses_and_grads(m, x0, t, w, kw, noise=noise)
-                assert torch.equal(g, g2), mode
-                m.profile_read()
-                out[mode] = (terms["loss"].clone(), g, m.profile_kernel(0))
-        finally:
-            _lib.set_option("WINO24G", None)
-        assert "k_conv_wino24g" in out[1][2] and "k_conv_wino24g" not in out[None][2], (out[None][2], out[1][2])
-        assert torch.equal(out[None][0], out[1][0]) and torch.equal(out[None][1], out[1][1]), mc
-
-
 def test_step_inputs_drawn_ahead_give_the_same_training_run():
     """TrainLoop draws step k + 1's timesteps, importance weights and noise while step k's backward pass runs (one pinned staging
     row + one asynchronous copy, the timestep_map lookup done on the host; src/diffusion/train_util.py:198-232,
@@ -690,34 +678,3 @@ def test_step_inputs_drawn_ahead_give_the_same_training_run():
                 os.environ.pop("S3D_PREFETCH_INPUTS", None)
         assert torch.isfinite(ends["0"][0]).all()
         assert torch.equal(ends["0"][0], ends["1"][0]) and torch.equal(ends["0"][1], ends["1"][1]), dkw
-
-
-def test_weight_gradient_operands_by_lds_dma_give_the_same_gradient_bits():
-    """The 3x3 weight gradient (the transpose of TriplaneConv's dense part in the own channels, src/diffusion/unet_triplane.py:27-58) on
-    k_wgrad_wino_dma (WGRAD_WINO = 2: half regions double-buffered in LDS, filled by buffer_load ... lds while the previous half is
-    multiplied; round 6, measured slower and not the default) against k_wgrad_wino (load -> registers -> ds_write, one region at a time): the same
-    products added in the same order, so the whole flat gradient is the same bits; ragged planes and a 96-channel layer (three
-    32-channel tiles) included."""
-    import torch
-    from sin3dm_amd import _lib
-    diffusion = _diffusion()
-    dev = torch.device("cuda:0")
-    for mc, (H, W, D), B in ((64, (48, 64, 40), 3), (32, (9, 13, 7), 2), (32, (20, 28, 12), 2)):
-        x0 = torch.from_numpy(T.synthetic_noise((B, 12, H + D, W + D), 440)).clamp(-1, 1).to(dev)
-        noise = torch.from_numpy(T.synthetic_noise((B, 12, H + D, W + D), 441)).to(dev)
-        t = torch.tensor([700, 3, 250][:B], device=dev)
-        w = torch.tensor([1.0, 0.5, 2.0][:B], device=dev)
-        kw = dict(H=H, W=W, D=D)
-        out = {}
-        try:
-            for mode in (None, 2):
-                _lib.set_option("WGRAD_WINO", mode)
-                m = _model(mc)
-                _, g = diffusion.training_losses_and_grads(m, x0, t, w, kw, noise=noise)
-                g = g.clone()
-                _, g2 = diffusion.training_losses_and_grads(m, x0, t, w, kw, noise=noise)
-                assert torch.equal(g, g2), mode
-                out[mode] = g
-        finally:
-            _lib.set_option("WGRAD_WINO", None)
-        assert torch.isfinite(out[None]).all() and torch.equal(out[None], out[2]), (mc, float((out[None] - out[2]).abs().max()))

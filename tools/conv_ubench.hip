@@ -1,7 +1,7 @@
 // Stand-alone timing harness for the MFMA convolution (tuning only; not part of the library).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DS3D_ABLATE=k] tools/conv_ubench.hip -o /tmp/ub && /tmp/ub
 #include "../sin3dm_amd/csrc/s3d_common.h"
-#include "ub_stubs.h"
+#include "ubench_stubs.h"
 namespace s3d { void set_error(const char*, ...) {} const char* get_error() { return ""; }
   // (the Winograd side of launch_conv is not linked into this harness)
   bool conv_use_wino24() { return false; } bool conv_use_wino() { return false; } void wino_gn_parts(const Geo&, int*) {} double wino_exec_fraction() { return 1.0; }

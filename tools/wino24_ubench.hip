@@ -3,7 +3,7 @@
 //   -DW24_TIMING: per-block phase stamps (+ -DW24_WHERE_ID and UB_WHERE=1: block durations per XCD / per CU — its own build, it slows k_conv_wino24s); -DW24W_RING=N: weight-fragment ring depth of the wide kernel
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/wino24_ubench.hip -o tools/ub_wino24
 #include "../sin3dm_amd/csrc/s3d_common.h"
-#include "ub_stubs.h"
+#include "ubench_stubs.h"
 namespace s3d { void set_error(const char*, ...) {} const char* get_error() { return ""; } bool conv_use_naive() { return false; } void conv_note_kernel(const char*) {} const char* conv_last_kernel() { return ""; }
   size_t push(std::vector<float>& st, const float* src, size_t n) { size_t off = (st.size() + 63) & ~size_t(63); st.resize(off + n); if (src) memcpy(st.data() + off, src, n * 4); return off; } }
 #include "../sin3dm_amd/csrc/s3d_wino.hip"
@@ -32,15 +32,15 @@ static void run(int cin, int cout, int hw, int B, int iters, bool extras) {
     CK(hipMemcpy(wgt, hw_.data(), hw_.size() * 4, hipMemcpyHostToDevice));
     { std::vector<float> r(npix * cout); for (auto& v : r) v = float(rand()) / RAND_MAX - 0.5f; CK(hipMemcpy(res, r.data(), r.size() * 4, hipMemcpyHostToDevice));
       std::vector<float> t(size_t(B) * hw * 4 * cout); for (auto& v : t) v = float(rand()) / RAND_MAX - 0.5f; CK(hipMemcpy(tab, t.data(), t.size() * 4, hipMemcpyHostToDevice)); }
-    const char* names[4] = {"wino4   F(2x2) 8x16 px x 32", "wino24s F(2x4) 8x16 px x 32", "wino24w F(2x4) 8x16 px x 64", "wino24g F(2x4) LDS-DMA persist"};
-    const double frac[4] = {4.0 / 9, 1.0 / 3, 1.0 / 3, 1.0 / 3};
+    const char* names[3] = {"wino4   F(2x2) 8x16 px x 32", "wino24s F(2x4) 8x16 px x 32", "wino24w F(2x4) 8x16 px x 64"};
+    const double frac[3] = {4.0 / 9, 1.0 / 3, 1.0 / 3};
     std::vector<float> ref_out;
     // GroupNorm partial records of the epilogue (one per tile and subgroup), compared bit for bit as well
     const int tiles = ((hw + 7) / 8) * ((hw + 15) / 16), sg = cout >= 32 ? gn_subgroup(cout) : 1, nsub = cout / sg;
     const size_t gn_n = size_t(B) * 3 * nsub * tiles * 2;
     double* gn; CK(hipMalloc(&gn, gn_n * 8));
     std::vector<double> ref_gn;
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < 3; ++k) {
         if (k == 2 && cout % 64) continue;
         if (getenv("UB_ONLY") && !strchr(getenv("UB_ONLY"), '0' + k) && k != 1) continue;
         ConvArgs a; memset(&a, 0, sizeof a);
@@ -51,7 +51,7 @@ static void run(int cin, int cout, int hw, int B, int iters, bool extras) {
             if (extras) { a.job[p].res = res + size_t(p) * hw * hw * B * cout; a.job[p].rrow = tab; a.job[p].rcol = tab; }
             if (extras && k >= 1) { a.job[p].gn_part = gn + size_t(p) * tiles * nsub * 2; a.gn_sg = sg; a.gn_nsub = nsub; a.gn_maxparts = tiles; }
         }
-        auto launch = [&]() { return k == 0 ? launch_conv_wino(a, 0) : (k == 1 ? launch_conv_wino24_narrow(a, 0) : (k == 2 ? launch_conv_wino24_wide(a, 0) : launch_conv_wino24_glds(a, 0))); };
+        auto launch = [&]() { return k == 0 ? launch_conv_wino(a, 0) : (k == 1 ? launch_conv_wino24_narrow(a, 0) : launch_conv_wino24_wide(a, 0)); };
         if (k >= 1) {                // the wide form must reproduce k_conv_wino24s bit for bit
             CK(hipMemset(out, 0xFF, npix * cout * 4)); CK(hipMemset(gn, 0xFF, gn_n * 8));
             launch(); CK(hipDeviceSynchronize());
@@ -78,7 +78,7 @@ static void run(int cin, int cout, int hw, int B, int iters, bool extras) {
             else {
                 size_t nbad = 0, first = 0;
                 for (size_t i = 0; i < o.size(); ++i) if (memcmp(&o[i], &ref_out[i], 4)) { if (!nbad) first = i; ++nbad; }
-                printf("    %s vs wino24s: %s", k == 2 ? "wino24w" : "wino24g", nbad ? "MISMATCH" : "bit-identical\n");
+                printf("    wino24w vs wino24s: %s", nbad ? "MISMATCH" : "bit-identical\n");
                 if (nbad) printf(" (%zu of %zu elements, first at %zu: %g vs %g)\n", nbad, o.size(), first, o[first], ref_out[first]);
             }
         }
@@ -127,13 +127,13 @@ static void run(int cin, int cout, int hw, int B, int iters, bool extras) {
                        std::min_element(cu.begin(), cu.end(), [](auto& a, auto& b) { return a.second.size() < b.second.size(); })->second.size(),
                        std::max_element(cu.begin(), cu.end(), [](auto& a, auto& b) { return a.second.size() < b.second.size(); })->second.size());
             }
-            printf("    %s phases, span %.1f us:", k == 1 ? "wino24s" : (k == 2 ? "wino24w" : "wino24g"), (t5 - t0) * 0.01);
+            printf("    %s phases, span %.1f us:", k == 1 ? "wino24s" : "wino24w", (t5 - t0) * 0.01);
             for (int l = 0; l < 2; ++l)
                 if (n[l]) printf("  [%s %d blocks] halo->LDS %.1f | first operands %.1f | k-loop %.1f | barrier + share images + operand loads %.1f | finish + stores %.1f us",
                                  l ? "later" : "first-wave", n[l], ph[l][0] / n[l], ph[l][1] / n[l], ph[l][2] / n[l], ph[l][3] / n[l], ph[l][4] / n[l]);
             printf("\n");
             // a grid of ONE block per CU (and, wide form, exactly two): what a block's phases take when it has the CU's matrix pipe to itself
-            for (int per_cu = 1; k != 3 && per_cu <= (k == 2 ? 2 : 3); ++per_cu) {
+            for (int per_cu = 1; per_cu <= (k == 2 ? 2 : 3); ++per_cu) {
                 const int nb = 256 * per_cu;
                 if (nb > blocks) break;
                 CK(hipMemset(tb, 0, size_t(blocks) * 64));
@@ -173,7 +173,7 @@ int main(int argc, char** argv) {          // arguments: indices of the cases to
                               {128, 256, 64, 8, 5}, {384, 128, 128, 8, 5},                                                      // 15-16 the other two shapes at batch 8
                               {64, 64, 96, 4, 10}, {64, 128, 48, 4, 10},                                                       // 17-18 the training tier's widths (64-channel UNet, batch 4)
                               {32, 32, 20, 2, 10}, {96, 32, 20, 2, 10}, {32, 64, 10, 3, 10}, {160, 96, 52, 2, 10},            // 19-22 two- and six-piece items, ragged planes, odd widths
-                              {64, 64, 200, 2, 5}, {96, 36, 100, 3, 5}};                                                      // 23-24 ... in persistent launches                                                      // 17-18 the training tier's widths (64-channel UNet, batch 4)
+                              {64, 64, 200, 2, 5}, {96, 36, 100, 3, 5}};                                                      // 23-24 ... in launches of many rounds of blocks
     for (int c = 0; c < NC; ++c) {
         bool on = argc < 2;
         for (int i = 1; i < argc; ++i) on |= atoi(argv[i]) == c;
