@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define S3D_ABI_VERSION 5
+#define S3D_ABI_VERSION 6
 #define S3D_API __attribute__((visibility("default")))
 
 typedef enum {
@@ -383,6 +383,31 @@ S3D_API int s3d_mc_extract(s3d_mc* m, float* verts, float* attrs, int n_attr, in
  * src/encoding/utils3d.py:204-208): labels[v] = smallest vertex index of v's component.  tris [n_tris][3], labels
  * [n_verts] on the device; synchronises `stream` (iterates to a fixed point). */
 S3D_API int s3d_mesh_components(const int32_t* tris, int64_t n_tris, int64_t n_verts, int32_t* labels, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * torch's CPU noise stream on the device: the float32 values `torch.randn` / `torch.rand` draw from
+ * torch's default CPU generator (MT19937), so that a sampling run consumes the stream the reference consumes on the CPU
+ * (src/diffusion/gaussian_diffusion.py:514, 431, 591) without a host draw and an upload per step.
+ * The handle owns the 624 state words on the device, the position inside them on the host (it is plain arithmetic on the
+ * sizes drawn) and the raw-word workspace.  pos: index of the next word, 0..624 (624: the next draw regenerates first —
+ * where `torch.manual_seed` leaves the generator).  One randn call of n >= 16 elements consumes n + 16 * (n % 16 != 0)
+ * words (the last 16 outputs are redrawn from 16 more words when n is not a multiple of 16); rand consumes n.
+ * All calls on one handle must be ordered (one stream, or event edges between streams): they read and write its state.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct s3d_rng s3d_rng;
+S3D_API int s3d_rng_create(s3d_rng** out);
+S3D_API void s3d_rng_destroy(s3d_rng* r);
+S3D_API int s3d_rng_set_state(s3d_rng* r, const uint32_t key[624], int pos, void* stream);
+/* synchronises `stream` */
+S3D_API int s3d_rng_get_state(s3d_rng* r, uint32_t key[624], int* pos, void* stream);
+/* grow the raw-word workspace to `words` 32-bit words (never shrinks; may synchronise the device).  s3d_rng_randn / s3d_rng_rand
+ * allocate nothing: a call that needs more words than reserved is S3D_ERR_INVALID. */
+S3D_API int s3d_rng_reserve(s3d_rng* r, int64_t words);
+/* out [n_calls][numel_per_call]: n_calls consecutive torch.randn(numel_per_call) calls.  numel_per_call < 16 is
+ * S3D_ERR_UNSUPPORTED (torch takes a double-precision path there). */
+S3D_API int s3d_rng_randn(s3d_rng* r, float* out, int64_t numel_per_call, int n_calls, void* stream);
+/* out [numel]: one torch.rand(numel) call */
+S3D_API int s3d_rng_rand(s3d_rng* r, float* out, int64_t numel, void* stream);
 
 #ifdef __cplusplus
 }

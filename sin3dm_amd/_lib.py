@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libsin3dm_hip.so")
 c_fp = C.POINTER(C.c_float)
 c_i64p = C.POINTER(C.c_int64)
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 TAB_ROWS = ("sqrt_recip", "sqrt_recipm1", "coef1", "coef2", "logvar", "acp", "acp_prev")
 STEP_DDPM, STEP_DDIM, STEP_MEAN_ONLY = 0, 1, 2
 CARRY_OUT, CARRY_IN = 1, 2               # s3d_unet_step_film_carry flags (include/sin3dm_hip.h)
@@ -115,6 +115,14 @@ SIGNATURES = {
                                c_i64p, c_i64p, C.c_void_p]),
     "s3d_mc_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "s3d_mesh_components": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    # torch's CPU noise stream on the device
+    "s3d_rng_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "s3d_rng_destroy": (None, [C.c_void_p]),
+    "s3d_rng_set_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.c_void_p]),
+    "s3d_rng_get_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.c_void_p]),
+    "s3d_rng_reserve": (C.c_int, [C.c_void_p, C.c_int64]),
+    "s3d_rng_randn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "s3d_rng_rand": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     # auto-encoder training tier
     "s3d_ae_create": (C.c_int, [C.POINTER(DecoderCfg), C.POINTER(C.c_void_p)]),
     "s3d_ae_destroy": (None, [C.c_void_p]),

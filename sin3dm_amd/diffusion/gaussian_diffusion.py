@@ -18,6 +18,7 @@ import numpy as np
 import torch as th
 
 from .. import _lib
+from .cpu_stream import TorchCpuStream, is_cpu_stream, side_stream
 
 
 def get_named_beta_schedule(schedule_name, num_diffusion_timesteps):
@@ -119,8 +120,8 @@ class GaussianDiffusion:
         self.posterior_mean_coef2 = (1.0 - acp) * np.sqrt(alphas) / (1.0 - ac)
 
         # eps source of p_sample/ddim_sample.  None = th.randn_like(x) on the device's generator, which is what
-        # the reference does on a GPU (:431, :591).  Parity runs against the PyTorch-CPU reference set e.g.
-        #   diffusion.noise_fn = lambda x: th.randn(x.shape).to(x.device)     # consume the CPU generator
+        # the reference does on a GPU (:431, :591).  A run that has to match the PyTorch-CPU reference seed for seed passes
+        # `generator=cpu_stream.TorchCpuStream(seed)` to the loops instead (torch's CPU stream, generated on the device).
         self.noise_fn = None
         self._dev_tables = {}
 
@@ -274,17 +275,27 @@ class GaussianDiffusion:
     # them; the 85-step draws of a 256-MB buffer were a 100-us stall every 85 steps — 5 us/step in any 20-step timing window
     # that happened to contain one, profiles/r04_bench_driver_flags.json)
     _NOISE_AHEAD_BYTES = 48 << 20
+    # TorchCpuStream generators: the chunks after the first are drawn on a side stream while the current chunk's steps run (the
+    # state walk of the MT19937 stream is one workgroup); False draws them in line.  Same values either way.
+    _CPU_STREAM_OVERLAP = True
 
     @staticmethod
     def _randn(shape, device, generator, lead=None):
         """N(0,1) of `shape` = [B, ...] (lead: k such tensors, [k, B, ...]).  generator: None (the device's default generator, one
         call), a torch.Generator (one call on it), or a sequence of B generators — sample b's values then come from generator b
-        alone, in calls whose size does not depend on B: a sample's noise is the same whatever it is batched with."""
+        alone, in calls whose size does not depend on B: a sample's noise is the same whatever it is batched with.
+        A cpu_stream.TorchCpuStream (or B of them) draws torch's CPU stream: one randn call of the whole [B, ...] tensor (of
+        [1, ...] per sample) per step, as the reference draws them; lead=k is k consecutive such calls."""
         pre = () if lead is None else (int(lead),)
+        if isinstance(generator, TorchCpuStream):
+            return generator.randn(tuple(shape), lead=lead, device=device)
         if generator is None or isinstance(generator, th.Generator):
             return th.randn(pre + tuple(shape), device=device, generator=generator)
         assert len(generator) == shape[0], "one generator per batch element"
-        per = [th.randn(pre + tuple(shape[1:]), device=device, generator=g) for g in generator]
+        if is_cpu_stream(generator):
+            per = [g.randn((1,) + tuple(shape[1:]), lead=lead, device=device).squeeze(len(pre)) for g in generator]
+        else:
+            per = [th.randn(pre + tuple(shape[1:]), device=device, generator=g) for g in generator]
         return per[0].unsqueeze(len(pre)) if len(per) == 1 else th.stack(per, dim=len(pre))
 
     def _loop(self, mode, model, shape, noise, device, progress, clip_denoised=True, denoised_fn=None, cond_fn=None,
@@ -301,14 +312,19 @@ class GaussianDiffusion:
         generator (an extension of the reference's signature): x_T and every eps come from it instead of the device's default
         generator — a torch.Generator, or one per batch element (`_randn`); with per-element generators the chunk length is
         fixed per SAMPLE, so a sample's whole trajectory depends on its generator only: not on the batch it is in, not on the
-        chain / stream / GPU it runs on (sample_loop_chains, sin3dm_amd.sample)."""
+        chain / stream / GPU it runs on (sample_loop_chains, sin3dm_amd.sample).  A cpu_stream.TorchCpuStream (or one per batch
+        element) makes the run consume torch's CPU generator as the reference does: same seed, same sample."""
         if cond_fn is not None:
             raise NotImplementedError("cond_fn guidance is out of scope (no caller in the reference)")
         if device is None:
             device = next(model.parameters()).device
         assert isinstance(shape, (tuple, list))
-        if generator is not None and not isinstance(generator, th.Generator):
+        if generator is not None and not isinstance(generator, (th.Generator, TorchCpuStream)):
             generator = list(generator)
+        # torch's CPU stream (TorchCpuStream): x_T, then one call per step — the reference's sequence (:514, :431, :591); k calls
+        # drawn at once are the same k calls, so the chunks do not change the values.  The first chunk is one step long, the
+        # following ones are drawn on a side stream one chunk ahead of the steps that read them.
+        cpu_noise = is_cpu_stream(generator) and self.noise_fn is None
         img = noise if noise is not None else self._randn(shape, device, generator)
         indices = list(range(self.num_timesteps))[::-1]
         if progress:
@@ -319,9 +335,9 @@ class GaussianDiffusion:
         prepare = getattr(self, "_prepare_loop", None)
         if prepare is not None:
             prepare(model, shape[0], device)         # per-schedule caches (timestep map, FiLM tables) in one go
-        ahead, ahead_k = None, 0
+        ahead, ahead_k, pending = None, 0, None
         per_step = 4
-        for d in (shape if generator is None or isinstance(generator, th.Generator) else shape[1:]):     # (per-element generators: per SAMPLE)
+        for d in (shape if generator is None or isinstance(generator, (th.Generator, TorchCpuStream)) else shape[1:]):     # (per-element generators: per SAMPLE)
             per_step *= int(d)
         chunk = max(1, min(self.num_timesteps, self._NOISE_AHEAD_BYTES // max(per_step, 1)))
         # The next step's in_conv rides on this step's output head (s3d_unet_step_film_carry) when nobody touches the sample in
@@ -335,8 +351,14 @@ class GaussianDiffusion:
             eps = None
             if self.noise_fn is None:
                 if ahead is None or ahead_k == ahead.shape[0]:
-                    ahead = self._randn(shape, device, generator, lead=min(chunk, self.num_timesteps - n))
+                    if pending is not None:
+                        ahead, pending = _join_side(pending, device), None
+                    else:
+                        ahead = self._randn(shape, device, generator, lead=1 if cpu_noise and n == 0 else min(chunk, self.num_timesteps - n))
                     ahead_k = 0
+                    nxt = n + ahead.shape[0]
+                    if cpu_noise and self._CPU_STREAM_OVERLAP and nxt < self.num_timesteps:
+                        pending = _on_side(device, self._randn, shape, device, generator, lead=min(chunk, self.num_timesteps - nxt))
                 eps = ahead[ahead_k]
                 ahead_k += 1
             with th.no_grad():
@@ -544,6 +566,27 @@ class GaussianDiffusion:
         g = model.backward_flat(_mse_grad(out, target, wgt, H, W, D, divisor=float(out.shape[0])), out=grad_out,
                                 **({"marks": grad_marks} if grad_marks else {}))
         return {"mse_xy": mse[:, 0], "mse_xz": mse[:, 1], "mse_yz": mse[:, 2], "loss": mse[:, 3]}, g
+
+
+def _on_side(device, fn, *a, **kw):
+    """fn(*a, **kw) enqueued on the noise side stream, after everything the current stream holds so far: (result, event)."""
+    main = th.cuda.current_stream(device)
+    side = side_stream(device)
+    side.wait_stream(main)
+    with th.cuda.stream(side):
+        out = fn(*a, **kw)
+        ev = th.cuda.Event()
+        ev.record(side)
+    return out, ev
+
+
+def _join_side(pending, device):
+    """The tensor of _on_side, usable on the current stream."""
+    out, ev = pending
+    main = th.cuda.current_stream(device)
+    main.wait_event(ev)
+    out.record_stream(main)
+    return out
 
 
 _CHAIN_STREAMS = {}

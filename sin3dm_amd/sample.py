@@ -20,8 +20,26 @@ from .utils import dist_util
 from .utils.parser_util import (diffusion_model_path, encoding_feat_path, encoding_log_dir, sample_args)
 
 
-def sample_diffusion(args, rank=0, world=1, base_seed=1000):
-    """Reference: src/sample.py:6-48, with per-sample seeds and rank striping."""
+def noise_source(noise=None):
+    """"device" (the device's Philox generators, the default) or "torch_cpu" (torch's CPU stream generated on the device,
+    diffusion/cpu_stream.py: sample i is what the reference writes for --n_samples 1 after torch.manual_seed of its seed).
+    noise=None reads the environment variable S3D_NOISE."""
+    name = noise if noise is not None else (os.environ.get("S3D_NOISE") or "device")
+    if name not in ("device", "torch_cpu"):
+        raise ValueError(f"noise source {name!r}: expected 'device' or 'torch_cpu'")
+    return name
+
+
+def sample_generators(groups, device, base_seed=1000, noise=None):
+    """One generator per sample of every batch in `groups` (lists of sample indices), seeded parallel.sample_seed(base_seed, i)."""
+    if noise_source(noise) == "torch_cpu":
+        from .diffusion.cpu_stream import TorchCpuStream
+        return [[TorchCpuStream(parallel.sample_seed(base_seed, i), device=device) for i in idx] for idx in groups]
+    return [[torch.Generator(device=device).manual_seed(parallel.sample_seed(base_seed, i)) for i in idx] for idx in groups]
+
+
+def sample_diffusion(args, rank=0, world=1, base_seed=1000, noise=None):
+    """Reference: src/sample.py:6-48, with per-sample seeds and rank striping.  noise: see noise_source."""
     from .diffusion.script_util import create_model_and_diffusion_from_args
     from .utils.triplane_util import decompose_featmaps, load_triplane_data, save_triplane_data
 
@@ -45,7 +63,7 @@ def sample_diffusion(args, rank=0, world=1, base_seed=1000):
     groups = list(parallel.batches(mine, args.diff_batch_size))
     # x_T and every step's eps of sample i come from ITS generator (seed = base + i): a sample does not depend on the batch it
     # is in, the chain it runs on or the number of GPUs
-    gens = [[torch.Generator(device=dev).manual_seed(parallel.sample_seed(base_seed, i)) for i in idx] for idx in groups]
+    gens = sample_generators(groups, dev, base_seed, noise)
     kw = {"H": H, "W": W, "D": D}
     nch = sample_chains(len(groups), args.diff_batch_size)
     full = [g for g in range(len(groups)) if len(groups[g]) == args.diff_batch_size]

@@ -165,3 +165,44 @@ def synthetic_noise(shape, seed):
     """Seeded N(0,1) fp32 array (used where a fixture does not store the noise explicitly)."""
     rng = np.random.Generator(np.random.PCG64([seed, 0xA11CE]))
     return np.ascontiguousarray(rng.standard_normal(size=shape).astype(np.float32))
+
+
+class TorchCpuStreamModel:
+    """Host model of torch's float32 CPU noise stream on numpy's MT19937: what the tests hold the device kernels of
+    diffusion/cpu_stream.py and the recorded torch draws against.  A test helper, not a product path.
+    seed=k is the stream after `torch.manual_seed(k)`; key / pos continue a parsed generator state."""
+
+    def __init__(self, seed=None, key=None, pos=None):
+        self.mt = np.random.MT19937()
+        if key is not None:
+            self.mt.state = {"bit_generator": "MT19937", "state": {"key": np.asarray(key, dtype=np.uint32), "pos": int(pos)}}
+        else:
+            self.mt._legacy_seeding(int(seed) & 0xFFFFFFFF)
+        self.words = 0                      # 32-bit words consumed so far
+
+    def state(self):
+        s = self.mt.state["state"]
+        return np.asarray(s["key"], dtype=np.uint32), int(s["pos"])
+
+    def rand(self, n):
+        self.words += int(n)
+        r = self.mt.random_raw(int(n)).astype(np.uint32)
+        return (r & np.uint32(0xFFFFFF)).astype(np.float32) * np.float32(2.0 ** -24)
+
+    @staticmethod
+    def _box_muller(u):
+        """rows of 16 uniforms -> rows of 16 normals: columns j and j + 8 are one pair"""
+        u1, u2 = np.float32(1) - u[:, :8], u[:, 8:]
+        rad = np.sqrt(np.float32(-2) * np.log(u1))
+        th = np.float32(2 * np.pi) * u2
+        return np.concatenate([rad * np.cos(th), rad * np.sin(th)], 1).astype(np.float32)
+
+    def randn(self, n):
+        n = int(n)
+        assert n >= 16, "torch draws fewer than 16 elements through another path"
+        d = self.rand(n)
+        m = n - n % 16
+        d[:m] = self._box_muller(d[:m].reshape(-1, 16)).ravel()
+        if n % 16:
+            d[n - 16:] = self._box_muller(self.rand(16).reshape(1, 16)).ravel()      # the last 16 are redrawn from 16 more words
+        return d
