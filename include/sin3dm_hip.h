@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define S3D_ABI_VERSION 6
+#define S3D_ABI_VERSION 7
 #define S3D_API __attribute__((visibility("default")))
 
 typedef enum {
@@ -383,6 +383,42 @@ S3D_API int s3d_mc_extract(s3d_mc* m, float* verts, float* attrs, int n_attr, in
  * src/encoding/utils3d.py:204-208): labels[v] = smallest vertex index of v's component.  tris [n_tris][3], labels
  * [n_verts] on the device; synchronises `stream` (iterates to a fixed point). */
 S3D_API int s3d_mesh_components(const int32_t* tris, int64_t n_tris, int64_t n_verts, int32_t* labels, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Textured mesh export: the device half of what follows the iso-surface in decode_texmesh
+ * (src/encoding/model.py:389-430) — decimation, texel positions of a UV atlas, texture finishing.  An own design
+ * (vertex clustering, an analytic per-face atlas): parity with open3d / xatlas / nvdiffrast is not claimed.
+ * Sorting, unique and compaction between these calls are the caller's (sin3dm_amd/encoding/isosurface.py).
+ * All arrays are device pointers unless marked host; every call only enqueues on `stream`.
+ * ------------------------------------------------------------------------------------------------ */
+/* keys[v] = ((ix * dims[1]) + iy) * dims[2] + iz, the cell of vertex v on a uniform grid: per axis
+ * min(dims[a] - 1, floor((verts[v][a] - origin[a]) / cell)) in fp32 (correctly rounded division).  origin, dims: host. */
+S3D_API int s3d_mesh_cluster_keys(const float* verts, int64_t n_verts, const float origin[3], float cell, const int dims[3],
+                                  int64_t* keys, void* stream);
+/* out[k][c] = mean of vals[order[j]][c] for j in [seg[k], seg[k+1]), added in that order (double accumulator).
+ * vals [n_verts][channels], order [n_verts] (vertex indices sorted by key), seg [n_clusters + 1]. */
+S3D_API int s3d_mesh_cluster_means(const float* vals, int channels, const int64_t* order, const int64_t* seg, int64_t n_clusters,
+                                   int64_t n_verts, float* out, void* stream);
+/* out_tris[f] = vmap[tris[f]]; face_keys[f] = the face's vertex set as one integer, (lo * n_clusters + mid) * n_clusters + hi,
+ * or -1 when two of its indices are equal.  n_clusters <= 2^20. */
+S3D_API int s3d_mesh_remap_faces(const int32_t* tris, int64_t n_tris, const int32_t* vmap, int64_t n_verts, int64_t n_clusters,
+                                 int32_t* out_tris, int64_t* face_keys, void* stream);
+/* corner0[f] in {0,1,2}: the vertex of face f opposite its longest edge (ties: the first of v0v1, v1v2, v2v0). */
+S3D_API int s3d_tex_face_corner0(const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_faces, int32_t* corner0,
+                                 void* stream);
+/* The atlas: cells_per_row^2 square cells of `cell` texels, face k in cell k / 2 (row-major), even k in the lower chart
+ * (1,1) (c-4,1) (1,c-4), odd k in the upper chart (c-1,c-1) (4,c-1) (c-1,4) (texels from the cell origin, c = cell).
+ * For every texel (x, y) at index y * texreso + x: face_id = the face whose closed chart holds the centre (x+.5, y+.5), or -1;
+ * pos = b0 V0 + b1 V1 + b2 V2 (zeros where face_id is -1), lower chart b1 = (x+.5-1)/(c-5), b2 = (y+.5-1)/(c-5), b0 = 1-b1-b2,
+ * upper chart mirrored; V0 = the corner0 vertex, V1, V2 follow in the face's cyclic order.  face_id [T*T], pos [T*T][3]. */
+S3D_API int s3d_tex_texel_positions(const float* verts, int64_t n_verts, const int32_t* tris, const int32_t* corner0, int64_t n_faces,
+                                    int texreso, int cells_per_row, int cell, int32_t* face_id, float* pos, void* stream);
+/* image [T*T][channels] uint8 = 0, then image[texel_index[i]][c] = uint8(colors[i][c] * 255) (truncated; clamped to 0..255) */
+S3D_API int s3d_tex_quantize(const float* colors, const int64_t* texel_index, int64_t n, int channels, int texreso, uint8_t* image,
+                             void* stream);
+/* out = image where face_id >= 0, elsewhere the per-channel maximum of image over the 3 x 3 neighbourhood inside the atlas
+ * (cv2.dilate with a 3 x 3 kernel blended by the mask, model.py:426-428).  out must not alias image. */
+S3D_API int s3d_tex_dilate(const uint8_t* image, const int32_t* face_id, int texreso, int channels, uint8_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * torch's CPU noise stream on the device: the float32 values `torch.randn` / `torch.rand` draw from

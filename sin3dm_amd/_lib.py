@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libsin3dm_hip.so")
 c_fp = C.POINTER(C.c_float)
 c_i64p = C.POINTER(C.c_int64)
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 TAB_ROWS = ("sqrt_recip", "sqrt_recipm1", "coef1", "coef2", "logvar", "acp", "acp_prev")
 STEP_DDPM, STEP_DDIM, STEP_MEAN_ONLY = 0, 1, 2
 CARRY_OUT, CARRY_IN = 1, 2               # s3d_unet_step_film_carry flags (include/sin3dm_hip.h)
@@ -115,6 +115,15 @@ SIGNATURES = {
                                c_i64p, c_i64p, C.c_void_p]),
     "s3d_mc_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "s3d_mesh_components": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    # textured mesh export: decimation, atlas texel positions, texture finishing
+    "s3d_mesh_cluster_keys": (C.c_int, [C.c_void_p, C.c_int64, c_fp, C.c_float, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
+    "s3d_mesh_cluster_means": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "s3d_mesh_remap_faces": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3d_tex_face_corner0": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "s3d_tex_texel_positions": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3d_tex_quantize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "s3d_tex_dilate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     # torch's CPU noise stream on the device
     "s3d_rng_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "s3d_rng_destroy": (None, [C.c_void_p]),

@@ -1,6 +1,7 @@
 """ShapeAutoEncoder (reference: src/encoding/model.py): checkpoints, decode, and the auto-encoder training loop
-(:51-139, 178-258, 309-317) on the MI355X.  Mesh/texture export (PyMCubes, xatlas, nvdiffrast) and the tensorboard
-figures are out of scope."""
+(:51-139, 178-258, 309-317) on the MI355X, and the mesh export: decode_mesh (vertex-coloured OBJ, the default) and
+decode_texmesh (:362-473: decimated, UV-mapped, textured OBJ/MTL/PNG or GLB by an own design).  The
+tensorboard figures are out of scope."""
 from __future__ import annotations
 
 import ctypes as C
@@ -137,9 +138,9 @@ class ShapeAutoEncoder:
     def decode_mesh(self, save_dir, triplane_feat, reso, name="object.obj", only_largest_cc=True, save_voxel=True):
         """The geometry half of decode_texmesh (reference :362-390): decode_grid -> voxel.npz -> iso-surface of the
         padded SDF grid at level 0 -> largest connected component -> `v / reso * box_size + box_min`, all on the device
-        (sdfgrid_to_mesh, utils3d.py:196-208, used PyMCubes + point_cloud_utils on the CPU).  What follows there —
-        quadric decimation, UV atlas, texture baking (open3d, xatlas, nvdiffrast) — is out of scope; the decoded colour
-        is interpolated onto the vertices and written as a vertex-coloured OBJ instead."""
+        (sdfgrid_to_mesh, utils3d.py:196-208, used PyMCubes + point_cloud_utils on the CPU).  The decoded colour is
+        interpolated onto the vertices and written as a vertex-coloured OBJ; decimation, UV atlas and the baked texture
+        that follow in the reference are decode_texmesh."""
         from .isosurface import export_obj, largest_component, marching_cubes
         H, W = triplane_feat[0].shape[-2:]
         D = triplane_feat[1].shape[-1]
@@ -156,6 +157,45 @@ class ShapeAutoEncoder:
         verts = verts / float(reso) * box_size + box_min
         export_obj(os.path.join(save_dir, name), verts, tris, cols)
         return verts, tris, cols
+
+    @torch.no_grad()
+    def decode_texmesh(self, save_dir, triplane_feat, reso, n_faces=10000, texture_reso=2048, only_largest_cc=True, save_voxel=True,
+                       mtl_path=None, file_format="obj"):
+        """Reference :362-473 for data_type sdftex: decode_grid -> voxel.npz -> iso-surface -> largest component -> the re-normalisation
+        of decode_mesh -> decimation to n_faces (isosurface.simplify_mesh) -> UV atlas at texture_reso and ONE decode_batch call over
+        its covered texels, quantised and dilated on the device (isosurface.bake_texture) -> object.obj + object.mtl + object.png, or
+        object.glb.  Decimation and atlas are an own design; n_surf_pc, save_highres_mesh and sdfpbr are not built.
+        Returns a dict of what was written (verts, tris, uvs, image, mask, gb_pos, corner0, info), or None for an empty iso-surface
+        (no mesh file is written then)."""
+        import warnings
+        from . import isosurface as iso
+        if file_format not in ("obj", "glb"):
+            raise NotImplementedError(f"file_format {file_format!r}: 'obj' or 'glb'")
+        H, W = triplane_feat[0].shape[-2:]
+        D = triplane_feat[1].shape[-1]
+        aabb = self._resize_aabb((H, W, D))
+        grid = self.decode_grid(triplane_feat, reso, aabb=aabb)
+        os.makedirs(save_dir, exist_ok=True)
+        if save_voxel:
+            np.savez_compressed(os.path.join(save_dir, "voxel.npz"), vox_grid=(grid[..., 0] < 0).cpu().numpy())
+        verts, tris, _ = iso.marching_cubes(grid, 0.0, 1.0)
+        if only_largest_cc:
+            verts, tris, _ = iso.largest_component(verts, tris)
+        if tris.shape[0] == 0:
+            warnings.warn(f"decode_texmesh: the decoded SDF has no zero level set at reso {reso}; no mesh written to {save_dir}")
+            return None
+        box_min = aabb[:3]
+        box_size = aabb[3:].max() - aabb[:3].min()
+        verts = verts / float(reso) * box_size + box_min
+        verts, tris, info = iso.simplify_mesh(verts, tris, n_faces)
+        image, mask, gb_pos, uvs, corner0 = iso.bake_texture(
+            verts, tris, texture_reso, lambda p: self.decode_batch(triplane_feat, p, aabb=aabb)[..., 1:])
+        if file_format == "obj":
+            mtl_str = iso.read_material_params_from_mtl(mtl_path) if mtl_path is not None else None
+            iso.export_textured_obj(os.path.join(save_dir, "object.obj"), verts, tris, uvs, image, material=self.material, mtl_str=mtl_str)
+        else:
+            iso.export_glb(os.path.join(save_dir, "object.glb"), verts, tris, uvs, image)
+        return {"verts": verts, "tris": tris, "uvs": uvs, "image": image, "mask": mask, "gb_pos": gb_pos, "corner0": corner0, "info": info}
 
     # ------------------------------------------------------------------ training (reference :51-139, 178-258)
     def _load_data(self, path, sdf_renorm=False):

@@ -7,7 +7,11 @@ Reads EXP/encoding/{args.json,feat.npz}, EXP/diffusion/{args.json,ema_<rate>_<it
 EXP/encoding/ckpt_final.pth written by the reference's train.py; writes EXP/<output>/NNN/feat.npz (and
 r<reso>_voxel.npz with --vox).  Multi-GPU: sample indices are striped over the ranks (sin3dm_amd/parallel.py).
 Without --vox the decode stage extracts the iso-surface on the device (marching cubes) and writes a vertex-coloured
-object.obj; the reference's UV atlas / baked texture (xatlas, nvdiffrast) is out of scope.
+object.obj.  The reference's default output, a decimated and textured mesh, is opt-in:
+
+    S3D_MESH=textured python -m sin3dm_amd.sample --tag EXP --n_samples N [--n_faces 10000 --texreso 2048 --file_format obj|glb --copy_mtl]
+
+writes object.obj + object.mtl + object.png (or object.glb) by this project's own decimation and atlas.
 """
 from __future__ import annotations
 
@@ -28,6 +32,24 @@ def noise_source(noise=None):
     if name not in ("device", "torch_cpu"):
         raise ValueError(f"noise source {name!r}: expected 'device' or 'torch_cpu'")
     return name
+
+
+def mesh_mode(mode=None):
+    """"vertex" (the vertex-coloured object.obj of decode_mesh, the default) or "textured" (decode_texmesh: --n_faces, --texreso,
+    --file_format and --copy_mtl apply).  mode=None reads the environment variable S3D_MESH."""
+    name = mode if mode is not None else (os.environ.get("S3D_MESH") or "vertex")
+    if name not in ("vertex", "textured"):
+        raise ValueError(f"mesh mode {name!r}: expected 'vertex' or 'textured'")
+    return name
+
+
+def find_copy_mtl(args):
+    """--copy_mtl: the first mesh/*.mtl beside args.data_path (reference: src/sample.py:70-76), or None."""
+    import glob
+    if not getattr(args, "copy_mtl", False) or not getattr(args, "data_path", None):
+        return None
+    found = sorted(glob.glob(os.path.join(os.path.dirname(args.data_path), "mesh", "*.mtl")))
+    return found[0] if found else None
 
 
 def sample_generators(groups, device, base_seed=1000, noise=None):
@@ -96,19 +118,22 @@ def sample_chains(n_batches, batch):
 
 
 def decode(args, paths):
-    """Reference: src/sample.py:51-78 (voxel branch; mesh export is out of scope)."""
+    """Reference: src/sample.py:51-78.  mesh_mode() picks between the vertex-coloured OBJ and the textured export."""
     from .encoding.model import ShapeAutoEncoder
     from .utils.triplane_util import load_triplane_data
 
+    textured = mesh_mode() == "textured"
     ae = ShapeAutoEncoder(encoding_log_dir(args.tag), args, device=dist_util.dev())
     ae.load_ckpt("final")
     for path in paths:
         fm = [f.unsqueeze(0) for f in load_triplane_data(path, device=dist_util.dev(), compose=False)]
         if args.vox:
             ae.decode_voxel(os.path.dirname(path), fm, args.reso)
+        elif textured:
+            ae.decode_texmesh(os.path.dirname(path), fm, args.reso, n_faces=args.n_faces, texture_reso=args.texreso,
+                              mtl_path=find_copy_mtl(args), file_format=args.file_format)
         else:
-            # iso-surface on the device, vertex-coloured object.obj (the UV-atlas / baked-texture export of the reference
-            # needs xatlas + nvdiffrast and stays out of scope)
+            # iso-surface on the device, vertex-coloured object.obj
             ae.decode_mesh(os.path.dirname(path), fm, args.reso)
 
 
