@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define S3D_ABI_VERSION 7
+#define S3D_ABI_VERSION 8
 #define S3D_API __attribute__((visibility("default")))
 
 typedef enum {
@@ -419,6 +419,47 @@ S3D_API int s3d_tex_quantize(const float* colors, const int64_t* texel_index, in
 /* out = image where face_id >= 0, elsewhere the per-channel maximum of image over the 3 x 3 neighbourhood inside the atlas
  * (cv2.dilate with a 3 x 3 kernel blended by the mask, model.py:426-428).  out must not alias image. */
 S3D_API int s3d_tex_dilate(const uint8_t* image, const int32_t* face_id, int texreso, int channels, uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Mesh to training data: what the reference's data/mesh_sampler.py computes with point_cloud_utils and
+ * trimesh — clipped signed distance, colour of the closest surface point, area-weighted surface samples — by an own
+ * design; parity with those libraries is not claimed.  The distance is exact inside a band (a uniform cell grid holds, per
+ * cell, the triangles whose band-dilated box overlaps it) and equals the band outside; the sign is the caller's, from the
+ * generalized winding number.  Triangles are passed as their nine corner floats, tri9 [n_faces][9] = {a, b, c}.  The cell
+ * grid: cell (ix, iy, iz) = per axis min(dims - 1, max(0, floor((x - origin) / cell))), linear index (ix * dims[1] + iy) *
+ * dims[2] + iz; origin and dims are host arrays.  Scan, sort and segment starts between the calls are the caller's
+ * (sin3dm_amd/data/mesh_sampler.py).  All other arrays are device pointers; every call only enqueues on `stream`.
+ * ------------------------------------------------------------------------------------------------ */
+#define S3D_MESHSDF_MAX_CELLS (1LL << 28)
+/* cap of the (cell, triangle) pair list: 2^27 pairs = 1.5 GiB of workspace (an int64 cell key and an int32 triangle per pair) */
+#define S3D_MESHSDF_MAX_PAIRS (1LL << 27)
+/* counts[f] = number of cells the box of triangle f, dilated by a little more than `band`, overlaps */
+S3D_API int s3d_meshsdf_bin_count(const float* tri9, int64_t n_faces, float band, const float origin[3], float cell, const int dims[3],
+                                  int64_t* counts, void* stream);
+/* offsets [n_faces] = exclusive scan of counts, n_pairs = their sum (more than S3D_MESHSDF_MAX_PAIRS: S3D_ERR_UNSUPPORTED).
+ * Triangle f writes (pair_cell, pair_tri) = (cell index, f) at offsets[f]... in ascending cell order. */
+S3D_API int s3d_meshsdf_bin_fill(const float* tri9, int64_t n_faces, float band, const float origin[3], float cell, const int dims[3],
+                                 const int64_t* offsets, int64_t n_pairs, int64_t* pair_cell, int32_t* pair_tri, void* stream);
+/* seg [cells + 1]: the pairs sorted by cell, cell c owns seg_tri[seg[c] .. seg[c+1]).  Per point: dist = distance to the closest
+ * point of those triangles (Ericson's region test, fp32; equal squared distances: the lower face index), face, bary [n][3] with
+ * closest = sum bary[k] * corner k.  Nothing nearer than band: dist = band, face = -1, bary = 0.  A point outside the grid
+ * looks the nearest border cell up. */
+S3D_API int s3d_meshsdf_closest(const float* points, int64_t n_points, const float* tri9, int64_t n_faces, float band, const float origin[3],
+                                float cell, const int dims[3], const int64_t* seg, const int32_t* seg_tri, int64_t n_pairs, float* dist,
+                                int32_t* face, float* bary, void* stream);
+/* wn[i] = sum over the faces, in index order, of the solid angle of face f seen from point i (Van Oosterom-Strackee), / 4 pi */
+S3D_API int s3d_meshsdf_winding(const float* points, int64_t n_points, const float* tri9, int64_t n_faces, float* wn, void* stream);
+S3D_API int s3d_meshsdf_face_areas(const float* tri9, int64_t n_faces, float* areas, void* stream);
+/* cdf [n_faces] (double): inclusive sums of the face areas.  uniforms [n][3] in [0, 1): u0 picks the first face with cdf > u0 *
+ * cdf[n_faces - 1], bary = (1 - sqrt(u1), sqrt(u1) (1 - u2), sqrt(u1) u2).  points [n][3], face [n], bary [n][3]. */
+S3D_API int s3d_meshsdf_sample_surface(const float* tri9, int64_t n_faces, const double* cdf, const float* uniforms, int64_t n,
+                                       float* points, int32_t* face, float* bary, void* stream);
+/* colors [n][3] in [0, 1]: uv [n_faces][3][2] per corner, interpolated with bary; material m = face_mat[f]; mat_table [n_mats][3]
+ * = {byte offset into images, W, H} of tightly packed 8-bit RGB rows (W = 0: no image), mat_kd [n_mats][3].  Texel x =
+ * round(u (W - 1)) mod W, y = round((1 - v) (H - 1)) mod H (half to even), colour = byte / 255; no image: Kd; face -1: 0. */
+S3D_API int s3d_meshsdf_texture(const int32_t* face, const float* bary, int64_t n, const float* uv, const int32_t* face_mat, int64_t n_faces,
+                                const int64_t* mat_table, const float* mat_kd, int n_mats, const uint8_t* images, int64_t image_bytes,
+                                float* colors, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * torch's CPU noise stream on the device: the float32 values `torch.randn` / `torch.rand` draw from
