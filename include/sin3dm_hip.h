@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define S3D_ABI_VERSION 8
+#define S3D_ABI_VERSION 9
 #define S3D_API __attribute__((visibility("default")))
 
 typedef enum {
@@ -460,6 +460,38 @@ S3D_API int s3d_meshsdf_sample_surface(const float* tri9, int64_t n_faces, const
 S3D_API int s3d_meshsdf_texture(const int32_t* face, const float* bary, int64_t n, const float* uv, const int32_t* face_mat, int64_t n_faces,
                                 const int64_t* mat_table, const float* mat_kd, int n_mats, const uint8_t* images, int64_t image_bytes,
                                 float* colors, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Geometry evaluation: the three metrics of the reference's evaluation/patch_utils.py that need nothing but
+ * voxel grids: LP-IoU, LP-F-score (eval_LP_IoU :77, eval_LP_Fscore :100) and the pairwise-IoU diversity (pairwise_IoU_dist :30).
+ * Volumes are uint8 [H][W][D], non-zero = occupied.  A patch of side ps is ceil(ps^3 / 64) 64-bit words: voxel (i, j, k) is bit
+ * t = (i * ps + j) * ps + k, word t / 64, bit t % 64 (least significant first), tail bits zero.  patch_size 2..32; anything else
+ * is S3D_ERR_INVALID and launches nothing.  Compaction, the shuffle and the means stay with the caller.
+ * ------------------------------------------------------------------------------------------------ */
+/* out[i][j][k] = OR over the window [floor(i * in / out), ceil((i + 1) * in / out)) per axis: adaptive_max_pool3d of an occupancy
+ * (load_voxgrid :26); min-pooling an SDF and testing <= 0 (load_sdfgrid2vox :14) is this pooling of the <= 0 mask. */
+S3D_API int s3d_eval_pool_or(const uint8_t* vox, const int in_dims[3], const int out_dims[3], uint8_t* out, void* stream);
+/* counts[k] = (dims[k] + 2 * (patch_size / 2) - patch_size) / stride + 1: the candidate patches per axis of the volume zero-padded
+ * by patch_size / 2 (extract_valid_patches_unfold :59-61).  Host only. */
+S3D_API int s3d_eval_patch_counts(const int dims[3], int patch_size, int stride, int counts[3]);
+/* flags [counts[0] * counts[1] * counts[2]], candidate (a, b, c) at (a * counts[1] + b) * counts[2] + c: 1 when the centre cube
+ * (side 2 for even, 3 for odd patch_size, from patch_size / 2 - 1) holds an occupied and a free voxel (:66-71).  The padding is
+ * implicit. */
+S3D_API int s3d_eval_patch_valid(const uint8_t* vox, const int dims[3], int patch_size, int stride, uint8_t* flags, void* stream);
+/* The listed candidates as words and population counts [n].  word_major = 0: words [n][n_words]; 1: words [n_words][n] (what
+ * s3d_eval_lp_max reads its reference set from).  A candidate index outside the grid packs as an empty patch. */
+S3D_API int s3d_eval_pack_patches(const uint8_t* vox, const int dims[3], int patch_size, int stride, const int64_t* candidates, int64_t n,
+                                  int word_major, uint64_t* words, int32_t* counts, void* stream);
+/* gen_words [n_gen][n_words] (patch-major), ref_words [n_words][n_ref] (word-major), counts >= 1 (true of every valid patch).
+ * max_iou[g] = max over r of float(i) / float(ng + nr - i), max_f[g] = max over r of (2 p q) / ((p + q) + 1e-8f) with
+ * p = float(i) / float(ng), q = float(i) / float(nr), i = |g & r|: every operation one correctly rounded float32 operation in this
+ * order, as the reference's tensors evaluate it.  n_ref = 0: both 0.  n_gen = 0: nothing is written. */
+S3D_API int s3d_eval_lp_max(const uint64_t* gen_words, const int32_t* gen_counts, int64_t n_gen, const uint64_t* ref_words,
+                            const int32_t* ref_counts, int64_t n_ref, int n_words, float* max_iou, float* max_f, void* stream);
+/* words [n][ceil(voxels / 64)]: bit b of word w of volume v = vols[v][w * 64 + b] != 0 */
+S3D_API int s3d_eval_pack_volumes(const uint8_t* vols, int64_t n, int64_t voxels, uint64_t* words, void* stream);
+/* inter[i][j] = |v_i & v_j|, uni[i][j] = |v_i | v_j|, both [n][n] */
+S3D_API int s3d_eval_pairwise_counts(const uint64_t* words, int64_t n, int64_t n_words, int64_t* inter, int64_t* uni, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * torch's CPU noise stream on the device: the float32 values `torch.randn` / `torch.rand` draw from

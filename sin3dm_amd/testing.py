@@ -206,3 +206,14 @@ class TorchCpuStreamModel:
         if n % 16:
             d[n - 16:] = self._box_muller(self.rand(16).reshape(1, 16)).ravel()      # the last 16 are redrawn from 16 more words
         return d
+
+
+def gyroid_sdf(shape, freq=2.0, phase=(0.0, 0.0, 0.0), thickness=0.35):
+    """A thickened gyroid |sin x cos y + sin y cos z + sin z cos x| - thickness on a grid of `shape` voxels (float32, negative
+    inside): `freq` periods along the longest axis, `phase` shifts it per axis.  A procedural stand-in for an SDF grid with many
+    near-surface patches, for the evaluation tests, their fixture generator and tools/bench_eval.py."""
+    n = float(max(shape))
+    x, y, z = (2.0 * np.pi * freq * (np.arange(s, dtype=np.float64) + 0.5) / n + p for s, p in zip(shape, phase))
+    x, y, z = x[:, None, None], y[None, :, None], z[None, None, :]
+    g = np.sin(x) * np.cos(y) + np.sin(y) * np.cos(z) + np.sin(z) * np.cos(x)
+    return np.ascontiguousarray((np.abs(g) - thickness).astype(np.float32))
