@@ -17,11 +17,11 @@ import torch.nn.functional as F
 PLANES = ("xy", "xz", "yz")
 
 
-def timestep_embedding(t, dim):
-    """src/diffusion/nn.py:103-121"""
+def timestep_embedding(t, dim, dtype=torch.float32):
+    """src/diffusion/nn.py:103-121; dtype: the reference's float32, or the parameters' dtype for a float64 evaluation."""
     half = dim // 2
-    freqs = torch.exp(-math.log(10000) * torch.arange(half, dtype=torch.float32, device=t.device) / half)
-    args = t[:, None].float() * freqs[None]
+    freqs = torch.exp(-math.log(10000) * torch.arange(half, dtype=dtype, device=t.device) / half)
+    args = t[:, None].to(dtype) * freqs[None]
     emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
     if dim % 2:
         emb = torch.cat([emb, torch.zeros_like(emb[:, :1])], dim=-1)
@@ -67,8 +67,9 @@ def resblock(sd, prefix, fm, emb, ssn, rollout):
 
 
 def unet_forward(sd, x, t, H, W, D, model_channels, channel_mult=(1, 2), use_scale_shift_norm=True, rollout=True):
-    """TriplaneUNetModelSmall.forward, src/diffusion/unet_triplane.py:465-510"""
-    emb = timestep_embedding(t, model_channels)
+    """TriplaneUNetModelSmall.forward, src/diffusion/unet_triplane.py:465-510.  Follows the dtype of the parameters (the
+    timestep embedding included): float64 parameters and inputs give a float64 evaluation."""
+    emb = timestep_embedding(t, model_channels, sd["time_embed.0.weight"].dtype)
     emb = F.linear(silu(F.linear(emb, sd["time_embed.0.weight"], sd["time_embed.0.bias"])),
                    sd["time_embed.2.weight"], sd["time_embed.2.bias"])
     fm = (x[..., :H, :W], x[..., :H, W:], x[..., H:, :W].transpose(-1, -2))
@@ -108,22 +109,28 @@ def p_sample_update(model_out, x, eps, tab, t):
 
 # ---------------------------------------------------------------------------------------------- training tier
 def q_sample(x0, noise, sqrt_ac, sqrt_1mac, t):
-    """src/diffusion/gaussian_diffusion.py:189-207; sqrt_ac / sqrt_1mac: float64 numpy tables, t: int64 [B]."""
-    a = torch.from_numpy(sqrt_ac).to(x0.device)[t].float()[:, None, None, None]
-    b = torch.from_numpy(sqrt_1mac).to(x0.device)[t].float()[:, None, None, None]
+    """src/diffusion/gaussian_diffusion.py:189-207; sqrt_ac / sqrt_1mac: float64 numpy tables, t: int64 [B].  The
+    coefficients are rounded to x0's dtype (the reference's float32; float64 keeps the tables as they are)."""
+    a = torch.from_numpy(sqrt_ac).to(x0.device)[t].to(x0.dtype)[:, None, None, None]
+    b = torch.from_numpy(sqrt_1mac).to(x0.device)[t].to(x0.dtype)[:, None, None, None]
     return a * x0 + b * noise
 
 
-def training_losses(sd, x0, t, noise, tabs, H, W, D, predict_xstart=True, **unet_kw):
+def training_losses(sd, x0, t, noise, tabs, H, W, D, predict_xstart=True, weights=None, **unet_kw):
     """training_losses with MSE (gaussian_diffusion.py:771-856): per-plane mean-squared errors summed; the target is x0
     (ModelMeanType.START_X) or, with predict_xstart=False, the noise (EPSILON, :829-835).
-    sd tensors may require grad; returns {"mse_xy","mse_xz","mse_yz","loss"} each [B], and x_t."""
+    sd tensors may require grad; returns {"mse_xy","mse_xz","mse_yz","loss"} each [B], and x_t.  Everything runs in the dtype of
+    x0 (float64 x0, noise and parameters: a float64 evaluation, x_t formed in float64 from the float64 tables).
+    weights [B] (TrainLoop.forward_backward, train_util.py:205-236): terms also holds "objective" = (loss * weights).mean(),
+    the scalar the training loop differentiates."""
     x_t = q_sample(x0, noise, tabs["sqrt_alphas_cumprod"], tabs["sqrt_one_minus_alphas_cumprod"], t)
-    out = unet_forward(sd, x_t, t.float(), H, W, D, **unet_kw)
+    out = unet_forward(sd, x_t, t.to(x0.dtype), H, W, D, **unet_kw)
     terms = {}
     for name, tgt, o in zip(PLANES, _decompose(x0 if predict_xstart else noise, H, W, D), _decompose(out, H, W, D)):
         terms["mse_" + name] = ((tgt - o) ** 2).flatten(1).mean(1)
     terms["loss"] = terms["mse_xy"] + terms["mse_xz"] + terms["mse_yz"]
+    if weights is not None:
+        terms["objective"] = (terms["loss"] * weights.to(x0.dtype)).mean()
     return terms, x_t
 
 
