@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define S3D_ABI_VERSION 9
+#define S3D_ABI_VERSION 10
 #define S3D_API __attribute__((visibility("default")))
 
 typedef enum {
@@ -251,6 +251,16 @@ typedef struct {
 } s3d_decoder_cfg;
 
 S3D_API int s3d_decoder_create(const s3d_decoder_cfg* cfg, s3d_decoder** out);
+/* The decoder's other networks (s3d_decoder_create is variant 0); every other s3d_decoder_* call works on any variant, its
+ * `out` rows being s3d_decoder_out_channels floats wide.
+ *   0  AutoEncoderGroupSkip, use_tex=True (tex_channels 1..8)           out = [sdf | sigmoid(tex[tex_channels])]
+ *   1  geometry only (use_tex=False of the skip or the PBR net: the same geo network; feature maps of geo_feat_channels)
+ *                                                                        out = [sdf]
+ *   2  AutoEncoderGroupPBR, use_tex=True (src/encoding/networks.py:227-316: tex_convs = two 3x3 blocks, the second on its
+ *      normalised input; rgb / mr / normal heads on one gathered feature)   out = [sdf | rgb 3 | mr 2 | normal 3], no sigmoid
+ * clamp_color clamps columns >= 1 to [0,1] in every variant. */
+S3D_API int s3d_decoder_create_variant(const s3d_decoder_cfg* cfg, int32_t variant, s3d_decoder** out);
+S3D_API int s3d_decoder_out_channels(const s3d_decoder* d);
 S3D_API void s3d_decoder_destroy(s3d_decoder* d);
 S3D_API int s3d_decoder_num_params(const s3d_decoder* d);
 S3D_API int s3d_decoder_param_info(const s3d_decoder* d, int i, const char** name, int64_t shape[4], int* ndim);
@@ -260,6 +270,9 @@ S3D_API int s3d_decoder_set_param(s3d_decoder* d, const char* name, const float*
  * xy [1,Cg+Ct,H,W], xz [1,Cg+Ct,H,D], yz [1,Cg+Ct,W,D] device fp32. */
 S3D_API int s3d_decoder_prepare_triplane(s3d_decoder* d, const float* xy, const float* xz, const float* yz,
                                  int H, int W, int D, void* stream);
+/* The prepared features of one plane as the reference's NCHW map: out device [feat_channel_up][h][w].
+ * group 0 geo_convs, 1 tex_convs; 2 (variant 2 only) the texture planes after tex_convs.0. */
+S3D_API int s3d_decoder_plane_features(s3d_decoder* d, int group, int plane, float* out, void* stream);
 /* net.decode(points, feat_maps, aabb): pts [N,3] device, aabb[6] host -> out [N, 1+tex_channels]
  * = (sdf, sigmoid(rgb)); clamp_color != 0 additionally applies decode_batch's clamp(0,1) (:332). */
 S3D_API int s3d_decoder_decode_points(s3d_decoder* d, const float* pts, int64_t N, const float aabb[6],

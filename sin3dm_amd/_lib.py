@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libsin3dm_hip.so")
 c_fp = C.POINTER(C.c_float)
 c_i64p = C.POINTER(C.c_int64)
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 TAB_ROWS = ("sqrt_recip", "sqrt_recipm1", "coef1", "coef2", "logvar", "acp", "acp_prev")
 STEP_DDPM, STEP_DDIM, STEP_MEAN_ONLY = 0, 1, 2
 CARRY_OUT, CARRY_IN = 1, 2               # s3d_unet_step_film_carry flags (include/sin3dm_hip.h)
@@ -99,6 +99,9 @@ SIGNATURES = {
                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.POINTER(C.c_char_p), C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
     "s3d_decoder_create": (C.c_int, [C.POINTER(DecoderCfg), C.POINTER(C.c_void_p)]),
+    "s3d_decoder_create_variant": (C.c_int, [C.POINTER(DecoderCfg), C.c_int32, C.POINTER(C.c_void_p)]),
+    "s3d_decoder_out_channels": (C.c_int, [C.c_void_p]),
+    "s3d_decoder_plane_features": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "s3d_decoder_destroy": (None, [C.c_void_p]),
     "s3d_decoder_num_params": (C.c_int, [C.c_void_p]),
     "s3d_decoder_param_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), c_i64p, C.POINTER(C.c_int)]),

@@ -16,18 +16,17 @@
 //        * weights stream through LDS in [rows][32 k] slabs shared by the block's 4 waves (each wave = 32 points),
 //          register-prefetched one slab ahead, one barrier per slab.
 //      Bound: fp32 MFMA (1.18 MFLOP per point, 16 B written per point).
+// The other networks (s3d_decoder_create_variant: geometry only, AutoEncoderGroupPBR, 8 texture channels) share the handle, the
+// registry, the packing and stage (1) below; their point stage is k_decode_heads (s3d_decoder_heads.hip), which keeps this
+// file's device code — and with it k_decode's code object — as it was.  The shared device pieces are in s3d_decoder_mlp.h.
 #include <algorithm>
 #include <cmath>
 #include <memory>
 
 #include "s3d_ae.h"
+#include "s3d_decoder_mlp.h"
 
 namespace s3d {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef const f32x4 __attribute__((address_space(1)))* gf4p;
-__device__ __forceinline__ gf4p g4(const float* p) { return (gf4p)(uintptr_t)p; }
 
 static const char* kPl[3] = {"xy", "xz", "yz"};
 static inline int rup32(int v) { return (v + 31) / 32 * 32; }
@@ -170,9 +169,6 @@ int launch_inorm_silu3(float* const x[3], double* const part[3], const float* co
 }
 
 // ------------------------------------------------------------------ fused gather + MLP
-struct MlpW {                 // device pointers of one DecoderMLPSkipConcat, padded to multiples of 32
-    const float* w[6]; const float* b[6];
-};
 struct DecodeArgs {
     const float* pts;         // [N][3] or null -> cell-centred grid points generated on the fly
     long long N;
@@ -186,98 +182,6 @@ struct DecodeArgs {
     float* out;               // [N][1 + tex_channels]
     int out_stride;
 };
-
-constexpr int kSlabLd = 36;   // padded slab row (floats)
-
-// One layer on the matrix cores: hout[m] (MT tiles of 32 rows) = W[MT*32][K] x [in0 | in1] + bias, optional ReLU.
-// in0 has KT0 tiles of 32 rows, in1 KT1.  All four waves run it in lockstep (they share the LDS weight slabs).
-template <int KT0, int KT1, int MT>
-__device__ __forceinline__ void mlp_layer(const float* __restrict__ Wg, const float* __restrict__ bias,
-                                          const f32x16* in0, const f32x16* in1, f32x16* hout, float* lds, bool relu) {
-    constexpr int KT = KT0 + KT1, K = KT * 32, M = MT * 32;
-    constexpr int ITEMS = M * 8, NI = (ITEMS + 255) / 256;
-    const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, half = lane >> 5;
-    // accumulators start at the bias of their rows
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) hout[m][r] = bias[m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
-    // slab staging descriptors: item -> (row, float4 q)
-    gf4p src[NI]; int dst[NI];
-#pragma unroll
-    for (int it = 0; it < NI; ++it) {
-        const int idx = min(it * 256 + tid, ITEMS - 1);
-        const int row = idx >> 3, q = idx & 7;
-        src[it] = g4(Wg + size_t(row) * K + q * 4);
-        dst[it] = row * kSlabLd + q * 4;
-    }
-    f32x4 rg[NI];
-    __syncthreads();                                   // previous layer's last slab reads are done
-#pragma unroll
-    for (int it = 0; it < NI; ++it) rg[it] = src[it][0];
-#pragma unroll
-    for (int it = 0; it < NI; ++it) *reinterpret_cast<f32x4*>(lds + dst[it]) = rg[it];
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < KT; ++t) {
-        constexpr int kLastT = KT - 1;
-        const int nt = t == kLastT ? t : t + 1;        // last slab re-fetches itself (harmless)
-#pragma unroll
-        for (int it = 0; it < NI; ++it) rg[it] = src[it][nt * 8];
-        __builtin_amdgcn_sched_barrier(0);
-        const float* slab = lds + (t & 1) * (M * kSlabLd);
-        const f32x16& hin = t < KT0 ? in0[t < KT0 ? t : 0] : in1[t >= KT0 ? t - KT0 : 0];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            f32x4 a4[MT];
-#pragma unroll
-            for (int m = 0; m < MT; ++m) a4[m] = *reinterpret_cast<const f32x4*>(slab + (m * 32 + j) * kSlabLd + q * 8 + half * 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int m = 0; m < MT; ++m)
-                    hout[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[m][e], hin[q * 4 + e], hout[m], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        float* nxt = lds + ((t + 1) & 1) * (M * kSlabLd);
-#pragma unroll
-        for (int it = 0; it < NI; ++it) *reinterpret_cast<f32x4*>(nxt + dst[it]) = rg[it];
-        __syncthreads();
-    }
-    if (relu) {
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) hout[m][r] = fmaxf(hout[m][r], 0.f);
-    }
-}
-
-// bilinear, padding_mode='border', align_corners=False sample of plane `fm` [h][w][UPT*32] at (u -> rows, v -> cols),
-// accumulated into the lane's operand registers: x[t][4q+e] is channel 32t + 8q + 4*half + e.
-template <int UPT>
-__device__ __forceinline__ void gather_plane(const float* __restrict__ fm, int h, int w, float u, float v, int half,
-                                             f32x16* x) {
-    constexpr int C = UPT * 32;
-    float fy = ((u + 1.f) * float(h) - 1.f) * 0.5f, fx = ((v + 1.f) * float(w) - 1.f) * 0.5f;
-    fy = fminf(fmaxf(fy, 0.f), float(h - 1)); fx = fminf(fmaxf(fx, 0.f), float(w - 1));
-    const int y0 = int(floorf(fy)), x0 = int(floorf(fx));
-    const float ty = fy - float(y0), tx = fx - float(x0);
-    const float w00 = (1.f - ty) * (1.f - tx), w01 = (1.f - ty) * tx, w10 = ty * (1.f - tx), w11 = ty * tx;
-    const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
-    const float* p00 = fm + (size_t(y0) * w + x0) * C + half * 4;
-    const float* p01 = fm + (size_t(y0) * w + x1) * C + half * 4;
-    const float* p10 = fm + (size_t(y1) * w + x0) * C + half * 4;
-    const float* p11 = fm + (size_t(y1) * w + x1) * C + half * 4;
-#pragma unroll
-    for (int t = 0; t < UPT; ++t)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int c = t * 32 + q * 8;
-            const f32x4 a = g4(p00 + c)[0], b = g4(p01 + c)[0], cc = g4(p10 + c)[0], d = g4(p11 + c)[0];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) x[t][q * 4 + e] += w00 * a[e] + w01 * b[e] + w10 * cc[e] + w11 * d[e];
-        }
-}
 
 template <int UPT, int HIDT>
 __global__ __launch_bounds__(256, 1) void k_decode(DecodeArgs a) {
@@ -340,20 +244,29 @@ using namespace s3d;
 
 struct s3d_decoder {
     s3d_decoder_cfg cfg;
+    int variant = 0;          // 0 skip net with texture, 1 geometry only, 2 AutoEncoderGroupPBR (include/sin3dm_hip.h)
     struct Spec { std::string name; std::vector<int64_t> shape; };
     std::vector<Spec> specs;
     std::map<std::string, std::vector<float>> host;
     bool packed = false;
     int up_p = 0, hid_p = 0;
     DevBuf wbuf;
-    struct Net { ConvW cin, cout_, sc; size_t gamma[3], beta[3]; size_t mw[6], mb[6]; int cin_ch; } net[2];
+    // plane blocks: [0] geo_convs (5x5), [1] tex_convs (5x5) or tex_convs.0 (3x3, PBR), [2] tex_convs.1 (3x3, PBR, no shortcut)
+    struct Net { ConvW cin, cout_, sc; size_t gamma[3], beta[3]; size_t mw[6], mb[6]; int cin_ch; } net[3];
+    // MLP heads in output-column order; net[0/1].mw / mb mirror heads 0 / 1 for k_decode
+    struct Head { std::string name; int group, nout, sigmoid; size_t mw[6], mb[6]; };
+    std::vector<Head> heads;
+    int ngroups = 2;
     // prepared features
     DevBuf feat;
     float* featp[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    float* feat0p[3] = {nullptr, nullptr, nullptr};      // PBR: the texture planes after block 0 (kept for plane_features)
     int ph[3] = {0, 0, 0}, pw[3] = {0, 0, 0};
     bool prepared = false;
     Arena arena;
     const float* dev(size_t off) const { return static_cast<const float*>(wbuf.p) + off; }
+    int out_channels() const { int c = 0; for (const auto& h : heads) c += h.nout; return c; }
+    bool classic() const { return variant == 0 && cfg.tex_channels <= 3; }      // k_decode's case
 };
 
 namespace s3d {
@@ -362,15 +275,15 @@ static void dec_specs(s3d_decoder* d) {
     const s3d_decoder_cfg& c = d->cfg;
     const int up = c.feat_channel_up, hid = c.mlp_hidden_channels, n = c.mlp_hidden_layers / 2;
     auto add = [&](const std::string& nme, std::vector<int64_t> sh) { d->specs.push_back({nme, sh}); };
-    const char* pre[2] = {"geo", "tex"};
-    const int cin[2] = {c.geo_feat_channels, c.tex_feat_channels}, cout[2] = {1, c.tex_channels};
-    for (int k = 0; k < 2; ++k) {
-        const std::string cv = std::string(pre[k]) + "_convs";
-        add(cv + ".in_layers.0.weight", {3 * up, cin[k], 5, 5}); add(cv + ".in_layers.0.bias", {3 * up});
+    // TriplaneGroupResnetBlock (blocks.py:190-235): the conv of in_layers sits behind a SiLU when the block activates its input
+    auto block = [&](const std::string& cv, int cin, int ks, int conv_idx, bool shortcut) {
+        const std::string il = cv + ".in_layers." + std::to_string(conv_idx);
+        add(il + ".weight", {3 * up, cin, ks, ks}); add(il + ".bias", {3 * up});
         for (int p = 0; p < 3; ++p) { add(cv + ".norm_" + kPl[p] + ".weight", {up}); add(cv + ".norm_" + kPl[p] + ".bias", {up}); }
-        add(cv + ".out_layers.1.weight", {3 * up, up, 5, 5}); add(cv + ".out_layers.1.bias", {3 * up});
-        add(cv + ".shortcut.weight", {3 * up, cin[k], 1, 1}); add(cv + ".shortcut.bias", {3 * up});
-        const std::string ml = std::string(pre[k]) + "_decoder";
+        add(cv + ".out_layers.1.weight", {3 * up, up, ks, ks}); add(cv + ".out_layers.1.bias", {3 * up});
+        if (shortcut) { add(cv + ".shortcut.weight", {3 * up, cin, 1, 1}); add(cv + ".shortcut.bias", {3 * up}); }
+    };
+    auto mlp = [&](const std::string& ml, int cout, int group, int sigmoid) {
         add(ml + ".first_layers.0.weight", {hid, up}); add(ml + ".first_layers.0.bias", {hid});
         for (int i = 0; i < n; ++i) {
             add(ml + ".first_layers." + std::to_string(2 * (i + 1)) + ".weight", {hid, hid});
@@ -381,8 +294,23 @@ static void dec_specs(s3d_decoder* d) {
             add(ml + ".second_layers." + std::to_string(2 * (i + 1)) + ".weight", {hid, hid});
             add(ml + ".second_layers." + std::to_string(2 * (i + 1)) + ".bias", {hid});
         }
-        add(ml + ".second_layers." + std::to_string(2 * n) + ".weight", {cout[k], hid});
-        add(ml + ".second_layers." + std::to_string(2 * n) + ".bias", {cout[k]});
+        add(ml + ".second_layers." + std::to_string(2 * n) + ".weight", {cout, hid});
+        add(ml + ".second_layers." + std::to_string(2 * n) + ".bias", {cout});
+        s3d_decoder::Head h; h.name = ml; h.group = group; h.nout = cout; h.sigmoid = sigmoid;
+        d->heads.push_back(h);
+    };
+    block("geo_convs", c.geo_feat_channels, 5, 0, true);
+    mlp("geo_decoder", 1, 0, 0);
+    d->ngroups = d->variant == 1 ? 1 : 2;
+    if (d->variant == 0) {
+        block("tex_convs", c.tex_feat_channels, 5, 0, true);
+        mlp("tex_decoder", c.tex_channels, 1, 1);
+    } else if (d->variant == 2) {                        // networks.py:246-253
+        block("tex_convs.0", c.tex_feat_channels, 3, 0, true);
+        block("tex_convs.1", up, 3, 1, false);
+        mlp("rgb_decoder", 3, 1, 0);
+        mlp("mr_decoder", 2, 1, 0);
+        mlp("normal_decoder", 3, 1, 0);
     }
 }
 
@@ -412,48 +340,52 @@ static int dec_pack(s3d_decoder* d) {
     const s3d_decoder_cfg& c = d->cfg;
     const int up = c.feat_channel_up, hid = c.mlp_hidden_channels, upp = d->up_p, hidp = d->hid_p;
     std::vector<float> st;
-    const char* pre[2] = {"geo", "tex"};
-    const int cin[2] = {c.geo_feat_channels, c.tex_feat_channels}, cout[2] = {1, c.tex_channels};
-    for (int k = 0; k < 2; ++k) {
-        auto& N = d->net[k];
-        N.cin_ch = cin[k];
-        const std::string cv = std::string(pre[k]) + "_convs";
-        const auto& Wi = d->host.at(cv + ".in_layers.0.weight"); const auto& bi = d->host.at(cv + ".in_layers.0.bias");
-        const auto& Wo = d->host.at(cv + ".out_layers.1.weight"); const auto& bo = d->host.at(cv + ".out_layers.1.bias");
-        const auto& Ws = d->host.at(cv + ".shortcut.weight"); const auto& bs = d->host.at(cv + ".shortcut.bias");
-        // pad every conv to (cin 32, cout upp): [tap][coutp][cinp]
-        auto pack_conv = [&](const std::vector<float>& W, const std::vector<float>& b, int ci, int cip, int kk, ConvW& cw) {
-            cw.cin = cip; cw.cout = upp; cw.k = kk; cw.rollout = false;
-            const int taps = kk * kk;
-            for (int p = 0; p < 3; ++p) {
-                cw.bias[p] = pack_vec(st, b.data() + size_t(p) * up, up, upp);
-                cw.dense[p] = push(st, nullptr, size_t(taps) * upp * cip);
-                float* dd = st.data() + cw.dense[p];
-                std::fill(dd, dd + size_t(taps) * upp * cip, 0.f);
-                for (int t = 0; t < taps; ++t)
-                    for (int co = 0; co < up; ++co)
-                        for (int ch = 0; ch < ci; ++ch)
-                            dd[(size_t(t) * upp + co) * cip + ch] = W[((size_t(p) * up + co) * ci + ch) * taps + t];
-            }
-        };
-        pack_conv(Wi, bi, cin[k], 32, 5, N.cin);
-        pack_conv(Wo, bo, up, upp, 5, N.cout_);
-        pack_conv(Ws, bs, cin[k], 32, 1, N.sc);
+    // pad every conv to (cin cip, cout upp): [tap][coutp][cinp]
+    auto pack_conv = [&](const std::vector<float>& W, const std::vector<float>& b, int ci, int cip, int kk, ConvW& cw) {
+        cw.cin = cip; cw.cout = upp; cw.k = kk; cw.rollout = false;
+        const int taps = kk * kk;
+        for (int p = 0; p < 3; ++p) {
+            cw.bias[p] = pack_vec(st, b.data() + size_t(p) * up, up, upp);
+            cw.dense[p] = push(st, nullptr, size_t(taps) * upp * cip);
+            float* dd = st.data() + cw.dense[p];
+            std::fill(dd, dd + size_t(taps) * upp * cip, 0.f);
+            for (int t = 0; t < taps; ++t)
+                for (int co = 0; co < up; ++co)
+                    for (int ch = 0; ch < ci; ++ch)
+                        dd[(size_t(t) * upp + co) * cip + ch] = W[((size_t(p) * up + co) * ci + ch) * taps + t];
+        }
+    };
+    auto pack_block = [&](s3d_decoder::Net& N, const std::string& cv, int ci, int cip, int kk, int conv_idx, bool shortcut) {
+        N.cin_ch = ci;
+        const std::string il = cv + ".in_layers." + std::to_string(conv_idx);
+        pack_conv(d->host.at(il + ".weight"), d->host.at(il + ".bias"), ci, cip, kk, N.cin);
+        pack_conv(d->host.at(cv + ".out_layers.1.weight"), d->host.at(cv + ".out_layers.1.bias"), up, upp, kk, N.cout_);
+        if (shortcut) pack_conv(d->host.at(cv + ".shortcut.weight"), d->host.at(cv + ".shortcut.bias"), ci, cip, 1, N.sc);
         for (int p = 0; p < 3; ++p) {
             N.gamma[p] = pack_vec(st, d->host.at(cv + ".norm_" + kPl[p] + ".weight").data(), up, upp);
             N.beta[p] = pack_vec(st, d->host.at(cv + ".norm_" + kPl[p] + ".bias").data(), up, upp);
         }
-        const std::string ml = std::string(pre[k]) + "_decoder";
+    };
+    pack_block(d->net[0], "geo_convs", c.geo_feat_channels, 32, 5, 0, true);
+    if (d->variant == 0) pack_block(d->net[1], "tex_convs", c.tex_feat_channels, 32, 5, 0, true);
+    if (d->variant == 2) {
+        pack_block(d->net[1], "tex_convs.0", c.tex_feat_channels, 32, 3, 0, true);
+        pack_block(d->net[2], "tex_convs.1", up, upp, 3, 1, false);
+    }
+    for (auto& H : d->heads) {
+        const std::string& ml = H.name;
         const char* ln[6] = {".first_layers.0", ".first_layers.2", ".first_layers.4", ".second_layers.0", ".second_layers.2", ".second_layers.4"};
-        const int outs[6] = {hid, hid, hid, hid, hid, cout[k]};
+        const int outs[6] = {hid, hid, hid, hid, hid, H.nout};
         const int outp[6] = {hidp, hidp, hidp, hidp, hidp, 32};
         const int s0[6] = {up, hid, hid, up, hid, hid}, s1[6] = {0, 0, 0, hid, 0, 0};
         const int s0p[6] = {upp, hidp, hidp, upp, hidp, hidp}, s1p[6] = {0, 0, 0, hidp, 0, 0};
         for (int l = 0; l < 6; ++l) {
-            N.mw[l] = pack_linear(st, d->host.at(ml + ln[l] + ".weight"), outs[l], s0[l], s1[l], outp[l], s0p[l], s1p[l]);
-            N.mb[l] = pack_vec(st, d->host.at(ml + ln[l] + ".bias").data(), outs[l], outp[l]);
+            H.mw[l] = pack_linear(st, d->host.at(ml + ln[l] + ".weight"), outs[l], s0[l], s1[l], outp[l], s0p[l], s1p[l]);
+            H.mb[l] = pack_vec(st, d->host.at(ml + ln[l] + ".bias").data(), outs[l], outp[l]);
         }
     }
+    for (int k = 0; k < 2 && k < int(d->heads.size()); ++k)
+        for (int l = 0; l < 6; ++l) { d->net[k].mw[l] = d->heads[k].mw[l]; d->net[k].mb[l] = d->heads[k].mb[l]; }
     S3D_TRY(upload(d->wbuf, st.data(), st.size() * sizeof(float)));
     d->packed = true;
     return 0;
@@ -467,10 +399,45 @@ static int launch_decode(const DecodeArgs& a, hipStream_t st) {
     S3D_HIP(hipGetLastError());
     return 0;
 }
+static int no_kernel(const s3d_decoder* d) {
+    set_error("decoder: feat_channel_up=%d / mlp_hidden_channels=%d has no compiled kernel (supported after padding to 32: "
+              "up<=64 with hidden 256, up<=32 with hidden 32 or 64, up 96 with hidden 128)", d->cfg.feat_channel_up,
+              d->cfg.mlp_hidden_channels);
+    return S3D_ERR_UNSUPPORTED;
+}
+
+// variants 1 and 2, and the skip net with more than 3 texture channels
+static int run_decode_heads(s3d_decoder* d, const float* pts, long long N, const float aabb[6], const int* gdim, int clamp,
+                            float* out, hipStream_t st) {
+    HeadsArgs a; memset(&a, 0, sizeof a);
+    a.pts = pts; a.N = N; a.clamp_color = clamp; a.out = out; a.out_stride = d->out_channels();
+    for (int k = 0; k < 3; ++k) {
+        a.amin[k] = aabb[k]; a.gsize[k] = aabb[3 + k] - aabb[k];
+        a.gdim[k] = gdim ? gdim[k] : 1; a.ph[k] = d->ph[k]; a.pw[k] = d->pw[k];
+    }
+    a.ngroups = d->ngroups;
+    for (int g = 0; g < d->ngroups; ++g)
+        for (int p = 0; p < 3; ++p) a.feat[g][p] = d->featp[g][p];
+    S3D_CHECK(int(d->heads.size()) <= kMaxHeads, S3D_ERR_INVALID, "decoder: %d heads", int(d->heads.size()));
+    int col = 0, h = 0;
+    for (int g = 0; g < 2; ++g) {                        // heads are stored group by group
+        a.hbeg[g] = h;
+        while (h < int(d->heads.size()) && d->heads[h].group == g) {
+            const auto& H = d->heads[h];
+            for (int l = 0; l < 6; ++l) { a.mlp[h].w[l] = d->dev(H.mw[l]); a.mlp[h].b[l] = d->dev(H.mb[l]); }
+            a.col0[h] = col; a.ncol[h] = H.nout; a.sigm[h] = H.sigmoid;
+            col += H.nout; ++h;
+        }
+    }
+    a.hbeg[2] = h;
+    const int rc = launch_decode_heads(a, d->up_p / 32, d->hid_p / 32, st);
+    return rc == S3D_ERR_UNSUPPORTED ? no_kernel(d) : rc;
+}
 
 static int run_decode(s3d_decoder* d, const float* pts, long long N, const float aabb[6], const int* gdim, int clamp,
                       float* out, hipStream_t st) {
     S3D_CHECK(d->prepared, S3D_ERR_INVALID, "decoder: call s3d_decoder_prepare_triplane first");
+    if (!d->classic()) return run_decode_heads(d, pts, N, aabb, gdim, clamp, out, st);
     DecodeArgs a; memset(&a, 0, sizeof a);
     a.pts = pts; a.N = N; a.clamp_color = clamp; a.out = out; a.out_stride = 1 + d->cfg.tex_channels;
     for (int k = 0; k < 3; ++k) {
@@ -488,31 +455,36 @@ static int run_decode(s3d_decoder* d, const float* pts, long long N, const float
     if (upt == 1 && hidt == 8) return launch_decode<1, 8>(a, st);
     if (upt == 1 && hidt == 2) return launch_decode<1, 2>(a, st);
     if (upt == 3 && hidt == 4) return launch_decode<3, 4>(a, st);
-    set_error("decoder: feat_channel_up=%d / mlp_hidden_channels=%d has no compiled kernel (supported after padding to 32: "
-              "up<=64 with hidden 256, up<=32 with hidden 32 or 64, up 96 with hidden 128)", d->cfg.feat_channel_up,
-              d->cfg.mlp_hidden_channels);
-    return S3D_ERR_UNSUPPORTED;
+    return no_kernel(d);
 }
 
 }  // namespace s3d
 
 extern "C" {
 
-int s3d_decoder_create(const s3d_decoder_cfg* cfg, s3d_decoder** out) {
+int s3d_decoder_create_variant(const s3d_decoder_cfg* cfg, int32_t variant, s3d_decoder** out) {
     S3D_CHECK(cfg && out, S3D_ERR_INVALID, "decoder_create: null argument");
+    S3D_CHECK(variant >= 0 && variant <= 2, S3D_ERR_INVALID, "decoder: variant %d (0 skip net with texture, 1 geometry only, 2 PBR)", int(variant));
     S3D_CHECK(cfg->mlp_hidden_layers == 4, S3D_ERR_UNSUPPORTED, "decoder: mlp_hidden_layers=%d (only the default 4 is built)", cfg->mlp_hidden_layers);
-    S3D_CHECK(cfg->geo_feat_channels >= 1 && cfg->geo_feat_channels <= 32 && cfg->tex_feat_channels >= 1 && cfg->tex_feat_channels <= 32,
+    S3D_CHECK(cfg->geo_feat_channels >= 1 && cfg->geo_feat_channels <= 32 && (variant == 1 || (cfg->tex_feat_channels >= 1 && cfg->tex_feat_channels <= 32)),
               S3D_ERR_UNSUPPORTED, "decoder: feature groups must have 1..32 channels");
-    S3D_CHECK(cfg->tex_channels >= 1 && cfg->tex_channels <= 3, S3D_ERR_UNSUPPORTED, "decoder: tex_channels must be 1..3");
+    S3D_CHECK(variant != 0 || (cfg->tex_channels >= 1 && cfg->tex_channels <= 8), S3D_ERR_UNSUPPORTED, "decoder: tex_channels must be 1..8");
     S3D_CHECK(cfg->feat_channel_up >= 1 && cfg->mlp_hidden_channels >= 1, S3D_ERR_INVALID, "decoder: bad widths");
     std::unique_ptr<s3d_decoder> d(new s3d_decoder());
     d->cfg = *cfg;
+    d->variant = variant;
     d->up_p = rup32(cfg->feat_channel_up);
     d->hid_p = rup32(cfg->mlp_hidden_channels);
     dec_specs(d.get());
     *out = d.release();
     return 0;
 }
+int s3d_decoder_create(const s3d_decoder_cfg* cfg, s3d_decoder** out) {
+    S3D_CHECK(cfg && out, S3D_ERR_INVALID, "decoder_create: null argument");
+    S3D_CHECK(cfg->tex_channels >= 1 && cfg->tex_channels <= 3, S3D_ERR_UNSUPPORTED, "decoder: tex_channels must be 1..3");
+    return s3d_decoder_create_variant(cfg, 0, out);
+}
+int s3d_decoder_out_channels(const s3d_decoder* d) { return d ? d->out_channels() : S3D_ERR_INVALID; }
 void s3d_decoder_destroy(s3d_decoder* d) { delete d; }
 int s3d_decoder_num_params(const s3d_decoder* d) { return d ? int(d->specs.size()) : S3D_ERR_INVALID; }
 int s3d_decoder_param_info(const s3d_decoder* d, int i, const char** name, int64_t shape[4], int* ndim) {
@@ -546,15 +518,17 @@ int s3d_decoder_prepare_triplane(s3d_decoder* d, const float* xy, const float* x
     const Geo g = Geo::from_hwd(H, W, D);
     const float* in[3] = {xy, xz, yz};
     const int upp = d->up_p;
-    // persistent outputs: 2 nets x 3 planes x [h][w][upp]
+    const bool pbr = d->variant == 2;
+    // persistent outputs: groups x 3 planes x [h][w][upp]  (+ the PBR texture planes after block 0)
     size_t tot = 0;
     for (int p = 0; p < 3; ++p) tot += size_t(g.h[p]) * g.w[p] * upp;
     S3D_HIP(hipStreamSynchronize(st));               // the feature buffer may still be read by an earlier decode
-    S3D_TRY(d->feat.reserve(2 * tot * sizeof(float)));
+    S3D_TRY(d->feat.reserve((d->ngroups + (pbr ? 1 : 0)) * tot * sizeof(float)));
     {
         float* base = static_cast<float*>(d->feat.p);
-        for (int n = 0; n < 2; ++n)
+        for (int n = 0; n < d->ngroups; ++n)
             for (int p = 0; p < 3; ++p) { d->featp[n][p] = base; base += size_t(g.h[p]) * g.w[p] * upp; }
+        for (int p = 0; p < 3; ++p) { d->feat0p[p] = pbr ? base : nullptr; if (pbr) base += size_t(g.h[p]) * g.w[p] * upp; }
     }
     for (int p = 0; p < 3; ++p) { d->ph[p] = g.h[p]; d->pw[p] = g.w[p]; }
     // temporaries (two passes: measure, then run)
@@ -564,9 +538,11 @@ int s3d_decoder_prepare_triplane(s3d_decoder* d, const float* xy, const float* x
         if (pass == 0) ar.high = 0;
         else if (ar.high > ar.buf.cap) S3D_TRY(ar.buf.reserve(ar.high));
         ar.reset();
-        for (int n = 0; n < 2; ++n) {
+        for (int n = 0; n < d->ngroups; ++n) {
             auto& N = d->net[n];
             const int c0 = n == 0 ? 0 : d->cfg.geo_feat_channels;
+            const bool two = pbr && n == 1;              // the PBR texture branch: two 3x3 blocks
+            const ConvKind kind = two ? CONV_3x3 : CONV_5x5;
             Tri x, a, y, s; x.C = 32; a.C = y.C = s.C = upp; x.g = a.g = y.g = s.g = g;
             double* part[3];
             for (int p = 0; p < 3; ++p) {
@@ -581,7 +557,7 @@ int s3d_decoder_prepare_triplane(s3d_decoder* d, const float* xy, const float* x
                 hipLaunchKernelGGL(k_slice_pad, dim3((unsigned)((size_t(hw) * 32 + 255) / 256)), dim3(256), 0, st, in[p], x.p[p], hw, c0, N.cin_ch);
             }
             S3D_HIP(hipGetLastError());
-            auto conv = [&](ConvKind kind, const ConvW& cw, const Tri& src, const Tri* res, float* const dst[3]) {
+            auto conv = [&](ConvKind kd, const ConvW& cw, const Tri& src, const Tri* res, float* const dst[3]) {
                 ConvArgs ca; memset(&ca, 0, sizeof ca);
                 ca.B = 1; ca.cin = cw.cin; ca.cout = cw.cout; ca.njobs = 3;
                 for (int p = 0; p < 3; ++p) {
@@ -589,22 +565,52 @@ int s3d_decoder_prepare_triplane(s3d_decoder* d, const float* xy, const float* x
                     J.in = src.p[p]; J.wgt = d->dev(cw.dense[p]); J.bias = d->dev(cw.bias[p]);
                     J.res = res ? res->p[p] : nullptr; J.out = dst[p]; J.h = g.h[p]; J.w = g.w[p];
                 }
-                return launch_conv(kind, ca, st);
+                return launch_conv(kd, ca, st);
             };
-            S3D_TRY(conv(CONV_5x5, N.cin, x, nullptr, a.p));                         // in_layers: conv5x5 (no norm/act on the input)
-            for (int p = 0; p < 3; ++p) {                                            // norm_{p} -> SiLU
-                const int hw = g.h[p] * g.w[p], cq = upp / 4, pl = std::max(1, 256 / cq);
-                hipLaunchKernelGGL(k_chan_partials, dim3(kInChunks), dim3(cq * pl), size_t(pl) * upp * 2 * sizeof(double), st, a.p[p], part[p], hw, upp);
-                hipLaunchKernelGGL(k_inorm_silu, dim3(std::min(1024, (hw * cq + 255) / 256)), dim3(256), size_t(2) * upp * sizeof(float), st,
-                                   a.p[p], part[p], d->dev(N.gamma[p]), d->dev(N.beta[p]), y.p[p], hw, upp, 1e-6f);
-            }
-            S3D_HIP(hipGetLastError());
+            // norm_{p} (+ SiLU) of src with the block's per-plane gamma / beta; keep != null also stores the normalised maps
+            auto inorm = [&](const s3d_decoder::Net& B, float* const src[3], float* const keep[3], float* const dst[3]) -> int {
+                for (int p = 0; p < 3; ++p) {
+                    const int hw = g.h[p] * g.w[p], cq = upp / 4, pl = std::max(1, 256 / cq);
+                    hipLaunchKernelGGL(k_chan_partials, dim3(kInChunks), dim3(cq * pl), size_t(pl) * upp * 2 * sizeof(double), st, src[p], part[p], hw, upp);
+                    if (keep) S3D_TRY(launch_inorm_keep(src[p], part[p], d->dev(B.gamma[p]), d->dev(B.beta[p]), keep[p], dst[p], hw, upp, 1e-6f, st));
+                    else
+                        hipLaunchKernelGGL(k_inorm_silu, dim3(std::min(1024, (hw * cq + 255) / 256)), dim3(256), size_t(2) * upp * sizeof(float), st,
+                                           src[p], part[p], d->dev(B.gamma[p]), d->dev(B.beta[p]), dst[p], hw, upp, 1e-6f);
+                }
+                S3D_HIP(hipGetLastError());
+                return 0;
+            };
+            S3D_TRY(conv(kind, N.cin, x, nullptr, a.p));                             // in_layers: conv (no norm/act on the input)
+            S3D_TRY(inorm(N, a.p, nullptr, y.p));                                    // norm_{p} -> SiLU
             S3D_TRY(conv(CONV_1x1, N.sc, x, nullptr, s.p));                          // shortcut(x)
-            S3D_TRY(conv(CONV_5x5, N.cout_, y, &s, d->featp[n]));                    // out_layers conv5x5 + shortcut
+            S3D_TRY(conv(kind, N.cout_, y, &s, two ? d->feat0p : d->featp[n]));      // out_layers conv + shortcut
+            if (two) {
+                // tex_convs.1 (input_norm, input_act): xn = IN(f0); a = conv(SiLU(xn)); y = SiLU(IN(a)) with the SAME norm_p;
+                // f1 = conv(y) + xn — the Identity shortcut acts on the block's `x`, which forward() rebuilt from the normalised maps
+                auto& N1 = d->net[2];
+                Tri f0; f0.C = upp; f0.g = g;
+                for (int p = 0; p < 3; ++p) f0.p[p] = d->feat0p[p];
+                S3D_TRY(inorm(N1, f0.p, s.p, y.p));                                  // s <- xn, y <- SiLU(xn)   (s is free again)
+                S3D_TRY(conv(CONV_3x3, N1.cin, y, nullptr, a.p));
+                S3D_TRY(inorm(N1, a.p, nullptr, y.p));
+                S3D_TRY(conv(CONV_3x3, N1.cout_, y, &s, d->featp[1]));
+            }
         }
     }
     d->prepared = true;
     return 0;
+}
+
+int s3d_decoder_plane_features(s3d_decoder* d, int group, int plane, float* out, void* stream) {
+    S3D_CHECK(d && out && plane >= 0 && plane < 3, S3D_ERR_INVALID, "plane_features: bad argument");
+    S3D_CHECK(d->prepared, S3D_ERR_INVALID, "decoder: call s3d_decoder_prepare_triplane first");
+    const float* src = nullptr;
+    if (group >= 0 && group < d->ngroups) src = d->featp[group][plane];
+    else if (group == 2 && d->variant == 2) src = d->feat0p[plane];
+    S3D_CHECK(src, S3D_ERR_INVALID, "plane_features: this decoder has no feature group %d", group);
+    const long long hw = (long long)d->ph[plane] * d->pw[plane];
+    const int up = d->cfg.feat_channel_up;
+    return launch_plane_to_nchw(src, out, hw, d->up_p, up, static_cast<hipStream_t>(stream));
 }
 
 int s3d_decoder_decode_points(s3d_decoder* d, const float* pts, int64_t N, const float aabb[6], int clamp_color, float* out,

@@ -368,6 +368,11 @@ def export_textured_obj(path, verts, tris, uvs, image, material=None, mtl_str=No
         fh.write(f"map_Kd {stem}.png\n")
     with open(path[:-4] + ".png", "wb") as fh:
         fh.write(png_bytes(_np(image)[::-1]))
+    _write_uv_obj(path, stem, v, vt, f)
+
+
+def _write_uv_obj(path, stem, v, vt, f):
+    """The .obj of the textured writers: mtllib, v, vt (three per face, in the face's vertex order), usemtl material_0, f v/vt."""
     ft = np.arange(3 * f.shape[0], dtype=np.int64).reshape(-1, 3) + 1
     with open(path, "w") as fh:
         fh.write(f"mtllib {stem}.mtl\n")
@@ -377,15 +382,86 @@ def export_textured_obj(path, verts, tris, uvs, image, material=None, mtl_str=No
         np.savetxt(fh, np.stack([f + 1, ft], 2).reshape(-1, 6), fmt="f %d/%d %d/%d %d/%d")
 
 
+def split_pbr_image(image):
+    """The 8 baked channels of data_type sdfpbr as the reference splits them (src/encoding/model.py:459-462):
+    albedo [..., :3], metallic [..., 3], roughness [..., 4], normal [..., 5:]."""
+    img = _np(image)
+    if img.ndim != 3 or img.shape[2] != 8 or img.dtype != np.uint8:
+        raise ValueError(f"split_pbr_image: expected uint8 [T,T,8], got {img.dtype} {img.shape}")
+    return img[..., :3], img[..., 3], img[..., 4], img[..., 5:]
+
+
+_PBR_MTL_DEFAULTS = (("Ns", 250), ("Ks", [0.5, 0.5, 0.5]), ("Ke", [0, 0, 0]), ("Ni", 1.5), ("d", 1.0), ("illum", 2), ("Ps", 0.0),
+                     ("Pc", 0.0), ("Pcr", 0.03), ("aniso", 0.0), ("anisor", 0.0))
+PBR_MAPS = (("map_Kd", "albedo"), ("map_Pm", "metallic"), ("map_Pr", "roughness"), ("map_Bump -bm 1.000000", "normal"))
+
+
+def export_pbr_obj(path, verts, tris, uvs, albedo, metallic, roughness, normal, **material):
+    """`path` (x.obj), x.mtl and textures/{albedo,metallic,roughness,normal}.png beside it: the files, the material block and
+    its defaults of the reference's save_mesh_with_pbr (src/encoding/utils3d.py:137-166; keyword arguments Ns, Ks, Ke, Ni, d,
+    illum, Ps, Pc, Pcr, aniso, anisor override them).  albedo / normal [T,T,3], metallic / roughness [T,T] uint8 (written as
+    single-channel PNGs), row 0 = texel row y = 0 = the BOTTOM row of each PNG, as in export_textured_obj."""
+    if not path.endswith(".obj"):
+        raise ValueError(f"export_pbr_obj: {path!r} does not end in .obj")
+    v, f, vt = _np(verts), _np(tris).astype(np.int64), _np(uvs)
+    if vt.shape[0] != 3 * f.shape[0]:
+        raise ValueError(f"export_pbr_obj: {vt.shape[0]} texture coordinates for {f.shape[0]} faces")
+    unknown = set(material) - {k for k, _ in _PBR_MTL_DEFAULTS}
+    if unknown:
+        raise TypeError(f"export_pbr_obj: unknown material parameter(s) {sorted(unknown)}")
+    maps = {"albedo": _np(albedo), "metallic": _np(metallic), "roughness": _np(roughness), "normal": _np(normal)}
+    for name, ch in (("albedo", 3), ("metallic", 1), ("roughness", 1), ("normal", 3)):
+        m = maps[name]
+        if m.dtype != np.uint8 or (m.ndim != 3 if ch == 3 else m.ndim != 2) or (ch == 3 and m.shape[2] != 3):
+            raise ValueError(f"export_pbr_obj: {name} must be uint8 {'[T,T,3]' if ch == 3 else '[T,T]'}, got {m.dtype} {m.shape}")
+    root = os.path.dirname(os.path.abspath(path))
+    os.makedirs(os.path.join(root, "textures"), exist_ok=True)
+    stem = os.path.basename(path)[:-4]
+    with open(path[:-4] + ".mtl", "w") as fh:
+        fh.write("newmtl material_0\n")
+        for k, dflt in _PBR_MTL_DEFAULTS:
+            x = material.get(k, dflt)
+            fh.write(f"{k} {x[0]} {x[1]} {x[2]}\n" if isinstance(x, (list, tuple)) else f"{k} {x}\n")
+        for key, name in PBR_MAPS:
+            fh.write(f"{key} textures/{name}.png\n")
+    for name, m in maps.items():
+        with open(os.path.join(root, "textures", name + ".png"), "wb") as fh:
+            fh.write(png_bytes(m[::-1]))
+    _write_uv_obj(path, stem, v, vt, f)
+
+
 def export_glb(path, verts, tris, uvs, image):
     """Binary glTF 2.0: one un-indexed triangle primitive of 3F vertices (POSITION, TEXCOORD_0 with v_gltf = 1 - v_obj), the PNG of
     export_textured_obj embedded as a bufferView, base colour factor 1, metallic 0, roughness 1, double sided."""
+    material = {"pbrMetallicRoughness": {"baseColorFactor": [1.0, 1.0, 1.0, 1.0], "baseColorTexture": {"index": 0},
+                                         "metallicFactor": 0.0, "roughnessFactor": 1.0}, "doubleSided": True}
+    _write_glb(path, verts, tris, uvs, [png_bytes(_np(image)[::-1])], material, "export_glb")
+
+
+def export_pbr_glb(path, verts, tris, uvs, albedo, metallic, roughness, normal):
+    """Binary glTF 2.0 with one metallic-roughness material (an own design: the reference has no PBR GLB): baseColorTexture =
+    albedo, metallicRoughnessTexture = ONE RGB image with G = roughness, B = metallic (glTF's channel assignment) and R = 0,
+    normalTexture = normal; three embedded PNGs, the albedo's bytes equal to export_pbr_obj's.  metallicFactor and
+    roughnessFactor are 1.0: glTF multiplies the texture by them, so export_glb's 0.0 / 1.0 would cancel the metallic map.
+    Double sided.  Arrays as in export_pbr_obj."""
+    al, me, ro, no = _np(albedo), _np(metallic), _np(roughness), _np(normal)
+    if me.shape != ro.shape or me.ndim != 2 or al.shape != me.shape + (3,) or no.shape != al.shape:
+        raise ValueError(f"export_pbr_glb: albedo {al.shape}, metallic {me.shape}, roughness {ro.shape}, normal {no.shape}")
+    packed = np.stack([np.zeros_like(ro), ro, me], axis=-1)
+    material = {"pbrMetallicRoughness": {"baseColorFactor": [1.0, 1.0, 1.0, 1.0], "baseColorTexture": {"index": 0},
+                                         "metallicRoughnessTexture": {"index": 1}, "metallicFactor": 1.0, "roughnessFactor": 1.0},
+                "normalTexture": {"index": 2}, "doubleSided": True}
+    _write_glb(path, verts, tris, uvs, [png_bytes(m[::-1]) for m in (al, packed, no)], material, "export_pbr_glb")
+
+
+def _write_glb(path, verts, tris, uvs, pngs, material, who):
+    """The GLB container of export_glb / export_pbr_glb: texture i = image i = pngs[i]."""
     v, f, vt = _np(verts).astype(np.float32), _np(tris).astype(np.int64), _np(uvs).astype(np.float32)
     if vt.shape[0] != 3 * f.shape[0]:
-        raise ValueError(f"export_glb: {vt.shape[0]} texture coordinates for {f.shape[0]} faces")
+        raise ValueError(f"{who}: {vt.shape[0]} texture coordinates for {f.shape[0]} faces")
     pos = np.ascontiguousarray(v[f.reshape(-1)], dtype="<f4").reshape(-1, 3)
     uv = np.ascontiguousarray(np.stack([vt[:, 0], 1.0 - vt[:, 1]], 1), dtype="<f4")
-    parts = [pos.tobytes(), uv.tobytes(), png_bytes(_np(image)[::-1])]
+    parts = [pos.tobytes(), uv.tobytes(), *pngs]
     views, blob = [], b""
     for p in parts:
         views.append({"buffer": 0, "byteOffset": len(blob), "byteLength": len(p)})
@@ -397,11 +473,10 @@ def export_glb(path, verts, tris, uvs, image):
         "asset": {"version": "2.0", "generator": "sin3dm_amd"},
         "scene": 0, "scenes": [{"nodes": [0]}], "nodes": [{"mesh": 0}],
         "meshes": [{"primitives": [{"attributes": {"POSITION": 0, "TEXCOORD_0": 1}, "material": 0, "mode": 4}]}],
-        "materials": [{"pbrMetallicRoughness": {"baseColorFactor": [1.0, 1.0, 1.0, 1.0], "baseColorTexture": {"index": 0},
-                                                "metallicFactor": 0.0, "roughnessFactor": 1.0}, "doubleSided": True}],
-        "textures": [{"source": 0, "sampler": 0}],
+        "materials": [material],
+        "textures": [{"source": i, "sampler": 0} for i in range(len(pngs))],
         "samplers": [{"magFilter": 9729, "minFilter": 9729, "wrapS": 33071, "wrapT": 33071}],
-        "images": [{"bufferView": 2, "mimeType": "image/png"}],
+        "images": [{"bufferView": 2 + i, "mimeType": "image/png"} for i in range(len(pngs))],
         "accessors": [{"bufferView": 0, "componentType": 5126, "count": n, "type": "VEC3", **bounds},
                       {"bufferView": 1, "componentType": 5126, "count": n, "type": "VEC2"}],
         "bufferViews": views, "buffers": [{"byteLength": len(blob)}],

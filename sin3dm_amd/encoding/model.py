@@ -119,7 +119,7 @@ class ShapeAutoEncoder:
 
     @torch.no_grad()
     def decode_grid(self, triplane_feat, reso, batch_size=2 ** 14, aabb=None):
-        """Reference :335-349 -> [Nx, Ny, Nz, 4]."""
+        """Reference :335-349 -> [Nx, Ny, Nz, 1 | 4 | 9] (sdf | sdftex | sdfpbr), colour / material columns clamped to [0,1]."""
         self.net.eval()
         return self.net.decode_grid(triplane_feat, reso, aabb=self.aabb if aabb is None else aabb)
 
@@ -139,8 +139,8 @@ class ShapeAutoEncoder:
         """The geometry half of decode_texmesh (reference :362-390): decode_grid -> voxel.npz -> iso-surface of the
         padded SDF grid at level 0 -> largest connected component -> `v / reso * box_size + box_min`, all on the device
         (sdfgrid_to_mesh, utils3d.py:196-208, used PyMCubes + point_cloud_utils on the CPU).  The decoded colour is
-        interpolated onto the vertices and written as a vertex-coloured OBJ; decimation, UV atlas and the baked texture
-        that follow in the reference are decode_texmesh."""
+        interpolated onto the vertices and written as a vertex-coloured OBJ (sdfpbr: the albedo; sdf: an OBJ without
+        colours); decimation, UV atlas and the baked texture that follow in the reference are decode_texmesh."""
         from .isosurface import export_obj, largest_component, marching_cubes
         H, W = triplane_feat[0].shape[-2:]
         D = triplane_feat[1].shape[-1]
@@ -149,7 +149,8 @@ class ShapeAutoEncoder:
         os.makedirs(save_dir, exist_ok=True)
         if save_voxel:
             np.savez_compressed(os.path.join(save_dir, "voxel.npz"), vox_grid=(grid[..., 0] < 0).cpu().numpy())
-        verts, tris, cols = marching_cubes(grid, 0.0, 1.0, n_attr=grid.shape[-1] - 1)
+        # vertex colour: the decoded rgb (sdftex), the albedo = columns 1..3 (sdfpbr), none (sdf)
+        verts, tris, cols = marching_cubes(grid, 0.0, 1.0, n_attr=min(grid.shape[-1] - 1, 3))
         if only_largest_cc:
             verts, tris, cols = largest_component(verts, tris, cols)
         box_min = aabb[:3]
@@ -164,9 +165,13 @@ class ShapeAutoEncoder:
         """Reference :362-473 for data_type sdftex: decode_grid -> voxel.npz -> iso-surface -> largest component -> the re-normalisation
         of decode_mesh -> decimation to n_faces (isosurface.simplify_mesh) -> UV atlas at texture_reso and ONE decode_batch call over
         its covered texels, quantised and dilated on the device (isosurface.bake_texture) -> object.obj + object.mtl + object.png, or
-        object.glb.  Decimation and atlas are an own design; n_surf_pc, save_highres_mesh and sdfpbr are not built.
-        Returns a dict of what was written (verts, tris, uvs, image, mask, gb_pos, corner0, info), or None for an empty iso-surface
-        (no mesh file is written then)."""
+        object.glb.  Decimation and atlas are an own design; n_surf_pc and save_highres_mesh are not built.
+        data_type sdf (:392-397): sdfgrid_r{reso}.npz (`sdf_grid`) and the decimated mesh_r{reso}_simple.obj, no atlas, no texture.
+        data_type sdfpbr (:459-471): ONE bake of all 8 channels, split into albedo [..., :3], metallic [..., 3], roughness [..., 4]
+        and normal [..., 5:] -> object.obj + object.mtl + textures/{albedo,metallic,roughness,normal}.png (export_pbr_obj), or
+        object.glb with one metallic-roughness material (export_pbr_glb).
+        Returns a dict of what was written (verts, tris, info, and with a texture uvs, image, mask, gb_pos, corner0), or None for
+        an empty iso-surface (no mesh file is written then)."""
         import warnings
         from . import isosurface as iso
         if file_format not in ("obj", "glb"):
@@ -178,6 +183,8 @@ class ShapeAutoEncoder:
         os.makedirs(save_dir, exist_ok=True)
         if save_voxel:
             np.savez_compressed(os.path.join(save_dir, "voxel.npz"), vox_grid=(grid[..., 0] < 0).cpu().numpy())
+        if self.data_type == "sdf":
+            np.savez_compressed(os.path.join(save_dir, f"sdfgrid_r{reso}.npz"), sdf_grid=grid[..., 0].cpu().numpy())
         verts, tris, _ = iso.marching_cubes(grid, 0.0, 1.0)
         if only_largest_cc:
             verts, tris, _ = iso.largest_component(verts, tris)
@@ -188,9 +195,18 @@ class ShapeAutoEncoder:
         box_size = aabb[3:].max() - aabb[:3].min()
         verts = verts / float(reso) * box_size + box_min
         verts, tris, info = iso.simplify_mesh(verts, tris, n_faces)
+        if self.data_type == "sdf":
+            iso.export_obj(os.path.join(save_dir, f"mesh_r{reso}_simple.obj"), verts, tris)
+            return {"verts": verts, "tris": tris, "info": info}
         image, mask, gb_pos, uvs, corner0 = iso.bake_texture(
             verts, tris, texture_reso, lambda p: self.decode_batch(triplane_feat, p, aabb=aabb)[..., 1:])
-        if file_format == "obj":
+        if self.data_type == "sdfpbr":
+            maps = iso.split_pbr_image(image)
+            if file_format == "obj":
+                iso.export_pbr_obj(os.path.join(save_dir, "object.obj"), verts, tris, uvs, *maps)
+            else:
+                iso.export_pbr_glb(os.path.join(save_dir, "object.glb"), verts, tris, uvs, *maps)
+        elif file_format == "obj":
             mtl_str = iso.read_material_params_from_mtl(mtl_path) if mtl_path is not None else None
             iso.export_textured_obj(os.path.join(save_dir, "object.obj"), verts, tris, uvs, image, material=self.material, mtl_str=mtl_str)
         else:
@@ -201,7 +217,8 @@ class ShapeAutoEncoder:
     def _load_data(self, path, sdf_renorm=False):
         """The preprocessed .npz of one shape: grid + near-surface samples (reference :51-112)."""
         if self.data_type != "sdftex":
-            raise NotImplementedError("only data_type sdftex is built (scripts/run_single.sh)")
+            raise NotImplementedError(f"auto-encoder training is built for data_type sdftex only; {self.data_type} experiments "
+                                      "are sampled and decoded here (DESIGN.md §18)")
         data = np.load(path)
         dev = self.device
         self.aabb = torch.from_numpy(data["aabb"]).float().to(dev)

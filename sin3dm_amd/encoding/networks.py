@@ -1,5 +1,10 @@
-"""AutoEncoderGroupSkip with the reference's constructor, parameter names and `decode` signature
-(src/encoding/networks.py:124-225) — decode runs in libsin3dm_hip.so.
+"""AutoEncoderGroupSkip and AutoEncoderGroupPBR with the reference's constructors, parameter names and `decode` signature
+(src/encoding/networks.py:124-225, 227-316) — decode runs in libsin3dm_hip.so.
+
+The decode side covers the reference's three data types: sdftex (skip net, 1+3 columns), sdf (use_tex=False: the geo network
+alone, 1 column, feature maps of fdim_geo channels) and sdfpbr (skip net with 8 sigmoid channels, or the PBR net: sdf | rgb 3 |
+metallic-roughness 2 | normal 3, no sigmoid).  The training tier below is built for the skip net with up to 3 texture channels
+only; on the other nets `encode`, `forward`, `loss_and_grads` and training raise NotImplementedError.
 
 `decode(x, feat_maps, aabb)` keeps the reference semantics (sdf, sigmoid(rgb)); the per-plane conv blocks are
 evaluated once per distinct triplane and cached (the reference recomputes them on every call with identical
@@ -19,33 +24,49 @@ import torch.nn as nn
 
 from .. import _lib
 from ..diffusion.unet_triplane import _register
-from ..testing import ae_param_shapes
+from ..testing import ae_param_shapes, geo_only_param_shapes, pbr_param_shapes
 
 
 def get_networks(cfg):
-    """Reference: src/encoding/networks.py:7-18 (only the `skip` variant is on the scored path)."""
-    if cfg.enc_net_type != "skip":
-        raise NotImplementedError("only --enc_net_type skip is built (scripts/run_single.sh:31 uses it)")
-    return AutoEncoderGroupSkip(cfg.fdim_geo, cfg.fdim_tex, cfg.fdim_up, cfg.hidden_dim, cfg.n_hidden_layers,
-                                use_tex=cfg.data_type != "sdf")
+    """Reference: src/encoding/networks.py:7-18."""
+    use_tex = cfg.data_type != "sdf"
+    tex_channels = 8 if cfg.data_type == "sdfpbr" else 3
+    args = (cfg.fdim_geo, cfg.fdim_tex, cfg.fdim_up, cfg.hidden_dim, cfg.n_hidden_layers)
+    if cfg.enc_net_type == "skip":
+        return AutoEncoderGroupSkip(*args, use_tex=use_tex, tex_channels=tex_channels)
+    if cfg.enc_net_type == "pbr":
+        if cfg.data_type == "sdftex":
+            # its decode has 8 material columns whatever tex_channels says: the reference can neither train (3-channel targets
+            # against 8 outputs) nor export this pair
+            raise ValueError("--enc_net_type pbr with --data_type sdftex: the PBR network decodes albedo, metallic, roughness "
+                             "and normal (8 channels); use --data_type sdfpbr (or sdf), or --enc_net_type skip")
+        return AutoEncoderGroupPBR(*args, use_tex=use_tex, tex_channels=tex_channels)
+    if cfg.enc_net_type == "base":
+        raise NotImplementedError("--enc_net_type base (AutoEncoderGroupV3) is not built: skip and pbr are")
+    raise ValueError("Unknown net type: {}".format(cfg.enc_net_type))
 
 
 class AutoEncoderGroupSkip(nn.Module):
     def __init__(self, geo_feat_channels, tex_feat_channels, feat_channel_up, mlp_hidden_channels, mlp_hidden_layers,
                  use_tex=True, tex_channels=3, posenc=0):
         super().__init__()
-        if not use_tex or posenc:
-            raise NotImplementedError("use_tex=False / posenc>0 are not on the run_single.sh path")
-        self.use_tex = use_tex
+        if posenc:
+            raise NotImplementedError("posenc>0 is not built")
+        self.use_tex = bool(use_tex)
         self.geo_feat_dim = geo_feat_channels
         self.tex_feat_dim = tex_feat_channels
         self.cfg = (geo_feat_channels, tex_feat_channels, feat_channel_up, mlp_hidden_channels, mlp_hidden_layers,
                     tex_channels)
-        shapes = dict(ae_param_shapes(*self.cfg))
+        # s3d_decoder_create_variant: 0 this net with texture, 1 geometry only, 2 the PBR net
+        self.variant = self._TEX_VARIANT if self.use_tex else 1
+        self.out_channels = {0: 1 + tex_channels, 1: 1, 2: 9}[self.variant]
+        self.in_feat_channels = geo_feat_channels + (tex_feat_channels if self.use_tex else 0)
+        shapes = dict(self._decode_shapes())
         # encoder parameters exist in the reference's checkpoints (ckpt_final.pth['net']); kept so they load
-        enc = {"geo_encoder.weight": (geo_feat_channels, 1, 4, 4, 4), "geo_encoder.bias": (geo_feat_channels,),
-               "tex_encoder.weight": (tex_feat_channels, tex_channels + 1, 4, 4, 4),
-               "tex_encoder.bias": (tex_feat_channels,)}
+        enc = {"geo_encoder.weight": (geo_feat_channels, 1, 4, 4, 4), "geo_encoder.bias": (geo_feat_channels,)}
+        if self.use_tex:
+            enc.update({"tex_encoder.weight": (tex_feat_channels, tex_channels + 1, 4, 4, 4),
+                        "tex_encoder.bias": (tex_feat_channels,)})
         self._decode_names = list(shapes)
         gen = torch.Generator().manual_seed(0)
         for name, shape in {**enc, **shapes}.items():
@@ -71,13 +92,24 @@ class AutoEncoderGroupSkip(nn.Module):
         self._ae_volume = None
         self.tex_group_begin = None
 
+    _TEX_VARIANT = 0
+    _TEX_PREFIXES = ("tex_encoder", "tex_convs", "tex_decoder")
+
+    def _decode_shapes(self):
+        return ae_param_shapes(*self.cfg) if self.use_tex else geo_only_param_shapes(*self.cfg[:1], *self.cfg[2:5])
+
+    @property
+    def training_tier_built(self):
+        """The s3d_ae_* tier covers the skip net with texture of up to 3 channels (sdftex)."""
+        return self.variant == 0 and self.cfg[5] <= 3
+
     def geo_parameters(self):
         """reference :146-147"""
         return [p for n, p in self.named_parameters() if n.startswith(("geo_encoder", "geo_convs", "geo_decoder"))]
 
     def tex_parameters(self):
-        """reference :149-150"""
-        return [p for n, p in self.named_parameters() if n.startswith(("tex_encoder", "tex_convs", "tex_decoder"))]
+        """reference :149-150 (:260-262 for the PBR net)"""
+        return [p for n, p in self.named_parameters() if n.startswith(self._TEX_PREFIXES)]
 
     def reset_aabb(self, aabb):
         if not isinstance(aabb, torch.Tensor):
@@ -86,6 +118,10 @@ class AutoEncoderGroupSkip(nn.Module):
 
     # ------------------------------------------------------------------ training tier (s3d_ae_*)
     def _ensure_ae(self):
+        if not self.training_tier_built:
+            raise NotImplementedError(
+                f"{type(self).__name__}(use_tex={self.use_tex}, tex_channels={self.cfg[5]}): encode, forward(vol, x), loss_and_grads "
+                "and training are not built for geometry-only, PBR and 8-channel networks; they decode only (DESIGN.md §18)")
         lib = _lib.load()
         params = dict(self.named_parameters())
         if self._ae is None:
@@ -194,7 +230,8 @@ class AutoEncoderGroupSkip(nn.Module):
         if self._handle is None:
             h = C.c_void_p()
             cfg = _lib.DecoderCfg(*self.cfg)
-            _lib.check(lib.s3d_decoder_create(C.byref(cfg), C.byref(h)))
+            _lib.check(lib.s3d_decoder_create_variant(C.byref(cfg), self.variant, C.byref(h)))
+            assert lib.s3d_decoder_out_channels(h) == self.out_channels
             self._handle = h
         params = dict(self.named_parameters())
         stamp = tuple((params[n].data_ptr(), params[n]._version) for n in self._decode_names)
@@ -225,7 +262,7 @@ class AutoEncoderGroupSkip(nn.Module):
         fm = [f.contiguous().float() for f in feat_maps]
         for f in fm:
             _lib.require_gpu(f)
-            assert f.dim() == 4 and f.shape[0] == 1 and f.shape[1] == self.geo_feat_dim + self.tex_feat_dim
+            assert f.dim() == 4 and f.shape[0] == 1 and f.shape[1] == self.in_feat_channels, (tuple(f.shape), self.in_feat_channels)
         key = tuple((f.data_ptr(), f._version, tuple(f.shape)) for f in feat_maps)
         if key == self._prepared_for:
             return lib
@@ -245,11 +282,12 @@ class AutoEncoderGroupSkip(nn.Module):
         return (C.c_float * 6)(*[float(v) for v in a])
 
     def decode(self, x, feat_maps, aabb=None, clamp_color=False):
-        """x [N,3] -> [N, 1+3] = (sdf, sigmoid(rgb))  (reference :192-220)."""
+        """x [N,3] -> [N, out_channels]: (sdf, sigmoid(tex)) for the skip net (reference :192-220), (sdf) without texture,
+        (sdf, rgb, metallic, roughness, normal) unactivated for the PBR net (:293-316).  clamp_color clamps columns >= 1."""
         lib = self.prepare(feat_maps)
         _lib.require_gpu(x)
         pts = x.contiguous().float()
-        out = torch.empty((pts.shape[0], 1 + self.cfg[5]), device=pts.device, dtype=torch.float32)
+        out = torch.empty((pts.shape[0], self.out_channels), device=pts.device, dtype=torch.float32)
         with torch.cuda.device(pts.device):
             _lib.check(lib.s3d_decoder_decode_points(self._handle, _lib.ptr(pts), pts.shape[0], self._aabb6(aabb),
                                                      int(bool(clamp_color)), _lib.ptr(out), _lib.stream_ptr()))
@@ -262,10 +300,24 @@ class AutoEncoderGroupSkip(nn.Module):
         dims = (C.c_int * 3)()
         _lib.check(lib.s3d_decoder_grid_dims(a6, int(reso), dims))
         dev = feat_maps[0].device
-        out = torch.empty((dims[0], dims[1], dims[2], 1 + self.cfg[5]), device=dev, dtype=torch.float32)
+        out = torch.empty((dims[0], dims[1], dims[2], self.out_channels), device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
             _lib.check(lib.s3d_decoder_decode_grid(self._handle, int(reso), a6, _lib.ptr(out), _lib.stream_ptr()))
         return out
+
+    def plane_features(self, feat_maps, group):
+        """The prepared feature maps of one group as the reference's [1, up, h, w] tensors: "geo" = geo_convs(...), "tex" =
+        tex_convs(...), "tex0" = the PBR net's texture planes after tex_convs[0]."""
+        lib = self.prepare(feat_maps)
+        gi = {"geo": 0, "tex": 1, "tex0": 2}[group]
+        H, W = feat_maps[0].shape[-2:]
+        D = feat_maps[1].shape[-1]
+        dev = feat_maps[0].device
+        outs = [torch.empty((1, self.cfg[2], a, b), device=dev, dtype=torch.float32) for a, b in ((H, W), (H, D), (W, D))]
+        with torch.cuda.device(dev):
+            for p, o in enumerate(outs):
+                _lib.check(lib.s3d_decoder_plane_features(self._handle, gi, p, _lib.ptr(o), _lib.stream_ptr()))
+        return outs
 
     def forward(self, vol, x, aabb=None):
         """net(vol, x) (reference :222-224) through the training-tier forward (no gradient)."""
@@ -275,3 +327,14 @@ class AutoEncoderGroupSkip(nn.Module):
         with torch.cuda.device(pts.device):
             _lib.check(lib.s3d_ae_forward(self._ae, _lib.ptr(pts), pts.shape[0], self._aabb6(aabb), _lib.ptr(pred), _lib.stream_ptr()))
         return pred
+
+
+class AutoEncoderGroupPBR(AutoEncoderGroupSkip):
+    """Reference :227-316: the geo side of the skip net; tex_convs = two 3x3 blocks (the second normalises its input and adds
+    that normalised input back); rgb / mr / normal heads on one gathered feature, no sigmoid.  Decode only: the handle, the
+    triplane cache, `decode`, `decode_grid`, `prepare`, `reset_aabb` and the parameter groups are the base class's."""
+    _TEX_VARIANT = 2
+    _TEX_PREFIXES = ("tex_encoder", "tex_convs", "rgb_decoder", "mr_decoder", "normal_decoder")
+
+    def _decode_shapes(self):
+        return pbr_param_shapes(*self.cfg, use_tex=self.use_tex)

@@ -12,6 +12,9 @@ object.obj.  The reference's default output, a decimated and textured mesh, is o
     S3D_MESH=textured python -m sin3dm_amd.sample --tag EXP --n_samples N [--n_faces 10000 --texreso 2048 --file_format obj|glb --copy_mtl]
 
 writes object.obj + object.mtl + object.png (or object.glb) by this project's own decimation and atlas.
+An experiment of --data_type sdfpbr writes object.obj + object.mtl + textures/{albedo,metallic,roughness,normal}.png (or a
+metallic-roughness object.glb) there, one of --data_type sdf writes sdfgrid_r<reso>.npz + mesh_r<reso>_simple.obj; in the default mode
+they write object.obj coloured by the albedo / without colours.  The data type comes from EXP/encoding/args.json.
 """
 from __future__ import annotations
 

@@ -12,6 +12,7 @@ Parameter names/shapes restate the reference constructors:
   AutoEncoderGroupSkip.__init__     src/encoding/networks.py:124-149
   TriplaneGroupResnetBlock.__init__ src/encoding/blocks.py:190-235
   DecoderMLPSkipConcat.__init__     src/encoding/blocks.py:66-83
+  AutoEncoderGroupPBR.__init__      src/encoding/networks.py:227-255
 """
 from __future__ import annotations
 
@@ -129,6 +130,48 @@ def ae_param_shapes(geo_feat_channels=4, tex_feat_channels=8, feat_channel_up=64
     mlp("geo_decoder", up, 1)
     block("tex_convs", tex_feat_channels)
     mlp("tex_decoder", up, tex_channels)
+    return sh
+
+
+def geo_only_param_shapes(geo_feat_channels=4, feat_channel_up=64, mlp_hidden_channels=256, mlp_hidden_layers=4,
+                          with_encoder=False):
+    """name -> shape for AutoEncoderGroupSkip / AutoEncoderGroupPBR with use_tex=False (data_type sdf): the geo side of
+    ae_param_shapes, which is the same network in both."""
+    full = ae_param_shapes(geo_feat_channels, 1, feat_channel_up, mlp_hidden_channels, mlp_hidden_layers, 1, with_encoder)
+    return OrderedDict((k, v) for k, v in full.items() if k.startswith("geo_"))
+
+
+def pbr_param_shapes(geo_feat_channels=4, tex_feat_channels=8, feat_channel_up=64, mlp_hidden_channels=256,
+                     mlp_hidden_layers=4, tex_channels=8, use_tex=True, with_encoder=False):
+    """name -> shape for AutoEncoderGroupPBR (src/encoding/networks.py:227-255) in state_dict order: the geo side of the skip
+    net; tex_convs = two 3x3 TriplaneGroupResnetBlocks, the second without shortcut parameters and with its conv at
+    in_layers.1 (a SiLU sits at index 0); the rgb / mr / normal DecoderMLPSkipConcat heads."""
+    if not use_tex:
+        return geo_only_param_shapes(geo_feat_channels, feat_channel_up, mlp_hidden_channels, mlp_hidden_layers, with_encoder)
+    up = feat_channel_up
+    skip = ae_param_shapes(geo_feat_channels, tex_feat_channels, up, mlp_hidden_channels, mlp_hidden_layers, tex_channels,
+                           with_encoder)
+    sh = OrderedDict((k, v) for k, v in skip.items() if k.startswith(("geo_", "tex_encoder")))
+
+    def block(prefix, cin, conv_idx, shortcut):
+        sh[f"{prefix}.in_layers.{conv_idx}.weight"] = (3 * up, cin, 3, 3)
+        sh[f"{prefix}.in_layers.{conv_idx}.bias"] = (3 * up,)
+        for p in PLANES:
+            sh[f"{prefix}.norm_{p}.weight"] = (up,)
+            sh[f"{prefix}.norm_{p}.bias"] = (up,)
+        sh[prefix + ".out_layers.1.weight"] = (3 * up, up, 3, 3)
+        sh[prefix + ".out_layers.1.bias"] = (3 * up,)
+        if shortcut:
+            sh[prefix + ".shortcut.weight"] = (3 * up, cin, 1, 1)
+            sh[prefix + ".shortcut.bias"] = (3 * up,)
+
+    block("tex_convs.0", tex_feat_channels, 0, True)
+    block("tex_convs.1", up, 1, False)
+    for head, cout in (("rgb_decoder", 3), ("mr_decoder", 2), ("normal_decoder", 3)):
+        one = ae_param_shapes(1, 1, up, mlp_hidden_channels, mlp_hidden_layers, cout)
+        for k, v in one.items():
+            if k.startswith("tex_decoder."):
+                sh[head + k[len("tex_decoder"):]] = v
     return sh
 
 
