@@ -33,7 +33,8 @@ typedef enum {
     S3D_ERR_INVALID = -1,     /* bad argument / shape (the shim raises AssertionError/ValueError) */
     S3D_ERR_MISSING = -2,     /* forward called with parameters not all set                      */
     S3D_ERR_HIP = -3,         /* a HIP runtime call failed                                        */
-    S3D_ERR_UNSUPPORTED = -4  /* a configuration the reference itself cannot construct/run        */
+    S3D_ERR_UNSUPPORTED = -4, /* a configuration the reference itself cannot construct/run        */
+    S3D_ERR_INTERNAL = -5     /* the library caught itself out (a bug to report); results invalid */
 } s3d_status;
 
 S3D_API int s3d_abi_version(void);
@@ -44,8 +45,11 @@ S3D_API int s3d_abi_version(void);
  * to the library's own choice; any other value is rejected (S3D_ERR_INVALID).  Until s3d_set_option is called for an option,
  * the environment variable S3D_<NAME> (read once, at the option's first use) supplies its value — the way earlier rounds selected
  * forms; a value the option does not take leaves it unset there.  The call is the documented way.  Options are read at every
- * launch; set them before creating handles: a training handle's repack plan (s3d_unet_train_attach) keeps only the weight images
- * of the forms selected THEN current.
+ * launch and may be switched between two launches on a live inference handle: every successful call moves a process-wide
+ * generation, and a handle whose measured workspace or carried in_conv is older than that measures again (and grows, as for a new
+ * shape) at its next launch — a forward under an option equals the same forward on a handle created under it.  A training
+ * handle's repack plan (s3d_unet_train_attach) keeps only the weight images of the forms selected THEN current: a launch that would
+ * read another image is refused (S3D_ERR_INVALID, "attach again"), so set those before attaching.
  *   WINO          24 (default) mixed Winograd F(2x4,3x3) | 4: F(2x2) | 0: direct MFMA convolution             (rounding differs)
  *   WINO24W       unset: by launch size | 0 never | 1 always the 64-output-channel block                    (bit-identical)
  *   VCAT          0: materialise upsample + concat in the output blocks (default: virtual concat)            (rounding differs)

@@ -19,7 +19,7 @@ TAB_ROWS = ("sqrt_recip", "sqrt_recipm1", "coef1", "coef2", "logvar", "acp", "ac
 STEP_DDPM, STEP_DDIM, STEP_MEAN_ONLY = 0, 1, 2
 CARRY_OUT, CARRY_IN = 1, 2               # s3d_unet_step_film_carry flags (include/sin3dm_hip.h)
 MEAN_START_X, MEAN_EPSILON = 0, 1
-ERR_INVALID, ERR_MISSING, ERR_HIP, ERR_UNSUPPORTED = -1, -2, -3, -4
+ERR_INVALID, ERR_MISSING, ERR_HIP, ERR_UNSUPPORTED, ERR_INTERNAL = -1, -2, -3, -4, -5
 MAX_LANES = 16
 MESHSDF_MAX_PAIRS = 1 << 27           # S3D_MESHSDF_MAX_PAIRS (include/sin3dm_hip.h): 1.5 GiB of (cell, triangle) pairs
 

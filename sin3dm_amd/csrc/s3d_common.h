@@ -70,6 +70,9 @@ struct DevBuf {                       // owning device allocation (grow-only)
 struct Arena {                        // bump allocator over one DevBuf; two-pass (measure, then run)
     DevBuf buf;
     size_t off = 0, high = 0;
+    // `high` is shared by everything that measures on this arena (lanes, the training tier); `peak` is one pass's own: the caller
+    // zeroes it before a run pass and holds it to that pass's measurement afterwards (workspace_overrun)
+    size_t peak = 0;
     bool measuring = false;
     void reset() { off = 0; }
     template <class T>
@@ -78,12 +81,16 @@ struct Arena {                        // bump allocator over one DevBuf; two-pas
         size_t o = off;
         off += bytes;
         if (off > high) high = off;
+        if (off > peak) peak = off;
         if (measuring) return reinterpret_cast<T*>(uintptr_t(256));   // never dereferenced
         return reinterpret_cast<T*>(static_cast<char*>(buf.p) + o);
     }
 };
 
 int upload(DevBuf& dst, const void* host, size_t bytes);
+// A run pass that bumped past what its measuring pass found: some input of the allocations is missing from the key that lets
+// the measuring walk be skipped.  The slack of the reservation may have absorbed it; the error is raised either way.
+int workspace_overrun(const char* what, size_t run_peak, size_t measured);
 
 // ------------------------------------------------------------------ process-wide options (s3d_set_option / environment)
 // Every kernel-form switch of the library.  Value = what s3d_set_option last stored; before that the environment variable
@@ -97,6 +104,10 @@ constexpr const char* kOptNames[] = {"WINO", "WINO24W", "VCAT", "WGRAD_WINO", "R
 static_assert(sizeof kOptNames / sizeof kOptNames[0] == OPT_COUNT, "one name per option");
 constexpr int kOptUnset = -1;
 int opt(Opt o);                       // kOptUnset when neither set nor in the environment
+// Counts the successful s3d_set_option calls of the process.  What a handle derives from the options and keeps between launches
+// (the measured workspace, a carried in_conv) is stamped with it and redone when it moves.  The lazy first read of an environment
+// variable changes no effective value and does not count.
+long long opt_generation();
 inline bool opt_on(Opt o) { return opt(o) != 0; }      // switches that default to on: anything but an explicit 0
 // compute units of the CURRENT device (cached per device index: one process may drive several)
 int device_cus();

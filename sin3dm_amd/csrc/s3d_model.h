@@ -93,20 +93,21 @@ struct s3d_unet {
 
     Arena arena;
     DevBuf film_ws;                                      // s3d_unet_film: the two hidden vectors of the timestep MLP
-    long long inf_key[4] = {-1, -1, -1, -1};             // (B,H,W,D) of the last measured inference forward ...
+    long long inf_key[5] = {-1, -1, -1, -1, -1};         // (B,H,W,D, option generation) of the last measured inference forward ...
     size_t inf_high = 0;                                 // ... and the workspace it needs
     // Workspace lanes (s3d_unet_select_lane): independent sample chains on different HIP streams through ONE handle — the weights
     // are shared, everything a forward writes (the activation arena, the timestep MLP's scratch, the measured-shape key) exists
     // once per lane.  The fields above ARE the selected lane; the others are parked here.
     // The next step's in_conv, left in this lane's workspace by the previous fused step's output head (s3d_unet_step_film_carry):
     // valid for exactly one following step on the tensor `sample` of that shape; any other forward, a workspace reallocation or
-    // a parameter change drops it.
-    struct CarryState { bool valid = false; const float* sample = nullptr; long long key[4] = {-1, -1, -1, -1}; };
+    // a parameter change drops it; so does an s3d_set_option call (key[4], the option generation: whether and where the tensor and
+    // its partials exist depends on the forms selected).
+    struct CarryState { bool valid = false; const float* sample = nullptr; long long key[5] = {-1, -1, -1, -1, -1}; };
     CarryState carry;
     struct LaneState {
         DevBuf arena_buf, film_ws;
         size_t off = 0, high = 0, inf_high = 0;
-        long long inf_key[4] = {-1, -1, -1, -1};
+        long long inf_key[5] = {-1, -1, -1, -1, -1};
         CarryState carry;
     };
     std::vector<std::unique_ptr<LaneState>> lanes;       // lanes[k] holds lane k's state while another lane is selected
@@ -116,7 +117,7 @@ struct s3d_unet {
         std::swap(arena.off, L.off); std::swap(arena.high, L.high);
         std::swap(film_ws.p, L.film_ws.p); std::swap(film_ws.cap, L.film_ws.cap);
         std::swap(inf_high, L.inf_high);
-        for (int k = 0; k < 4; ++k) std::swap(inf_key[k], L.inf_key[k]);
+        for (int k = 0; k < 5; ++k) std::swap(inf_key[k], L.inf_key[k]);
         std::swap(carry, L.carry);
     }
     void drop_carries() { carry.valid = false; for (auto& L : lanes) if (L) L->carry.valid = false; }
@@ -127,7 +128,7 @@ struct s3d_unet {
     int64_t flat_numel = 0;
     std::vector<size_t> flat_off;
     std::map<std::string, size_t> flat_index;            // parameter name -> offset in the flat vector
-    long long train_key[4] = {-1, -1, -1, -1};           // (B,H,W,D) of the last measured forward+backward
+    long long train_key[5] = {-1, -1, -1, -1, -1};       // (B,H,W,D, option generation) of the last measured forward+backward
     size_t train_high = 0;
     DevBuf tbuf, descs_dev;
     std::vector<PackDesc> descs;

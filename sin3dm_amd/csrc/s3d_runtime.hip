@@ -26,6 +26,12 @@ void DevBuf::release() {
     p = nullptr;
     cap = 0;
 }
+int workspace_overrun(const char* what, size_t run_peak, size_t measured) {
+    if (run_peak <= measured) return 0;
+    set_error("%s: the run pass took %zu bytes of workspace, the measuring pass found %zu (internal error: the workspace key "
+              "misses something the allocations depend on)", what, run_peak, measured);
+    return S3D_ERR_INTERNAL;
+}
 int upload(DevBuf& dst, const void* host, size_t bytes) {
     S3D_TRY(dst.reserve(bytes));
     S3D_HIP(hipMemcpy(dst.p, host, bytes, hipMemcpyHostToDevice));
@@ -35,6 +41,8 @@ int upload(DevBuf& dst, const void* host, size_t bytes) {
 // ---- options
 static std::atomic<int> g_opt[OPT_COUNT];
 static std::atomic<int> g_opt_state[OPT_COUNT];          // 0: not looked at yet, 1: resolved (environment or unset), 2: set through the ABI
+static std::atomic<long long> g_opt_gen{0};
+long long opt_generation() { return g_opt_gen.load(std::memory_order_acquire); }
 // The value a string selects, or kOptUnset when the option does not take it: CONV_IMPL "naive" -> 1, any other string -> 0;
 // WINO 0 / 4 / 24; every other option 0 / 1.
 static int parse_opt(int o, const char* v) {
@@ -90,6 +98,7 @@ int s3d_set_option(const char* name, const char* value) {
     S3D_CHECK(!given || v != kOptUnset, S3D_ERR_INVALID, "set_option: %s takes %s, not '%s'", kOptNames[o], opt_values(o), value);
     g_opt[o].store(v, std::memory_order_relaxed);
     g_opt_state[o].store(2, std::memory_order_release);
+    g_opt_gen.fetch_add(1, std::memory_order_acq_rel);
     return 0;
 }
 

@@ -473,9 +473,9 @@ int s3d_unet_forward_train(s3d_unet* m, const float* x, const float* t, int B, i
     S3D_CHECK(B >= 1 && H >= 1 && W >= 1 && D >= 1, S3D_ERR_INVALID, "forward_train: B,H,W,D must be >= 1");
     hipStream_t st = static_cast<hipStream_t>(stream);
     // measure forward + backward together: the workspace must not move between the two.  Pure host work that depends
-    // only on the shapes: skipped when they repeat (every step of a training run).
-    const long long key[4] = {B, H, W, D};
-    const bool same = m->train_key[0] == key[0] && m->train_key[1] == key[1] && m->train_key[2] == key[2] && m->train_key[3] == key[3];
+    // on the shapes and on the options (GNB_FUSED, WGRAD_WINO, BWD_SIDE, ...): skipped when both repeat (every step of a training run).
+    const long long key[5] = {B, H, W, D, opt_generation()};
+    const bool same = memcmp(m->train_key, key, sizeof key) == 0;
     int rc = 0;
     if (!same || m->train_high > m->arena.buf.cap) {
         m->arena.measuring = true;
@@ -486,7 +486,7 @@ int s3d_unet_forward_train(s3d_unet* m, const float* x, const float* t, int B, i
         m->tape.valid = false;
         if (rc) return rc;
         m->train_high = m->arena.high;
-        for (int k = 0; k < 4; ++k) m->train_key[k] = key[k];
+        memcpy(m->train_key, key, sizeof key);
         if (m->arena.high > m->arena.buf.cap) {
             S3D_HIP(hipStreamSynchronize(st));
             S3D_TRY(m->arena.buf.reserve(m->arena.high + (m->arena.high >> 3)));
@@ -498,8 +498,10 @@ int s3d_unet_forward_train(s3d_unet* m, const float* x, const float* t, int B, i
     ++m->fwd_count;
     if (m->prof_now) ++m->prof_forwards;
     m->prof_train = m->prof_now;
+    m->arena.peak = 0;
     rc = run_forward(m, x, t, B, H, W, D, out, st, &m->tape);
     m->prof_now = false;
+    if (!rc) rc = workspace_overrun("forward_train", m->arena.peak, m->train_high);
     if (rc) m->tape.valid = false;
     return rc;
 }
@@ -519,7 +521,8 @@ int s3d_unet_backward_marked(s3d_unet* m, const float* d_out, float* grads, void
     m->prof_now = m->prof_train;
     const int rc_b = run_backward(m, d_out, grads, static_cast<hipStream_t>(stream), marks, n_events);
     m->prof_now = m->prof_train = false;
-    return rc_b;
+    if (rc_b) return rc_b;
+    return workspace_overrun("backward", m->arena.peak, m->train_high);       // (the peak continues the forward's)
 }
 
 int s3d_train_q_sample(const float* x0, int64_t x0_batch_stride, const float* noise, const float* sqrt_ac, const float* sqrt_1mac,

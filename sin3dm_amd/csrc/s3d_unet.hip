@@ -159,6 +159,9 @@ int pack_all(s3d_unet* m) {
     const s3d_unet_cfg& c = m->cfg;
     const int mc = c.model_channels, ted = 4 * mc;
     const bool ssn = c.use_scale_shift_norm != 0, roll = c.is_rollout != 0;
+    // new weights: a carried in_conv was formed with the old ones.  Here and not at a caller: s3d_unet_film packs too, and in a
+    // sampling step it runs BEFORE the forward, which then finds the image packed and would take the stale tensor
+    m->drop_carries();
     m->stage.clear();
     m->te0_w = push(m->stage, H(m, "time_embed.0.weight").data(), size_t(ted) * mc);
     m->te0_b = push(m->stage, H(m, "time_embed.0.bias").data(), ted);
@@ -260,10 +263,11 @@ int run_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W
     Tri h = f.alloc_tri(c.channel_mult[0] * mc, g0);
     // The previous fused step's output head may have left THIS step's in_conv here (s3d_unet_step_film_carry; the workspace is
     // bump-allocated in a fixed order, so the tensor and its GroupNorm partials sit where this forward allocates them): taken when
-    // the caller vouches for the input (S3D_CARRY_IN) and it is that step's sample, same shape, same lane, nothing in between.
-    const long long ckey[4] = {B, H, W, D};
+    // the caller vouches for the input (S3D_CARRY_IN) and it is that step's sample, same shape, same lane, same options, nothing in
+    // between.
+    const long long ckey[5] = {B, H, W, D, opt_generation()};
     const bool take = !meas && !tape && (carry_flags & S3D_CARRY_IN) && m->carry.valid && m->carry.sample == x &&
-                      m->carry.key[0] == ckey[0] && m->carry.key[1] == ckey[1] && m->carry.key[2] == ckey[2] && m->carry.key[3] == ckey[3];
+                      memcmp(m->carry.key, ckey, sizeof ckey) == 0;
     if (!meas) m->carry.valid = false;                             // consumed, or void: one step only
     Tri h0 = h;
     GnPartials part0{nullptr, 0, {0, 0, 0}, 0};
@@ -381,7 +385,7 @@ int run_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W
         }
         S3D_TRY(launch_out_head(h, B, stats, aa, m->dev(m->out_w), m->dev(m->out_b), c.out_channels, H, W, D, out, st, fuse, head_adds ? &h.part : nullptr,
                                 give ? &cy : nullptr));
-        if (give) { m->carry.valid = true; m->carry.sample = fuse->sample; for (int k = 0; k < 4; ++k) m->carry.key[k] = ckey[k]; }
+        if (give) { m->carry.valid = true; m->carry.sample = fuse->sample; memcpy(m->carry.key, ckey, sizeof ckey); }
     }
     return 0;
 }
@@ -510,13 +514,14 @@ int s3d_unet_step_film_carry(s3d_unet* m, const float* film, int film_stride, in
 static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, void* stream,
                         const float* ext_film, int ext_film_stride, const s3d_sampler_args* fuse, int carry_flags) {
     S3D_CHECK(B >= 1 && H >= 1 && W >= 1 && D >= 1, S3D_ERR_INVALID, "unet_forward: B,H,W,D must be >= 1");
-    if (!m->packed) { m->drop_carries(); S3D_TRY(pack_all(m)); }      // (new weights: a carried in_conv was formed with the old ones)
+    if (!m->packed) S3D_TRY(pack_all(m));                             // (drops a carried in_conv: it was formed with the old weights)
     m->tape.valid = false;                    // the workspace is shared with the training tape
     hipStream_t st = static_cast<hipStream_t>(stream);
     // pass 1: measure the workspace; grow it if needed (synchronising only when it really grows).  The walk is pure host
-    // work and depends only on the shapes: skipped when they repeat (every step of a sampling loop).
-    const long long key[4] = {B, H, W, D | (fuse && !out ? 1LL << 40 : 0)};      // (a fused step without a caller buffer may need one from the workspace)
-    const bool same = m->inf_key[0] == key[0] && m->inf_key[1] == key[1] && m->inf_key[2] == key[2] && m->inf_key[3] == key[3];
+    // work and depends on the shapes and on the options (VCAT, GN_FUSED, RANK1_SLICES, ... decide what is allocated): skipped
+    // when both repeat (every step of a sampling loop).
+    const long long key[5] = {B, H, W, D | (fuse && !out ? 1LL << 40 : 0), opt_generation()};      // (a fused step without a caller buffer may need one from the workspace)
+    const bool same = memcmp(m->inf_key, key, sizeof key) == 0;
     int rc = 0;
     if (!same || m->inf_high > m->arena.buf.cap) {
         m->arena.measuring = true;
@@ -525,7 +530,7 @@ static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int 
         m->arena.measuring = false;
         if (rc) return rc;
         m->inf_high = m->arena.high;
-        for (int k = 0; k < 4; ++k) m->inf_key[k] = key[k];
+        memcpy(m->inf_key, key, sizeof key);
         if (m->arena.high > m->arena.buf.cap) {
             S3D_HIP(hipStreamSynchronize(st));
             S3D_TRY(m->arena.buf.reserve(m->arena.high + (m->arena.high >> 3)));
@@ -535,9 +540,11 @@ static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int 
     m->prof_now = m->prof_every > 0 && (m->fwd_count % m->prof_every) == 0;
     ++m->fwd_count;
     if (m->prof_now) ++m->prof_forwards;
+    m->arena.peak = 0;
     rc = run_forward(m, x, t, B, H, W, D, out, st, nullptr, ext_film, ext_film_stride, fuse, carry_flags);
     m->prof_now = false;
-    return rc;
+    if (rc) return rc;
+    return workspace_overrun("unet_forward", m->arena.peak, m->inf_high);
 }
 
 extern "C" {
