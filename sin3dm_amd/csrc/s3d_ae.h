@@ -29,10 +29,8 @@ int launch_mr_from_partials3(double* const part[3], int nchunks, int C, const si
 int launch_inorm_silu3(float* const x[3], double* const part[3], const float* const gamma[3], const float* const beta[3], float* const y[3],
                        const size_t hw[3], int C, float eps, float* mr, hipStream_t st);
 int launch_colsum3(const float* const x[3], const size_t rows[3], int C, float* ws, float* const out[3], float* const out2[3], hipStream_t st);   // ws: 3 * colsum_ws_floats(C)
-// InstanceNorm2d(affine, eps) + SiLU of one NHWC plane (s3d_decoder.hip); part: kInNormChunks*C*2 doubles
+// pixel chunks of the InstanceNorm partial sums (s3d_decoder.hip); part: kInNormChunks*C*2 doubles per plane
 constexpr int kInNormChunks = 64;
-int launch_inorm_silu(const float* x, double* part, const float* gamma, const float* beta, float* y, int hw, int C, float eps,
-                      hipStream_t st);
 
 struct PointSet { const float* pts; long long N, Np; float aabb[6]; };   // Np = N rounded up to the GEMM row tile
 int launch_gather(const PointSet& ps, const float* const feat[2][3], const int ph[3], const int pw[3], int C, int nnets,

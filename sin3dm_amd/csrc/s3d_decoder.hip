@@ -6,8 +6,8 @@
 //      MFMA convolution of s3d_conv.hip (the reference recomputes it for every 16 384-point chunk,
 //      src/encoding/model.py:327-330; the result does not depend on the points).
 //  (2) decode: one fused kernel per 128 points — bilinear border-clamped gather of the three feature planes
-//      (F.grid_sample semantics, networks.py:182-190) straight into MFMA operand registers, then both
-//      DecoderMLPSkipConcat chains (blocks.py:65-91) on the fp32 matrix cores without the activations ever
+//      (F.grid_sample semantics, networks.py:182-190) straight into MFMA operand registers, then every
+//      head's DecoderMLPSkipConcat chain (blocks.py:65-91) on the fp32 matrix cores without the activations ever
 //      leaving the register file:
 //        * the GEMM is evaluated transposed, D[hidden unit][point] = W · Xᵀ, so a layer's accumulator (lane =
 //          point, registers = 16 hidden rows of a 32-row tile) IS the next layer's B operand: row order
@@ -16,15 +16,14 @@
 //        * weights stream through LDS in [rows][32 k] slabs shared by the block's 4 waves (each wave = 32 points),
 //          register-prefetched one slab ahead, one barrier per slab.
 //      Bound: fp32 MFMA (1.18 MFLOP per point, 16 B written per point).
-// The other networks (s3d_decoder_create_variant: geometry only, AutoEncoderGroupPBR, 8 texture channels) share the handle, the
-// registry, the packing and stage (1) below; their point stage is k_decode_heads (s3d_decoder_heads.hip), which keeps this
-// file's device code — and with it k_decode's code object — as it was.  The shared device pieces are in s3d_decoder_mlp.h.
+// Every network runs the same point kernel (s3d_decoder_create_variant: geometry only, AutoEncoderGroupPBR, up to 8 texture
+// channels): the chains are organised as feature groups that each carry a list of heads (DecodeArgs), and the skip net with
+// texture is the table {geo: [sdf]}, {tex: [tex_channels, sigmoid]}.
 #include <algorithm>
 #include <cmath>
 #include <memory>
 
 #include "s3d_ae.h"
-#include "s3d_decoder_mlp.h"
 
 namespace s3d {
 
@@ -40,16 +39,22 @@ __global__ void k_slice_pad(const float* __restrict__ in, float* __restrict__ ou
     const long long pix = i >> 5;
     out[i] = c < cin ? in[size_t(c0 + c) * hw + pix] : 0.f;
 }
+// channels [0, up) of an NHWC [h][w][C] plane -> NCHW [up][h][w]  (s3d_decoder_plane_features)
+__global__ void k_plane_to_nchw(const float* __restrict__ in, float* __restrict__ out, long long hw, int C, int up) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= hw * up) return;
+    const long long pix = i % hw;
+    const int c = int(i / hw);
+    out[i] = in[pix * C + c];
+}
 
-// InstanceNorm2d(C, eps=1e-6, affine) + SiLU over one NHWC plane [hw][C]  (src/encoding/blocks.py:219-221, 94-96)
-constexpr int kInChunks = 64;
-__global__ void k_chan_partials(const float* __restrict__ x, double* __restrict__ part, int hw, int C) {
-    // grid (kInChunks), block: C/4 quads x pl pixel lanes; part[chunk][C][2]
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    double* sm = reinterpret_cast<double*>(smem_raw);
+// InstanceNorm2d(C, eps=1e-6, affine) + SiLU over one NHWC plane [hw][C]  (src/encoding/blocks.py:219-221, 94-96), in two
+// launches: per-chunk partial sums in double (kInNormChunks chunks of pixels), then statistics + apply.
+// block: C/4 quads x pl pixel lanes, chunk = blockIdx.x; part[chunk][C][2] = {sum, sum of squares}; sm: pl*C*2 doubles of LDS
+__device__ __forceinline__ void chan_partials(const float* __restrict__ x, double* __restrict__ part, int hw, int C, double* sm) {
     const int cq = C / 4, pl = blockDim.x / cq;
     const int q = threadIdx.x % cq, l = threadIdx.x / cq;
-    const int per = (hw + kInChunks - 1) / kInChunks;
+    const int per = (hw + kInNormChunks - 1) / kInNormChunks;
     const int p0 = blockIdx.x * per, p1 = min(hw, p0 + per);
     double s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
     for (int pix = p0 + l; pix < p1; pix += pl) {
@@ -65,92 +70,80 @@ __global__ void k_chan_partials(const float* __restrict__ x, double* __restrict_
         part[(size_t(blockIdx.x) * C + c) * 2] = S; part[(size_t(blockIdx.x) * C + c) * 2 + 1] = SS;
     }
 }
-__global__ void k_inorm_silu(const float* __restrict__ x, const double* __restrict__ part, const float* __restrict__ gamma,
-                             const float* __restrict__ beta, float* __restrict__ y, int hw, int C, float eps) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    float* A = reinterpret_cast<float*>(smem_raw); float* Bc = A + C;
+// per-channel scale = gamma * rstd and shift = beta - scale * mean from the chunk partials, in double
+__device__ __forceinline__ void scale_shift_from_partials(const double* __restrict__ part, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, float* A, float* Bc, int hw, int C, float eps) {
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         double S = 0, SS = 0;
-        for (int k = 0; k < kInChunks; ++k) { S += part[(size_t(k) * C + c) * 2]; SS += part[(size_t(k) * C + c) * 2 + 1]; }
+        for (int k = 0; k < kInNormChunks; ++k) { S += part[(size_t(k) * C + c) * 2]; SS += part[(size_t(k) * C + c) * 2 + 1]; }
         const double m = S / hw;
         double var = SS / hw - m * m; if (var < 0) var = 0;
         const float scale = float(1.0 / sqrt(var + double(eps))) * gamma[c];
         A[c] = scale; Bc[c] = beta[c] - scale * float(m);
     }
-    __syncthreads();
+}
+// xn = x * A + Bc per channel and y = SiLU(xn) over the blocks of grid dimension x; xn is stored only when KEEP
+template <bool KEEP>
+__device__ __forceinline__ void inorm_apply(const float* __restrict__ x, const float* A, const float* Bc, float* __restrict__ xn,
+                                            float* __restrict__ y, int hw, int C) {
     const int cq = C / 4;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (long long)hw * cq; i += (long long)gridDim.x * blockDim.x) {
         const int q = int(i % cq);
         const float4 v = reinterpret_cast<const float4*>(x)[i];
         const float4 a = reinterpret_cast<const float4*>(A)[q], b = reinterpret_cast<const float4*>(Bc)[q];
-        float4 o;
-        o.x = fmaf(v.x, a.x, b.x); o.y = fmaf(v.y, a.y, b.y); o.z = fmaf(v.z, a.z, b.z); o.w = fmaf(v.w, a.w, b.w);
-        o.x = o.x / (1.f + expf(-o.x)); o.y = o.y / (1.f + expf(-o.y)); o.z = o.z / (1.f + expf(-o.z)); o.w = o.w / (1.f + expf(-o.w));
+        float4 n, o;
+        n.x = fmaf(v.x, a.x, b.x); n.y = fmaf(v.y, a.y, b.y); n.z = fmaf(v.z, a.z, b.z); n.w = fmaf(v.w, a.w, b.w);
+        o.x = n.x / (1.f + expf(-n.x)); o.y = n.y / (1.f + expf(-n.y)); o.z = n.z / (1.f + expf(-n.z)); o.w = n.w / (1.f + expf(-n.w));
+        if (KEEP) reinterpret_cast<float4*>(xn)[i] = n;
         reinterpret_cast<float4*>(y)[i] = o;
     }
 }
+template <bool KEEP>
+__device__ __forceinline__ void inorm_silu(const float* __restrict__ x, const double* __restrict__ part, const float* __restrict__ gamma,
+                                           const float* __restrict__ beta, float* __restrict__ xn, float* __restrict__ y, int hw, int C,
+                                           float eps, float* A) {
+    scale_shift_from_partials(part, gamma, beta, A, A + C, hw, C, eps);
+    __syncthreads();
+    inorm_apply<KEEP>(x, A, A + C, xn, y, hw, C);
+}
 
-int launch_inorm_silu(const float* x, double* part, const float* gamma, const float* beta, float* y, int hw, int C, float eps,
-                      hipStream_t st) {
-    static_assert(kInNormChunks == kInChunks, "chunk count");
-    const int cq = C / 4, pl = std::max(1, 256 / cq);
-    hipLaunchKernelGGL(k_chan_partials, dim3(kInChunks), dim3(cq * pl), size_t(pl) * C * 2 * sizeof(double), st, x, part, hw, C);
-    hipLaunchKernelGGL(k_inorm_silu, dim3(std::min(1024, (hw * cq + 255) / 256)), dim3(256), size_t(2) * C * sizeof(float), st, x, part,
-                       gamma, beta, y, hw, C, eps);
-    S3D_HIP(hipGetLastError());
-    return 0;
+__global__ void k_chan_partials(const float* __restrict__ x, double* __restrict__ part, int hw, int C) {      // grid (kInNormChunks)
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    chan_partials(x, part, hw, C, reinterpret_cast<double*>(smem_raw));
+}
+__global__ void k_inorm_silu(const float* __restrict__ x, const double* __restrict__ part, const float* __restrict__ gamma,
+                             const float* __restrict__ beta, float* __restrict__ y, int hw, int C, float eps) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    inorm_silu<false>(x, part, gamma, beta, nullptr, y, hw, C, eps, reinterpret_cast<float*>(smem_raw));
+}
+// The PBR texture branch's second block normalises its INPUT (blocks.py:238-239) and adds that normalised input back as the
+// residual: k_inorm_silu with both results kept, xn = IN(x) and y = SiLU(xn).
+__global__ void k_inorm_keep(const float* __restrict__ x, const double* __restrict__ part, const float* __restrict__ gamma,
+                             const float* __restrict__ beta, float* __restrict__ xn, float* __restrict__ y, int hw, int C, float eps) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    inorm_silu<true>(x, part, gamma, beta, xn, y, hw, C, eps, reinterpret_cast<float*>(smem_raw));
 }
 
 // The auto-encoder training tier's form (round 5): three planes per launch (blockIdx.y), the statistics finished by their own
 // small launch between the two (launch_mr_from_partials3, s3d_ae_kernels.hip — every block of the apply pass used to walk the 64
-// chunk records of its channels itself, 10 of its 18 us)
+// chunk records of its channels itself, 10 of its 18 us); scale and shift are formed in float from those {mean, rstd}
 struct InNorm3Args { const float* x[3]; float* y[3]; double* part[3]; const float* gamma[3]; const float* beta[3]; const float* mr; int hw[3]; int C; };
 __global__ void k_chan_partials3(InNorm3Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    double* sm = reinterpret_cast<double*>(smem_raw);
-    const int p = blockIdx.y, C = a.C, hw = a.hw[p];
-    const float* x = a.x[p];
-    double* part = a.part[p];
-    const int cq = C / 4, pl = blockDim.x / cq;
-    const int q = threadIdx.x % cq, l = threadIdx.x / cq;
-    const int per = (hw + kInChunks - 1) / kInChunks;
-    const int p0 = blockIdx.x * per, p1 = min(hw, p0 + per);
-    double s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
-    for (int pix = p0 + l; pix < p1; pix += pl) {
-        const float4 v = reinterpret_cast<const float4*>(x)[size_t(pix) * cq + q];
-        s[0] += v.x; ss[0] += double(v.x) * v.x; s[1] += v.y; ss[1] += double(v.y) * v.y;
-        s[2] += v.z; ss[2] += double(v.z) * v.z; s[3] += v.w; ss[3] += double(v.w) * v.w;
-    }
-    for (int k = 0; k < 4; ++k) { sm[(size_t(l) * C + 4 * q + k) * 2] = s[k]; sm[(size_t(l) * C + 4 * q + k) * 2 + 1] = ss[k]; }
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        double S = 0, SS = 0;
-        for (int ll = 0; ll < pl; ++ll) { S += sm[(size_t(ll) * C + c) * 2]; SS += sm[(size_t(ll) * C + c) * 2 + 1]; }
-        part[(size_t(blockIdx.x) * C + c) * 2] = S; part[(size_t(blockIdx.x) * C + c) * 2 + 1] = SS;
-    }
+    const int p = blockIdx.y;
+    chan_partials(a.x[p], a.part[p], a.hw[p], a.C, reinterpret_cast<double*>(smem_raw));
 }
 __global__ void k_inorm_silu3(InNorm3Args a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const int p = blockIdx.y, C = a.C, hw = a.hw[p];
+    const int p = blockIdx.y, C = a.C;
     float* A = reinterpret_cast<float*>(smem_raw); float* Bc = A + C;
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         const float m = a.mr[(size_t(p) * C + c) * 2], scale = a.mr[(size_t(p) * C + c) * 2 + 1] * a.gamma[p][c];
         A[c] = scale; Bc[c] = a.beta[p][c] - scale * m;
     }
     __syncthreads();
-    const int cq = C / 4;
-    const float* x = a.x[p]; float* y = a.y[p];
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (long long)hw * cq; i += (long long)gridDim.x * blockDim.x) {
-        const int q = int(i % cq);
-        const float4 v = reinterpret_cast<const float4*>(x)[i];
-        const float4 s = reinterpret_cast<const float4*>(A)[q], b = reinterpret_cast<const float4*>(Bc)[q];
-        float4 o;
-        o.x = fmaf(v.x, s.x, b.x); o.y = fmaf(v.y, s.y, b.y); o.z = fmaf(v.z, s.z, b.z); o.w = fmaf(v.w, s.w, b.w);
-        o.x = o.x / (1.f + expf(-o.x)); o.y = o.y / (1.f + expf(-o.y)); o.z = o.z / (1.f + expf(-o.z)); o.w = o.w / (1.f + expf(-o.w));
-        reinterpret_cast<float4*>(y)[i] = o;
-    }
+    inorm_apply<false>(a.x[p], A, Bc, nullptr, a.y[p], a.hw[p], C);
 }
-int launch_mr_from_partials3(double* const part[3], int nchunks, int C, const size_t hw[3], float eps, float* mr, hipStream_t st);
 int launch_inorm_silu3(float* const x[3], double* const part[3], const float* const gamma[3], const float* const beta[3], float* const y[3],
                        const size_t hw[3], int C, float eps, float* mr, hipStream_t st) {
     InNorm3Args a; a.C = C; a.mr = mr;
@@ -160,26 +153,136 @@ int launch_inorm_silu3(float* const x[3], double* const part[3], const float* co
         mx = std::max(mx, a.hw[p]);
     }
     const int cq = C / 4, pl = std::max(1, 256 / cq);
-    hipLaunchKernelGGL(k_chan_partials3, dim3(kInChunks, 3), dim3(cq * pl), size_t(pl) * C * 2 * sizeof(double), st, a);
+    hipLaunchKernelGGL(k_chan_partials3, dim3(kInNormChunks, 3), dim3(cq * pl), size_t(pl) * C * 2 * sizeof(double), st, a);
     S3D_HIP(hipGetLastError());
-    S3D_TRY(launch_mr_from_partials3(part, kInChunks, C, hw, eps, mr, st));
+    S3D_TRY(launch_mr_from_partials3(part, kInNormChunks, C, hw, eps, mr, st));
     hipLaunchKernelGGL(k_inorm_silu3, dim3(std::min(1024, (mx * cq + 255) / 256), 3), dim3(256), size_t(2) * C * sizeof(float), st, a);
     S3D_HIP(hipGetLastError());
     return 0;
 }
 
 // ------------------------------------------------------------------ fused gather + MLP
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef const f32x4 __attribute__((address_space(1)))* gf4p;
+__device__ __forceinline__ gf4p g4(const float* p) { return (gf4p)(uintptr_t)p; }
+
+struct MlpW {                 // device pointers of one DecoderMLPSkipConcat, padded to multiples of 32
+    const float* w[6]; const float* b[6];
+};
+
+constexpr int kSlabLd = 36;   // padded slab row (floats)
+
+// One layer on the matrix cores: hout[m] (MT tiles of 32 rows) = W[MT*32][K] x [in0 | in1] + bias, optional ReLU.
+// in0 has KT0 tiles of 32 rows, in1 KT1.  All four waves run it in lockstep (they share the LDS weight slabs).
+template <int KT0, int KT1, int MT>
+__device__ __forceinline__ void mlp_layer(const float* __restrict__ Wg, const float* __restrict__ bias,
+                                          const f32x16* in0, const f32x16* in1, f32x16* hout, float* lds, bool relu) {
+    constexpr int KT = KT0 + KT1, K = KT * 32, M = MT * 32;
+    constexpr int ITEMS = M * 8, NI = (ITEMS + 255) / 256;
+    const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, half = lane >> 5;
+    // accumulators start at the bias of their rows
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) hout[m][r] = bias[m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
+    // slab staging descriptors: item -> (row, float4 q)
+    gf4p src[NI]; int dst[NI];
+#pragma unroll
+    for (int it = 0; it < NI; ++it) {
+        const int idx = min(it * 256 + tid, ITEMS - 1);
+        const int row = idx >> 3, q = idx & 7;
+        src[it] = g4(Wg + size_t(row) * K + q * 4);
+        dst[it] = row * kSlabLd + q * 4;
+    }
+    f32x4 rg[NI];
+    __syncthreads();                                   // previous layer's last slab reads are done
+#pragma unroll
+    for (int it = 0; it < NI; ++it) rg[it] = src[it][0];
+#pragma unroll
+    for (int it = 0; it < NI; ++it) *reinterpret_cast<f32x4*>(lds + dst[it]) = rg[it];
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < KT; ++t) {
+        constexpr int kLastT = KT - 1;
+        const int nt = t == kLastT ? t : t + 1;        // last slab re-fetches itself (harmless)
+#pragma unroll
+        for (int it = 0; it < NI; ++it) rg[it] = src[it][nt * 8];
+        __builtin_amdgcn_sched_barrier(0);
+        const float* slab = lds + (t & 1) * (M * kSlabLd);
+        const f32x16& hin = t < KT0 ? in0[t < KT0 ? t : 0] : in1[t >= KT0 ? t - KT0 : 0];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            f32x4 a4[MT];
+#pragma unroll
+            for (int m = 0; m < MT; ++m) a4[m] = *reinterpret_cast<const f32x4*>(slab + (m * 32 + j) * kSlabLd + q * 8 + half * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int m = 0; m < MT; ++m)
+                    hout[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[m][e], hin[q * 4 + e], hout[m], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        float* nxt = lds + ((t + 1) & 1) * (M * kSlabLd);
+#pragma unroll
+        for (int it = 0; it < NI; ++it) *reinterpret_cast<f32x4*>(nxt + dst[it]) = rg[it];
+        __syncthreads();
+    }
+    if (relu) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) hout[m][r] = fmaxf(hout[m][r], 0.f);
+    }
+}
+
+// bilinear, padding_mode='border', align_corners=False sample of plane `fm` [h][w][UPT*32] at (u -> rows, v -> cols),
+// accumulated into the lane's operand registers: x[t][4q+e] is channel 32t + 8q + 4*half + e.
+template <int UPT>
+__device__ __forceinline__ void gather_plane(const float* __restrict__ fm, int h, int w, float u, float v, int half,
+                                             f32x16* x) {
+    constexpr int C = UPT * 32;
+    float fy = ((u + 1.f) * float(h) - 1.f) * 0.5f, fx = ((v + 1.f) * float(w) - 1.f) * 0.5f;
+    fy = fminf(fmaxf(fy, 0.f), float(h - 1)); fx = fminf(fmaxf(fx, 0.f), float(w - 1));
+    const int y0 = int(floorf(fy)), x0 = int(floorf(fx));
+    const float ty = fy - float(y0), tx = fx - float(x0);
+    const float w00 = (1.f - ty) * (1.f - tx), w01 = (1.f - ty) * tx, w10 = ty * (1.f - tx), w11 = ty * tx;
+    const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
+    const float* p00 = fm + (size_t(y0) * w + x0) * C + half * 4;
+    const float* p01 = fm + (size_t(y0) * w + x1) * C + half * 4;
+    const float* p10 = fm + (size_t(y1) * w + x0) * C + half * 4;
+    const float* p11 = fm + (size_t(y1) * w + x1) * C + half * 4;
+#pragma unroll
+    for (int t = 0; t < UPT; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int c = t * 32 + q * 8;
+            const f32x4 a = g4(p00 + c)[0], b = g4(p01 + c)[0], cc = g4(p10 + c)[0], d = g4(p11 + c)[0];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[t][q * 4 + e] += w00 * a[e] + w01 * b[e] + w10 * cc[e] + w11 * d[e];
+        }
+}
+
+// Feature groups that each carry a list of heads: a group's three planes are gathered ONCE into operand registers and every head
+// of the group (its own DecoderMLPSkipConcat) runs on them, one after the other, so two heads' hidden tiles are never live
+// together and nothing goes to memory between layers or heads.
+//   skip net with texture  {geo: [sdf]}, {tex: [tex_channels 1..8, sigmoid]}
+//   geometry only          {geo: [sdf]}
+//   AutoEncoderGroupPBR    {geo: [sdf]}, {tex: [rgb 3, mr 2, normal 3]}      (no sigmoid, networks.py:311-315)
+constexpr int kMaxHeads = 4;
 struct DecodeArgs {
     const float* pts;         // [N][3] or null -> cell-centred grid points generated on the fly
     long long N;
-    float amin[3];            // aabb min
-    int gdim[3]; float gsize[3];   // decode_grid: resolutions and aabb size
-    const float* feat[2][3];  // [geo|tex][plane] NHWC [h][w][UP]
+    float amin[3];
+    int gdim[3]; float gsize[3];
+    const float* feat[2][3];  // [group][plane] NHWC [h][w][UP]
     int ph[3], pw[3];
-    MlpW mlp[2];
-    int nout[2];              // 1, tex_channels
-    int clamp_color;
-    float* out;               // [N][1 + tex_channels]
+    int ngroups;
+    int hbeg[3];              // heads [hbeg[g], hbeg[g+1]) belong to group g
+    MlpW mlp[kMaxHeads];
+    int col0[kMaxHeads], ncol[kMaxHeads], sigm[kMaxHeads];   // output columns [col0, col0+ncol) (ncol <= 8), sigmoid flag
+    int clamp_color;          // clamp columns >= 1 to [0,1] (never the sdf)
+    float* out;               // [N][out_stride]
     int out_stride;
 };
 
@@ -193,8 +296,8 @@ __global__ __launch_bounds__(256, 1) void k_decode(DecodeArgs a) {
     if (live) {
         if (a.pts) { p[0] = a.pts[pt * 3]; p[1] = a.pts[pt * 3 + 1]; p[2] = a.pts[pt * 3 + 2]; }
         else {        // sample_grid_points_aabb (src/encoding/utils3d.py:13-25): cell centres, 'ij' order
-            const long long iz = pt % a.gdim[2], iy = (pt / a.gdim[2]) % a.gdim[1], ix = pt / ((long long)a.gdim[2] * a.gdim[1]);
             // linspace(0.5, r-0.5, r) / r * size + min, one rounding per torch op (no fma contraction)
+            const long long iz = pt % a.gdim[2], iy = (pt / a.gdim[2]) % a.gdim[1], ix = pt / ((long long)a.gdim[2] * a.gdim[1]);
             p[0] = __fadd_rn(__fmul_rn(__fdiv_rn(0.5f + float(ix), float(a.gdim[0])), a.gsize[0]), a.amin[0]);
             p[1] = __fadd_rn(__fmul_rn(__fdiv_rn(0.5f + float(iy), float(a.gdim[1])), a.gsize[1]), a.amin[1]);
             p[2] = __fadd_rn(__fmul_rn(__fdiv_rn(0.5f + float(iz), float(a.gdim[2])), a.gsize[2]), a.amin[2]);
@@ -205,35 +308,41 @@ __global__ __launch_bounds__(256, 1) void k_decode(DecodeArgs a) {
     for (int k = 0; k < 3; ++k)                                                    // x = 2 * (x - min) / (max - min) - 1  (:196)
         qn[k] = __fsub_rn(__fdiv_rn(2.f * __fsub_rn(p[k], a.amin[k]), a.gsize[k]), 1.f);
     const float uu[3] = {qn[0], qn[0], qn[1]}, vv[3] = {qn[1], qn[2], qn[2]};      // coords_list [[0,1],[0,2],[1,2]] (:201)
+    // rows are out_stride floats (36 B for the PBR net): no 16-byte alignment to rely on, so the lane writes its columns one by one
+    float* orow = a.out + (live ? pt : 0) * a.out_stride;
 
-    float result[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int net = 0; net < 2; ++net) {
-        f32x16 x[UPT], hA[HIDT], hB[HIDT], ho[1];
+    for (int g = 0; g < 2; ++g) {
+        if (g < a.ngroups) {
+            f32x16 x[UPT];
 #pragma unroll
-        for (int t = 0; t < UPT; ++t)
+            for (int t = 0; t < UPT; ++t)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) x[t][r] = 0.f;
+                for (int r = 0; r < 16; ++r) x[t][r] = 0.f;
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) gather_plane<UPT>(a.feat[net][pl], a.ph[pl], a.pw[pl], uu[pl], vv[pl], half, x);
-        const MlpW& M = a.mlp[net];
-        mlp_layer<UPT, 0, HIDT>(M.w[0], M.b[0], x, x, hA, lds, true);          // first_layers
-        mlp_layer<HIDT, 0, HIDT>(M.w[1], M.b[1], hA, hA, hB, lds, true);
-        mlp_layer<HIDT, 0, HIDT>(M.w[2], M.b[2], hB, hB, hA, lds, true);
-        mlp_layer<UPT, HIDT, HIDT>(M.w[3], M.b[3], x, hA, hB, lds, true);        // second_layers on cat([x, h])
-        mlp_layer<HIDT, 0, HIDT>(M.w[4], M.b[4], hB, hB, hA, lds, true);
-        mlp_layer<HIDT, 0, 1>(M.w[5], M.b[5], hA, hA, ho, lds, false);
-        // rows 0..3 of the output tile live in registers 0..3 of lane half 0
-        if (net == 0) result[0] = ho[0][0];
-        else { result[1] = ho[0][0]; result[2] = ho[0][1]; result[3] = ho[0][2]; }
-    }
-    if (live && half == 0) {
-        float* o = a.out + pt * a.out_stride;
-        o[0] = result[0];
-        for (int k = 0; k < a.nout[1]; ++k) {
-            float c = 1.f / (1.f + expf(-result[1 + k]));                        // .sigmoid() (:216)
-            if (a.clamp_color) c = fminf(fmaxf(c, 0.f), 1.f);                    // decode_batch clamp (model.py:332)
-            o[1 + k] = c;
+            for (int pl = 0; pl < 3; ++pl) gather_plane<UPT>(a.feat[g][pl], a.ph[pl], a.pw[pl], uu[pl], vv[pl], half, x);
+            for (int hd = a.hbeg[g]; hd < a.hbeg[g + 1]; ++hd) {                 // block-uniform trip count (barriers inside)
+                const MlpW& M = a.mlp[hd];
+                f32x16 hA[HIDT], hB[HIDT], ho[1];
+                mlp_layer<UPT, 0, HIDT>(M.w[0], M.b[0], x, x, hA, lds, true);
+                mlp_layer<HIDT, 0, HIDT>(M.w[1], M.b[1], hA, hA, hB, lds, true);
+                mlp_layer<HIDT, 0, HIDT>(M.w[2], M.b[2], hB, hB, hA, lds, true);
+                mlp_layer<UPT, HIDT, HIDT>(M.w[3], M.b[3], x, hA, hB, lds, true);
+                mlp_layer<HIDT, 0, HIDT>(M.w[4], M.b[4], hB, hB, hA, lds, true);
+                mlp_layer<HIDT, 0, 1>(M.w[5], M.b[5], hA, hA, ho, lds, false);
+                // rows 0..3 of the output tile are registers 0..3 of lane half 0, rows 4..7 those of half 1
+                const int col0 = a.col0[hd], ncol = a.ncol[hd], sg = a.sigm[hd];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int row = e + 4 * half;
+                    if (live && row < ncol) {
+                        float c = ho[0][e];
+                        if (sg) c = 1.f / (1.f + expf(-c));
+                        if (a.clamp_color && col0 + row >= 1) c = fminf(fmaxf(c, 0.f), 1.f);
+                        orow[col0 + row] = c;
+                    }
+                }
+            }
         }
     }
 }
@@ -252,8 +361,8 @@ struct s3d_decoder {
     int up_p = 0, hid_p = 0;
     DevBuf wbuf;
     // plane blocks: [0] geo_convs (5x5), [1] tex_convs (5x5) or tex_convs.0 (3x3, PBR), [2] tex_convs.1 (3x3, PBR, no shortcut)
-    struct Net { ConvW cin, cout_, sc; size_t gamma[3], beta[3]; size_t mw[6], mb[6]; int cin_ch; } net[3];
-    // MLP heads in output-column order; net[0/1].mw / mb mirror heads 0 / 1 for k_decode
+    struct Net { ConvW cin, cout_, sc; size_t gamma[3], beta[3]; int cin_ch; } net[3];
+    // MLP heads in output-column order, group by group
     struct Head { std::string name; int group, nout, sigmoid; size_t mw[6], mb[6]; };
     std::vector<Head> heads;
     int ngroups = 2;
@@ -266,7 +375,6 @@ struct s3d_decoder {
     Arena arena;
     const float* dev(size_t off) const { return static_cast<const float*>(wbuf.p) + off; }
     int out_channels() const { int c = 0; for (const auto& h : heads) c += h.nout; return c; }
-    bool classic() const { return variant == 0 && cfg.tex_channels <= 3; }      // k_decode's case
 };
 
 namespace s3d {
@@ -384,13 +492,10 @@ static int dec_pack(s3d_decoder* d) {
             H.mb[l] = pack_vec(st, d->host.at(ml + ln[l] + ".bias").data(), outs[l], outp[l]);
         }
     }
-    for (int k = 0; k < 2 && k < int(d->heads.size()); ++k)
-        for (int l = 0; l < 6; ++l) { d->net[k].mw[l] = d->heads[k].mw[l]; d->net[k].mb[l] = d->heads[k].mb[l]; }
     S3D_TRY(upload(d->wbuf, st.data(), st.size() * sizeof(float)));
     d->packed = true;
     return 0;
 }
-
 template <int UPT, int HIDT>
 static int launch_decode(const DecodeArgs& a, hipStream_t st) {
     const long long blocks = (a.N + 127) / 128;
@@ -399,17 +504,11 @@ static int launch_decode(const DecodeArgs& a, hipStream_t st) {
     S3D_HIP(hipGetLastError());
     return 0;
 }
-static int no_kernel(const s3d_decoder* d) {
-    set_error("decoder: feat_channel_up=%d / mlp_hidden_channels=%d has no compiled kernel (supported after padding to 32: "
-              "up<=64 with hidden 256, up<=32 with hidden 32 or 64, up 96 with hidden 128)", d->cfg.feat_channel_up,
-              d->cfg.mlp_hidden_channels);
-    return S3D_ERR_UNSUPPORTED;
-}
 
-// variants 1 and 2, and the skip net with more than 3 texture channels
-static int run_decode_heads(s3d_decoder* d, const float* pts, long long N, const float aabb[6], const int* gdim, int clamp,
-                            float* out, hipStream_t st) {
-    HeadsArgs a; memset(&a, 0, sizeof a);
+static int run_decode(s3d_decoder* d, const float* pts, long long N, const float aabb[6], const int* gdim, int clamp,
+                      float* out, hipStream_t st) {
+    S3D_CHECK(d->prepared, S3D_ERR_INVALID, "decoder: call s3d_decoder_prepare_triplane first");
+    DecodeArgs a; memset(&a, 0, sizeof a);
     a.pts = pts; a.N = N; a.clamp_color = clamp; a.out = out; a.out_stride = d->out_channels();
     for (int k = 0; k < 3; ++k) {
         a.amin[k] = aabb[k]; a.gsize[k] = aabb[3 + k] - aabb[k];
@@ -430,33 +529,18 @@ static int run_decode_heads(s3d_decoder* d, const float* pts, long long N, const
         }
     }
     a.hbeg[2] = h;
-    const int rc = launch_decode_heads(a, d->up_p / 32, d->hid_p / 32, st);
-    return rc == S3D_ERR_UNSUPPORTED ? no_kernel(d) : rc;
-}
-
-static int run_decode(s3d_decoder* d, const float* pts, long long N, const float aabb[6], const int* gdim, int clamp,
-                      float* out, hipStream_t st) {
-    S3D_CHECK(d->prepared, S3D_ERR_INVALID, "decoder: call s3d_decoder_prepare_triplane first");
-    if (!d->classic()) return run_decode_heads(d, pts, N, aabb, gdim, clamp, out, st);
-    DecodeArgs a; memset(&a, 0, sizeof a);
-    a.pts = pts; a.N = N; a.clamp_color = clamp; a.out = out; a.out_stride = 1 + d->cfg.tex_channels;
-    for (int k = 0; k < 3; ++k) {
-        a.amin[k] = aabb[k]; a.gsize[k] = aabb[3 + k] - aabb[k];
-        a.gdim[k] = gdim ? gdim[k] : 1; a.ph[k] = d->ph[k]; a.pw[k] = d->pw[k];
-    }
-    for (int n = 0; n < 2; ++n) {
-        for (int p = 0; p < 3; ++p) a.feat[n][p] = d->featp[n][p];
-        for (int l = 0; l < 6; ++l) { a.mlp[n].w[l] = d->dev(d->net[n].mw[l]); a.mlp[n].b[l] = d->dev(d->net[n].mb[l]); }
-    }
-    a.nout[0] = 1; a.nout[1] = d->cfg.tex_channels;
     const int upt = d->up_p / 32, hidt = d->hid_p / 32;
     if (upt == 2 && hidt == 8) return launch_decode<2, 8>(a, st);
     if (upt == 1 && hidt == 1) return launch_decode<1, 1>(a, st);
     if (upt == 1 && hidt == 8) return launch_decode<1, 8>(a, st);
     if (upt == 1 && hidt == 2) return launch_decode<1, 2>(a, st);
     if (upt == 3 && hidt == 4) return launch_decode<3, 4>(a, st);
-    return no_kernel(d);
+    set_error("decoder: feat_channel_up=%d / mlp_hidden_channels=%d has no compiled kernel (supported after padding to 32: "
+              "up<=64 with hidden 256, up<=32 with hidden 32 or 64, up 96 with hidden 128)", d->cfg.feat_channel_up,
+              d->cfg.mlp_hidden_channels);
+    return S3D_ERR_UNSUPPORTED;
 }
+
 
 }  // namespace s3d
 
@@ -549,7 +633,7 @@ int s3d_decoder_prepare_triplane(s3d_decoder* d, const float* xy, const float* x
                 const size_t hw = size_t(g.h[p]) * g.w[p];
                 x.p[p] = ar.alloc<float>(hw * 32); a.p[p] = ar.alloc<float>(hw * upp);
                 y.p[p] = ar.alloc<float>(hw * upp); s.p[p] = ar.alloc<float>(hw * upp);
-                part[p] = ar.alloc<double>(size_t(kInChunks) * upp * 2);
+                part[p] = ar.alloc<double>(size_t(kInNormChunks) * upp * 2);
             }
             if (pass == 0) continue;
             for (int p = 0; p < 3; ++p) {
@@ -571,11 +655,14 @@ int s3d_decoder_prepare_triplane(s3d_decoder* d, const float* xy, const float* x
             auto inorm = [&](const s3d_decoder::Net& B, float* const src[3], float* const keep[3], float* const dst[3]) -> int {
                 for (int p = 0; p < 3; ++p) {
                     const int hw = g.h[p] * g.w[p], cq = upp / 4, pl = std::max(1, 256 / cq);
-                    hipLaunchKernelGGL(k_chan_partials, dim3(kInChunks), dim3(cq * pl), size_t(pl) * upp * 2 * sizeof(double), st, src[p], part[p], hw, upp);
-                    if (keep) S3D_TRY(launch_inorm_keep(src[p], part[p], d->dev(B.gamma[p]), d->dev(B.beta[p]), keep[p], dst[p], hw, upp, 1e-6f, st));
+                    hipLaunchKernelGGL(k_chan_partials, dim3(kInNormChunks), dim3(cq * pl), size_t(pl) * upp * 2 * sizeof(double), st, src[p], part[p], hw, upp);
+                    const dim3 grid(std::min(1024, (hw * cq + 255) / 256));
+                    if (keep)
+                        hipLaunchKernelGGL(k_inorm_keep, grid, dim3(256), size_t(2) * upp * sizeof(float), st, src[p], part[p],
+                                           d->dev(B.gamma[p]), d->dev(B.beta[p]), keep[p], dst[p], hw, upp, 1e-6f);
                     else
-                        hipLaunchKernelGGL(k_inorm_silu, dim3(std::min(1024, (hw * cq + 255) / 256)), dim3(256), size_t(2) * upp * sizeof(float), st,
-                                           src[p], part[p], d->dev(B.gamma[p]), d->dev(B.beta[p]), dst[p], hw, upp, 1e-6f);
+                        hipLaunchKernelGGL(k_inorm_silu, grid, dim3(256), size_t(2) * upp * sizeof(float), st, src[p], part[p],
+                                           d->dev(B.gamma[p]), d->dev(B.beta[p]), dst[p], hw, upp, 1e-6f);
                 }
                 S3D_HIP(hipGetLastError());
                 return 0;
@@ -610,7 +697,10 @@ int s3d_decoder_plane_features(s3d_decoder* d, int group, int plane, float* out,
     S3D_CHECK(src, S3D_ERR_INVALID, "plane_features: this decoder has no feature group %d", group);
     const long long hw = (long long)d->ph[plane] * d->pw[plane];
     const int up = d->cfg.feat_channel_up;
-    return launch_plane_to_nchw(src, out, hw, d->up_p, up, static_cast<hipStream_t>(stream));
+    hipLaunchKernelGGL(k_plane_to_nchw, dim3((unsigned)((hw * up + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), src, out, hw,
+                       d->up_p, up);
+    S3D_HIP(hipGetLastError());
+    return 0;
 }
 
 int s3d_decoder_decode_points(s3d_decoder* d, const float* pts, int64_t N, const float aabb[6], int clamp_color, float* out,

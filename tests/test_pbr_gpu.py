@@ -67,14 +67,14 @@ def test_pbr_decoder_golden(tag):
     # the geo parameters have the names of variant 0's: the identical network
     skip = make_net("skip", up, hid)
     sdf0 = skip.decode(pts, fm, aabb=aabb)[:, 0]
-    errs["sdf_vs_variant0(abs)"] = float((out[:, 0] - sdf0).abs().max())
+    assert torch.equal(out[:, 0], sdf0), "sdf_vs_variant0: one point kernel, one geo network, the same bits"
     # ---- geometry only (variant 1), planes of fdim_geo channels
     gfm = [f[:, :4].contiguous() for f in fm]
     gnet = make_net("geo", up, hid)
     gout = check_clamp_and_empty(gnet, pts, gfm, aabb, 1)
     errs["geo.out"] = relerr(gout.cpu().numpy(), g[f"geo.{tag}.out"])
     errs["geo.out_default_aabb"] = relerr(gnet.decode(pts[:33], gfm).cpu().numpy(), g[f"geo.{tag}.out_default_aabb"])
-    errs["geo.sdf_vs_variant0(abs)"] = float((gout[:, 0] - sdf0).abs().max())
+    assert torch.equal(gout[:, 0], sdf0), "geo.sdf_vs_variant0"
     for p, f in zip(T.PLANES, gnet.plane_features(gfm, "geo")):
         errs[f"geo.geo_{p}"] = relerr(f.cpu().numpy(), g[f"pbr.{tag}.geo_{p}"])
     with pytest.raises(AssertionError):
@@ -124,6 +124,66 @@ def test_pbr_grid(grid_reference, kind):
     print(kind, f"grid vs restatement {e_ref:.2e}, grid mode vs point mode {e_pts:.2e}")
     assert e_ref < TOL_FWD
     assert e_pts < 1e-5, "grid mode and point mode must agree"            # (in-kernel coordinates: one ulp from torch's linspace/div)
+
+
+def head_table_nets(up, hid):
+    """Four nets on one set of weights: A the skip net with 3 texture channels, B the same with 8 (every tensor of equal shape and
+    rows 0..2 of the last texture layer are A's, rows 3..7 arbitrary), C geometry only and D the PBR net with A's geo parameters."""
+    from sin3dm_amd.encoding.networks import AutoEncoderGroupPBR, AutoEncoderGroupSkip
+    sd_a = T.synthetic_state_dict(P.shapes_of("skip", up, hid), 5)
+    sd_b = T.synthetic_state_dict(P.shapes_of("skip8", up, hid), 9)
+    for k, v in sd_a.items():
+        if sd_b[k].shape == v.shape:
+            sd_b[k] = v.clone()
+    last = "tex_decoder.second_layers.4."
+    assert sd_b[last + "weight"].shape == (8, hid) and sd_a[last + "weight"].shape == (3, hid)
+    for leaf in ("weight", "bias"):
+        sd_b[last + leaf][:3] = sd_a[last + leaf]
+    geo = {k: v for k, v in sd_a.items() if k.startswith("geo_")}
+    sd_c = {k: geo[k].clone() for k in P.shapes_of("geo", up, hid)}
+    sd_d = T.synthetic_state_dict(P.shapes_of("pbr", up, hid), 9)
+    sd_d.update({k: v.clone() for k, v in geo.items()})
+    nets = {"A": AutoEncoderGroupSkip(4, 8, up, hid, 4, use_tex=True, tex_channels=3),
+            "B": AutoEncoderGroupSkip(4, 8, up, hid, 4, use_tex=True, tex_channels=8),
+            "C": AutoEncoderGroupSkip(4, 8, up, hid, 4, use_tex=False),
+            "D": AutoEncoderGroupPBR(4, 8, up, hid, 4, use_tex=True, tex_channels=8)}
+    for tag, sd in (("A", sd_a), ("B", sd_b), ("C", sd_c), ("D", sd_d)):
+        missing, unexpected = nets[tag].load_state_dict(sd, strict=False)
+        assert not unexpected and all(k.startswith(("geo_encoder", "tex_encoder", "aabb")) for k in missing)
+        nets[tag].to("cuda:0").eval()
+    return nets
+
+
+# the five compiled (up, hidden) tile pairs and one unpadded width
+@pytest.mark.parametrize("up,hid", [(64, 256), (32, 32), (32, 256), (32, 64), (96, 128), (48, 256)])
+def test_head_columns_do_not_depend_on_the_other_heads(up, hid):
+    """A head's output columns are the same bits whichever other heads or groups its network has: the sdf of the skip net, of the
+    geometry-only net and of the PBR net, and the first three texture channels of the skip net with 3 and with 8 of them."""
+    nets = head_table_nets(up, hid)
+    fm = [cu(f) for f in P.synthetic_planes(6, 5, 4)]
+    planes = {"A": fm, "B": fm, "C": [f[:, :4].contiguous() for f in fm], "D": fm}
+    aabb = torch.tensor(GRID["aabb"])
+    # 130 points: a second block with two live lanes; both lane halves store (B's columns 5..8 come from half 1); some outside
+    g = np.random.Generator(np.random.PCG64(17))
+    half = np.asarray(GRID["aabb"][3:])
+    pts = g.uniform(-1.0, 1.0, size=(130, 3)) * half
+    axis = np.asarray([0, 1, 2, 0, 1, 2])
+    pts[[0, 31, 64, 127, 128, 129], axis] = np.asarray([1.3, -1.2, 1.5, -1.1, 1.25, -1.4]) * half[axis]      # the border clamp acts
+    assert int((np.abs(pts) > half).any(axis=1).sum()) == 6
+    pts = cu(pts)
+    modes = {"decode": lambda n, f: n.decode(pts, f, aabb=aabb),
+             "decode, clamp_color": lambda n, f: n.decode(pts, f, aabb=aabb, clamp_color=True),
+             "decode_grid": lambda n, f: n.decode_grid(f, 9, aabb=aabb)}            # dims (9, 5, 7): three blocks, the last partial
+    for mode, run in modes.items():
+        out = {tag: run(net, planes[tag]) for tag, net in nets.items()}
+        if mode == "decode_grid":
+            assert tuple(out["A"].shape) == (9, 5, 7, 4)
+            out = {tag: o.reshape(315, -1) for tag, o in out.items()}
+        assert [o.shape[1] for o in out.values()] == [4, 9, 1, 9] and bool(torch.isfinite(out["A"]).all())
+        assert float(out["A"][:, 0].std()) > 0 and float(out["A"][:, 1:].std()) > 0
+        assert torch.equal(out["B"][:, :4], out["A"]), mode
+        assert torch.equal(out["C"][:, 0], out["A"][:, 0]), mode
+        assert torch.equal(out["D"][:, 0], out["A"][:, 0]), mode
 
 
 def test_prepare_cache_and_retarget(monkeypatch):

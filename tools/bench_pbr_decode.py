@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""decode_grid of the three decoder variants on one MI355X in one run: variant 0 (skip net, sdf + rgb: k_decode), variant 1
-(geometry only) and variant 2 (AutoEncoderGroupPBR: sdf + rgb + mr + normal), both on k_decode_heads.  Full-width nets (up 64,
+"""decode_grid of the three decoder variants on one MI355X in one run: variant 0 (skip net, sdf + rgb), variant 1 (geometry
+only) and variant 2 (AutoEncoderGroupPBR: sdf + rgb + mr + normal), all on k_decode with their head tables.  Full-width nets (up 64,
 hidden 256), a 128^3 triplane, reso 256 over a cubic aabb = 16.8 M points.  Synthetic weights and features (same arithmetic as
 trained ones).  The plane stage is run once per net before timing (it is cached per triplane); each timed call is one fused
 launch, timed with device events, the three variants interleaved round by round after a warm-up round; medians are reported.
@@ -43,12 +43,12 @@ def chain_flops(out):
 
 GATHER = 2.0 * 3 * 4 * UP
 VARIANTS = {
-    "variant 0  skip net, sdf + rgb (k_decode)": (AutoEncoderGroupSkip(4, 8, UP, HID, 4), T.ae_param_shapes(4, 8, UP, HID, 4), fm12,
-                                                   chain_flops(1) + chain_flops(3) + 2 * GATHER),
-    "variant 1  geometry only (k_decode_heads)": (AutoEncoderGroupSkip(4, 8, UP, HID, 4, use_tex=False), T.geo_only_param_shapes(4, UP, HID, 4), fm4,
-                                                   chain_flops(1) + GATHER),
-    "variant 2  PBR net, 4 heads (k_decode_heads)": (AutoEncoderGroupPBR(4, 8, UP, HID, 4, tex_channels=8), T.pbr_param_shapes(4, 8, UP, HID, 4, 8), fm12,
-                                                      chain_flops(1) + chain_flops(3) + chain_flops(2) + chain_flops(3) + 2 * GATHER),
+    "variant 0  skip net, sdf + rgb, 2 heads": (AutoEncoderGroupSkip(4, 8, UP, HID, 4), T.ae_param_shapes(4, 8, UP, HID, 4), fm12,
+                                                 chain_flops(1) + chain_flops(3) + 2 * GATHER),
+    "variant 1  geometry only, 1 head": (AutoEncoderGroupSkip(4, 8, UP, HID, 4, use_tex=False), T.geo_only_param_shapes(4, UP, HID, 4), fm4,
+                                          chain_flops(1) + GATHER),
+    "variant 2  PBR net, 4 heads": (AutoEncoderGroupPBR(4, 8, UP, HID, 4, tex_channels=8), T.pbr_param_shapes(4, 8, UP, HID, 4, 8), fm12,
+                                     chain_flops(1) + chain_flops(3) + chain_flops(2) + chain_flops(3) + 2 * GATHER),
 }
 nets = {}
 for label, (net, shapes, fm, flops) in VARIANTS.items():
