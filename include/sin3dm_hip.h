@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define S3D_ABI_VERSION 10
+#define S3D_ABI_VERSION 11
 #define S3D_API __attribute__((visibility("default")))
 
 typedef enum {
@@ -436,6 +436,44 @@ S3D_API int s3d_tex_quantize(const float* colors, const int64_t* texel_index, in
 /* out = image where face_id >= 0, elsewhere the per-channel maximum of image over the 3 x 3 neighbourhood inside the atlas
  * (cv2.dilate with a 3 x 3 kernel blended by the mask, model.py:426-428).  out must not alias image. */
 S3D_API int s3d_tex_dilate(const uint8_t* image, const int32_t* face_id, int texreso, int channels, uint8_t* out, void* stream);
+
+/* Quadric-error decimation (Garland-Heckbert edge collapse in parallel rounds of independent collapses, DESIGN.md §15;
+ * isosurface.simplify_mesh_quadric drives the rounds and does the sorting, unique and compaction in between).
+ * A quadric is the upper triangle of a symmetric 4 x 4 matrix as 10 doubles: xx xy xz xw yy yz yw zz zw ww.  Edges are
+ * (edge_u[e] < edge_v[e]).  CSR lists: nbr_off [n_verts + 1] into nbr [n_nbr] (the neighbours of a vertex, ascending),
+ * vf_off [n_verts + 1] into vf_face [3 n_tris] (the faces at a vertex, ascending).  No floating-point atomics. */
+/* quadrics[v] = sum over the faces at v, in the order of vf_face, of area * p p^T, p the unit plane (faces without area skipped) */
+S3D_API int s3d_mesh_qem_quadrics(const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_tris, const int64_t* vf_off,
+                                  const int32_t* vf_face, double* quadrics, void* stream);
+/* Per edge, with Q = Q_u + Q_v = [A b; b^T c]: target = -A^-1 b (double) where |det A| > 1e-6 (trace A / 3)^3 and the solution
+ * lies within 2 edge lengths of the midpoint; else the midpoint, unless u (then v) is cheaper by more than
+ * 1e-10 trace A (1 + |mid|^2).  cost = fp32(max(0, target^T Q target)), target [n_edges][3] rounded to fp32. */
+S3D_API int s3d_mesh_qem_edge_cost(const float* verts, int64_t n_verts, const double* quadrics, const int32_t* edge_u,
+                                   const int32_t* edge_v, int64_t n_edges, float* target, float* cost, void* stream);
+/* frozen[w] = 1 iff w lies on an edge with edge_faces != 2.  flags[e] = 1 (edge_faces[e] == 2) | 2 (no frozen endpoint)
+ * | 4 (link condition: exactly two common neighbours w1, w2, and not both faces u w1 w2 and v w1 w2) | 8 (every face at u or v
+ * that does not hold both keeps, with that vertex at target[e], a non-zero area and cos(old normal, new normal) > 0.2).
+ * An edge may collapse iff flags == 15. */
+S3D_API int s3d_mesh_qem_edge_valid(const float* verts, int64_t n_verts, const int32_t* tris, int64_t n_tris, const int32_t* edge_u,
+                                    const int32_t* edge_v, const int32_t* edge_faces, int64_t n_edges, const int64_t* nbr_off,
+                                    const int32_t* nbr, int64_t n_nbr, const int64_t* vf_off, const int32_t* vf_face, const float* target,
+                                    uint8_t* frozen, int32_t* flags, void* stream);
+/* keys[e] = (bits of cost[e] << 32) | mix(e), mix(i): i *= 0x9E3779B1, i ^= i >> 16, i *= 0x85EBCA6B, i ^= i >> 13 on 32 bits
+ * (a bijection: equal costs are ordered by a scattered, not an ascending, index); m1[w] = min key of the edges with flags == 15 at w (integer atomic minimum,
+ * 2^63 - 1 where there is none); m2[w] = min of m1 over w and its neighbours; selected[e] = flags == 15 and
+ * keys[e] == m2[u] == m2[v].  No two selected edges have equal or adjacent endpoints.  n_edges < 2^32. */
+S3D_API int s3d_mesh_qem_select(const int32_t* edge_u, const int32_t* edge_v, const float* cost, const int32_t* flags, int64_t n_edges,
+                                const int64_t* nbr_off, const int32_t* nbr, int64_t n_nbr, int64_t n_verts, int64_t* keys, int64_t* m1,
+                                int64_t* m2, uint8_t* selected, void* stream);
+/* For every edge e = chosen[k] (pairwise non-adjacent, as selected above): verts[u] = target[e], quadrics[u] += quadrics[v],
+ * attrs[u] = (1 - t) attrs[u] + t attrs[v] with t in [0, 1] the parameter of the target on the segment u v, vmap[v] = u.
+ * attrs [n_verts][n_attr] or null with n_attr = 0. */
+S3D_API int s3d_mesh_qem_apply(const int64_t* chosen, int64_t n_chosen, const int32_t* edge_u, const int32_t* edge_v, int64_t n_edges,
+                               const float* target, float* verts, int64_t n_verts, double* quadrics, float* attrs, int n_attr,
+                               int32_t* vmap, void* stream);
+/* out_tris[f] = vmap[tris[f]]; keep[f] = 1 unless two of its indices are now equal */
+S3D_API int s3d_mesh_qem_remap_faces(const int32_t* tris, int64_t n_tris, const int32_t* vmap, int64_t n_verts, int32_t* out_tris,
+                                     uint8_t* keep, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Mesh to training data: what the reference's data/mesh_sampler.py computes with point_cloud_utils and

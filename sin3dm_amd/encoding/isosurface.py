@@ -2,9 +2,9 @@
 src/encoding/utils3d.py:196-213) and s3d_mesh_components its connected-component filter.  What follows there in
 decode_texmesh (model.py:389-473: open3d decimation, xatlas atlas, nvdiffrast rasterisation, cv2 dilation, PIL / trimesh
 writers) is an own design here (no parity with those libraries claimed): vertex-clustering decimation to a
-face budget (simplify_mesh), an analytic per-face atlas (triangle_atlas), texel positions and texture finishing on the device
-(bake_texture, s3d_tex_*), and OBJ/MTL/PNG and GLB writers that need nothing beyond the standard library.  The vertex-coloured
-OBJ (export_obj) stays the default output."""
+face budget (simplify_mesh) or, on request, quadric-error edge collapse (simplify_mesh_quadric, s3d_mesh_qem_*), an analytic
+per-face atlas (triangle_atlas), texel positions and texture finishing on the device (bake_texture, s3d_tex_*), and OBJ/MTL/PNG
+and GLB writers that need nothing beyond the standard library.  The vertex-coloured OBJ (export_obj) stays the default output."""
 from __future__ import annotations
 
 import ctypes as C
@@ -207,6 +207,130 @@ def simplify_mesh(verts, tris, n_faces, attrs=None):
     info = {"R": lo, "lo": lo, "s": float(s), "origin": origin, "dims": dims, "vmap": vmap, "keys": keys,
             "attrs": amean[used] if amean is not None else None}
     return means[used], out_tris, info
+
+
+# ------------------------------------------------------------------ decimation to a face budget: quadric-error edge collapse
+QEM_TWO_FACES, QEM_NOT_FROZEN, QEM_LINK, QEM_NO_FLIP, QEM_VALID = 1, 2, 4, 8, 15        # the bits of s3d_mesh_qem_edge_valid's flags
+
+
+def _csr(owner_sorted, n):
+    """offsets [n + 1] (int64) of the segments of a sorted owner list"""
+    off = torch.zeros(n + 1, device=owner_sorted.device, dtype=torch.int64)
+    off[1:] = torch.cumsum(torch.bincount(owner_sorted, minlength=n), 0)
+    return off
+
+
+def _vertex_faces(t, nv):
+    """CSR vertex -> face of the faces t [nf,3]: (vf_off [nv + 1] int64, vf_face [3 nf] int32), the faces of a vertex ascending"""
+    nf = t.shape[0]
+    key = torch.sort(t.long().reshape(-1) * nf + torch.arange(nf, device=t.device).repeat_interleave(3))[0]
+    return _csr(key // nf, nv), (key % nf).to(torch.int32).contiguous()
+
+
+def _qem_round(v, t, Q):
+    """What one round knows before it changes anything: the edges (one key lo * nv + hi per face side, sorted, unique with counts),
+    both CSR lists, and per edge the cost, the target, the validity flags, the key and whether the independent set holds it."""
+    lib, dev, nv, nf = _lib.load(), v.device, v.shape[0], t.shape[0]
+    tl = t.long()
+    a, b = tl.reshape(-1), tl[:, [1, 2, 0]].reshape(-1)
+    ekey, ecount = torch.unique_consecutive(torch.sort(torch.minimum(a, b) * nv + torch.maximum(a, b))[0], return_counts=True)
+    ne = ekey.shape[0]
+    lo, hi = ekey // nv, ekey % nv
+    eu, ev, ecount = lo.to(torch.int32).contiguous(), hi.to(torch.int32).contiguous(), ecount.to(torch.int32).contiguous()
+    dkey = torch.sort(torch.cat([ekey, hi * nv + lo]))[0]                  # every edge from both of its ends: (vertex, neighbour) ascending
+    nbr_off, nbr = _csr(dkey // nv, nv), (dkey % nv).to(torch.int32).contiguous()
+    vf_off, vf_face = _vertex_faces(t, nv)
+    target = torch.empty((ne, 3), device=dev, dtype=torch.float32)
+    cost = torch.empty(ne, device=dev, dtype=torch.float32)
+    frozen = torch.empty(nv, device=dev, dtype=torch.uint8)
+    flags = torch.empty(ne, device=dev, dtype=torch.int32)
+    keys = torch.empty(ne, device=dev, dtype=torch.int64)
+    m1 = torch.empty(nv, device=dev, dtype=torch.int64)
+    m2 = torch.empty(nv, device=dev, dtype=torch.int64)
+    selected = torch.empty(ne, device=dev, dtype=torch.uint8)
+    st = _lib.stream_ptr()
+    _lib.check(lib.s3d_mesh_qem_edge_cost(_lib.ptr(v), nv, _lib.ptr(Q), _lib.ptr(eu), _lib.ptr(ev), ne, _lib.ptr(target), _lib.ptr(cost), st))
+    _lib.check(lib.s3d_mesh_qem_edge_valid(_lib.ptr(v), nv, _lib.ptr(t), nf, _lib.ptr(eu), _lib.ptr(ev), _lib.ptr(ecount), ne, _lib.ptr(nbr_off),
+                                           _lib.ptr(nbr), nbr.shape[0], _lib.ptr(vf_off), _lib.ptr(vf_face), _lib.ptr(target), _lib.ptr(frozen),
+                                           _lib.ptr(flags), st))
+    _lib.check(lib.s3d_mesh_qem_select(_lib.ptr(eu), _lib.ptr(ev), _lib.ptr(cost), _lib.ptr(flags), ne, _lib.ptr(nbr_off), _lib.ptr(nbr),
+                                       nbr.shape[0], nv, _lib.ptr(keys), _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(selected), st))
+    return {"eu": eu, "ev": ev, "edge_faces": ecount, "cost": cost, "target": target, "flags": flags, "frozen": frozen.bool(),
+            "keys": keys, "selected": selected.bool(), "nbr_off": nbr_off, "nbr": nbr, "vf_off": vf_off, "vf_face": vf_face}
+
+
+def simplify_mesh_quadric(verts, tris, n_faces, attrs=None, max_rounds=None, return_round=False):
+    """Decimate to at most `n_faces` faces by quadric-error edge collapse (Garland & Heckbert; where the reference calls open3d's
+    simplify_quadric_decimation, utils3d.py mesh_decimation — parity with open3d's output is not claimed), run as parallel rounds
+    of independent collapses on the device (s3d_mesh_qem_*).  Every vertex carries a quadric (the area-weighted
+    planes of its faces, in double); a round computes for every edge the target and its cost, tests the edge (two faces, no
+    endpoint on an edge without two faces, the link condition, no flipped face), picks the valid edges whose (cost, index) key is
+    the smallest among all valid edges around both endpoints and their neighbours — no two of those touch the same face — cut to
+    the cheapest ceil((faces - n_faces) / 2) of them, and collapses these: the lower endpoint moves to the target, takes both
+    quadrics and the attributes interpolated along the edge, the faces that held the edge go.  It stops at faces <= n_faces, or
+    when a round finds nothing to collapse (info["stuck"]); a closed manifold stays one, vertices on boundary or non-manifold edges
+    never move.  The surviving faces keep their order; unreferenced vertices are dropped.  Same input, same bits.
+    Returns (verts, tris, info); info: rounds, per_round [(collapses, faces after)], stuck, vmap (int32: the output vertex every
+    input vertex was merged into), attrs (or None).  max_rounds bounds the rounds; return_round=True adds info["round"], the
+    per-edge state of the LAST round run (_qem_round) as it was before that round's collapses, with "chosen" (the edges collapsed)."""
+    _lib.require_gpu(verts)
+    n_faces = int(n_faces)
+    if n_faces < 0:
+        raise ValueError(f"n_faces {n_faces}: expected a face budget >= 0")
+    nv = verts.shape[0]
+    dev = verts.device
+    lib = _lib.load()
+    info = {"rounds": 0, "per_round": [], "stuck": False, "attrs": attrs, "vmap": torch.arange(nv, device=dev, dtype=torch.int32)}
+    if tris.shape[0] <= n_faces:
+        return verts, tris, info
+    if attrs is not None and attrs.shape[0] != nv:
+        raise ValueError(f"simplify_mesh_quadric: {attrs.shape[0]} attribute rows for {nv} vertices")
+    with torch.cuda.device(dev):
+        v = verts.contiguous().float().clone()
+        t = tris.contiguous().to(torch.int32)
+        at = attrs.contiguous().float().reshape(nv, -1).clone() if attrs is not None else None
+        if t.shape[0] and (int(t.min()) < 0 or int(t.max()) >= nv):
+            raise ValueError(f"simplify_mesh_quadric: face indices outside [0, {nv})")
+        st = _lib.stream_ptr()
+        Q = torch.empty((nv, 10), device=dev, dtype=torch.float64)
+        vf_off, vf_face = _vertex_faces(t, nv)
+        _lib.check(lib.s3d_mesh_qem_quadrics(_lib.ptr(v), nv, _lib.ptr(t), t.shape[0], _lib.ptr(vf_off), _lib.ptr(vf_face), _lib.ptr(Q), st))
+        parent = torch.arange(nv, device=dev, dtype=torch.int32)
+        while t.shape[0] > n_faces and (max_rounds is None or info["rounds"] < max_rounds):
+            rd = _qem_round(v, t, Q)
+            chosen = torch.nonzero(rd["selected"]).squeeze(1)
+            need = (t.shape[0] - n_faces + 1) // 2                      # a collapse takes exactly two faces away
+            if chosen.shape[0] > need:
+                chosen = chosen[torch.sort(rd["keys"][chosen])[1][:need]].contiguous()
+            if return_round:
+                info["round"] = dict(rd, chosen=chosen, verts=v.clone(), tris=t)
+            if chosen.shape[0] == 0:
+                info["stuck"] = True
+                break
+            _lib.check(lib.s3d_mesh_qem_apply(_lib.ptr(chosen), chosen.shape[0], _lib.ptr(rd["eu"]), _lib.ptr(rd["ev"]), rd["eu"].shape[0],
+                                              _lib.ptr(rd["target"]), _lib.ptr(v), nv, _lib.ptr(Q), _lib.ptr(at),
+                                              at.shape[1] if at is not None else 0, _lib.ptr(parent), st))
+            mapped = torch.empty_like(t)
+            keep = torch.empty(t.shape[0], device=dev, dtype=torch.uint8)
+            _lib.check(lib.s3d_mesh_qem_remap_faces(_lib.ptr(t), t.shape[0], _lib.ptr(parent), nv, _lib.ptr(mapped), _lib.ptr(keep), st))
+            t = mapped[keep.bool()].contiguous()
+            info["rounds"] += 1
+            info["per_round"].append((int(chosen.shape[0]), int(t.shape[0])))
+        root = parent.long()
+        while True:                                                    # follow v -> u to the surviving vertex
+            nxt = root[root]
+            if torch.equal(nxt, root):
+                break
+            root = nxt
+        used = torch.zeros(nv, device=dev, dtype=torch.bool)
+        used[t.reshape(-1).long()] = True
+        remap = torch.cumsum(used.to(torch.int32), 0, dtype=torch.int32) - 1
+        out_tris = remap[t.long()].contiguous()
+        # (an input vertex that no face referenced maps to -1: it has no surviving vertex)
+        info["vmap"] = torch.where(used[root], remap[root], torch.full_like(remap, -1))
+        info["attrs"] = at[used].reshape((-1,) + tuple(attrs.shape[1:])) if at is not None else None
+        torch.cuda.current_stream().synchronize()
+    return v[used], out_tris, info
 
 
 # ------------------------------------------------------------------ analytic per-face atlas

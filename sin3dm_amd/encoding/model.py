@@ -161,11 +161,13 @@ class ShapeAutoEncoder:
 
     @torch.no_grad()
     def decode_texmesh(self, save_dir, triplane_feat, reso, n_faces=10000, texture_reso=2048, only_largest_cc=True, save_voxel=True,
-                       mtl_path=None, file_format="obj"):
+                       mtl_path=None, file_format="obj", decimation="cluster"):
         """Reference :362-473 for data_type sdftex: decode_grid -> voxel.npz -> iso-surface -> largest component -> the re-normalisation
         of decode_mesh -> decimation to n_faces (isosurface.simplify_mesh) -> UV atlas at texture_reso and ONE decode_batch call over
         its covered texels, quantised and dilated on the device (isosurface.bake_texture) -> object.obj + object.mtl + object.png, or
         object.glb.  Decimation and atlas are an own design; n_surf_pc and save_highres_mesh are not built.
+        decimation: "cluster" (vertex clustering, isosurface.simplify_mesh) or "quadric" (quadric-error edge collapse,
+        isosurface.simplify_mesh_quadric, the kind of decimation the reference asks open3d for).
         data_type sdf (:392-397): sdfgrid_r{reso}.npz (`sdf_grid`) and the decimated mesh_r{reso}_simple.obj, no atlas, no texture.
         data_type sdfpbr (:459-471): ONE bake of all 8 channels, split into albedo [..., :3], metallic [..., 3], roughness [..., 4]
         and normal [..., 5:] -> object.obj + object.mtl + textures/{albedo,metallic,roughness,normal}.png (export_pbr_obj), or
@@ -176,6 +178,8 @@ class ShapeAutoEncoder:
         from . import isosurface as iso
         if file_format not in ("obj", "glb"):
             raise NotImplementedError(f"file_format {file_format!r}: 'obj' or 'glb'")
+        if decimation not in ("cluster", "quadric"):
+            raise ValueError(f"decimation {decimation!r}: expected 'cluster' or 'quadric'")
         H, W = triplane_feat[0].shape[-2:]
         D = triplane_feat[1].shape[-1]
         aabb = self._resize_aabb((H, W, D))
@@ -194,7 +198,7 @@ class ShapeAutoEncoder:
         box_min = aabb[:3]
         box_size = aabb[3:].max() - aabb[:3].min()
         verts = verts / float(reso) * box_size + box_min
-        verts, tris, info = iso.simplify_mesh(verts, tris, n_faces)
+        verts, tris, info = (iso.simplify_mesh_quadric if decimation == "quadric" else iso.simplify_mesh)(verts, tris, n_faces)
         if self.data_type == "sdf":
             iso.export_obj(os.path.join(save_dir, f"mesh_r{reso}_simple.obj"), verts, tris)
             return {"verts": verts, "tris": tris, "info": info}

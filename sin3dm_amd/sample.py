@@ -12,6 +12,7 @@ object.obj.  The reference's default output, a decimated and textured mesh, is o
     S3D_MESH=textured python -m sin3dm_amd.sample --tag EXP --n_samples N [--n_faces 10000 --texreso 2048 --file_format obj|glb --copy_mtl]
 
 writes object.obj + object.mtl + object.png (or object.glb) by this project's own decimation and atlas.
+S3D_DECIMATE=quadric beside it decimates by quadric-error edge collapse instead of vertex clustering (the default, `cluster`).
 An experiment of --data_type sdfpbr writes object.obj + object.mtl + textures/{albedo,metallic,roughness,normal}.png (or a
 metallic-roughness object.glb) there, one of --data_type sdf writes sdfgrid_r<reso>.npz + mesh_r<reso>_simple.obj; in the default mode
 they write object.obj coloured by the albedo / without colours.  The data type comes from EXP/encoding/args.json.
@@ -43,6 +44,16 @@ def mesh_mode(mode=None):
     name = mode if mode is not None else (os.environ.get("S3D_MESH") or "vertex")
     if name not in ("vertex", "textured"):
         raise ValueError(f"mesh mode {name!r}: expected 'vertex' or 'textured'")
+    return name
+
+
+def decimation_mode(mode=None):
+    """"cluster" (vertex clustering, isosurface.simplify_mesh, the default) or "quadric" (quadric-error edge collapse,
+    isosurface.simplify_mesh_quadric): how the textured export cuts the iso-surface to --n_faces.  mode=None reads the
+    environment variable S3D_DECIMATE."""
+    name = mode if mode is not None else (os.environ.get("S3D_DECIMATE") or "cluster")
+    if name not in ("cluster", "quadric"):
+        raise ValueError(f"decimation {name!r}: expected 'cluster' or 'quadric'")
     return name
 
 
@@ -126,6 +137,8 @@ def decode(args, paths):
     from .utils.triplane_util import load_triplane_data
 
     textured = mesh_mode() == "textured"
+    # only a choice other than the default is passed on: the default call is the one it always was
+    decimate = {"decimation": "quadric"} if decimation_mode() == "quadric" else {}
     ae = ShapeAutoEncoder(encoding_log_dir(args.tag), args, device=dist_util.dev())
     ae.load_ckpt("final")
     for path in paths:
@@ -134,7 +147,7 @@ def decode(args, paths):
             ae.decode_voxel(os.path.dirname(path), fm, args.reso)
         elif textured:
             ae.decode_texmesh(os.path.dirname(path), fm, args.reso, n_faces=args.n_faces, texture_reso=args.texreso,
-                              mtl_path=find_copy_mtl(args), file_format=args.file_format)
+                              mtl_path=find_copy_mtl(args), file_format=args.file_format, **decimate)
         else:
             # iso-surface on the device, vertex-coloured object.obj
             ae.decode_mesh(os.path.dirname(path), fm, args.reso)

@@ -75,13 +75,14 @@ ae.decode_batch = timed("  of which decode_batch over the covered texels", ae.de
 iso.marching_cubes = timed("marching_cubes", sized("iso-surface", iso.marching_cubes))
 iso.largest_component = timed("largest_component", sized("largest component", iso.largest_component))
 iso.simplify_mesh = timed("simplify_mesh", sized("decimated", iso.simplify_mesh))
+iso.simplify_mesh_quadric = timed("simplify_mesh_quadric (decimation=\"quadric\")", sized("decimated (quadric)", iso.simplify_mesh_quadric))
 iso.atlas_texels = timed("  of which corner0 + texel positions", iso.atlas_texels)
 iso.bake_texture = timed("bake_texture", iso.bake_texture)
 iso.export_textured_obj = timed("export_textured_obj (host: OBJ + MTL + PNG)", iso.export_textured_obj)
 iso.export_obj = timed("export_obj (host: vertex-coloured OBJ)", iso.export_obj)
 
 
-ORDER = ["decode_grid", "marching_cubes", "largest_component", "simplify_mesh", "bake_texture", "  of which corner0 + texel positions",
+ORDER = ["decode_grid", "marching_cubes", "largest_component", "simplify_mesh", "simplify_mesh_quadric (decimation=\"quadric\")", "bake_texture", "  of which corner0 + texel positions",
          "  of which decode_batch over the covered texels", "export_textured_obj (host: OBJ + MTL + PNG)",
          "export_obj (host: vertex-coloured OBJ)", "TOTAL (wall clock)"]
 
@@ -90,12 +91,16 @@ def run(which):
     cur.clear()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    if which == "texmesh":
-        out = ae.decode_texmesh(work, fm, args.reso, n_faces=args.n_faces, texture_reso=args.texreso, save_voxel=False)
+    if which in ("texmesh", "texmesh_quadric"):
+        kw = {"decimation": "quadric"} if which == "texmesh_quadric" else {}
+        out = ae.decode_texmesh(work, fm, args.reso, n_faces=args.n_faces, texture_reso=args.texreso, save_voxel=False, **kw)
         if out is None:
             raise SystemExit("the synthetic decoder gave an empty iso-surface: nothing to measure")
         sizes["covered texels"] = int(out["mask"].sum())
-        sizes["R"] = out["info"]["R"]
+        if which == "texmesh":
+            sizes["R"] = out["info"]["R"]
+        else:
+            sizes["rounds"], sizes["stuck"] = out["info"]["rounds"], out["info"]["stuck"]
     else:
         ae.decode_mesh(work, fm, args.reso, save_voxel=False)
     torch.cuda.synchronize()
@@ -106,13 +111,19 @@ def run(which):
 
 print(f"decode_texmesh per stage, one MI355X: reso {args.reso}, n_faces {args.n_faces}, texreso {args.texreso}, feature maps {args.fm}^3, "
       f"synthetic weights; median of {args.repeats} runs after one warm-up [min .. max], ms")
-for which in ("texmesh", "mesh"):
+TITLES = {"texmesh": "decode_texmesh (textured OBJ, save_voxel=False)",
+          "texmesh_quadric": "decode_texmesh(decimation=\"quadric\") (textured OBJ, save_voxel=False)",
+          "mesh": "decode_mesh (vertex-coloured OBJ, save_voxel=False; unchanged by this export)"}
+for which in ("texmesh", "texmesh_quadric", "mesh"):
     run(which)                                      # warm-up: allocations, code objects, first-call packing
     runs = [run(which) for _ in range(args.repeats)]
-    print(f"\n{'decode_texmesh (textured OBJ, save_voxel=False)' if which == 'texmesh' else 'decode_mesh (vertex-coloured OBJ, save_voxel=False; unchanged by this export)'}")
+    print(f"\n{TITLES[which]}")
     for label in sorted(runs[0], key=lambda l: ORDER.index(l) if l in ORDER else len(ORDER)):
         vals = [r[label] for r in runs]
         print(f"  {label:<52s} {statistics.median(vals):9.2f}  [{min(vals):8.2f} .. {max(vals):8.2f}]")
+    if which == "texmesh_quadric":
+        print(f"  mesh: decimated ({sizes['rounds']} rounds, stuck {sizes['stuck']}) {sizes['decimated (quadric)'][0]} / {sizes['decimated (quadric)'][1]}, "
+              f"{sizes['covered texels']} covered texels")
     if which == "texmesh":
         at = iso.triangle_atlas(sizes["decimated"][1], args.texreso)
         print(f"  mesh: iso-surface {sizes['iso-surface'][0]} vertices / {sizes['iso-surface'][1]} faces, largest component "
