@@ -66,12 +66,12 @@ def plane_stage(kind, sd, fm, geo=4):
     return out
 
 
-def _gather(planes, x):
+def _gather(planes, x, padding_mode="border", align_corners=False):
     """sum over the three planes of grid_sample(border, align_corners=False) at coords [[0,1],[0,2],[1,2]]."""
     h = 0
     for fmap, (i, j) in zip(planes, ((0, 1), (0, 2), (1, 2))):
         uv = torch.stack([x[:, j], x[:, i]], dim=-1).view(1, 1, -1, 2)            # grid_sample wants (x = column, y = row)
-        h = h + F.grid_sample(fmap, uv, align_corners=False, padding_mode="border")[0, :, 0, :].t()
+        h = h + F.grid_sample(fmap, uv, align_corners=align_corners, padding_mode=padding_mode)[0, :, 0, :].t()
     return h
 
 
@@ -85,19 +85,21 @@ def _mlp(sd, prefix, x):
     return F.linear(h, sd[f"{prefix}.second_layers.4.weight"], sd[f"{prefix}.second_layers.4.bias"])
 
 
-def decode(kind, sd, pts, fm, aabb, feats=None):
-    """pts [N,3], fm three [1,C,h,w] planes, aabb [6] -> [N, 9 | 1 | 4 | 9] float64 (unclamped)."""
-    pts = torch.as_tensor(pts, dtype=torch.float64)
-    aabb = torch.as_tensor(aabb, dtype=torch.float64)
-    fm = [torch.as_tensor(f, dtype=torch.float64) for f in fm]
+def decode(kind, sd, pts, fm, aabb, feats=None, dtype=torch.float64, **gather):
+    """pts [N,3], fm three [1,C,h,w] planes, aabb [6] -> [N, 9 | 1 | 4 | 9] (unclamped), evaluated in `dtype` throughout (sd
+    must hold that dtype: weights(.., dtype=)).  gather: padding_mode / align_corners other than the network's, for tests that
+    need a wrong sampler."""
+    pts = torch.as_tensor(pts, dtype=dtype)
+    aabb = torch.as_tensor(aabb, dtype=dtype)
+    fm = [torch.as_tensor(f, dtype=dtype) for f in fm]
     feats = feats or plane_stage(kind, sd, fm)
     x = 2 * (pts - aabb[:3]) / (aabb[3:] - aabb[:3]) - 1
-    cols = [_mlp(sd, "geo_decoder", _gather(feats["geo"], x))]
+    cols = [_mlp(sd, "geo_decoder", _gather(feats["geo"], x, **gather))]
     if kind == "pbr":
-        ht = _gather(feats["tex"], x)
+        ht = _gather(feats["tex"], x, **gather)
         cols += [_mlp(sd, "rgb_decoder", ht), _mlp(sd, "mr_decoder", ht), _mlp(sd, "normal_decoder", ht)]
     elif kind != "geo":
-        cols.append(torch.sigmoid(_mlp(sd, "tex_decoder", _gather(feats["tex"], x))))
+        cols.append(torch.sigmoid(_mlp(sd, "tex_decoder", _gather(feats["tex"], x, **gather))))
     return torch.cat(cols, dim=1)
 
 
