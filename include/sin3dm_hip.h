@@ -69,6 +69,12 @@ S3D_API int s3d_abi_version(void);
  * s3d_get_option: the current value, -1 when unset. */
 S3D_API int s3d_set_option(const char* name, const char* value);
 S3D_API int s3d_get_option(const char* name, int* value);
+/* Riders: in the inference forward's virtual-concat path the GroupNorm launches that a neighbouring default-form 1x1 convolution
+ * neither feeds nor needs (k_gn_partials_up, the k_gn_finalize behind the pooling, k_gn_finalize_cat) run in that convolution's
+ * first blocks.  on = 0: every stage in a launch of its own; anything else: riders (the default; S3D_RIDERS=0 in the environment,
+ * read once before the first call, starts the process with them off).  The same kernel bodies either way: bit-identical.  Not an
+ * option of the table above: it selects no kernel form and no workspace depends on it; it may be switched between two launches. */
+S3D_API int s3d_set_riders(int on);
 S3D_API const char* s3d_last_error(void);
 /* number of visible HIP devices, or a negative s3d_status: lets the shim fail loudly without torch */
 S3D_API int s3d_device_count(void);

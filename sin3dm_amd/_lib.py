@@ -63,6 +63,7 @@ SIGNATURES = {
     "s3d_device_count": (C.c_int, []),
     "s3d_set_option": (C.c_int, [C.c_char_p, C.c_char_p]),
     "s3d_get_option": (C.c_int, [C.c_char_p, C.POINTER(C.c_int)]),
+    "s3d_set_riders": (C.c_int, [C.c_int]),
     "s3d_unet_create": (C.c_int, [C.POINTER(UNetCfg), C.POINTER(C.c_void_p)]),
     "s3d_unet_destroy": (None, [C.c_void_p]),
     "s3d_unet_num_params": (C.c_int, [C.c_void_p]),
@@ -268,6 +269,11 @@ def get_option(name):
     v = C.c_int(0)
     check(load().s3d_get_option(str(name).encode(), C.byref(v)))
     return None if v.value == -1 else v.value
+
+
+def set_riders(on):
+    """Riders of the inference forward on (the default) or off (include/sin3dm_hip.h: s3d_set_riders); bit-identical."""
+    check(load().s3d_set_riders(1 if on else 0))
 
 
 def stream_ptr():

@@ -109,6 +109,9 @@ int opt(Opt o);                       // kOptUnset when neither set nor in the e
 // variable changes no effective value and does not count.
 long long opt_generation();
 inline bool opt_on(Opt o) { return opt(o) != 0; }      // switches that default to on: anything but an explicit 0
+// The rider switch (s3d_set_riders; S3D_RIDERS=0 in the environment, read once, before the first call).  Not one of the options
+// above: it selects no kernel form and nothing a handle keeps between launches depends on it, so it moves no generation.
+bool riders_enabled();
 // compute units of the CURRENT device (cached per device index: one process may drive several)
 int device_cus();
 
@@ -185,8 +188,38 @@ struct ConvArgs {
 };
 // CONV_1x3_ROLL: the forward rollout tables — args.cout = the convolution's cout, out [B][pos][4 variants][cout] (k_rank1<true>)
 enum ConvKind { CONV_3x3 = 0, CONV_1x1 = 1, CONV_1x3_VEC = 2, CONV_5x5 = 3, CONV_1x3_ROLL = 4 };
+// A rider: a small launch that needs nothing from a 1x1 convolution and gives it nothing, run by the first n_blocks blocks of
+// that convolution's launch instead of in a slot of its own on the step's chain (s3d_riders.h; blocks of 256 threads).
+struct GnFinArgs {
+    const double* part; float* mr;
+    int maxparts, nparts[3], nsub, subs_per_group;
+    double count[3];      // elements per group = (C/32)*h*w
+};
+struct GnPartUpArgs {
+    const float* u[3];
+    int hi[3], wi[3];
+    int C, cq, pl, sg, nsub, maxparts;
+    double* part;   // [B][3][nsub][maxparts][2]
+};
+struct GnFinCatArgs {
+    const double* pu; const double* ps; float* mr;
+    int maxparts_u, maxparts_s, nparts_u[3], nparts_s[3], nsub_u, nsub_s, subs_per_group;
+    double count[3];
+};
+enum RiderKind { RIDER_NONE = 0, RIDER_GN_PARTIALS_UP, RIDER_GN_FINALIZE, RIDER_GN_FINALIZE_CAT };
+struct ConvRider {
+    int kind;                 // RiderKind
+    int n_blocks;             // gx * 3 planes * B: logical block i of the rider is (x = i % gx, plane = i / gx % 3, sample = i / (3 * gx))
+    int gx;
+    union { GnPartUpArgs up; GnFinArgs fin; GnFinCatArgs cat; };
+};
+constexpr int kRiderLdsBytes = 16384;         // what a rider body may use of its host's LDS (k_gn_partials_up at 256 threads: pl * C * 16)
 // Enqueue all jobs (same B/cin/cout/kind) as ONE launch.  cin must be a multiple of 32.
-int launch_conv(ConvKind kind, ConvArgs& a, hipStream_t st);
+// rider (CONV_1x1 only, and only where conv1x1_takes_rider() said so for this launch): carried by the launch's first blocks
+int launch_conv(ConvKind kind, ConvArgs& a, hipStream_t st, const ConvRider* rider = nullptr);
+// whether the plain 1x1 launch of `cout` output channels over g x B can carry a rider: the default form only (S3D_RIDERS not 0,
+// S3D_CONV1X1_T unset and the launch below the size that takes the transposed epilogue, not S3D_CONV_IMPL=naive)
+bool conv1x1_takes_rider(const Geo& g, int B, int cout);
 // Debug/triangulation path: a plain one-thread-per-output direct convolution (no MFMA, no LDS).
 // Selected with S3D_CONV_IMPL=naive; never the default.
 int launch_conv_naive(ConvKind kind, ConvArgs& a, hipStream_t st);
@@ -255,6 +288,11 @@ inline int gn_subgroup(int C) {   // largest power of two dividing C/32, at most
 }
 int launch_gn_partials(const Tri& x, int B, GnPartials out, hipStream_t st);   // out: maxparts=kGnChunks, nsub=32
 int launch_gn_finalize(const GnPartials& part, const Geo& g, int C, int B, GnStats out, hipStream_t st);
+// The same three launches as riders of a 1x1 convolution (ConvRider): false when the shape does not fit a rider (the caller then
+// launches the kernel itself), same arguments and the same bits otherwise
+bool gn_finalize_rider(const GnPartials& part, const Geo& g, int C, int B, GnStats out, ConvRider& r);
+bool gn_partials_up_rider(const Tri& u, int B, int sg, GnPartials out, ConvRider& r);
+bool gn_finalize_cat_rider(const GnPartials& pu, const GnPartials& ps, const Geo& g, int C, int B, GnStats out, ConvRider& r);
 // GroupNorm statistics of the VIRTUAL tensor [bilinear2x(u) | sk] (TriplaneUpsample2x + concat, unet_triplane.py:106-124,
 // 501-503) without materialising it: launch_gn_partials_up reduces the upsampled half per subgroup of `sg` channels
 // (out: nparts from gn_up_parts, nsub = u.C / sg), the skip half brings the partials its producing convolution left

@@ -19,6 +19,7 @@
 //   * epilogue: + bias (+ per-sample bias) + rank-1 row/column terms + residual, 128-byte runs per pixel.
 #include "s3d_common.h"
 #include "s3d_rank1.h"
+#include "s3d_riders.h"
 
 namespace s3d {
 
@@ -69,8 +70,14 @@ __device__ __forceinline__ int edge_variant(int idx, int n) {
     return n == 1 ? 3 : (idx == 0 ? 1 : (idx == n - 1 ? 2 : 0));
 }
 
-template <class CFG>
-__global__ __launch_bounds__(256) void k_conv_mfma(ConvArgs args) {
+// RIDER (the default 1x1 form only): the launch carries a rider (ConvRider, s3d_riders.h) — blocks [0, n_blocks) run the rider's
+// body in the convolution's LDS and leave, the others are the convolution's blocks 0 .. gridDim.x - n_blocks - 1.  The rider's
+// blocks come first, so the short ones never form the launch's tail.  A shift by n_blocks rotates which XCD a logical range
+// lands on, not what shares one.
+template <bool RIDER> struct RiderArg {};
+template <> struct RiderArg<true> { ConvRider r; };
+template <class CFG, bool RIDER = false>
+__global__ __launch_bounds__(256) void k_conv_mfma(ConvArgs args, RiderArg<RIDER> rider) {
     constexpr int TW = CFG::TW, KH = CFG::KH, KW = CFG::KW, MTW = CFG::MTW, NTW = CFG::NTW;
     constexpr int HW = CFG::HW, TAPS = KH * KW;
     __shared__ __attribute__((aligned(16))) float smem[2 * (CFG::A_ELEMS + CFG::B_ELEMS)];
@@ -80,8 +87,14 @@ __global__ __launch_bounds__(256) void k_conv_mfma(ConvArgs args) {
     // workgroup i runs on XCD i % 8: contiguous logical ranges per XCD keep a tile's column blocks and its halo
     // neighbours in one L2
     int bid = blockIdx.x;
+    int nblocks = gridDim.x;
+    if constexpr (RIDER) {
+        static_assert(sizeof smem >= size_t(kRiderLdsBytes) && KH == 1 && !CFG::TR, "the rider bodies work in the 1x1 convolution's LDS");
+        if (bid < rider.r.n_blocks) { run_rider(rider.r, bid, smem); return; }
+        bid -= rider.r.n_blocks; nblocks -= rider.r.n_blocks;
+    }
     if (args.xcd_swizzle) {
-        const int chunk = int(gridDim.x) >> 3;
+        const int chunk = nblocks >> 3;
         if (bid < (chunk << 3)) bid = (bid & 7) * chunk + (bid >> 3);
     }
     int j = 0;
@@ -778,8 +791,13 @@ int launch_conv_naive(ConvKind kind, ConvArgs& a, hipStream_t st) {
     return 0;
 }
 
+static const char* rider_name(int kind) {
+    return kind == RIDER_GN_PARTIALS_UP ? "k_conv_mfma<1x1> direct MFMA convolution carrying k_gn_partials_up"
+         : kind == RIDER_GN_FINALIZE ? "k_conv_mfma<1x1> direct MFMA convolution carrying k_gn_finalize (plain)"
+                                     : "k_conv_mfma<1x1> direct MFMA convolution carrying k_gn_finalize_cat";
+}
 template <class CFG>
-static int launch_cfg(ConvArgs& a, hipStream_t st) {
+static int launch_cfg(ConvArgs& a, hipStream_t st, const ConvRider* rider = nullptr) {
     int blocks = 0;
     for (int j = 0; j < a.njobs; ++j) {
         ConvJob& J = a.job[j];
@@ -793,7 +811,15 @@ static int launch_cfg(ConvArgs& a, hipStream_t st) {
     if (!blocks) return 0;
     a.xcd_swizzle = 1;                       // XCD-aware block order (was switchable in rounds 1-2: always a win)
     conv_note_kernel(CFG::KH == 3 ? "k_conv_mfma<3x3> direct MFMA convolution" : (CFG::KH == 1 ? (CFG::TR ? "k_conv_mfma<1x1, transposed accumulators> direct MFMA convolution" : "k_conv_mfma<1x1> direct MFMA convolution") : "k_conv_mfma<5x5> direct MFMA convolution"));
-    hipLaunchKernelGGL(k_conv_mfma<CFG>, dim3(blocks), dim3(256), 0, st, a);
+    if constexpr (CFG::KH == 1 && !CFG::TR) {
+        if (rider && rider->n_blocks > 0) {
+            conv_note_kernel(rider_name(rider->kind));
+            hipLaunchKernelGGL((k_conv_mfma<CFG, true>), dim3(blocks + rider->n_blocks), dim3(256), 0, st, a, RiderArg<true>{*rider});
+            S3D_HIP(hipGetLastError());
+            return 0;
+        }
+    }
+    hipLaunchKernelGGL(k_conv_mfma<CFG>, dim3(blocks), dim3(256), 0, st, a, RiderArg<false>());
     S3D_HIP(hipGetLastError());
     return 0;
 }
@@ -814,7 +840,22 @@ double conv_exec_fraction(ConvKind kind, const ConvArgs& a) {
     return 1.0;
 }
 
-int launch_conv(ConvKind kind, ConvArgs& a, hipStream_t st) {
+// the transposed-accumulator epilogue takes a plain 1x1 launch of `blocks` blocks (see launch_conv)
+static bool conv1x1_transposed(int cout, long long blocks) {
+    const int tr_mode = opt(OPT_CONV1X1_T);
+    return tr_mode != 0 && cout % 4 == 0 && (tr_mode == 1 || blocks >= 4 * 768);
+}
+static long long conv1x1_blocks(const Geo& g, int B, int cout) {
+    long long blocks = 0;
+    for (int p = 0; p < 3; ++p) blocks += (long long)((g.w[p] + 7) / 8) * ((g.h[p] + 7) / 8) * ((cout + 63) / 64) * B;
+    return blocks;
+}
+bool conv1x1_takes_rider(const Geo& g, int B, int cout) {
+    return riders_enabled() && !conv_use_naive() && opt(OPT_CONV1X1_T) == kOptUnset && !conv1x1_transposed(cout, conv1x1_blocks(g, B, cout));
+}
+
+int launch_conv(ConvKind kind, ConvArgs& a, hipStream_t st, const ConvRider* rider) {
+    S3D_CHECK(!rider || (kind == CONV_1x1 && !conv_use_naive() && opt(OPT_CONV1X1_T) == kOptUnset), S3D_ERR_INTERNAL, "conv: a rider on a launch that cannot carry one");
     S3D_CHECK(a.njobs >= 1 && a.njobs <= kMaxConvJobs, S3D_ERR_INVALID, "conv: %d jobs", a.njobs);
     S3D_CHECK(a.cin % KC == 0 && a.cin > 0, S3D_ERR_INVALID, "conv: cin=%d must be a positive multiple of %d", a.cin, KC);
     if (conv_use_naive()) return kind == CONV_1x3_ROLL ? launch_rank1(a, st, true) : launch_conv_naive(kind, a, st);   // (the three-tap table form has its own plain kernel)
@@ -841,16 +882,18 @@ int launch_conv(ConvKind kind, ConvArgs& a, hipStream_t st) {
                 // partials, channel quads — of at least four rounds of blocks: batch 8 0.383 -> 0.357 ms/step, the auto-encoder
                 // iteration 6.31 -> 6.26 ms; the one-round launches of the batch-1 step are a latency chain either way
                 // (0.0693 -> 0.0714 ms/step) and keep the 4-byte epilogue.  S3D_CONV1X1_T=0 never / =1 always (tests).
-                const int tr_mode = opt(OPT_CONV1X1_T);
-                bool plain = tr_mode != 0 && a.cout % 4 == 0;
+                bool plain = true;
                 long long blocks = 0;
                 for (int j = 0; j < a.njobs; ++j) {
                     plain = plain && !a.job[j].rrow && !a.job[j].rcol && !a.job[j].gn_part;
                     blocks += (long long)((a.job[j].w + 7) / 8) * ((a.job[j].h + 7) / 8) * ((a.cout + 63) / 64) * a.B;
                 }
-                if (plain && (tr_mode == 1 || blocks >= 4 * 768)) return launch_cfg<ConvCfg<8, 8, 1, 1, 2, 2, 1, 1, 1, 2, true>>(a, st);
+                if (plain && conv1x1_transposed(a.cout, blocks)) {
+                    S3D_CHECK(!rider, S3D_ERR_INTERNAL, "conv: a rider on a launch of the transposed 1x1 form");
+                    return launch_cfg<ConvCfg<8, 8, 1, 1, 2, 2, 1, 1, 1, 2, true>>(a, st);
+                }
             }
-            return launch_cfg<ConvCfg<8, 8, 1, 1, 2, 2, 1, 1, 1, 2>>(a, st);
+            return launch_cfg<ConvCfg<8, 8, 1, 1, 2, 2, 1, 1, 1, 2>>(a, st, rider);
         case CONV_1x3_VEC:
             return launch_rank1(a, st, false);
         case CONV_1x3_ROLL:

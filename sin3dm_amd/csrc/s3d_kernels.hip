@@ -8,6 +8,7 @@
 // bit-repeatable run to run.
 #include "s3d_common.h"
 #include "s3d_rank1.h"
+#include "s3d_riders.h"
 #include "s3d_sampler.h"
 
 namespace s3d {
@@ -73,12 +74,6 @@ __device__ __forceinline__ void gn_chunk_reduce(double* sm, const double s[4], c
             }
         out[size_t(g) * gstride * 2] = S; out[size_t(g) * gstride * 2 + 1] = SS;
     }
-}
-__device__ __forceinline__ void gn_acc(double s[4], double ss[4], const float4& v) {
-    s[0] += v.x; ss[0] += double(v.x) * v.x;
-    s[1] += v.y; ss[1] += double(v.y) * v.y;
-    s[2] += v.z; ss[2] += double(v.z) * v.z;
-    s[3] += v.w; ss[3] += double(v.w) * v.w;
 }
 static void thread_shape(int C, int& cq, int& pl) {
     cq = C / 4;
@@ -268,48 +263,27 @@ int launch_gn_partials(const Tri& x, int B, GnPartials out, hipStream_t st) {
 }
 
 // Stage 2: {mean, rstd} of every (b, plane, group) from the partials, added in part order, in double.
-struct GnFinArgs {
-    const double* part; float* mr;
-    int maxparts, nparts[3], nsub, subs_per_group;
-    double count[3];      // elements per group = (C/32)*h*w
-};
-// fixed-order reduction of one double per thread over a 256-thread block: butterfly inside each wave (the same pairing for
-// every launch), then the four wave sums in wave order: bit-repeatable
-__device__ __forceinline__ double block_sum256(double v, double* sm4) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0) sm4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double r = (sm4[0] + sm4[1]) + (sm4[2] + sm4[3]);
-    __syncthreads();
-    return r;
-}
+// (GnFinArgs and the body: s3d_common.h / s3d_riders.h — a 1x1 convolution can carry this launch)
 __global__ __launch_bounds__(256) void k_gn_finalize(GnFinArgs a) {                   // one block per (group, plane, sample): 96 blocks at batch 1, not 3
     __shared__ double sm4[4];
-    const int g = blockIdx.x, p = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
-    const double* base = a.part + (size_t(b) * 3 + p) * a.maxparts * a.nsub * 2;
-    double S = 0, SS = 0;
-    for (int k = 0; k < a.subs_per_group; ++k) {               // [sub][part]: a group's parts are contiguous
-        const double2* row = reinterpret_cast<const double2*>(base + (size_t(g) * a.subs_per_group + k) * a.maxparts * 2);
-        for (int part = tid; part < a.nparts[p]; part += 256) { const double2 v = row[part]; S += v.x; SS += v.y; }
-    }
-    S = block_sum256(S, sm4);
-    SS = block_sum256(SS, sm4);
-    if (tid == 0) {
-        const double m = S / a.count[p];
-        double var = SS / a.count[p] - m * m;
-        if (var < 0) var = 0;
-        float* o = a.mr + ((size_t(b) * 3 + p) * 32 + g) * 2;
-        o[0] = float(m);
-        o[1] = float(1.0 / sqrt(var + 1e-5));
-    }
+    gn_finalize_block(a, blockIdx.x, blockIdx.y, blockIdx.z, sm4);
+}
+static bool gn_finalize_args(const GnPartials& part, const Geo& g, int C, GnStats out, GnFinArgs& a) {
+    a.part = part.p; a.mr = out.mr; a.maxparts = part.maxparts; a.nsub = part.nsub;
+    if (part.nsub % 32 != 0) return false;
+    a.subs_per_group = part.nsub / 32;
+    for (int p = 0; p < 3; ++p) { a.nparts[p] = part.nparts[p]; a.count[p] = double(C / 32) * g.h[p] * g.w[p]; }
+    return true;
+}
+bool gn_finalize_rider(const GnPartials& part, const Geo& g, int C, int B, GnStats out, ConvRider& r) {
+    memset(&r, 0, sizeof r);
+    if (!B || !gn_finalize_args(part, g, C, out, r.fin)) return false;
+    r.kind = RIDER_GN_FINALIZE; r.gx = 32; r.n_blocks = 32 * 3 * B;
+    return true;
 }
 int launch_gn_finalize(const GnPartials& part, const Geo& g, int C, int B, GnStats out, hipStream_t st) {
     GnFinArgs a;
-    a.part = part.p; a.mr = out.mr; a.maxparts = part.maxparts; a.nsub = part.nsub;
-    S3D_CHECK(part.nsub % 32 == 0, S3D_ERR_INVALID, "gn_finalize: nsub=%d", part.nsub);
-    a.subs_per_group = part.nsub / 32;
-    for (int p = 0; p < 3; ++p) { a.nparts[p] = part.nparts[p]; a.count[p] = double(C / 32) * g.h[p] * g.w[p]; }
+    S3D_CHECK(gn_finalize_args(part, g, C, out, a), S3D_ERR_INVALID, "gn_finalize: nsub=%d", part.nsub);
     if (!B) return 0;
     hipLaunchKernelGGL(k_gn_finalize, dim3(32, 3, B), dim3(256), 0, st, a);
     S3D_HIP(hipGetLastError());
@@ -335,136 +309,65 @@ __device__ __forceinline__ float4 up2x_sample(const float4* __restrict__ src, in
     return o;
 }
 
-// Eight consecutive output rows i0..i0+7 (i0 a multiple of 8) of output column j: the six low-resolution rows they touch
-// are interpolated horizontally once (12 loads instead of 32) and combined with the per-row weights of the exact formula;
-// the values equal up2x_sample's bit for bit (same products, same order).
-struct Up8Rows { int rk[6]; float ly0[8], ly1[8]; };
-__device__ __forceinline__ Up8Rows up8_rows(int i0, int hi) {
-    Up8Rows R;
-    const int base = (i0 >> 1) - 1;
-#pragma unroll
-    for (int k = 0; k < 6; ++k) { const int r = base + k; R.rk[k] = r < 0 ? 0 : (r > hi - 1 ? hi - 1 : r); }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        float fy = 0.5f * (float(i0 + r) + 0.5f) - 0.5f; fy = fy < 0.f ? 0.f : fy;
-        int y0 = int(fy); y0 = y0 > hi - 1 ? hi - 1 : y0;
-        R.ly1[r] = fy - float(y0); R.ly0[r] = 1.f - R.ly1[r];
-    }
-    return R;
-}
-__device__ __forceinline__ void up8_column(const float4* __restrict__ src, int wi, int cuq, const Up8Rows& R, int j, float4 out[8]) {
-    float fx = 0.5f * (float(j) + 0.5f) - 0.5f; fx = fx < 0.f ? 0.f : fx;
-    int x0 = int(fx); x0 = x0 > wi - 1 ? wi - 1 : x0;
-    const int x1 = x0 + (x0 < wi - 1 ? 1 : 0);
-    const float lx1 = fx - float(x0), lx0 = 1.f - lx1;
-    float4 hl[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        const float4 a = src[(size_t(R.rk[k]) * wi + x0) * cuq], b = src[(size_t(R.rk[k]) * wi + x1) * cuq];
-        hl[k].x = lx0 * a.x + lx1 * b.x; hl[k].y = lx0 * a.y + lx1 * b.y; hl[k].z = lx0 * a.z + lx1 * b.z; hl[k].w = lx0 * a.w + lx1 * b.w;
-    }
-    // output row r uses low-resolution rows (base + ka, base + ka + 1): ka = (r + 1) >> 1
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const float4 p = hl[(r + 1) >> 1], q = hl[((r + 1) >> 1) + 1];
-        out[r].x = R.ly0[r] * p.x + R.ly1[r] * q.x; out[r].y = R.ly0[r] * p.y + R.ly1[r] * q.y;
-        out[r].z = R.ly0[r] * p.z + R.ly1[r] * q.z; out[r].w = R.ly0[r] * p.w + R.ly1[r] * q.w;
-    }
-}
+// (up8_rows / up8_column, eight output rows of one column from six low-resolution ones: s3d_riders.h)
 
 // GroupNorm partials of bilinear2x(u) per subgroup of sg channels; one part per 8x8 tile of the OUTPUT.
-struct GnPartUpArgs {
-    const float* u[3];
-    int hi[3], wi[3];
-    int C, cq, pl, sg, nsub, maxparts;
-    double* part;   // [B][3][nsub][maxparts][2]
-};
 __global__ void k_gn_partials_up(GnPartUpArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    double* sm = reinterpret_cast<double*>(smem_raw);        // [pl][C][2]
-    const int p = blockIdx.y, b = blockIdx.z;
-    const int hi = a.hi[p], wi = a.wi[p], h = 2 * hi, w = 2 * wi;
-    const int ntc = (w + kActCols - 1) / kActCols, ntr = (h + kActRows - 1) / kActRows;
-    if (int(blockIdx.x) >= ntc * ntr) return;
-    const int tr = blockIdx.x / ntc, tc = blockIdx.x % ntc;
-    const int i0 = tr * kActRows, j0 = tc * kActCols, i1 = min(h, i0 + kActRows), j1 = min(w, j0 + kActCols);
-    const int q = threadIdx.x % a.cq, l = threadIdx.x / a.cq;
-    double s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
-    const float4* src = reinterpret_cast<const float4*>(a.u[p] + size_t(b) * hi * wi * a.C) + q;
-    const Up8Rows R = up8_rows(i0, hi);
-    for (int j = j0 + l; j < j1; j += a.pl) {
-        float4 v[8];
-        up8_column(src, wi, a.cq, R, j, v);
-#pragma unroll
-        for (int r = 0; r < 8; ++r) if (i0 + r < i1) gn_acc(s, ss, v[r]);
-    }
-    for (int k = 0; k < 4; ++k) {
-        sm[(size_t(l) * a.C + 4 * q + k) * 2 + 0] = s[k];
-        sm[(size_t(l) * a.C + 4 * q + k) * 2 + 1] = ss[k];
-    }
-    __syncthreads();
-    for (int sub = threadIdx.x; sub < a.nsub; sub += blockDim.x) {
-        double S = 0, SS = 0;
-        for (int ll = 0; ll < a.pl; ++ll)
-            for (int c = sub * a.sg; c < (sub + 1) * a.sg; ++c) { S += sm[(size_t(ll) * a.C + c) * 2]; SS += sm[(size_t(ll) * a.C + c) * 2 + 1]; }
-        double* o = a.part + (((size_t(b) * 3 + p) * a.nsub + sub) * a.maxparts + blockIdx.x) * 2;
-        o[0] = S; o[1] = SS;
-    }
+    gn_partials_up_block(a, blockIdx.x, blockIdx.y, blockIdx.z, reinterpret_cast<double*>(smem_raw));        // [pl][C][2]
 }
 void gn_up_parts(const Geo& out_g, int nparts[3]) {
     for (int p = 0; p < 3; ++p) nparts[p] = cdiv(out_g.h[p], kActRows) * cdiv(out_g.w[p], kActCols);
 }
-int launch_gn_partials_up(const Tri& u, int B, int sg, GnPartials out, hipStream_t st) {
-    GnPartUpArgs a;
-    int maxtiles = 0;
+static bool gn_partials_up_args(const Tri& u, int sg, GnPartials out, GnPartUpArgs& a, int& maxtiles) {
+    maxtiles = 0;
     for (int p = 0; p < 3; ++p) {
         a.u[p] = u.p[p]; a.hi[p] = u.g.h[p]; a.wi[p] = u.g.w[p];
         maxtiles = std::max(maxtiles, cdiv(2 * u.g.h[p], kActRows) * cdiv(2 * u.g.w[p], kActCols));
     }
     a.C = u.C; thread_shape(u.C, a.cq, a.pl); a.sg = sg; a.nsub = u.C / sg; a.part = out.p; a.maxparts = out.maxparts;
-    S3D_CHECK(u.C % sg == 0 && a.cq <= 1024 && out.nsub == a.nsub && out.maxparts >= maxtiles, S3D_ERR_INVALID, "gn_partials_up: layout");
+    return u.C % sg == 0 && a.cq <= 1024 && out.nsub == a.nsub && out.maxparts >= maxtiles;
+}
+int launch_gn_partials_up(const Tri& u, int B, int sg, GnPartials out, hipStream_t st) {
+    GnPartUpArgs a;
+    int maxtiles = 0;
+    S3D_CHECK(gn_partials_up_args(u, sg, out, a, maxtiles), S3D_ERR_INVALID, "gn_partials_up: layout");
     if (!maxtiles || !B) return 0;
     hipLaunchKernelGGL(k_gn_partials_up, dim3(maxtiles, 3, B), dim3(a.cq * a.pl), size_t(a.pl) * a.C * 2 * sizeof(double), st, a);
     S3D_HIP(hipGetLastError());
     return 0;
 }
+// as a rider its block has the host's 256 threads: only where that is the kernel's own block size (same per-thread mapping)
+bool gn_partials_up_rider(const Tri& u, int B, int sg, GnPartials out, ConvRider& r) {
+    memset(&r, 0, sizeof r);
+    int maxtiles = 0;
+    if (!gn_partials_up_args(u, sg, out, r.up, maxtiles) || !maxtiles || !B) return false;
+    if (r.up.cq * r.up.pl != 256 || size_t(r.up.pl) * r.up.C * 2 * sizeof(double) > size_t(kRiderLdsBytes)) return false;
+    r.kind = RIDER_GN_PARTIALS_UP; r.gx = maxtiles; r.n_blocks = maxtiles * 3 * B;
+    return true;
+}
 // {mean, rstd} per (b, plane, group) of the concat [up | skip]: the group's subgroups come first from the up partials,
 // then from the skip partials; parts added in index order, in double.
-struct GnFinCatArgs {
-    const double* pu; const double* ps; float* mr;
-    int maxparts_u, maxparts_s, nparts_u[3], nparts_s[3], nsub_u, nsub_s, subs_per_group;
-    double count[3];
-};
 __global__ __launch_bounds__(256) void k_gn_finalize_cat(GnFinCatArgs a) {
     __shared__ double sm4[4];
-    const int g = blockIdx.x, p = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
-    double S = 0, SS = 0;
-    for (int k = 0; k < a.subs_per_group; ++k) {
-        const int sub = g * a.subs_per_group + k;
-        const bool up = sub < a.nsub_u;
-        const double2* row = reinterpret_cast<const double2*>(
-            up ? a.pu + (((size_t(b) * 3 + p) * a.nsub_u + sub) * a.maxparts_u) * 2
-               : a.ps + (((size_t(b) * 3 + p) * a.nsub_s + (sub - a.nsub_u)) * a.maxparts_s) * 2);
-        const int n = up ? a.nparts_u[p] : a.nparts_s[p];
-        for (int part = tid; part < n; part += 256) { const double2 v = row[part]; S += v.x; SS += v.y; }
-    }
-    S = block_sum256(S, sm4);
-    SS = block_sum256(SS, sm4);
-    if (tid == 0) {
-        const double m = S / a.count[p];
-        double var = SS / a.count[p] - m * m;
-        if (var < 0) var = 0;
-        float* o = a.mr + ((size_t(b) * 3 + p) * 32 + g) * 2;
-        o[0] = float(m);
-        o[1] = float(1.0 / sqrt(var + 1e-5));
-    }
+    gn_finalize_cat_block(a, blockIdx.x, blockIdx.y, blockIdx.z, sm4);
+}
+static bool gn_finalize_cat_args(const GnPartials& pu, const GnPartials& ps, const Geo& g, int C, GnStats out, GnFinCatArgs& a) {
+    a.pu = pu.p; a.ps = ps.p; a.mr = out.mr; a.maxparts_u = pu.maxparts; a.maxparts_s = ps.maxparts; a.nsub_u = pu.nsub; a.nsub_s = ps.nsub;
+    if ((pu.nsub + ps.nsub) % 32 != 0) return false;
+    a.subs_per_group = (pu.nsub + ps.nsub) / 32;
+    for (int p = 0; p < 3; ++p) { a.nparts_u[p] = pu.nparts[p]; a.nparts_s[p] = ps.nparts[p]; a.count[p] = double(C / 32) * g.h[p] * g.w[p]; }
+    return true;
+}
+bool gn_finalize_cat_rider(const GnPartials& pu, const GnPartials& ps, const Geo& g, int C, int B, GnStats out, ConvRider& r) {
+    memset(&r, 0, sizeof r);
+    if (!B || !gn_finalize_cat_args(pu, ps, g, C, out, r.cat)) return false;
+    r.kind = RIDER_GN_FINALIZE_CAT; r.gx = 32; r.n_blocks = 32 * 3 * B;
+    return true;
 }
 int launch_gn_finalize_cat(const GnPartials& pu, const GnPartials& ps, const Geo& g, int C, int B, GnStats out, hipStream_t st) {
     GnFinCatArgs a;
-    a.pu = pu.p; a.ps = ps.p; a.mr = out.mr; a.maxparts_u = pu.maxparts; a.maxparts_s = ps.maxparts; a.nsub_u = pu.nsub; a.nsub_s = ps.nsub;
-    S3D_CHECK((pu.nsub + ps.nsub) % 32 == 0, S3D_ERR_INVALID, "gn_finalize_cat: nsub=%d+%d", pu.nsub, ps.nsub);
-    a.subs_per_group = (pu.nsub + ps.nsub) / 32;
-    for (int p = 0; p < 3; ++p) { a.nparts_u[p] = pu.nparts[p]; a.nparts_s[p] = ps.nparts[p]; a.count[p] = double(C / 32) * g.h[p] * g.w[p]; }
+    S3D_CHECK(gn_finalize_cat_args(pu, ps, g, C, out, a), S3D_ERR_INVALID, "gn_finalize_cat: nsub=%d+%d", pu.nsub, ps.nsub);
     if (!B) return 0;
     hipLaunchKernelGGL(k_gn_finalize_cat, dim3(32, 3, B), dim3(256), 0, st, a);
     S3D_HIP(hipGetLastError());

@@ -164,8 +164,8 @@ struct s3d_unet {
         else if (hipEventCreate(&e) != hipSuccess) e = nullptr;
         return e;
     }
-    int timed_conv(int cls, ConvKind kind, ConvArgs& ca, hipStream_t st) {
-        if (!prof_now || !((prof_mask >> cls) & 1)) return launch_conv(kind, ca, st);
+    int timed_conv(int cls, ConvKind kind, ConvArgs& ca, hipStream_t st, const ConvRider* rider = nullptr) {
+        if (!prof_now || !((prof_mask >> cls) & 1)) return launch_conv(kind, ca, st, rider);
         // algorithmic flops of the layer (direct-convolution count); the Winograd path executes 4/9 of them on the MFMA
         int taps = kind == CONV_3x3 ? 9 : (kind == CONV_1x1 ? 1 : (kind == CONV_1x3_VEC ? 3 : (kind == CONV_1x3_ROLL ? 9 : 25)));
         double pix = 0;
@@ -173,7 +173,7 @@ struct s3d_unet {
         ProfRec r{cls, prof_event(), prof_event(), 2.0 * taps * ca.cin * ca.cout * pix * ca.B, 0.0};
         r.mfma_flops = r.flops * conv_exec_fraction(kind, ca);
         if (r.e0) (void)hipEventRecord(r.e0, st);
-        int rc = launch_conv(kind, ca, st);
+        int rc = launch_conv(kind, ca, st, rider);
         note_prof_kernel(cls);
         if (r.e1) (void)hipEventRecord(r.e1, st);
         prof_recs.push_back(r);
@@ -341,10 +341,18 @@ struct Fwd {
         return rank1_tables(y, *cw, mp, mv, rrow, rcol);
     }
 
+    // Riders (ConvRider): in the inference forward of the virtual-concat path, three small GroupNorm launches that neither need
+    // nor feed the 1x1 convolution next to them run in that convolution's first blocks instead of in a slot of their own
+    // (s3d_set_riders(0) / S3D_RIDERS=0: every stage a launch of its own; the same kernels' bodies either way, the same bits).
+    bool riders_on() const { return !tape && riders_enabled() && opt_on(OPT_VCAT); }
+    bool rides(const ConvW& cw, const Geo& g) const { return riders_on() && cw.k == 1 && conv1x1_takes_rider(g, B, cw.cout); }
+
     // want_stats (3x3 MFMA paths only): 1 = reduce the GroupNorm statistics of the output (partials in the epilogue +
     // finalize), 2 = leave only the partials with the tensor (it is normalised later as the skip half of a concat)
+    // rider (1x1, only where rides() holds): carried by this launch
     int conv(const Tri& y, const ConvW& cw, const float* bbias, const float* const rrow[3], const float* const rcol[3],
-             const Tri* res, Tri& out, int want_stats = 0, hipStream_t on = nullptr, bool no_bias = false, bool res_up = false) {
+             const Tri* res, Tri& out, int want_stats = 0, hipStream_t on = nullptr, bool no_bias = false, bool res_up = false,
+             const ConvRider* rider = nullptr) {
         hipStream_t st = on ? on : this->st;
         out = alloc_tri(cw.cout, y.g);
         if (!(cw.k == 3 && !conv_use_naive())) want_stats = 0;
@@ -378,7 +386,7 @@ struct Fwd {
             J.res = res ? res->p[p] : nullptr; J.res_up = res && res_up ? 1 : 0; J.out = out.p[p]; J.h = y.g.h[p]; J.w = y.g.w[p];
             J.gn_part = want_stats ? part.p + size_t(p) * part.maxparts * part.nsub * 2 : nullptr;
         }
-        S3D_TRY(m->timed_conv(cw.k == 3 ? 0 : 1, cw.k == 3 ? CONV_3x3 : CONV_1x1, ca, st));
+        S3D_TRY(m->timed_conv(cw.k == 3 ? 0 : 1, cw.k == 3 ? CONV_3x3 : CONV_1x1, ca, st, rider));
         if (want_stats == 1) S3D_TRY(launch_gn_finalize(part, y.g, cw.cout, B, gs, st));
         return 0;
     }
@@ -386,6 +394,7 @@ struct Fwd {
     // the same block on the VIRTUAL input [bilinear2x(u) | sk] (:494-503 + :269-311), inference only: the concat is never
     // written.  Statistics: the upsampled half by one read pass over u, the skip half from its producer's partials; the
     // first norm samples u on the fly; the 1x1 skip_connection runs per half (W_a at low resolution, then upsampled).
+    // The read pass over u rides in W_a's launch (both read u, neither needs the other), the statistics' finalize in W_b's.
     int resblock_cat(const ResBlockW& rb, const Tri& u, const Tri& sk, Tri& out, int out_stats) {
         const bool ssn = m->cfg.use_scale_shift_norm != 0;
         const float* film_ptr = film ? film + rb.film_off : nullptr;
@@ -400,11 +409,15 @@ struct Fwd {
         stats.mr = ar().alloc<float>(size_t(B) * 3 * 64);
         // skip path: z = W_a u (low resolution), up(z), then W_b sk + bias + up(z)
         Tri z, skip;
-        S3D_TRY(conv(u, rb.skip_a, nullptr, nullptr, nullptr, nullptr, z, 0, nullptr, true));
-        S3D_TRY(conv(sk, rb.skip_b, nullptr, nullptr, nullptr, &z, skip, 0, nullptr, false, true));     // + up(z) in the epilogue
+        ConvRider r_up, r_fin;
+        const bool up_rides = !measuring && rides(rb.skip_a, u.g) && gn_partials_up_rider(u, B, sg, pu, r_up);
+        // (the finalize reads the partials of u: it can only ride behind a launch that has carried them)
+        const bool fin_rides = up_rides && rides(rb.skip_b, sk.g) && gn_finalize_cat_rider(pu, sk.part, sk.g, C, B, stats, r_fin);
+        S3D_TRY(conv(u, rb.skip_a, nullptr, nullptr, nullptr, nullptr, z, 0, nullptr, true, false, up_rides ? &r_up : nullptr));
+        S3D_TRY(conv(sk, rb.skip_b, nullptr, nullptr, nullptr, &z, skip, 0, nullptr, false, true, fin_rides ? &r_fin : nullptr));     // + up(z) in the epilogue
         if (!measuring) {
-            S3D_TRY(launch_gn_partials_up(u, B, sg, pu, st));
-            S3D_TRY(launch_gn_finalize_cat(pu, sk.part, sk.g, C, B, stats, st));
+            if (!up_rides) S3D_TRY(launch_gn_partials_up(u, B, sg, pu, st));
+            if (!fin_rides) S3D_TRY(launch_gn_finalize_cat(pu, sk.part, sk.g, C, B, stats, st));
         }
         // first norm + rollout tables on the virtual tensor
         Tri y1, h1, y2;
@@ -429,7 +442,9 @@ struct Fwd {
     }
 
     // TriplaneResBlock._forward (src/diffusion/unet_triplane.py:269-311)
-    int resblock(const ResBlockW& rb, const Tri& x, Tri& out, bool out_feeds_norm, int out_stats_override = -1) {
+    // fin: x.gn is still to be written from these partials (a deferred finish()): the finalize rides in the skip_connection's
+    // launch, which does not read the statistics, or runs ahead of everything as finish() would have
+    int resblock(const ResBlockW& rb, const Tri& x, Tri& out, bool out_feeds_norm, int out_stats_override = -1, const ChunkStats* fin = nullptr) {
         const bool ssn = m->cfg.use_scale_shift_norm != 0;
         const float* film_ptr = film ? film + rb.film_off : nullptr;
         Tri y1, h1, y2;
@@ -438,8 +453,11 @@ struct Fwd {
         // queue of its own — 5: the event edges cost more than the overlap returns, profiles/r05_fwd_side.txt — the switch is gone)
         Tri skip;
         const Tri* res = &x;
+        ConvRider r_fin;
+        const bool fin_rides = fin && !ar().measuring && rb.has_skip && rides(rb.skip, x.g) && gn_finalize_rider(fin->part, x.g, x.C, B, fin->gs, r_fin);
+        if (fin && !fin_rides && !ar().measuring) S3D_TRY(launch_gn_finalize(fin->part, x.g, x.C, B, fin->gs, st));
         if (rb.has_skip) {
-            S3D_TRY(conv(x, rb.skip, nullptr, nullptr, nullptr, nullptr, skip, false));
+            S3D_TRY(conv(x, rb.skip, nullptr, nullptr, nullptr, nullptr, skip, false, nullptr, false, false, fin_rides ? &r_fin : nullptr));
             res = &skip;
         }
         RBTape rt;

@@ -73,6 +73,18 @@ static int find_opt(const char* name) {
     for (int o = 0; o < OPT_COUNT; ++o) if (strcmp(name, kOptNames[o]) == 0) return o;
     return -1;
 }
+// the rider switch: -1 not looked at yet (the environment decides at the first query), 0 off, 1 on
+static std::atomic<int> g_riders{-1};
+bool riders_enabled() {
+    int v = g_riders.load(std::memory_order_acquire);
+    if (v < 0) {
+        const char* e = getenv("S3D_RIDERS");
+        int expect = -1;
+        g_riders.compare_exchange_strong(expect, e && strcmp(e, "0") == 0 ? 0 : 1, std::memory_order_acq_rel);   // (a concurrent s3d_set_riders wins)
+        v = g_riders.load(std::memory_order_acquire);
+    }
+    return v != 0;
+}
 int device_cus() {
     static std::atomic<int> cache[64];
     int dev = 0;
@@ -107,6 +119,11 @@ int s3d_get_option(const char* name, int* value) {
     const int o = find_opt(name);
     S3D_CHECK(o >= 0 && value, S3D_ERR_INVALID, "get_option: unknown option '%s'", name ? name : "(null)");
     *value = opt(Opt(o));
+    return 0;
+}
+
+int s3d_set_riders(int on) {
+    s3d::g_riders.store(on ? 1 : 0, std::memory_order_release);
     return 0;
 }
 

@@ -284,20 +284,24 @@ int run_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W
 
     std::vector<Tri> hs;
     for (int level = 0; level < c.n_levels; ++level) {
+        Fwd::ChunkStats pool_fin; bool defer_fin = false;
         if (level != 0) {                                           // TriplaneDownsample2x (:127-145)
             Tri d = f.alloc_tri(h.C, h.g.half());
             for (int p = 0; p < 3; ++p)
                 S3D_CHECK(d.g.h[p] > 0 && d.g.w[p] > 0, S3D_ERR_INVALID, "plane too small to downsample (level %d)", level);
             const Fwd::ChunkStats cs = f.chunk_stats();
             if (!meas) S3D_TRY(launch_avgpool(h, B, d, st, &cs.part));
-            S3D_TRY(f.finish(cs, d));
+            // the statistics' finalize: in the launch of the block's 1x1 skip_connection where that can carry it (Fwd::resblock)
+            const ResBlockW& rbn = m->in_blocks[level];
+            if (rbn.has_skip && f.rides(rbn.skip, d.g)) { d.gn = cs.gs.mr; pool_fin = cs; defer_fin = true; }
+            else S3D_TRY(f.finish(cs, d));
             h = d;
         }
         Tri o;
         // the deepest output goes straight into a norm; the others become the skip half of a concat later: in the
         // inference forward their producing convolution leaves the GroupNorm partials with them (Fwd::resblock_cat)
         // (... and the deepest one's too: the GN-act kernel of the first output block adds them itself)
-        S3D_TRY(f.resblock(m->in_blocks[level], h, o, level == c.n_levels - 1, tape ? (level == c.n_levels - 1 ? -1 : 0) : 2));
+        S3D_TRY(f.resblock(m->in_blocks[level], h, o, level == c.n_levels - 1, tape ? (level == c.n_levels - 1 ? -1 : 0) : 2, defer_fin ? &pool_fin : nullptr));
         if (tape) { f.last_rb.index = level; f.last_rb.is_out = false; tape->in_rb.push_back(f.last_rb); }
         h = o;
         hs.push_back(o);
