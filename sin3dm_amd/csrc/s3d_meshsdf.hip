@@ -72,48 +72,90 @@ __global__ void __launch_bounds__(kMeshThreads) k_mesh_bin_fill(const float* __r
             }
 }
 
-// ------------------------------------------------------------------ closest point on a triangle (Ericson, Real-Time Collision
-// Detection 5.1.5: the Voronoi region of the point decides between a vertex, an edge and the face); barycentrics of a, b, c
-__device__ __forceinline__ void closest_on_triangle(const float p[3], const float* __restrict__ t, float bc[3]) {
-    float ab[3], ac[3], ap[3], bp[3], cp[3];
+// ------------------------------------------------------------------ closest point on a triangle: barycentrics of a, b, c and the
+// squared distance.  Ericson's region test (Real-Time Collision Detection 5.1.5: the Voronoi region of the point decides between a
+// vertex, an edge and the face) is exact in exact arithmetic, but va, vb and vc are differences of products: on a needle or cap
+// sliver, or a face without area, their true value lies below their rounding in fp32, the wrong region is chosen and the answer is
+// a point of the triangle far from the nearest one (or 0 / 0).  So its answer is one candidate of four: the other three are the
+// projections onto the edges ab, ac and bc, clamped to the segment.  Every candidate is a point of the triangle (barycentrics
+// clamped to >= 0 with sum 1), so none lies nearer than the truth; the edges bound the result by the distance to the boundary,
+// which is the distance itself where the face has no area and at most a sliver's height above it otherwise.  The nearest
+// candidate by the squared distance reconstructed from its own barycentrics wins, the earlier one on a tie, a NaN never.
+__device__ __forceinline__ float bary_dist2(const float p[3], const float* __restrict__ t, float b0, float b1, float b2) {
+    float d2 = 0.0f;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        ab[k] = t[3 + k] - t[k]; ac[k] = t[6 + k] - t[k];
+        const float q = b0 * t[k] + b1 * t[3 + k] + b2 * t[6 + k] - p[k];
+        d2 += q * q;
+    }
+    return d2;
+}
+__device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }      // (fmaxf drops a NaN: 0)
+
+__device__ __forceinline__ float closest_on_triangle(const float p[3], const float* __restrict__ t, float bc[3]) {
+    float ab[3], ac[3], cb[3], ap[3], bp[3], cp[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        ab[k] = t[3 + k] - t[k]; ac[k] = t[6 + k] - t[k]; cb[k] = t[6 + k] - t[3 + k];
         ap[k] = p[k] - t[k]; bp[k] = p[k] - t[3 + k]; cp[k] = p[k] - t[6 + k];
     }
     const float d1 = ab[0] * ap[0] + ab[1] * ap[1] + ab[2] * ap[2], d2 = ac[0] * ap[0] + ac[1] * ap[1] + ac[2] * ap[2];
-    if (d1 <= 0.0f && d2 <= 0.0f) { bc[0] = 1.0f; bc[1] = 0.0f; bc[2] = 0.0f; return; }
     const float d3 = ab[0] * bp[0] + ab[1] * bp[1] + ab[2] * bp[2], d4 = ac[0] * bp[0] + ac[1] * bp[1] + ac[2] * bp[2];
-    if (d3 >= 0.0f && d4 <= d3) { bc[0] = 0.0f; bc[1] = 1.0f; bc[2] = 0.0f; return; }
-    const float vc = d1 * d4 - d3 * d2;
-    if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {
-        const float v = __fdiv_rn(d1, d1 - d3);
-        bc[0] = 1.0f - v; bc[1] = v; bc[2] = 0.0f;
-        return;
-    }
     const float d5 = ab[0] * cp[0] + ab[1] * cp[1] + ab[2] * cp[2], d6 = ac[0] * cp[0] + ac[1] * cp[1] + ac[2] * cp[2];
-    if (d6 >= 0.0f && d5 <= d6) { bc[0] = 0.0f; bc[1] = 0.0f; bc[2] = 1.0f; return; }
-    const float vb = d5 * d2 - d1 * d6;
-    if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    // candidate 0: the region test
+    float e0, e1, e2;
+    if (d1 <= 0.0f && d2 <= 0.0f) { e0 = 1.0f; e1 = 0.0f; e2 = 0.0f; }
+    else if (d3 >= 0.0f && d4 <= d3) { e0 = 0.0f; e1 = 1.0f; e2 = 0.0f; }
+    else if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {
+        const float v = __fdiv_rn(d1, d1 - d3);                   // in [0, 1], or NaN where a == b
+        e0 = 1.0f - v; e1 = v; e2 = 0.0f;
+    } else if (d6 >= 0.0f && d5 <= d6) { e0 = 0.0f; e1 = 0.0f; e2 = 1.0f; }
+    else if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {
         const float w = __fdiv_rn(d2, d2 - d6);
-        bc[0] = 1.0f - w; bc[1] = 0.0f; bc[2] = w;
-        return;
-    }
-    const float va = d3 * d6 - d5 * d4;
-    if (va <= 0.0f && (d4 - d3) >= 0.0f && (d5 - d6) >= 0.0f) {
+        e0 = 1.0f - w; e1 = 0.0f; e2 = w;
+    } else if (va <= 0.0f && (d4 - d3) >= 0.0f && (d5 - d6) >= 0.0f) {
         const float w = __fdiv_rn(d4 - d3, (d4 - d3) + (d5 - d6));
-        bc[0] = 0.0f; bc[1] = 1.0f - w; bc[2] = w;
-        return;
+        e0 = 0.0f; e1 = 1.0f - w; e2 = w;
+    } else {
+        const float den = va + vb + vc;
+        const float v = clamp01(__fdiv_rn(vb, den)), u = 1.0f - v;
+        const float w = fminf(fmaxf(__fdiv_rn(vc, den), 0.0f), u);     // (v + w may round past 1 on an edge; past anything on a sliver)
+        e0 = u - w; e1 = v; e2 = w;
     }
-    const float den = va + vb + vc;
-    const float v = __fdiv_rn(vb, den), w = __fdiv_rn(vc, den);
-    bc[0] = fmaxf(0.0f, 1.0f - v - w); bc[1] = v; bc[2] = w;      // (v + w may round past 1 on an edge)
+    float best = INFINITY;
+    bc[0] = 1.0f; bc[1] = 0.0f; bc[2] = 0.0f;
+    {
+        const float d = bary_dist2(p, t, e0, e1, e2);
+        if (d < best) { best = d; bc[0] = e0; bc[1] = e1; bc[2] = e2; }
+    }
+    // candidates 1 to 3: the edges ab, ac, bc
+    {
+        const float l2 = ab[0] * ab[0] + ab[1] * ab[1] + ab[2] * ab[2];
+        const float s = l2 > 0.0f ? clamp01(__fdiv_rn(d1, l2)) : 0.0f;
+        const float d = bary_dist2(p, t, 1.0f - s, s, 0.0f);
+        if (d < best) { best = d; bc[0] = 1.0f - s; bc[1] = s; bc[2] = 0.0f; }
+    }
+    {
+        const float l2 = ac[0] * ac[0] + ac[1] * ac[1] + ac[2] * ac[2];
+        const float s = l2 > 0.0f ? clamp01(__fdiv_rn(d2, l2)) : 0.0f;
+        const float d = bary_dist2(p, t, 1.0f - s, 0.0f, s);
+        if (d < best) { best = d; bc[0] = 1.0f - s; bc[1] = 0.0f; bc[2] = s; }
+    }
+    {
+        const float l2 = cb[0] * cb[0] + cb[1] * cb[1] + cb[2] * cb[2];
+        const float s = l2 > 0.0f ? clamp01(__fdiv_rn(cb[0] * bp[0] + cb[1] * bp[1] + cb[2] * bp[2], l2)) : 0.0f;
+        const float d = bary_dist2(p, t, 0.0f, 1.0f - s, s);
+        if (d < best) { best = d; bc[0] = 0.0f; bc[1] = 1.0f - s; bc[2] = s; }
+    }
+    return best;
 }
 
-// One thread per query point: the triangles of its cell's segment, the minimum squared distance kept, a tie to the lower face
-// index (so the order inside the segment does not matter).  dist = the distance, or `band` with face -1 and zero barycentrics when
-// nothing lies nearer than the band.  A point outside the grid looks its border cell up: the grid covers the mesh dilated by the
-// band, so such a point has nothing within the band and the walk finds nothing either.
+// One thread per query point: the triangles of its cell's segment, the minimum squared distance kept (finite for every face: an
+// edge candidate always is), a tie to the lower face index (so the order inside the segment does not matter).  dist = the
+// distance, or `band` with face -1 and zero barycentrics when nothing lies nearer than the band.  A point outside the grid looks
+// its border cell up: the grid covers the mesh dilated by the band, so such a point has nothing within the band and the walk finds
+// nothing either.
 __global__ void __launch_bounds__(kMeshThreads) k_mesh_closest(const float* __restrict__ pts, long long N, const float* __restrict__ tri9,
                                                                long long F, float band, CellGrid g, const long long* __restrict__ seg,
                                                                const int* __restrict__ seg_tri, long long n_pairs,
@@ -131,13 +173,7 @@ __global__ void __launch_bounds__(kMeshThreads) k_mesh_closest(const float* __re
         if (f < 0 || f >= F) continue;
         const float* t = tri9 + (long long)f * 9;
         float bc[3];
-        closest_on_triangle(p, t, bc);
-        float d2 = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float q = bc[0] * t[k] + bc[1] * t[3 + k] + bc[2] * t[6 + k] - p[k];
-            d2 += q * q;
-        }
+        const float d2 = closest_on_triangle(p, t, bc);
         if (d2 < best || (d2 == best && f < bf)) { best = d2; bf = f; bb[0] = bc[0]; bb[1] = bc[1]; bb[2] = bc[2]; }
     }
     float d = bf >= 0 ? sqrtf(best) : band;

@@ -1,7 +1,7 @@
-"""GPU tests of the mesh preprocessing (sin3dm_amd/data, s3d_meshsdf.hip) against a float64 NumPy brute force written here: all
-points x all faces with the kernels' formulas (Ericson's region test, the Van Oosterom-Strackee solid angle).
+"""GPU tests of the mesh preprocessing (sin3dm_amd/data, s3d_meshsdf.hip) against a float64 NumPy brute force (tests/meshprep_cases.py):
+all points x all faces with the kernels' formulas (Ericson's region test, the Van Oosterom-Strackee solid angle).
 
-Tolerances.  The same brute force run in float32 (`python tests/test_meshprep_gpu.py` prints the figures, CPU only) differs from
+Tolerances.  The same brute force run in float32 (`python tests/meshprep_cases.py` prints the figures, CPU only) differs from
 float64, over every mesh and query set used below, by at most
     FP32_GAP_DIST = 1.3e-7 in the distance (measured 1.288e-7)   and   FP32_GAP_WN = 8.4e-7 in the winding number (8.345e-7);
 the device is allowed 8x that (FMA contraction, device sqrt, division and atan2): TOL_DIST = 1.04e-6, TOL_WN = 6.72e-6.
@@ -13,156 +13,13 @@ import numpy as np
 import pytest
 
 from conftest import REPO
-
-FP32_GAP_DIST, FP32_GAP_WN = 1.3e-7, 8.4e-7
-TOL_DIST, TOL_WN = 8 * FP32_GAP_DIST, 8 * FP32_GAP_WN
-R_MAJOR, R_MINOR = 0.55, 0.22
-
-
-# ------------------------------------------------------------------ meshes
-def torus(nu=24, nv=12):
-    """Vertices [nu * nv, 3] on the torus around the y axis and 2 * nu * nv outward-oriented faces."""
-    u, v = np.meshgrid(np.arange(nu) * 2 * np.pi / nu, np.arange(nv) * 2 * np.pi / nv, indexing="ij")
-    V = np.stack([(R_MAJOR + R_MINOR * np.cos(v)) * np.cos(u), R_MINOR * np.sin(v), (R_MAJOR + R_MINOR * np.cos(v)) * np.sin(u)], -1).reshape(-1, 3)
-    F = []
-    for i in range(nu):
-        for j in range(nv):
-            a, b, c, d = i * nv + j, ((i + 1) % nu) * nv + j, ((i + 1) % nu) * nv + (j + 1) % nv, i * nv + (j + 1) % nv
-            F += [[a, c, b], [a, d, c]]
-    return V, np.asarray(F, dtype=np.int64)
-
-
-def rotation():
-    cz, sz, cx, sx = np.cos(0.3), np.sin(0.3), np.cos(0.2), np.sin(0.2)
-    return np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]]) @ np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+from meshprep_cases import (FP32_GAP_DIST, FP32_GAP_WN, R_MAJOR, R_MINOR, TOL_DIST, TOL_WN, Case, box_mesh, brute_closest,  # noqa: F401
+                            brute_winding, case, check_closest, pair_closest, rotation, torus)
 
 
 def torus_phi(p0):
     """Signed distance to the analytic torus in its own frame."""
     return np.sqrt((np.sqrt(p0[..., 0] ** 2 + p0[..., 2] ** 2) - R_MAJOR) ** 2 + p0[..., 1] ** 2) - R_MINOR
-
-
-def box_mesh(aabb):
-    lo, hi = aabb[:3], aabb[3:]
-    V = np.array([[(lo, hi)[(i >> k) & 1][k] for k in range(3)] for i in range(8)], dtype=np.float64)
-    F = [[0, 2, 1], [1, 2, 3], [4, 5, 6], [5, 7, 6], [0, 1, 4], [1, 5, 4], [2, 6, 3], [3, 6, 7], [0, 4, 2], [2, 4, 6], [1, 3, 5], [3, 7, 5]]
-    return V, np.asarray(F, dtype=np.int64)
-
-
-# ------------------------------------------------------------------ the oracle (dtype float64) and its float32 restatement
-def pair_closest(P, T, dtype=np.float64):
-    """Closest point of triangles T [..., 9] to points P [..., 3] (broadcast): (distance, barycentrics [..., 3])."""
-    P, T = np.asarray(P, dtype=dtype), np.asarray(T, dtype=dtype)
-    a, b, c = T[..., 0:3], T[..., 3:6], T[..., 6:9]
-    ab, ac, ap, bp, cp = b - a, c - a, P - a, P - b, P - c
-    dot = lambda x, y: (x * y).sum(-1)                    # noqa: E731
-    d1, d2, d3, d4, d5, d6 = dot(ab, ap), dot(ac, ap), dot(ab, bp), dot(ac, bp), dot(ab, cp), dot(ac, cp)
-    vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
-    zero, one = np.zeros_like(d1), np.ones_like(d1)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        vab, wac, wbc, den = d1 / (d1 - d3), d2 / (d2 - d6), (d4 - d3) / ((d4 - d3) + (d5 - d6)), va + vb + vc
-        conds = [(d1 <= 0) & (d2 <= 0), (d3 >= 0) & (d4 <= d3), (vc <= 0) & (d1 >= 0) & (d3 <= 0), (d6 >= 0) & (d5 <= d6),
-                 (vb <= 0) & (d2 >= 0) & (d6 <= 0), (va <= 0) & ((d4 - d3) >= 0) & ((d5 - d6) >= 0)]
-        v = np.select(conds, [zero, one, vab, zero, zero, one - wbc], vb / den)
-        w = np.select(conds, [zero, zero, zero, one, wac, wbc], vc / den)
-    q = a + ab * v[..., None] + ac * w[..., None] - P
-    return np.sqrt(dot(q, q)), np.stack([1 - v - w, v, w], -1)
-
-
-def brute_closest(P, T, dtype=np.float64, chunk=1024):
-    """Per point: (distance to the mesh, first face at that distance)."""
-    d, f = np.empty(len(P), dtype=dtype), np.empty(len(P), dtype=np.int64)
-    for s in range(0, len(P), chunk):
-        dd, _ = pair_closest(P[s:s + chunk, None, :], T[None], dtype)
-        f[s:s + chunk] = dd.argmin(1)
-        d[s:s + chunk] = dd.min(1)
-    return d, f
-
-
-def brute_winding(P, T, dtype=np.float64, chunk=1024):
-    out = np.empty(len(P), dtype=dtype)
-    T = np.asarray(T, dtype=dtype)
-    for s in range(0, len(P), chunk):
-        p = np.asarray(P[s:s + chunk], dtype=dtype)[:, None, :]
-        a, b, c = T[None, :, 0:3] - p, T[None, :, 3:6] - p, T[None, :, 6:9] - p
-        la, lb, lc = np.sqrt((a * a).sum(-1)), np.sqrt((b * b).sum(-1)), np.sqrt((c * c).sum(-1))
-        num = (a * np.cross(b, c)).sum(-1)
-        den = la * lb * lc + (a * b).sum(-1) * lc + (b * c).sum(-1) * la + (c * a).sum(-1) * lb
-        out[s:s + chunk] = (2 * np.arctan2(num, den)).sum(1) / dtype(4 * np.pi)
-    return out
-
-
-# ------------------------------------------------------------------ the shared case: mesh, queries, oracle results (computed once)
-class Case:
-    def __init__(self):
-        from sin3dm_amd.data.utils import normalize_aabb, sample_grid_points_aabb
-        V0, self.F = torus()
-        self.rot = rotation()
-        V = V0 @ self.rot.T
-        self.aabb, self.translation, self.scale = normalize_aabb(V, reso=24, mult=4)
-        self.V = (V + self.translation) * self.scale
-        self.grid = sample_grid_points_aabb(self.aabb, 24)
-        assert self.grid.shape[:3] == (24, 16, 24)
-        self.band = 2. / 24 * 3
-        self.V32 = self.V.astype(np.float32)                       # what the device sees; the oracle reads the same values
-        self.T = self.V32[self.F].reshape(-1, 9).astype(np.float64)
-        rng = np.random.Generator(np.random.PCG64(11))
-        tri = self.V32[self.F].astype(np.float64)
-        exact = np.concatenate([self.V32.astype(np.float64), (tri[:, [0, 1, 2]] + tri[:, [1, 2, 0]]).reshape(-1, 3) / 2, tri.mean(1)])
-        self.queries = np.concatenate([self.grid.reshape(-1, 3), rng.uniform(-1.3, 1.3, size=(1000, 3)), exact]).astype(np.float32)
-        self.box_V, self.box_F = box_mesh(self.aabb)
-        self.box_T = self.box_V.astype(np.float32)[self.box_F].reshape(-1, 9).astype(np.float64)
-        self.wn_points = np.concatenate([self.grid.reshape(-1, 3), rng.uniform(-1, 1, size=(7, 3))]).astype(np.float32)
-        self.open_keep = np.ones(len(self.F), dtype=bool)
-        self.open_keep[100:140] = False
-        self._memo = {}
-
-    def memo(self, key, fn):
-        if key not in self._memo:
-            self._memo[key] = fn()
-        return self._memo[key]
-
-    def to_torus_frame(self, p):
-        return (np.asarray(p, dtype=np.float64) / self.scale - self.translation) @ self.rot
-
-    def sampler(self, **kw):
-        from sin3dm_amd.data.mesh_sampler import MeshSampler
-        return MeshSampler(verts=self.V32.astype(np.float64), faces=self.F, **kw)
-
-
-_CASE = None
-
-
-def case():
-    global _CASE
-    if _CASE is None:
-        _CASE = Case()
-    return _CASE
-
-
-def check_closest(ms, T, queries, d_or, band):
-    """The per-query assertions of the closest-point kernel (tests 1 and 2); returns (dist, face, bary) as NumPy arrays."""
-    dist, face, bary = (t.cpu().numpy() for t in ms.closest(queries, band))
-    band32 = np.float32(band)
-    P = queries.astype(np.float64)
-    err = np.abs(dist - np.minimum(d_or, float(band32)))
-    print(f"band {band}: {len(P)} queries, {int((face >= 0).sum())} within the band, distance error max {err.max():.3e} (tol {TOL_DIST:.3e})")
-    assert err.max() <= TOL_DIST
-    hit = face >= 0
-    far, near = d_or >= float(band32) + TOL_DIST, d_or < float(band32) - TOL_DIST     # rounding may decide either way in between
-    assert (dist[far] == band32).all() and (face[far] == -1).all() and (bary[far] == 0).all()
-    assert hit[near].all()
-    assert (dist[~hit] == band32).all() and (face < len(T)).all()
-    bc = bary[hit].astype(np.float64)
-    assert (bary[hit] >= 0).all() and np.abs(bc.sum(1) - 1).max() <= 4 * 2.0 ** -23
-    tri = T[face[hit]]
-    recon = bc[:, 0:1] * tri[:, 0:3] + bc[:, 1:2] * tri[:, 3:6] + bc[:, 2:3] * tri[:, 6:9]
-    gap = np.abs(np.linalg.norm(P[hit] - recon, axis=1) - dist[hit])
-    d_face, _ = pair_closest(P[hit], tri)
-    print(f"   |p - sum bc v| vs distance: {gap.max():.3e}; reported face above the minimum by {np.max(d_face - d_or[hit]):.3e}")
-    assert gap.max() <= TOL_DIST
-    assert np.max(d_face - d_or[hit]) <= TOL_DIST              # the reported face is one at the minimum distance (not: the same index)
-    return dist, face, bary
 
 
 pytestmark = pytest.mark.gpu
@@ -372,21 +229,3 @@ def test_cli_end_to_end(tmp_path):
         losses = ae.train_step(ae._sample_batch(ae.batch_size))
         assert all(np.isfinite(float(v)) for v in losses.values()), losses
     torch.cuda.synchronize()
-
-
-if __name__ == "__main__":                                  # the fp32 restatement's gap to float64 (CPU): the source of the tolerances
-    c = Case()
-    Q = c.queries.astype(np.float64)
-    worst_d = worst_w = 0.0
-    for name, T in (("torus", c.T), ("box", c.box_T)):
-        d64, _ = brute_closest(Q, T)
-        d32, _ = brute_closest(Q, T, np.float32)
-        worst_d = max(worst_d, float(np.abs(d64 - d32).max()))
-        print(f"closest, {name}: fp32 vs float64 {np.abs(d64 - d32).max():.3e}")
-    for name, F in (("closed", c.F), ("open", c.F[c.open_keep]), ("triangle", c.F[:1]), ("flipped", c.F[:, ::-1])):
-        T = c.V32[F].reshape(-1, 9).astype(np.float64)
-        w64, w32 = brute_winding(c.wn_points.astype(np.float64), T), brute_winding(c.wn_points.astype(np.float64), T, np.float32)
-        worst_w = max(worst_w, float(np.abs(w64 - w32).max()))
-        sure = np.abs(np.abs(w64) - 0.5) > 10 * TOL_WN
-        print(f"winding, {name}: fp32 vs float64 {np.abs(w64 - w32).max():.3e}, undecided share {1 - sure.mean():.5f}")
-    print(f"FP32_GAP_DIST {worst_d:.3e}  FP32_GAP_WN {worst_w:.3e}; nearest grid point to the surface {brute_closest(c.grid.reshape(-1, 3), c.T)[0].min():.3e}")
