@@ -397,7 +397,8 @@ S3D_API int s3d_ae_loss_grads(s3d_ae* a, const float* pts, const float* sdf, con
 typedef struct s3d_mc s3d_mc;
 S3D_API int s3d_mc_create(s3d_mc** out);
 S3D_API void s3d_mc_destroy(s3d_mc* m);
-/* pass 1: classify and scan; synchronises `stream` to return the counts.  pad = 1 surrounds the grid with pad_value. */
+/* pass 1: classify and scan; synchronises `stream` to return the counts.  pad = 1 surrounds the grid with pad_value.
+ * 3 (X + 2 pad)(Y + 2 pad)(Z + 2 pad) >= 2^31 is refused with S3D_ERR_UNSUPPORTED before anything is allocated or launched. */
 S3D_API int s3d_mc_count(s3d_mc* m, const float* grid, int X, int Y, int Z, int stride, float iso, int pad, float pad_value,
                          int64_t* n_verts, int64_t* n_tris, void* stream);
 /* pass 2: verts [n_verts][3], attrs [n_verts][n_attr] or null (channels 1..n_attr of the grid), tris [n_tris][3] */

@@ -61,15 +61,22 @@ def _edge_of_vertex(p, off):
     return (axis, int(base[0]), int(base[1]), int(base[2]))
 
 
-def check_mesh(grid, verts, tris, iso=0.0, pad_value=1.0, tol=2e-5):
-    """Raises AssertionError with a description if the mesh violates any of (1)-(4); returns a dict of counts."""
+def check_mesh(grid, verts, tris, iso=0.0, pad_value=1.0, tol=2e-5, keys=None):
+    """Raises AssertionError with a description if the mesh violates any of (1)-(4); returns a dict of counts.
+    keys: the grid edge (axis, i, j, k) of every vertex, indices in the padded grid, where the caller knows it from the vertex
+    ORDER.  Without it the edge is read off the position's fractional part, which is blind to a vertex on a lattice point (an
+    end value equal to the level, t rounded to 1): such meshes need keys."""
     g = _padded(grid, pad_value)
     off = 1.0 if pad_value is not None else 0.0
     want = expected_vertices(grid, iso, pad_value)
     verts = np.asarray(verts, np.float64)
     tris = np.asarray(tris, np.int64)
     # (1) vertex set
-    keys = [_edge_of_vertex(p, off) for p in verts]
+    if keys is None:
+        keys = [_edge_of_vertex(p, off) for p in verts]
+    else:
+        keys = [tuple(int(x) for x in k) for k in keys]
+        assert len(keys) == len(verts), f"{len(keys)} edge keys for {len(verts)} vertices"
     assert len(set(keys)) == len(keys), "two mesh vertices on one grid edge"
     assert set(keys) == set(want), (f"vertex set differs: {len(set(keys) - set(want))} unexpected, "
                                     f"{len(set(want) - set(keys))} missing")

@@ -259,6 +259,11 @@ def _qem_round(v, t, Q):
             "keys": keys, "selected": selected.bool(), "nbr_off": nbr_off, "nbr": nbr, "vf_off": vf_off, "vf_face": vf_face}
 
 
+def _qem_state(v, t, Q, at, parent):
+    """copies of what a round changes, for the trace of simplify_mesh_quadric"""
+    return {"verts": v.clone(), "tris": t.clone(), "Q": Q.clone(), "attrs": at.clone() if at is not None else None, "parent": parent.clone()}
+
+
 def simplify_mesh_quadric(verts, tris, n_faces, attrs=None, max_rounds=None, return_round=False):
     """Decimate to at most `n_faces` faces by quadric-error edge collapse (Garland & Heckbert; where the reference calls open3d's
     simplify_quadric_decimation, utils3d.py mesh_decimation — parity with open3d's output is not claimed), run as parallel rounds
@@ -272,7 +277,10 @@ def simplify_mesh_quadric(verts, tris, n_faces, attrs=None, max_rounds=None, ret
     never move.  The surviving faces keep their order; unreferenced vertices are dropped.  Same input, same bits.
     Returns (verts, tris, info); info: rounds, per_round [(collapses, faces after)], stuck, vmap (int32: the output vertex every
     input vertex was merged into), attrs (or None).  max_rounds bounds the rounds; return_round=True adds info["round"], the
-    per-edge state of the LAST round run (_qem_round) as it was before that round's collapses, with "chosen" (the edges collapsed)."""
+    per-edge state of the LAST round run (_qem_round) as it was before that round's collapses, with "chosen" (the edges collapsed).
+    return_round="all" adds info["trace"] instead: one entry per round run — that dictionary, "chosen", and copies of verts, tris, Q
+    ([nv,10] double), attrs and parent (int32: v -> the u it was collapsed into) as they were BEFORE the round — and a final entry
+    with those five after the last round.  The trace changes no arithmetic."""
     _lib.require_gpu(verts)
     n_faces = int(n_faces)
     if n_faces < 0:
@@ -296,13 +304,17 @@ def simplify_mesh_quadric(verts, tris, n_faces, attrs=None, max_rounds=None, ret
         vf_off, vf_face = _vertex_faces(t, nv)
         _lib.check(lib.s3d_mesh_qem_quadrics(_lib.ptr(v), nv, _lib.ptr(t), t.shape[0], _lib.ptr(vf_off), _lib.ptr(vf_face), _lib.ptr(Q), st))
         parent = torch.arange(nv, device=dev, dtype=torch.int32)
+        if return_round == "all":
+            info["trace"] = []
         while t.shape[0] > n_faces and (max_rounds is None or info["rounds"] < max_rounds):
             rd = _qem_round(v, t, Q)
             chosen = torch.nonzero(rd["selected"]).squeeze(1)
             need = (t.shape[0] - n_faces + 1) // 2                      # a collapse takes exactly two faces away
             if chosen.shape[0] > need:
                 chosen = chosen[torch.sort(rd["keys"][chosen])[1][:need]].contiguous()
-            if return_round:
+            if return_round == "all":
+                info["trace"].append(dict(rd, chosen=chosen, **_qem_state(v, t, Q, at, parent)))
+            elif return_round:
                 info["round"] = dict(rd, chosen=chosen, verts=v.clone(), tris=t)
             if chosen.shape[0] == 0:
                 info["stuck"] = True
@@ -316,6 +328,8 @@ def simplify_mesh_quadric(verts, tris, n_faces, attrs=None, max_rounds=None, ret
             t = mapped[keep.bool()].contiguous()
             info["rounds"] += 1
             info["per_round"].append((int(chosen.shape[0]), int(t.shape[0])))
+        if return_round == "all":
+            info["trace"].append(_qem_state(v, t, Q, at, parent))
         root = parent.long()
         while True:                                                    # follow v -> u to the surviving vertex
             nxt = root[root]

@@ -18,10 +18,10 @@ TARGET_TOL, COST_TOL = 5.23e-7, 5.81e-7
 CLUSTER_RMS, QUADRIC_RMS = 1.19070, 0.00525
 
 
-def _field(kind):
+def _field(kind, n=None):
     """box: a box with a box-shaped hole through it along z (sharp edges, genus 1), on a 44^3 grid; torus: a torus with bumps
-    (smooth, genus 1), on a 48^3 grid.  The offsets keep the surface off the grid points."""
-    n = {"box": 44, "torus": 48}[kind]
+    (smooth, genus 1), on a 48^3 grid (or on n^3).  The offsets keep the surface off the grid points."""
+    n = n or {"box": 44, "torus": 48}[kind]
     ax = np.linspace(-1, 1, n)
     x, y, z = np.meshgrid(ax + 0.0131, ax * 0.95 - 0.0072, ax * 1.05 + 0.0057, indexing="ij")
     if kind == "box":
