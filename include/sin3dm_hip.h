@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define S3D_ABI_VERSION 11
+#define S3D_ABI_VERSION 12
 #define S3D_API __attribute__((visibility("default")))
 
 typedef enum {
@@ -219,6 +219,36 @@ S3D_API int s3d_unet_step_film(s3d_unet* m, const float* film, int film_stride, 
 enum { S3D_CARRY_OUT = 1, S3D_CARRY_IN = 2 };
 S3D_API int s3d_unet_step_film_carry(s3d_unet* m, const float* film, int film_stride, int B, int H, int W, int D,
                        const s3d_sampler_args* step, float* model_out, void* stream, int carry_flags);
+
+/* Known-region sampling (outpainting / local editing; DESIGN.md section 20 — no counterpart in the reference).  After the update of a
+ * DDPM or DDIM step at schedule index i = t[b], the known part of x_{t-1} is replaced by the source latent noised to level i - 1:
+ *     k      = (sa[i] * y0) + (sb[i] * noise)                  q_sample(y0, i - 1, noise); i == 0: sa = 1, sb = 0
+ *     sample = (mask * k) + ((1 - mask) * x_prev)              x_prev: what the step writes to `sample` without a known region
+ * every product and sum its own fp32 round-to-nearest operation in this order.  pred_xstart and mean are not touched by the blend and
+ * `sample` is stored once.  y0, mask (values in [0, 1]) and noise are device fp32 tensors of x's full shape [B, per_sample], all
+ * required.  `tables` is a device fp32 array [S3D_KTAB_ROWS][T] of float64 schedule values cast to fp32 — sa = row SQRT_ACP_PREV,
+ * sb = row SQRT_1M_ACP_PREV; the two other rows serve s3d_sampler_renoise.  The step's own y0 / mask (the reference's DDIM
+ * x0 replacement) must be NULL and its mode is not S3D_STEP_MEAN_ONLY. */
+enum { S3D_KTAB_SQRT_ACP_PREV = 0, S3D_KTAB_SQRT_1M_ACP_PREV, S3D_KTAB_SQRT_1M_BETA, S3D_KTAB_SQRT_BETA, S3D_KTAB_ROWS };
+typedef struct {
+    const float* y0;             /* [B, per_sample] the source latent on the target canvas           */
+    const float* mask;           /* [B, per_sample] 1 = keep y0, 0 = free                            */
+    const float* noise;          /* [B, per_sample] eps of the q_sample above                        */
+    const float* tables;         /* [S3D_KTAB_ROWS][T] device fp32                                   */
+} s3d_known_region;
+/* s3d_sampler_step with the blend (the stand-alone kernel). */
+S3D_API int s3d_sampler_step_known(const s3d_sampler_args* a, const s3d_known_region* known, void* stream);
+/* s3d_unet_step_film_carry with the blend applied in the output head's launch; with S3D_CARRY_OUT the next step's in_conv is evaluated
+ * on the BLENDED sample.  Identical bits to s3d_unet_forward_film followed by s3d_sampler_step_known.  model_out != NULL: the model
+ * output is stored there and the step runs as output head + the stand-alone kernel (the in-head form stores neither the model output
+ * nor the posterior mean: its registers hold the known-region pointers instead); S3D_CARRY_OUT then leaves nothing behind, and
+ * step->mean is only accepted together with model_out. */
+S3D_API int s3d_unet_step_film_known(s3d_unet* m, const float* film, int film_stride, int B, int H, int W, int D,
+                       const s3d_sampler_args* step, const s3d_known_region* known, float* model_out, void* stream, int carry_flags);
+/* One level of re-noising between two repeats of a step (RePaint's resampling): x_t = (sqrt(1 - beta_i) * x_prev) + (sqrt(beta_i) * noise)
+ * with i = t[b], each operation rounded as above.  `known_tables` as in s3d_known_region; x_t may not alias its inputs' other rows. */
+S3D_API int s3d_sampler_renoise(const float* x_prev, const float* noise, const float* known_tables, const int64_t* t, int32_t T,
+                       int64_t batch, int64_t per_sample, float* x_t, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Leaf operators, exported so the parity tests can pin each kernel to the reference op it replaces

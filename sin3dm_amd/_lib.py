@@ -14,8 +14,9 @@ LIB_PATH = os.path.join(_HERE, "libsin3dm_hip.so")
 c_fp = C.POINTER(C.c_float)
 c_i64p = C.POINTER(C.c_int64)
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 TAB_ROWS = ("sqrt_recip", "sqrt_recipm1", "coef1", "coef2", "logvar", "acp", "acp_prev")
+KTAB_ROWS = ("sqrt_acp_prev", "sqrt_1m_acp_prev", "sqrt_1m_beta", "sqrt_beta")     # s3d_known_region.tables (S3D_KTAB_*)
 STEP_DDPM, STEP_DDIM, STEP_MEAN_ONLY = 0, 1, 2
 CARRY_OUT, CARRY_IN = 1, 2               # s3d_unet_step_film_carry flags (include/sin3dm_hip.h)
 MEAN_START_X, MEAN_EPSILON = 0, 1
@@ -36,6 +37,11 @@ class SamplerArgs(C.Structure):
                 ("per_sample", C.c_int64), ("model_out", C.c_void_p), ("x", C.c_void_p), ("noise", C.c_void_p),
                 ("t", C.c_void_p), ("tables", C.c_void_p), ("y0", C.c_void_p), ("mask", C.c_void_p),
                 ("sample", C.c_void_p), ("pred_xstart", C.c_void_p), ("mean", C.c_void_p)]
+
+
+class KnownRegionArgs(C.Structure):
+    """s3d_known_region: the known-region blend of a step (include/sin3dm_hip.h)."""
+    _fields_ = [("y0", C.c_void_p), ("mask", C.c_void_p), ("noise", C.c_void_p), ("tables", C.c_void_p)]
 
 
 PROF_CLASSES = 4
@@ -86,6 +92,11 @@ SIGNATURES = {
                                      C.POINTER(SamplerArgs), C.c_void_p, C.c_void_p]),
     "s3d_unet_step_film_carry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.POINTER(SamplerArgs), C.c_void_p, C.c_void_p, C.c_int]),
+    "s3d_sampler_step_known": (C.c_int, [C.POINTER(SamplerArgs), C.POINTER(KnownRegionArgs), C.c_void_p]),
+    "s3d_unet_step_film_known": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.POINTER(SamplerArgs), C.POINTER(KnownRegionArgs), C.c_void_p, C.c_void_p, C.c_int]),
+    "s3d_sampler_renoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
+                                      C.c_void_p]),
     "s3d_op_triplane_conv": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                        C.POINTER(C.c_void_p), C.c_void_p]),

@@ -381,7 +381,8 @@ int launch_copy_slice(const float* in, int B, int C, int h, int w, float* out, i
 struct InConvCarry { const float* wT; const float* bias; float* out[3]; double* part; int maxparts, Cin; };
 int launch_out_head(const Tri& x, int B, GnStats stats, const ActArgs& a, const float* w /*[3][Cout][C]*/,
                     const float* bias /*[3][Cout]*/, int Cout, int H, int W, int D, float* out, hipStream_t st,
-                    const s3d_sampler_args* fuse = nullptr, const GnPartials* part = nullptr, const InConvCarry* carry = nullptr);
+                    const s3d_sampler_args* fuse = nullptr, const GnPartials* part = nullptr, const InConvCarry* carry = nullptr,
+                    const s3d_known_region* known = nullptr);          // known: the step's known-region blend (fuse != null)
 bool out_head_can_carry(int C, int Cin, int Cout_head);  // the pixel-chunk head of this width can run the in_conv tail
 bool out_head_fuses_sampler(int C, int Cout, int B);     // the update happens inside the head's launch (else: head, then k_sampler)
 bool out_head_px_takes(int C, int Cout);                 // the pixel-chunk head serves this width (it can add GroupNorm partials itself)
@@ -395,5 +396,8 @@ int launch_linear(const float* in, int B, int I, const float* W, const float* bi
                   int in_mode, int out_silu, hipStream_t st);
 
 int launch_sampler(const s3d_sampler_args& a, hipStream_t st);
+int launch_sampler_known(const s3d_sampler_args& a, const s3d_known_region& kr, hipStream_t st);
+int launch_renoise(const float* xprev, const float* er, const float* ktab, const int64_t* t, int T, long long batch, long long per_sample,
+                   float* xt, hipStream_t st);
 
 }  // namespace s3d

@@ -1113,8 +1113,19 @@ constexpr int kOhPx = 64;
 // CARRY (FUSED only): the block then runs the NEXT step's in_conv on the 64 x_{t-1} pixels it has just formed —
 // k_in_conv_lds<32, CQ>'s body twice (its blocks own 32 pixels), fed from LDS instead of from memory: the same products in the same
 // order, the same thread mapping and the same per-block GroupNorm partial sums, written to the tensors the next forward reads.
-template <int CQ, bool FUSED, bool CARRY = false>          // channel quads per pixel: 16, 32 or 64
-__global__ __launch_bounds__(256, 3) void k_out_head_px(OutHeadArgs a, int segs0, int segs1, int segs2, s3d_sampler_args sa, InConvCarry cy = InConvCarry()) {
+// KNOWN (FUSED only): the known-region blend of s3d_sampler.h follows the update at all three places it is applied
+// (pixel loop, the two pre-fetched corner elements, the corner's tail loop); with CARRY the in_conv tail reads the blended values.
+// y0 / mask / eps_known are read where they are used, not ahead with x_t and eps: twelve more registers held across the
+// contraction would not fit the 168 of three blocks per CU at CQ = 32.  A template parameter and a kernel argument that is an empty
+// struct without it: the instantiations of the default path keep their code.  The KNOWN instantiations store no model output and no
+// posterior mean and know no x0 replacement (a step that asks for the model output runs head, then k_sampler_known; launch_out_head):
+// the three known-region pointers take the scalar registers those pointers held — with both sets the kernel spilled scalars.
+template <bool KNOWN> struct KnownArg {};
+template <> struct KnownArg<true> { s3d_known_region kr; };
+template <int CQ, bool FUSED, bool CARRY = false, bool KNOWN = false>          // channel quads per pixel: 16, 32 or 64
+__global__ __launch_bounds__(256, 3) void k_out_head_px(OutHeadArgs a, int segs0, int segs1, int segs2, s3d_sampler_args sa, InConvCarry cy = InConvCarry(),
+                                                        KnownArg<KNOWN> kn = KnownArg<KNOWN>()) {
+    static_assert(FUSED || !KNOWN, "the blend belongs to the sampler update");
     constexpr int C = 4 * CQ, CPW = C / 4, LANES = 256 / CQ, LD = C + 4;
     __shared__ __attribute__((aligned(16))) float sx[kOhPx * LD];
     __shared__ float sp[4][16][kOhPx];
@@ -1177,6 +1188,8 @@ __global__ __launch_bounds__(256, 3) void k_out_head_px(OutHeadArgs a, int segs0
         }
         sc = sampler_coef(sa, int(sa.t[b]));                  // (t, then the seven table entries it selects: two dependent round trips, behind the requests above)
     }
+    KnownCoef kc{0.f, 0.f};
+    if constexpr (KNOWN) kc = known_coef(kn.kr, sa.T, int(sa.t[b]));
     const float* st = sst;
     if (a.mr) {
         if (tid < 32) {
@@ -1264,9 +1277,11 @@ __global__ __launch_bounds__(256, 3) void k_out_head_px(OutHeadArgs a, int segs0
         const float v = ((sp[0][co][e] + sp[1][co][e]) + (sp[2][co][e] + sp[3][co][e])) + a.bias[p * a.Cout + co];
         const int sy = p == 2 ? a.H + line : line, sx0 = p == 1 ? a.W + s0 : s0;
         const size_t o = ((size_t(b) * a.Cout + co) * Hc + sy) * Wc + sx0 + e;
-        if (!FUSED || a.out) a.out[o] = v;
+        if (!FUSED || (!KNOWN && a.out)) a.out[o] = v;
         if (FUSED) {
-            const float xprev = sampler_element(sa, sc, (long long)o, v, pre_x[k], pre_n[k]);
+            float xprev;
+            if constexpr (KNOWN) xprev = sampler_element_known<true>(sa, sc, kn.kr, kc, (long long)o, v, pre_x[k], pre_n[k]);
+            else xprev = sampler_element(sa, sc, (long long)o, v, pre_x[k], pre_n[k]);
             if (CARRY) xnext[k] = xprev;
         }
     }
@@ -1360,14 +1375,16 @@ __global__ __launch_bounds__(256, 3) void k_out_head_px(OutHeadArgs a, int segs0
 #pragma unroll
     for (int u = 0; u < CU_; ++u) {
         if (corner_i1 + u * corner_stride >= n_corner) continue;
-        if (!FUSED || a.out) a.out[corner_o[u]] = 0.f;
-        if (FUSED) sampler_element(sa, sc, (long long)corner_o[u], 0.f, corner_x[u], corner_n[u]);
+        if (!FUSED || (!KNOWN && a.out)) a.out[corner_o[u]] = 0.f;
+        if constexpr (KNOWN) sampler_element_known<true>(sa, sc, kn.kr, kc, (long long)corner_o[u], 0.f, corner_x[u], corner_n[u]);
+        else if (FUSED) sampler_element(sa, sc, (long long)corner_o[u], 0.f, corner_x[u], corner_n[u]);
     }
     for (long long i = corner_i1 + CU_ * corner_stride; i < n_corner; i += corner_stride) {      // (shapes with D*D > 2 x the plane pixels)
         const int dx = int(i % a.D), dy = int((i / a.D) % a.D), co = int(i / a.D / a.D);
         const size_t o = ((size_t(b) * a.Cout + co) * Hc + a.H + dy) * Wc + a.W + dx;
-        if (!FUSED || a.out) a.out[o] = 0.f;
-        if (FUSED) sampler_element(sa, sc, (long long)o, 0.f);
+        if (!FUSED || (!KNOWN && a.out)) a.out[o] = 0.f;
+        if constexpr (KNOWN) sampler_element_known<true>(sa, sc, kn.kr, kc, (long long)o, 0.f);
+        else if (FUSED) sampler_element(sa, sc, (long long)o, 0.f);
     }
 }
 static bool out_head_px_form(int C, int Cout) { return (C == 64 || C == 128 || C == 256) && Cout <= 16; }      // (other widths: k_out_head)
@@ -1389,7 +1406,7 @@ bool out_head_adds_parts(const GnPartials& part, int C, int Cout) { return out_h
 bool out_head_can_carry(int C, int Cin, int Cout_head) { return out_head_px_form(C, Cout_head) && Cin <= 16 && Cin == Cout_head; }
 int launch_out_head(const Tri& x, int B, GnStats stats, const ActArgs& aa, const float* w, const float* bias,
                     int Cout, int H, int W, int D, float* out, hipStream_t st, const s3d_sampler_args* fuse, const GnPartials* part,
-                    const InConvCarry* carry) {
+                    const InConvCarry* carry, const s3d_known_region* known) {
     OutHeadArgs a;
     int maxpix = D * D ? 1 : 0;
     for (int p = 0; p < 3; ++p) {
@@ -1407,8 +1424,10 @@ int launch_out_head(const Tri& x, int B, GnStats stats, const ActArgs& aa, const
     S3D_CHECK(x.C % 32 == 0 && a.cq <= 1024, S3D_ERR_INVALID, "out head: C=%d unsupported", x.C);
     if (!maxpix || !B) return 0;
     if (fuse) S3D_CHECK(fuse->batch == B && fuse->per_sample == (long long)Cout * (H + D) * (W + D), S3D_ERR_INVALID, "out head: the sampler step does not match the model output's shape");
-    const bool fuse_here = fuse && out_head_fuses_sampler(x.C, Cout, B);
+    if (known) S3D_CHECK(!fuse || !fuse->mean || !out_head_fuses_sampler(x.C, Cout, B) || out, S3D_ERR_INVALID, "out head: a known-region step that wants the posterior mean needs a model-output buffer");
+    const bool fuse_here = fuse && out_head_fuses_sampler(x.C, Cout, B) && !(known && out);
     if (fuse && !fuse_here) S3D_CHECK(out, S3D_ERR_INVALID, "out head: this step needs a model-output buffer");
+    if (known) S3D_CHECK(fuse && fuse->sample && fuse->mode != S3D_STEP_MEAN_ONLY && !fuse->y0 && !fuse->mask, S3D_ERR_INVALID, "out head: a known region needs a DDPM / DDIM step without the x0 replacement");
     if (out_head_px_form(x.C, Cout)) {
         int segs[3];
         for (int p = 0; p < 3; ++p) { const int len = p == 2 ? a.h[p] : a.wd[p], lines = p == 2 ? a.wd[p] : a.h[p]; segs[p] = lines * cdiv(len, kOhPx); }
@@ -1416,7 +1435,20 @@ int launch_out_head(const Tri& x, int B, GnStats stats, const ActArgs& aa, const
         s3d_sampler_args sa;
         memset(&sa, 0, sizeof sa);
         if (carry) S3D_CHECK(fuse_here && out_head_can_carry(x.C, carry->Cin, Cout) && fuse->mode != S3D_STEP_MEAN_ONLY, S3D_ERR_INVALID, "out head: this step cannot carry the next in_conv");
-        if (fuse_here && carry) {
+        if (fuse_here && known) {
+            sa = *fuse;
+            KnownArg<true> kn; kn.kr = *known;
+            const InConvCarry cy = carry ? *carry : InConvCarry();
+            if (carry) {
+                if (x.C == 64) hipLaunchKernelGGL((k_out_head_px<16, true, true, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, kn);
+                else if (x.C == 128) hipLaunchKernelGGL((k_out_head_px<32, true, true, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, kn);
+                else hipLaunchKernelGGL((k_out_head_px<64, true, true, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, kn);
+            } else {
+                if (x.C == 64) hipLaunchKernelGGL((k_out_head_px<16, true, false, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, kn);
+                else if (x.C == 128) hipLaunchKernelGGL((k_out_head_px<32, true, false, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, kn);
+                else hipLaunchKernelGGL((k_out_head_px<64, true, false, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, kn);
+            }
+        } else if (fuse_here && carry) {
             sa = *fuse;
             if (x.C == 64) hipLaunchKernelGGL((k_out_head_px<16, true, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, *carry);
             else if (x.C == 128) hipLaunchKernelGGL((k_out_head_px<32, true, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, *carry);
@@ -1432,14 +1464,14 @@ int launch_out_head(const Tri& x, int B, GnStats stats, const ActArgs& aa, const
             else hipLaunchKernelGGL((k_out_head_px<64, false>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa);
         }
         S3D_HIP(hipGetLastError());
-        if (fuse && !fuse_here) { s3d_sampler_args sb = *fuse; sb.model_out = out; return launch_sampler(sb, st); }
+        if (fuse && !fuse_here) { s3d_sampler_args sb = *fuse; sb.model_out = out; return known ? launch_sampler_known(sb, *known, st) : launch_sampler(sb, st); }
         return 0;
     }
     S3D_CHECK(out, S3D_ERR_INVALID, "out head: this width needs a model-output buffer");
     size_t shm = std::max(size_t(64), size_t(a.ppb) * kOutCo * (a.cq + 1)) * sizeof(float);
     hipLaunchKernelGGL(k_out_head, dim3(cdiv(maxpix, a.ppb), 4, B), dim3(a.cq * a.ppb), shm, st, a);
     S3D_HIP(hipGetLastError());
-    if (fuse) { s3d_sampler_args sa = *fuse; sa.model_out = out; return launch_sampler(sa, st); }
+    if (fuse) { s3d_sampler_args sa = *fuse; sa.model_out = out; return known ? launch_sampler_known(sa, *known, st) : launch_sampler(sa, st); }
     return 0;
 }
 
@@ -1505,6 +1537,42 @@ int launch_sampler(const s3d_sampler_args& a, hipStream_t st) {
     if (n <= 0) return 0;
     unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 4096);
     hipLaunchKernelGGL(k_sampler, dim3(blocks), dim3(256), 0, st, a);
+    S3D_HIP(hipGetLastError());
+    return 0;
+}
+// ... with the known-region blend (s3d_sampler_step_known; widths the pixel-chunk head does not take)
+__global__ void k_sampler_known(s3d_sampler_args a, s3d_known_region kr) {
+    const long long n = a.batch * a.per_sample;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int b = int(i / a.per_sample), t = int(a.t[b]);
+        const SamplerCoef c = sampler_coef(a, t);
+        const KnownCoef kc = known_coef(kr, a.T, t);
+        sampler_element_known(a, c, kr, kc, i, a.model_out[i]);
+    }
+}
+int launch_sampler_known(const s3d_sampler_args& a, const s3d_known_region& kr, hipStream_t st) {
+    const long long n = a.batch * a.per_sample;
+    if (n <= 0) return 0;
+    unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_sampler_known, dim3(blocks), dim3(256), 0, st, a, kr);
+    S3D_HIP(hipGetLastError());
+    return 0;
+}
+// x_t = (sqrt(1 - beta_t) * x_prev) + (sqrt(beta_t) * er): one level of re-noising between two repeats of a known-region step
+__global__ void k_renoise(const float* __restrict__ xprev, const float* __restrict__ er, const float* __restrict__ ktab,
+                          const int64_t* __restrict__ t, int T, long long batch, long long per_sample, float* __restrict__ xt) {
+    const long long n = batch * per_sample;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int ti = int(t[i / per_sample]);
+        xt[i] = renoise_element(ktab[S3D_KTAB_SQRT_1M_BETA * T + ti], ktab[S3D_KTAB_SQRT_BETA * T + ti], xprev[i], er[i]);
+    }
+}
+int launch_renoise(const float* xprev, const float* er, const float* ktab, const int64_t* t, int T, long long batch, long long per_sample,
+                   float* xt, hipStream_t st) {
+    const long long n = batch * per_sample;
+    if (n <= 0) return 0;
+    unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_renoise, dim3(blocks), dim3(256), 0, st, xprev, er, ktab, t, T, batch, per_sample, xt);
     S3D_HIP(hipGetLastError());
     return 0;
 }

@@ -155,4 +155,26 @@ int s3d_sampler_step(const s3d_sampler_args* a, void* stream) {
     return launch_sampler(*a, static_cast<hipStream_t>(stream));
 }
 
+int s3d_sampler_step_known(const s3d_sampler_args* a, const s3d_known_region* known, void* stream) {
+    using namespace s3d;
+    S3D_CHECK(a != nullptr && known != nullptr, S3D_ERR_INVALID, "sampler_step_known: null args");
+    S3D_CHECK(a->model_out && a->x && a->t && a->tables && a->pred_xstart && a->sample, S3D_ERR_INVALID,
+              "sampler_step_known: model_out, x, t, tables, sample and pred_xstart are required");
+    S3D_CHECK(a->mode == S3D_STEP_DDPM || a->mode == S3D_STEP_DDIM, S3D_ERR_INVALID, "sampler_step_known: a DDPM or DDIM step, not mode %d", a->mode);
+    S3D_CHECK(a->mode != S3D_STEP_DDPM || a->noise, S3D_ERR_INVALID, "sampler_step_known: DDPM step needs noise");
+    S3D_CHECK(a->mode != S3D_STEP_DDIM || a->eta == 0.f || a->noise, S3D_ERR_INVALID, "sampler_step_known: eta>0 needs noise");
+    S3D_CHECK(!a->y0 && !a->mask, S3D_ERR_INVALID, "sampler_step_known: the step's own y0 / mask (x0 replacement) cannot be combined with a known region");
+    S3D_CHECK(known->y0 && known->mask && known->noise && known->tables, S3D_ERR_INVALID, "sampler_step_known: y0, mask, noise and tables are required");
+    S3D_CHECK(a->T > 0 && a->batch >= 0 && a->per_sample >= 0, S3D_ERR_INVALID, "sampler_step_known: bad sizes");
+    return launch_sampler_known(*a, *known, static_cast<hipStream_t>(stream));
+}
+
+int s3d_sampler_renoise(const float* x_prev, const float* noise, const float* known_tables, const int64_t* t, int32_t T, int64_t batch,
+                        int64_t per_sample, float* x_t, void* stream) {
+    using namespace s3d;
+    S3D_CHECK(x_prev && noise && known_tables && t && x_t, S3D_ERR_INVALID, "sampler_renoise: null argument");
+    S3D_CHECK(T > 0 && batch >= 0 && per_sample >= 0, S3D_ERR_INVALID, "sampler_renoise: bad sizes");
+    return launch_renoise(x_prev, noise, known_tables, t, T, batch, per_sample, x_t, static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

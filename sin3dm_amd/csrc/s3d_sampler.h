@@ -37,6 +37,10 @@ __device__ __forceinline__ SamplerCoef sampler_coef(const s3d_sampler_args& a, i
 
 // element i of the step: mo = the model's output there, xt = x_t[i], nv = the step's eps there (0 when the step has none).
 // Writes sample / pred_xstart / mean as the mode asks; returns the value written to `sample` (x_{t-1}; 0 for MEAN_ONLY).
+// STORE = false (sampler_element_known): `sample` is left to the caller, which stores the blended value once.
+// LEAN (the output head's known-region instantiations, which sit at the scalar-register limit): the caller vouches that a.mean, a.y0
+// and a.mask are null — the posterior-mean output and the x0 replacement are compiled out with the registers that held their pointers.
+template <bool STORE = true, bool LEAN = false>
 __device__ __forceinline__ float sampler_element(const s3d_sampler_args& a, const SamplerCoef& c, long long i, float mo, float xt, float nv) {
 #pragma clang fp contract(off)
     float x0 = mo;
@@ -47,7 +51,7 @@ __device__ __forceinline__ float sampler_element(const s3d_sampler_args& a, cons
     }
     if (a.clip_denoised) x0 = fminf(fmaxf(x0, -1.f), 1.f);
     if (a.mode == S3D_STEP_DDIM) {
-        if (a.y0 && a.mask) {                                                                               // in-painting (:568-577)
+        if (!LEAN && a.y0 && a.mask) {                                                                               // in-painting (:568-577)
             const float m = a.mask[i];
             const float q1 = m * a.y0[i], q2 = (1.f - m) * x0;
             const float mixed = q1 + q2;
@@ -60,19 +64,60 @@ __device__ __forceinline__ float sampler_element(const s3d_sampler_args& a, cons
         const float mean_pred = m1 + m2;
         const float nzs = (c.nz * c.sigma) * nv;
         xprev = mean_pred + nzs;
-        a.sample[i] = xprev;
+        if (STORE) a.sample[i] = xprev;
         a.pred_xstart[i] = x0;
     } else {
         const float m1 = c.c1 * x0, m2 = c.c2 * xt;                                                         // q_posterior_mean_variance (:218-221)
         const float mean = m1 + m2;
-        if (a.mean) a.mean[i] = mean;
+        if (!LEAN && a.mean) a.mean[i] = mean;
         a.pred_xstart[i] = x0;
-        if (a.mode == S3D_STEP_DDPM) { const float nzs = c.sig_ddpm * nv; xprev = mean + nzs; a.sample[i] = xprev; }
+        if (a.mode == S3D_STEP_DDPM) { const float nzs = c.sig_ddpm * nv; xprev = mean + nzs; if (STORE) a.sample[i] = xprev; }
     }
     return xprev;
 }
 __device__ __forceinline__ float sampler_element(const s3d_sampler_args& a, const SamplerCoef& c, long long i, float mo) {
     return sampler_element(a, c, i, mo, a.x[i], a.noise ? a.noise[i] : 0.f);
+}
+
+// Known-region sampling (outpainting / local editing; our own design, the reference has no such code): the
+// known part of x_{t-1} is the source latent noised to level t - 1,
+//     k      = (sa * y0) + (sb * ek)                     q_sample(y0, t - 1, ek); t == 0: sa = 1, sb = 0 (the table says so)
+//     x_prev = (m * k) + ((1 - m) * x_prev_plain)
+// every product and sum rounded on its own, in this order.  sa / sb are fp32 casts of float64 table values: derived here from
+// S3D_TAB_ACP_PREV they would be one more rounding away from the float64 schedule.
+struct KnownCoef { float sa, sb; };
+__device__ __forceinline__ KnownCoef known_coef(const s3d_known_region& kr, int T, int t) {
+    KnownCoef k;
+    k.sa = kr.tables[S3D_KTAB_SQRT_ACP_PREV * T + t]; k.sb = kr.tables[S3D_KTAB_SQRT_1M_ACP_PREV * T + t];
+    return k;
+}
+__device__ __forceinline__ float known_blend(const KnownCoef& kc, float y0, float m, float ek, float xprev_plain) {
+#pragma clang fp contract(off)
+    const float k1 = kc.sa * y0, k2 = kc.sb * ek;
+    const float k = k1 + k2;
+    const float b1 = m * k, b2 = (1.f - m) * xprev_plain;
+    return b1 + b2;
+}
+// sampler_element with the blend: pred_xstart / mean as without it, `sample` stored once, blended; returns it.
+template <bool LEAN = false>
+__device__ __forceinline__ float sampler_element_known(const s3d_sampler_args& a, const SamplerCoef& c, const s3d_known_region& kr,
+                                                       const KnownCoef& kc, long long i, float mo, float xt, float nv) {
+    const float y0 = kr.y0[i], m = kr.mask[i], ek = kr.noise[i];             // (requested ahead of the update's arithmetic)
+    const float plain = sampler_element<false, LEAN>(a, c, i, mo, xt, nv);
+    const float xprev = known_blend(kc, y0, m, ek, plain);
+    a.sample[i] = xprev;
+    return xprev;
+}
+template <bool LEAN = false>
+__device__ __forceinline__ float sampler_element_known(const s3d_sampler_args& a, const SamplerCoef& c, const s3d_known_region& kr,
+                                                       const KnownCoef& kc, long long i, float mo) {
+    return sampler_element_known<LEAN>(a, c, kr, kc, i, mo, a.x[i], a.noise ? a.noise[i] : 0.f);
+}
+// one level of re-noising between two repeats of a step: x_t = (sqrt(1 - beta_t) * x_prev) + (sqrt(beta_t) * er)
+__device__ __forceinline__ float renoise_element(float c1mb, float cb, float xprev, float er) {
+#pragma clang fp contract(off)
+    const float p1 = c1mb * xprev, p2 = cb * er;
+    return p1 + p2;
 }
 
 }  // namespace s3d

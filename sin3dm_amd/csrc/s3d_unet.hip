@@ -235,7 +235,8 @@ int pack_all(s3d_unet* m) {
 // ------------------------------------------------------------------ forward
 
 int run_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, hipStream_t st,
-                Tape* tape, const float* ext_film, int ext_film_stride, const s3d_sampler_args* fuse, int carry_flags) {
+                Tape* tape, const float* ext_film, int ext_film_stride, const s3d_sampler_args* fuse, int carry_flags,
+                const s3d_known_region* known) {
     const s3d_unet_cfg& c = m->cfg;
     const int mc = c.model_channels, ted = 4 * mc;
     Fwd f{m, B, st, nullptr};
@@ -381,14 +382,14 @@ int run_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W
         // S3D_CARRY_OUT: the head also runs the NEXT step's in_conv on the x_{t-1} it forms (unet_triplane.py:378, 482: a pointwise
         // TriplaneConv) into h0 / part0 — dead since this step's first block consumed them
         InConvCarry cy;
-        const bool give = (carry_flags & S3D_CARRY_OUT) && fuse && fuse->sample && fuse->mode != S3D_STEP_MEAN_ONLY && !tape && part0.p &&
+        const bool give = (carry_flags & S3D_CARRY_OUT) && fuse && !(known && out) && fuse->sample && fuse->mode != S3D_STEP_MEAN_ONLY && !tape && part0.p &&
                           h.C == h0.C && out_head_fuses_sampler(h.C, c.out_channels, B) && out_head_can_carry(h.C, c.in_channels, c.out_channels);
         if (give) {
             cy.wT = m->dev(m->in_wT); cy.bias = m->dev(m->in_b); cy.part = part0.p; cy.maxparts = part0.maxparts; cy.Cin = c.in_channels;
             for (int p = 0; p < 3; ++p) cy.out[p] = h0.p[p];
         }
         S3D_TRY(launch_out_head(h, B, stats, aa, m->dev(m->out_w), m->dev(m->out_b), c.out_channels, H, W, D, out, st, fuse, head_adds ? &h.part : nullptr,
-                                give ? &cy : nullptr));
+                                give ? &cy : nullptr, known));
         if (give) { m->carry.valid = true; m->carry.sample = fuse->sample; memcpy(m->carry.key, ckey, sizeof ckey); }
     }
     return 0;
@@ -443,7 +444,8 @@ int s3d_unet_set_param(s3d_unet* m, const char* name, const float* data, const i
 }
 
 static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, void* stream,
-                        const float* ext_film, int ext_film_stride, const s3d_sampler_args* fuse = nullptr, int carry_flags = 0);
+                        const float* ext_film, int ext_film_stride, const s3d_sampler_args* fuse = nullptr, int carry_flags = 0,
+                        const s3d_known_region* known = nullptr);
 
 int s3d_unet_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, void* stream) {
     S3D_CHECK(m && x && t && out, S3D_ERR_INVALID, "unet_forward: null argument");
@@ -513,10 +515,27 @@ int s3d_unet_step_film_carry(s3d_unet* m, const float* film, int film_stride, in
     return forward_impl(m, step->x, nullptr, B, H, W, D, model_out, stream, film, film_stride, step, carry_flags);
 }
 
+int s3d_unet_step_film_known(s3d_unet* m, const float* film, int film_stride, int B, int H, int W, int D, const s3d_sampler_args* step,
+                             const s3d_known_region* known, float* model_out, void* stream, int carry_flags) {
+    S3D_CHECK(m && film && step && known, S3D_ERR_INVALID, "unet_step_film_known: null argument");
+    S3D_CHECK((carry_flags & ~(S3D_CARRY_OUT | S3D_CARRY_IN)) == 0, S3D_ERR_INVALID, "unet_step_film_known: unknown flag bits %d", carry_flags);
+    S3D_CHECK(film_stride == 0 || film_stride == m->film_total, S3D_ERR_INVALID, "unet_step_film_known: film_stride must be 0 or %d", m->film_total);
+    S3D_CHECK(step->x && step->t && step->tables && step->pred_xstart && step->sample && (step->mode == S3D_STEP_DDPM || step->mode == S3D_STEP_DDIM) &&
+                  (step->mode != S3D_STEP_DDPM || step->noise) && (step->mode != S3D_STEP_DDIM || step->eta == 0.f || step->noise),
+              S3D_ERR_INVALID, "unet_step_film_known: incomplete sampler arguments (a DDPM or DDIM step)");
+    S3D_CHECK(!step->mean || model_out, S3D_ERR_INVALID, "unet_step_film_known: the posterior mean is only written by a step that also stores the model output (model_out != NULL)");
+    S3D_CHECK(!step->y0 && !step->mask, S3D_ERR_INVALID, "unet_step_film_known: the step's own y0 / mask (x0 replacement) cannot be combined with a known region");
+    S3D_CHECK(known->y0 && known->mask && known->noise && known->tables, S3D_ERR_INVALID, "unet_step_film_known: y0, mask, noise and tables are required");
+    S3D_CHECK(step->batch == B && step->per_sample == (long long)m->cfg.out_channels * (H + D) * (W + D) && m->cfg.in_channels == m->cfg.out_channels,
+              S3D_ERR_INVALID, "unet_step_film_known: the step's shape is not the model's");
+    return forward_impl(m, step->x, nullptr, B, H, W, D, model_out, stream, film, film_stride, step, carry_flags, known);
+}
+
 }  // extern "C"
 
 static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, void* stream,
-                        const float* ext_film, int ext_film_stride, const s3d_sampler_args* fuse, int carry_flags) {
+                        const float* ext_film, int ext_film_stride, const s3d_sampler_args* fuse, int carry_flags,
+                        const s3d_known_region* known) {
     S3D_CHECK(B >= 1 && H >= 1 && W >= 1 && D >= 1, S3D_ERR_INVALID, "unet_forward: B,H,W,D must be >= 1");
     if (!m->packed) S3D_TRY(pack_all(m));                             // (drops a carried in_conv: it was formed with the old weights)
     m->tape.valid = false;                    // the workspace is shared with the training tape
@@ -530,7 +549,7 @@ static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int 
     if (!same || m->inf_high > m->arena.buf.cap) {
         m->arena.measuring = true;
         m->arena.high = 0;
-        rc = run_forward(m, x, t, B, H, W, D, out, st, nullptr, ext_film, ext_film_stride, fuse);
+        rc = run_forward(m, x, t, B, H, W, D, out, st, nullptr, ext_film, ext_film_stride, fuse, 0, known);
         m->arena.measuring = false;
         if (rc) return rc;
         m->inf_high = m->arena.high;
@@ -545,7 +564,7 @@ static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int 
     ++m->fwd_count;
     if (m->prof_now) ++m->prof_forwards;
     m->arena.peak = 0;
-    rc = run_forward(m, x, t, B, H, W, D, out, st, nullptr, ext_film, ext_film_stride, fuse, carry_flags);
+    rc = run_forward(m, x, t, B, H, W, D, out, st, nullptr, ext_film, ext_film_stride, fuse, carry_flags, known);
     m->prof_now = false;
     if (rc) return rc;
     return workspace_overrun("unet_forward", m->arena.peak, m->inf_high);

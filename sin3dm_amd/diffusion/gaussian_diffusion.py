@@ -11,6 +11,7 @@ reference; training_losses with LossType.KL raises there too, :793).
 """
 from __future__ import annotations
 
+import collections
 import enum
 import math
 
@@ -84,6 +85,26 @@ class HostTimesteps(th.Tensor):
         return out
 
 
+class KnownRegion(collections.namedtuple("KnownRegion", ["y0", "mask"])):
+    """The known part of a sample for the loops' `known=`: `y0` the source latent laid out on the target canvas, `mask` in [0, 1]
+    (1 = keep y0, 0 = generate; soft edges allowed), both [C, H+D, W+D], [1, C, H+D, W+D] or the full batch shape
+    (utils/region_util.py builds them from boxes on the volume)."""
+    __slots__ = ()
+
+
+def known_region_schedule(num_timesteps, resample=1):
+    """The evaluations of a sampling loop with `resample` repeats per step, as (i, renoise_follows) in the order they run: for
+    i = T-1 .. 1 the step runs `resample` times with one re-noising x_i = renoise(x_{i-1}, i) between two repeats, at i = 0 it runs
+    once — (T - 1) * resample + 1 model evaluations.  Pure host code."""
+    resample = int(resample)
+    if resample < 1:
+        raise ValueError("resample must be >= 1")
+    for i in range(int(num_timesteps) - 1, -1, -1):
+        reps = resample if i > 0 else 1
+        for r in range(reps):
+            yield i, r < reps - 1
+
+
 def host_values_of(t):
     return getattr(t, "host_values", None) if isinstance(t, HostTimesteps) else None
 
@@ -149,6 +170,18 @@ class GaussianDiffusion:
             self._dev_tables[key] = tab
         return tab
 
+    def _known_tables(self, device):
+        """fp32 device image [S3D_KTAB_ROWS][T] for the known-region blend and the re-noise kernel: float64 values cast once (in
+        fp32, 1 - acp / acp_prev would lose three digits of beta to cancellation)."""
+        key = "known/" + str(device)
+        tab = self._dev_tables.get(key)
+        if tab is None:
+            rows = np.stack([np.sqrt(self.alphas_cumprod_prev), np.sqrt(1.0 - self.alphas_cumprod_prev),
+                             np.sqrt(1.0 - self.betas), np.sqrt(self.betas)])
+            tab = th.from_numpy(rows.astype(np.float32)).contiguous().to(device)
+            self._dev_tables[key] = tab
+        return tab
+
     def _mean_type_code(self):
         if self.model_mean_type == ModelMeanType.START_X:
             return _lib.MEAN_START_X
@@ -185,11 +218,13 @@ class GaussianDiffusion:
 
     # ------------------------------------------------------------------ one fused update
     def _step(self, mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta=0.0, y0=None, mask=None,
-              is_mask_t0=False, want_mean=False, fuse=False, noise=None, carry=0):
+              is_mask_t0=False, want_mean=False, fuse=False, noise=None, carry=0, known=None):
         """fuse (the sampling loops): when the denoiser offers `denoise_step` and the timestep values are known on the host,
         the UNet's output head applies the update itself — one launch instead of head + sampler kernel, and the model output
         never reaches memory (SURVEY.md section 2b, K8 + K9).  noise: this step's eps when the caller drew it ahead.
-        carry (fused steps of the loops only): _lib.CARRY_OUT / CARRY_IN of TriplaneUNetModelSmall.denoise_step."""
+        carry (fused steps of the loops only): _lib.CARRY_OUT / CARRY_IN of TriplaneUNetModelSmall.denoise_step.
+        known: (y0, mask, eps_known), each of x's shape, fp32, contiguous, on x's device — the known-region blend follows the update
+        in the same launch (s3d_unet_step_film_known / s3d_sampler_step_known)."""
         _lib.require_gpu(x)
         if model_kwargs is None:
             model_kwargs = {}
@@ -223,6 +258,15 @@ class GaussianDiffusion:
             y0, mask = y0.contiguous().float(), mask.contiguous().float()
         else:
             y0 = mask = None
+        kr = None
+        if known is not None:
+            if y0 is not None:
+                raise ValueError("known= cannot be combined with the DDIM x0 replacement (y0= / mask=)")
+            assert mode in (_lib.STEP_DDPM, _lib.STEP_DDIM) and not want_mean
+            for k in known:
+                assert k.shape == x.shape and k.dtype == th.float32 and k.is_contiguous() and k.device == x.device
+            kr = _lib.KnownRegionArgs(y0=known[0].data_ptr(), mask=known[1].data_ptr(), noise=known[2].data_ptr(),
+                                      tables=self._known_tables(x.device).data_ptr())
         tab = self._tables(x.device)
         t64 = t.to(device=x.device, dtype=th.int64).contiguous()
         a = _lib.SamplerArgs(mode=mode, mean_type=self._mean_type_code(), clip_denoised=int(bool(clip_denoised)),
@@ -234,6 +278,9 @@ class GaussianDiffusion:
                              mask=mask.data_ptr() if mask is not None else None,
                              sample=sample.data_ptr() if sample is not None else None, pred_xstart=pred.data_ptr(),
                              mean=mean.data_ptr() if mean is not None else None)
+        if fused and kr is not None:
+            step_fn(x, ts, a, carry=carry if getattr(model, "carries_in_conv", False) else 0, known=kr, **model_kwargs)
+            return sample, pred, mean
         if fused:
             if carry and getattr(model, "carries_in_conv", False):
                 step_fn(x, ts, a, carry=carry, **model_kwargs)
@@ -241,8 +288,26 @@ class GaussianDiffusion:
                 step_fn(x, ts, a, **model_kwargs)
             return sample, pred, mean
         with th.cuda.device(x.device):
-            _lib.check(_lib.load().s3d_sampler_step(a, _lib.stream_ptr()))
+            if kr is not None:
+                _lib.check(_lib.load().s3d_sampler_step_known(a, kr, _lib.stream_ptr()))
+            else:
+                _lib.check(_lib.load().s3d_sampler_step(a, _lib.stream_ptr()))
         return sample, pred, mean
+
+    def renoise(self, x_prev, t, noise):
+        """One level of re-noising, x_t = sqrt(1 - beta_t) * x_{t-1} + sqrt(beta_t) * noise (t: [B] indices into this schedule):
+        what the loops run between two repeats of a step (`resample`).  One element-wise kernel, every operation rounded."""
+        _lib.require_gpu(x_prev)
+        x_prev = x_prev.contiguous().float()
+        noise = noise.contiguous().float()
+        assert noise.shape == x_prev.shape and t.shape == (x_prev.shape[0],)
+        t64 = t.to(device=x_prev.device, dtype=th.int64).contiguous()
+        out = th.empty_like(x_prev)
+        with th.cuda.device(x_prev.device):
+            _lib.check(_lib.load().s3d_sampler_renoise(_lib.ptr(x_prev), _lib.ptr(noise), _lib.ptr(self._known_tables(x_prev.device)),
+                                                       _lib.ptr(t64), self.num_timesteps, x_prev.shape[0], x_prev[0].numel(),
+                                                       _lib.ptr(out), _lib.stream_ptr()))
+        return out
 
     def p_mean_variance(self, model, x, t, clip_denoised=True, denoised_fn=None, model_kwargs=None):
         """p(x_{t-1} | x_t) and the x_0 prediction (:233-327)."""
@@ -299,7 +364,7 @@ class GaussianDiffusion:
         return per[0].unsqueeze(len(pre)) if len(per) == 1 else th.stack(per, dim=len(pre))
 
     def _loop(self, mode, model, shape, noise, device, progress, clip_denoised=True, denoised_fn=None, cond_fn=None,
-              model_kwargs=None, generator=None, **kw):
+              model_kwargs=None, generator=None, known=None, resample=1, **kw):
         """Shared body of p_sample_loop_progressive / ddim_sample_loop_progressive (:488-536, 687-734).  Every step is ONE call
         into the library when the denoiser is the HIP UNet (`_step(fuse=True)`); the per-step eps comes from the device
         generator like the reference's randn_like on a GPU, drawn for many steps at a time (`noise_fn`, if set, is asked every
@@ -313,7 +378,13 @@ class GaussianDiffusion:
         generator — a torch.Generator, or one per batch element (`_randn`); with per-element generators the chunk length is
         fixed per SAMPLE, so a sample's whole trajectory depends on its generator only: not on the batch it is in, not on the
         chain / stream / GPU it runs on (sample_loop_chains, sin3dm_amd.sample).  A cpu_stream.TorchCpuStream (or one per batch
-        element) makes the run consume torch's CPU generator as the reference does: same seed, same sample."""
+        element) makes the run consume torch's CPU generator as the reference does: same seed, same sample.
+        known (KnownRegion) / resample (not in the reference): after every step the known part of x_{t-1} is
+        replaced by y0 noised to level t - 1, in the step's own launch; with resample = r every step but the last runs r times with a
+        re-noising between two repeats (known_region_schedule) and every evaluation is yielded.  Draws, each of x's shape and all from
+        the loop's one source (generator / noise_fn) in this order: the step's eps, the blend's eps_known, then the re-noising's eps
+        when one follows.  A step that a re-noising follows leaves no in_conv behind (no CARRY_OUT) and the repeated step reads a
+        tensor no step wrote (no CARRY_IN).  Defaults: today's launches and bits."""
         if cond_fn is not None:
             raise NotImplementedError("cond_fn guidance is out of scope (no caller in the reference)")
         if device is None:
@@ -325,11 +396,18 @@ class GaussianDiffusion:
         # drawn at once are the same k calls, so the chunks do not change the values.  The first chunk is one step long, the
         # following ones are drawn on a side stream one chunk ahead of the steps that read them.
         cpu_noise = is_cpu_stream(generator) and self.noise_fn is None
+        if known is not None and (kw.get("y0") is not None or kw.get("mask") is not None):
+            raise ValueError("known= cannot be combined with the DDIM x0 replacement (y0= / mask=)")
         img = noise if noise is not None else self._randn(shape, device, generator)
-        indices = list(range(self.num_timesteps))[::-1]
+        evals = list(known_region_schedule(self.num_timesteps, resample))
+        n_draws = sum(1 + (known is not None) + int(rn) for _, rn in evals)     # x-shaped N(0,1) tensors this loop consumes after x_T
+        if known is not None:
+            # y0 / mask given for one sample are expanded over the batch here, once per loop
+            known = tuple(_expand_known(k, shape, device) for k in (known.y0, known.mask))
+        last = len(evals) - 1
         if progress:
             from tqdm.auto import tqdm
-            indices = tqdm(indices)
+            evals = tqdm(evals)
         # every step's timestep batch as a row of one tensor built up front (a th.full per step is a kernel launch)
         all_t = th.arange(self.num_timesteps, device=device, dtype=th.int64)[:, None].expand(-1, shape[0]).contiguous()
         prepare = getattr(self, "_prepare_loop", None)
@@ -339,70 +417,86 @@ class GaussianDiffusion:
         per_step = 4
         for d in (shape if generator is None or isinstance(generator, (th.Generator, TorchCpuStream)) else shape[1:]):     # (per-element generators: per SAMPLE)
             per_step *= int(d)
-        chunk = max(1, min(self.num_timesteps, self._NOISE_AHEAD_BYTES // max(per_step, 1)))
+        chunk = max(1, min(n_draws, self._NOISE_AHEAD_BYTES // max(per_step, 1)))
+        drawn = 0
+
+        def draw(like):
+            """The loop's next N(0,1) tensor of x's shape: from noise_fn, else from the draws made ahead in chunks."""
+            nonlocal ahead, ahead_k, pending, drawn
+            if self.noise_fn is not None:
+                return self.noise_fn(like).contiguous()
+            if ahead is None or ahead_k == ahead.shape[0]:
+                if pending is not None:
+                    ahead, pending = _join_side(pending, device), None
+                else:
+                    ahead = self._randn(shape, device, generator, lead=1 if cpu_noise and drawn == 0 else min(chunk, n_draws - drawn))
+                ahead_k = 0
+                nxt = drawn + ahead.shape[0]
+                if cpu_noise and self._CPU_STREAM_OVERLAP and nxt < n_draws:
+                    pending = _on_side(device, self._randn, shape, device, generator, lead=min(chunk, n_draws - nxt))
+            out = ahead[ahead_k]
+            ahead_k += 1
+            drawn += 1
+            return out
+
         # The next step's in_conv rides on this step's output head (s3d_unet_step_film_carry) when nobody touches the sample in
         # between: CARRY_OUT on every step but the last; CARRY_IN when `img` still IS the tensor the previous step wrote — same
         # object, same version counter (a consumer of this generator that replaces or edits out["sample"] switches it off).
-        last = self.num_timesteps - 1
         prev_sample, prev_version = None, -1
-        for n, i in enumerate(indices):
+        for n, (i, renoise_follows) in enumerate(evals):
             t = HostTimesteps(all_t[i], (i,) * shape[0])
-            carry = (_lib.CARRY_OUT if n < last else 0) | (_lib.CARRY_IN if img is prev_sample and img._version == prev_version else 0)
-            eps = None
-            if self.noise_fn is None:
-                if ahead is None or ahead_k == ahead.shape[0]:
-                    if pending is not None:
-                        ahead, pending = _join_side(pending, device), None
-                    else:
-                        ahead = self._randn(shape, device, generator, lead=1 if cpu_noise and n == 0 else min(chunk, self.num_timesteps - n))
-                    ahead_k = 0
-                    nxt = n + ahead.shape[0]
-                    if cpu_noise and self._CPU_STREAM_OVERLAP and nxt < self.num_timesteps:
-                        pending = _on_side(device, self._randn, shape, device, generator, lead=min(chunk, self.num_timesteps - nxt))
-                eps = ahead[ahead_k]
-                ahead_k += 1
+            carry = ((_lib.CARRY_OUT if n < last and not renoise_follows else 0)
+                     | (_lib.CARRY_IN if img is prev_sample and img._version == prev_version else 0))
+            # (noise_fn without a known region: _step asks it, as ever)
+            eps = draw(img) if self.noise_fn is None or known is not None else None
+            kn = known + (draw(img),) if known is not None else None
             with th.no_grad():
                 sample, pred, _ = self._step(mode, model, img, t, clip_denoised, denoised_fn, model_kwargs, fuse=True,
-                                             noise=eps, carry=carry, **kw)
+                                             noise=eps, carry=carry, known=kn, **kw)
             prev_sample, prev_version = sample, (sample._version if sample is not None else -1)
             out = {"sample": sample, "pred_xstart": pred}
             yield out                 # (outside the no_grad block: a generator abandoned mid-loop must not unwind a context manager at interpreter exit)
             img = out["sample"]
+            if renoise_follows:
+                with th.no_grad():
+                    img = self.renoise(img, all_t[i], draw(img))
 
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                                  model_kwargs=None, device=None, progress=False, generator=None):
-        """Generator over the per-step dicts of p_sample (:488-536).  `generator`: see _loop."""
+                                  model_kwargs=None, device=None, progress=False, generator=None, known=None, resample=1):
+        """Generator over the per-step dicts of p_sample (:488-536).  `generator`, `known`, `resample`: see _loop."""
         yield from self._loop(_lib.STEP_DDPM, model, shape, noise, device, progress, clip_denoised=clip_denoised,
-                              denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs, generator=generator)
+                              denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs, generator=generator,
+                              known=known, resample=resample)
 
     def p_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
-                      model_kwargs=None, device=None, progress=False, generator=None):
+                      model_kwargs=None, device=None, progress=False, generator=None, known=None, resample=1):
         """Full ancestral sampling run, returns the final sample (:442-486)."""
         final = None
         for final in self.p_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
                                                     denoised_fn=denoised_fn, cond_fn=cond_fn,
                                                     model_kwargs=model_kwargs, device=device, progress=progress,
-                                                    generator=generator):
+                                                    generator=generator, known=known, resample=resample):
             pass
         return final["sample"]
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                      cond_fn=None, model_kwargs=None, device=None, progress=False, eta=0.0, y0=None,
-                                     mask=None, is_mask_t0=False, generator=None):
-        """Generator over the per-step dicts of ddim_sample (:687-734).  `generator`: see _loop."""
+                                     mask=None, is_mask_t0=False, generator=None, known=None, resample=1):
+        """Generator over the per-step dicts of ddim_sample (:687-734).  `generator`, `known`, `resample`: see _loop."""
         yield from self._loop(_lib.STEP_DDIM, model, shape, noise, device, progress, clip_denoised=clip_denoised,
                               denoised_fn=denoised_fn, cond_fn=cond_fn, model_kwargs=model_kwargs, generator=generator,
-                              eta=eta, y0=y0, mask=mask, is_mask_t0=is_mask_t0)
+                              known=known, resample=resample, eta=eta, y0=y0, mask=mask, is_mask_t0=is_mask_t0)
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, y0=None, mask=None,
-                         is_mask_t0=False, generator=None):
+                         is_mask_t0=False, generator=None, known=None, resample=1):
         """Full DDIM run, returns the final sample (:640-685)."""
         final = None
         for final in self.ddim_sample_loop_progressive(model, shape, noise=noise, clip_denoised=clip_denoised,
                                                        denoised_fn=denoised_fn, cond_fn=cond_fn,
                                                        model_kwargs=model_kwargs, device=device, progress=progress,
-                                                       eta=eta, y0=y0, mask=mask, is_mask_t0=is_mask_t0, generator=generator):
+                                                       eta=eta, y0=y0, mask=mask, is_mask_t0=is_mask_t0, generator=generator,
+                                                       known=known, resample=resample):
             pass
         return final["sample"]
 
@@ -566,6 +660,16 @@ class GaussianDiffusion:
         g = model.backward_flat(_mse_grad(out, target, wgt, H, W, D, divisor=float(out.shape[0])), out=grad_out,
                                 **({"marks": grad_marks} if grad_marks else {}))
         return {"mse_xy": mse[:, 0], "mse_xz": mse[:, 1], "mse_yz": mse[:, 2], "loss": mse[:, 3]}, g
+
+
+def _expand_known(k, shape, device):
+    """y0 / mask of a KnownRegion as a dense fp32 device tensor of the batch shape."""
+    k = th.as_tensor(k).to(device=device, dtype=th.float32)
+    if k.dim() == len(shape) - 1:
+        k = k[None]
+    if tuple(k.shape[1:]) != tuple(shape[1:]) or k.shape[0] not in (1, shape[0]):
+        raise ValueError(f"known region of shape {tuple(k.shape)} does not fit samples of shape {tuple(shape)}")
+    return k.expand(*shape).contiguous()
 
 
 def _on_side(device, fn, *a, **kw):

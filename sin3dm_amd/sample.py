@@ -74,8 +74,10 @@ def sample_generators(groups, device, base_seed=1000, noise=None):
     return [[torch.Generator(device=device).manual_seed(parallel.sample_seed(base_seed, i)) for i in idx] for idx in groups]
 
 
-def sample_diffusion(args, rank=0, world=1, base_seed=1000, noise=None):
-    """Reference: src/sample.py:6-48, with per-sample seeds and rank striping.  noise: see noise_source."""
+def sample_diffusion(args, rank=0, world=1, base_seed=1000, noise=None, hwd=None, loop_kw=None):
+    """Reference: src/sample.py:6-48, with per-sample seeds and rank striping.  noise: see noise_source.
+    hwd / loop_kw (sin3dm_amd.edit): the canvas when it is not the --resize one, and further keywords of the sampling loops
+    (known=, resample=)."""
     from .diffusion.script_util import create_model_and_diffusion_from_args
     from .utils.triplane_util import decompose_featmaps, load_triplane_data, save_triplane_data
 
@@ -90,7 +92,8 @@ def sample_diffusion(args, rank=0, world=1, base_seed=1000, noise=None):
     result_dir = os.path.join(args.tag, args.output)
     os.makedirs(result_dir, exist_ok=True)
     C = src_data.shape[0]
-    H, W, D = (int(s * r) for s, r in zip(sizes, args.resize))
+    H, W, D = hwd if hwd is not None else (int(s * r) for s, r in zip(sizes, args.resize))
+    loop_kw = dict(loop_kw or {})
     if rank == 0:
         print("H, W, D:", H, W, D)
 
@@ -108,11 +111,12 @@ def sample_diffusion(args, rank=0, world=1, base_seed=1000, noise=None):
         # several batches of equal shape on this GPU: up to `nch` of them in flight as independent chains (one stream + one
         # workspace lane each) instead of one after the other (src/sample.py:33-47)
         res = diffusion.sample_loop_chains(model, [args.diff_batch_size, C, H + D, W + D], len(full), chains=nch,
-                                           ddim=bool(args.use_ddim), generators=[gens[g] for g in full], device=dev, model_kwargs=kw)
+                                           ddim=bool(args.use_ddim), generators=[gens[g] for g in full], device=dev, model_kwargs=kw,
+                                           **loop_kw)
         outs = dict(zip(full, res))
     for g, idx in enumerate(groups):
         samples = outs[g] if g in outs else sample_fn(model, [len(idx), C, H + D, W + D], progress=rank == 0, model_kwargs=kw,
-                                                      generator=gens[g])
+                                                      generator=gens[g], **loop_kw)
         xy, xz, yz = (t.detach().cpu().numpy() for t in decompose_featmaps(samples, (H, W, D)))
         for j, i in enumerate(idx):
             path = os.path.join(result_dir, f"{i:03d}", "feat.npz")
