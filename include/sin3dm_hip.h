@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define S3D_ABI_VERSION 12
+#define S3D_ABI_VERSION 13
 #define S3D_API __attribute__((visibility("default")))
 
 typedef enum {
@@ -584,6 +584,36 @@ S3D_API int s3d_eval_lp_max(const uint64_t* gen_words, const int32_t* gen_counts
 S3D_API int s3d_eval_pack_volumes(const uint8_t* vols, int64_t n, int64_t voxels, uint64_t* words, void* stream);
 /* inter[i][j] = |v_i & v_j|, uni[i][j] = |v_i | v_j|, both [n][n] */
 S3D_API int s3d_eval_pairwise_counts(const uint64_t* words, int64_t n, int64_t n_words, int64_t* inter, int64_t* uni, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * SSFID activation statistics: the first two layers of the reference's 3-D voxel classifier
+ * (evaluation/classifier3D.py: Conv3d(k4, s2, p1) + InstanceNorm3d (no affine, eps 1e-5, biased variance) + leaky_relu(0.01), 1 -> 32
+ * -> 64 channels) and the statistics evaluation/ssfid.py :65-77 takes of them: the rows' mean and their ddof = 1 covariance.
+ * The zero padding of the second convolution pads the activated tensor.  Output extents are floor(n / 2) per axis and layer.
+ * The Frechet distance itself is host arithmetic on two 64 x 64 matrices and stays with the caller.
+ * The handle owns the packed weights and a workspace that grows on demand; calls on one handle must be ordered.  Growing the
+ * workspace may synchronise the device.  The same input gives the same bits on every call and handle.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct s3d_ssfid s3d_ssfid;
+S3D_API int s3d_ssfid_create(s3d_ssfid** out);
+S3D_API void s3d_ssfid_destroy(s3d_ssfid* h);
+/* name / shape: conv_1.weight [32][1][4][4][4], conv_1.bias [32], conv_2.weight [64][32][4][4][4], conv_2.bias [64], host float32.
+ * One of these names with another shape is S3D_ERR_UNSUPPORTED (the reference's classifier() is always ef_dim = 32); another name
+ * is S3D_ERR_INVALID. */
+S3D_API int s3d_ssfid_set_param(s3d_ssfid* h, const char* name, const float* data, const int64_t* shape, int ndim);
+/* out_dims[k] = dims[k] >> out_layer, channels = 32 (layer 1) or 64 (layer 2).  Host only; the checks of s3d_ssfid_features. */
+S3D_API int s3d_ssfid_out_dims(const int dims[3], int out_layer, int out_dims[3], int* channels);
+/* vox: device uint8 [X][Y][Z], non-zero = occupied.  out_layer 1 or 2 (3 and 4: S3D_ERR_UNSUPPORTED).  act: null, or device
+ * float32 [X' Y' Z'][C], rows in [X'][Y'][Z'] order (act.permute(0, 2, 3, 4, 1).view(-1, C)).  mu [C], sigma [C][C]: device
+ * float64.  An axis whose output extent would be 0, or a parameter not yet set, is S3D_ERR_INVALID and launches nothing.  One
+ * row gives the NaN covariance np.cov gives. */
+S3D_API int s3d_ssfid_features(s3d_ssfid* h, const uint8_t* vox, const int dims[3], int out_layer, float* act, double* mu, double* sigma,
+                               void* stream);
+/* Stage timing for tools/bench_ssfid.py.  on != 0: every following s3d_ssfid_features records device events between its stages.
+ * s3d_ssfid_profile_read waits for the last timed call and gives its milliseconds: layer 1, its statistics, layer 2, its
+ * statistics, the covariance (normalise + Gram + reduction); layer 2's two are 0 for out_layer 1. */
+S3D_API int s3d_ssfid_profile(s3d_ssfid* h, int on);
+S3D_API int s3d_ssfid_profile_read(s3d_ssfid* h, double ms[5]);
 
 /* ------------------------------------------------------------------------------------------------
  * torch's CPU noise stream on the device: the float32 values `torch.randn` / `torch.rand` draw from

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libsin3dm_hip.so")
 c_fp = C.POINTER(C.c_float)
 c_i64p = C.POINTER(C.c_int64)
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 TAB_ROWS = ("sqrt_recip", "sqrt_recipm1", "coef1", "coef2", "logvar", "acp", "acp_prev")
 KTAB_ROWS = ("sqrt_acp_prev", "sqrt_1m_acp_prev", "sqrt_1m_beta", "sqrt_beta")     # s3d_known_region.tables (S3D_KTAB_*)
 STEP_DDPM, STEP_DDIM, STEP_MEAN_ONLY = 0, 1, 2
@@ -174,6 +174,14 @@ SIGNATURES = {
                                   C.c_void_p]),
     "s3d_eval_pack_volumes": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
     "s3d_eval_pairwise_counts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # SSFID: classifier features, their mean and covariance
+    "s3d_ssfid_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "s3d_ssfid_destroy": (None, [C.c_void_p]),
+    "s3d_ssfid_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_i64p, C.c_int]),
+    "s3d_ssfid_out_dims": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "s3d_ssfid_features": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3d_ssfid_profile": (C.c_int, [C.c_void_p, C.c_int]),
+    "s3d_ssfid_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     # torch's CPU noise stream on the device
     "s3d_rng_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "s3d_rng_destroy": (None, [C.c_void_p]),

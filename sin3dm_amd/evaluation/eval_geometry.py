@@ -2,6 +2,10 @@
 
 SRC/*/*voxel.npz (sorted) are the generated shapes, the first of REF/*.npz (sorted) is the training shape's SDF grid.  Writes the
 five numbers LP-IOU-avg, LP-IOU-percent, LP-F-score-avg, LP-F-score-percent and Div as JSON.
+
+With --ssfid_weights PATH (the reference's classifier checkpoint, Clsshapenet_128.pth) SSFID_avg and SSFID_std come first, in the
+order of eval_full.py: seven of its keys.  --ssfid_layer {1,2} selects the classifier layer (default 2, the reference's).  SIFID
+and LPIPS are not computed.
 """
 from __future__ import annotations
 
@@ -13,6 +17,7 @@ import sys
 
 NOT_COMPUTED = ("eval_geometry: SSFID, SIFID and LPIPS are not computed: they need a 3D classifier checkpoint, Inception and VGG weights "
                 "and rendered views, none of which can be obtained offline")
+NOT_COMPUTED_WITH_SSFID = ("eval_geometry: SIFID and LPIPS are not computed: they need Inception and VGG weights and rendered views")
 
 
 def build_parser():
@@ -22,6 +27,9 @@ def build_parser():
     parser.add_argument("--patch_size", type=int, default=11, help="patch size")
     parser.add_argument("--stride", type=int, default=5, help="patch stride")
     parser.add_argument("--patch_num", type=int, default=1000, help="max number of patches sampled from each generated shape")
+    parser.add_argument("--ssfid_weights", type=str, default=None,
+                        help="classifier checkpoint (Clsshapenet_128.pth): also compute SSFID_avg and SSFID_std")
+    parser.add_argument("--ssfid_layer", type=int, default=2, choices=(1, 2), help="classifier layer the SSFID statistics are taken of")
     parser.add_argument("-o", "--output", type=str, default=None, help="result save path (default: SRC + '_eval.json')")
     return parser
 
@@ -46,8 +54,11 @@ def main(argv=None):
     from .patch_utils import eval_div, eval_lp
     _lib.require_gpu()
     gen, ref = find_inputs(args.src, args.ref)
-    print(NOT_COMPUTED, file=sys.stderr)
+    print(NOT_COMPUTED if args.ssfid_weights is None else NOT_COMPUTED_WITH_SSFID, file=sys.stderr)
     result = {}
+    if args.ssfid_weights is not None:
+        from .ssfid import eval_ssfid
+        result.update(eval_ssfid(gen, ref, args.ssfid_weights, args.ssfid_layer))
     result.update(eval_lp(gen, ref, args.patch_size, args.stride, args.patch_num))
     result.update(eval_div(gen))
     print(result)

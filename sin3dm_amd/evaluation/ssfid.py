@@ -1,0 +1,137 @@
+"""SSFID of the reference's evaluation/ssfid.py (s3d_ssfid.hip): the first two layers of the 3-D voxel classifier
+on the device, the mean and covariance of their activations, and the Frechet distance between a generated shape's statistics and
+the training shape's.
+
+The classifier checkpoint (`Clsshapenet_128.pth`) is the only outside input: pass its path.  The features have no CPU fallback;
+the Frechet distance is float64 NumPy on the host.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .patch_utils import _as_occupancy, _dims, load_sdfgrid2vox, load_voxgrid
+
+PARAM_SHAPES = {"conv_1.weight": (32, 1, 4, 4, 4), "conv_1.bias": (32,), "conv_2.weight": (64, 32, 4, 4, 4), "conv_2.bias": (64,)}
+
+
+def check_classifier_weights(state):
+    """The four tensors of PARAM_SHAPES out of a state dict of the reference's `classifier`, as contiguous float32 on the host;
+    every other key (conv_3 ... linear1) is ignored.  KeyError names a missing key, ValueError a wrong shape."""
+    out = {}
+    for name, shape in PARAM_SHAPES.items():
+        if name not in state:
+            raise KeyError(f"classifier weights: key '{name}' is missing")
+        t = torch.as_tensor(state[name]).detach().to("cpu", torch.float32).contiguous()
+        if tuple(t.shape) != shape:
+            raise ValueError(f"classifier weights: '{name}' has shape {tuple(t.shape)}, expected {shape} (the classifier of ef_dim = 32)")
+        out[name] = t
+    return out
+
+
+def load_classifier_weights(path):
+    """torch.load of the reference's Clsshapenet_128.pth (a state dict), reduced to the two layers SSFID reads."""
+    state = torch.load(path, map_location="cpu")
+    if not hasattr(state, "keys"):
+        raise ValueError(f"{path}: a state dict is expected, got {type(state).__name__}")
+    return check_classifier_weights(state)
+
+
+class VoxelClassifier:
+    """Layers 1 and 2 of the reference's classifier on the device.  weights: a path or a state dict."""
+
+    def __init__(self, weights=None):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        _lib.check(self._lib.s3d_ssfid_create(C.byref(self._h)))
+        if weights is not None:
+            self.load_weights(weights)
+
+    def load_weights(self, weights):
+        w = load_classifier_weights(weights) if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__") else check_classifier_weights(weights)
+        for name, t in w.items():
+            shape = (C.c_int64 * t.dim())(*t.shape)
+            _lib.check(self._lib.s3d_ssfid_set_param(self._h, name.encode(), C.c_void_p(t.data_ptr()), shape, t.dim()))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.s3d_ssfid_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def features_device(self, vox, out_layer=2, return_activations=False):
+        """(mu [C], sigma [C][C]) as float64 device tensors, and the activations [rows][C] (float32) when asked for."""
+        vox = _as_occupancy(vox)
+        dims, od, ch = _dims(vox.shape), (C.c_int * 3)(), C.c_int(0)
+        _lib.check(self._lib.s3d_ssfid_out_dims(dims, int(out_layer), od, C.byref(ch)))
+        c = ch.value
+        mu = torch.empty(c, dtype=torch.float64, device=vox.device)
+        sigma = torch.empty((c, c), dtype=torch.float64, device=vox.device)
+        act = torch.empty((od[0] * od[1] * od[2], c), dtype=torch.float32, device=vox.device) if return_activations else None
+        _lib.check(self._lib.s3d_ssfid_features(self._h, _lib.ptr(vox), dims, int(out_layer), _lib.ptr(act), _lib.ptr(mu), _lib.ptr(sigma),
+                                                _lib.stream_ptr()))
+        return (mu, sigma, act) if return_activations else (mu, sigma)
+
+    def profile(self, on=True):
+        """Record device events between the stages of every following call (tools/bench_ssfid.py)."""
+        _lib.check(self._lib.s3d_ssfid_profile(self._h, int(bool(on))))
+
+    def stage_ms(self):
+        """Milliseconds of the last timed call: layer 1, its statistics, layer 2, its statistics, the covariance."""
+        ms = (C.c_double * 5)()
+        _lib.check(self._lib.s3d_ssfid_profile_read(self._h, ms))
+        return tuple(ms)
+
+    def features(self, vox, out_layer=2, return_activations=False):
+        """calculate_activation_statistics (:65): (mu, sigma) as float64 NumPy; with return_activations also the activations, rows
+        in [X'][Y'][Z'] order, as a device tensor."""
+        out = self.features_device(vox, out_layer, return_activations)
+        mu, sigma = out[0].cpu().numpy(), out[1].cpu().numpy()
+        return (mu, sigma, out[2]) if return_activations else (mu, sigma)
+
+
+def _sqrt_psd(s):
+    """The symmetric square root of a symmetric positive semi-definite matrix: eigh, eigenvalues clipped at 0."""
+    w, v = np.linalg.eigh((s + s.T) * 0.5)
+    return (v * np.sqrt(np.clip(w, 0.0, None))) @ v.T
+
+
+def frechet_distance(mu1, sigma1, mu2, sigma2):
+    """|mu1 - mu2|^2 + Tr s1 + Tr s2 - 2 Tr sqrt(s1 s2) (calculate_frechet_distance :11) in float64.  s1 s2 is similar to the
+    symmetric positive semi-definite s1^(1/2) s2 s1^(1/2), so the trace of its square root is the sum of the square roots of that
+    matrix's eigenvalues: no square root of a non-symmetric matrix, nothing imaginary, finite for rank-deficient inputs."""
+    mu1, mu2 = np.atleast_1d(np.asarray(mu1, dtype=np.float64)), np.atleast_1d(np.asarray(mu2, dtype=np.float64))
+    s1, s2 = np.atleast_2d(np.asarray(sigma1, dtype=np.float64)), np.atleast_2d(np.asarray(sigma2, dtype=np.float64))
+    assert mu1.shape == mu2.shape, "Training and test mean vectors have different lengths"
+    assert s1.shape == s2.shape, "Training and test covariances have different dimensions"
+    r = _sqrt_psd(s1)
+    m = r @ s2 @ r
+    w = np.linalg.eigvalsh((m + m.T) * 0.5)
+    tr_covmean = float(np.sum(np.sqrt(np.clip(w, 0.0, None))))
+    diff = mu1 - mu2
+    return float(diff.dot(diff) + np.trace(s1) + np.trace(s2) - 2.0 * tr_covmean)
+
+
+def ssfid_values(paths, ref_path, weights, out_layer=2, resolution=128):
+    """The per-shape distances of eval_SSFID_given_paths (:81); the reference shape's statistics are computed once."""
+    net = weights if isinstance(weights, VoxelClassifier) else VoxelClassifier(weights)
+    ref = load_sdfgrid2vox(ref_path, resolution=resolution)
+    mu_r, sigma_r = net.features(ref, out_layer)
+    values = []
+    for path in paths:
+        gen = load_voxgrid(path, resolution=resolution)
+        if gen.shape != ref.shape:
+            raise RuntimeError("Generated shape and reference shape shall have equal size.")
+        mu_f, sigma_f = net.features(gen, out_layer)
+        values.append(frechet_distance(mu_r, sigma_r, mu_f, sigma_f))
+    return values
+
+
+def eval_ssfid(paths, ref_path, weights, out_layer=2, resolution=128):
+    """eval_SSFID_given_paths (:81): the mean and the (population) standard deviation of the distances, round(6)."""
+    values = ssfid_values(paths, ref_path, weights, out_layer, resolution)
+    return {"SSFID_avg": float(np.mean(values).round(6)), "SSFID_std": float(np.std(values).round(6))}
