@@ -616,6 +616,61 @@ S3D_API int s3d_ssfid_profile(s3d_ssfid* h, int on);
 S3D_API int s3d_ssfid_profile_read(s3d_ssfid* h, double ms[5]);
 
 /* ------------------------------------------------------------------------------------------------
+ * Multi-view renders of triangle meshes: a tiled rasteriser, so that the views the reference's
+ * evaluation/eval_full.py compares (rendering/blender_render_multiview.py makes them with Blender) can be made of an exported
+ * mesh and of the input mesh.  Parity with Blender is not claimed: flat shading, one light, no shadows.
+ * The sample grid is ws x hs = the image size times the supersampling factor; sample (i, j) has its centre at (i + 0.5, j + 0.5)
+ * and index j * ws + i, row 0 on top.  Coordinates are snapped to 1 / S3D_RENDER_SUBPIXEL of a sample, and coverage is decided on
+ * them in integer arithmetic: with the corners ordered so that the doubled area is positive, a sample lies in a triangle when
+ * every edge value E = (xb - xa)(py - ya) - (yb - ya)(px - xa) is positive, or zero on an edge with yb > ya, or yb == ya and
+ * xb < xa (the top-left rule), so two triangles that share an edge cover each sample once.  Both orientations are drawn.
+ * A triangle is dropped when a corner is flagged (w <= near), a snapped coordinate lies beyond +-S3D_RENDER_MAX_COORD, a vertex
+ * index lies outside the table, or its doubled area is zero; there is no near-plane clipping.
+ * Scan, sort and segment starts between the calls are the caller's (sin3dm_amd/rendering/rasterizer.py).  Matrices and the light
+ * are host arrays; all other arrays are device pointers; every call only enqueues on `stream`.  The same input gives the same bits.
+ * ------------------------------------------------------------------------------------------------ */
+#define S3D_RENDER_TILE 16
+#define S3D_RENDER_SUBPIXEL 256
+#define S3D_RENDER_MAX_COORD (1 << 20)
+#define S3D_RENDER_MAX_GRID 4096
+/* cap of the (tile, triangle) pair list: 2^27 pairs = 1 GiB of workspace (two int32 per pair) */
+#define S3D_RENDER_MAX_PAIRS (1LL << 27)
+/* shade = S3D_RENDER_AMBIENT + S3D_RENDER_DIFFUSE * max(0, n . light) */
+#define S3D_RENDER_AMBIENT 0.35f
+#define S3D_RENDER_DIFFUSE 0.65f
+/* view_proj: row-major 4 x 4, clip = M (x, y, z, 1); only the x, y and w rows are read.  xy_fixed [n_verts][2] = round(256 * ((x / w
+ * / 2 + 1 / 2) ws, (1 / 2 - y / w / 2) hs)) clamped to +-2^30, inv_w [n_verts] = 1 / w; a vertex with w <= near (or not finite) is
+ * flagged: inv_w = 0 and xy_fixed = 0. */
+S3D_API int s3d_render_project(const float* verts, int64_t n_verts, const float view_proj[16], int ws, int hs, float near, int32_t* xy_fixed,
+                               float* inv_w, void* stream);
+/* faces [n_faces][3] int32.  counts[f] = tiles of S3D_RENDER_TILE^2 samples that hold a sample centre inside the box of the snapped
+ * corners (clamped to the grid), 0 for a dropped triangle; status[f] = 0 drawn, 1 a flagged corner, 2 a coordinate or an index out
+ * of range, 3 zero area. */
+S3D_API int s3d_render_bin_count(const int32_t* xy_fixed, const float* inv_w, int64_t n_verts, const int32_t* faces, int64_t n_faces, int ws,
+                                 int hs, int64_t* counts, uint8_t* status, void* stream);
+/* offsets [n_faces] = exclusive scan of counts, n_pairs = their sum (more than S3D_RENDER_MAX_PAIRS: S3D_ERR_UNSUPPORTED).  Triangle
+ * f writes (pair_tile, pair_tri) = (ty * ceil(ws / 16) + tx, f) at offsets[f]... in ascending tile order. */
+S3D_API int s3d_render_bin_fill(const int32_t* xy_fixed, const float* inv_w, int64_t n_verts, const int32_t* faces, int64_t n_faces, int ws,
+                                int hs, const int64_t* offsets, int64_t n_pairs, int32_t* pair_tile, int32_t* pair_tri, void* stream);
+/* seg [tiles + 1]: the pairs sorted by tile (a stable sort keeps each tile's triangles ascending), tile t owns seg_tri[seg[t] ..
+ * seg[t+1]).  Per sample: count = covering triangles (clamped at 255), depth = the largest 1 / w among them, interpolated with the
+ * edge values as weights, face_id = its triangle (equal 1 / w: the lower index); nothing covers: face_id -1, depth 0. */
+S3D_API int s3d_render_raster(const int32_t* xy_fixed, const float* inv_w, int64_t n_verts, const int32_t* faces, int64_t n_faces, int ws,
+                              int hs, const int64_t* seg, const int32_t* seg_tri, int64_t n_pairs, int32_t* face_id, float* depth,
+                              uint8_t* count, void* stream);
+/* rgba [hs / supersample][ws / supersample][4]: per covered sample the base colour at the perspective-correct barycentrics times
+ * the shade of the flat normal turned towards the camera (light: unit vector towards the light, in the space of verts), clamped to
+ * [0, 1]; RGB = the mean over a pixel's covered samples in row order, A = the covered share, both as uint8(255 x + 0.5).
+ * Base colour: vertex_colors [n_verts][3] when given; else the material m = face_mat[f] (null: 0) of mat_table / mat_kd / images as
+ * for s3d_meshsdf_texture — its image at uv [n_faces][3][2], bilinear with the GL convention (texel (i, j) centred at u = (i + 0.5) / W,
+ * v = 1 - (j + 0.5) / H, row 0 of the image on top, clamp to edge), or its Kd without image or uv; n_mats = 0: white. */
+S3D_API int s3d_render_shade(const float* verts, const int32_t* xy_fixed, const float* inv_w, int64_t n_verts, const int32_t* faces,
+                             int64_t n_faces, const int32_t* face_id, int ws, int hs, int supersample, const float view_proj[16],
+                             const float light[3], const float* vertex_colors, const float* uv, const int32_t* face_mat,
+                             const int64_t* mat_table, const float* mat_kd, int n_mats, const uint8_t* images, int64_t image_bytes,
+                             uint8_t* rgba, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * torch's CPU noise stream on the device: the float32 values `torch.randn` / `torch.rand` draw from
  * torch's default CPU generator (MT19937), so that a sampling run consumes the stream the reference consumes on the CPU
  * (src/diffusion/gaussian_diffusion.py:514, 431, 591) without a host draw and an upload per step.

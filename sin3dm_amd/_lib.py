@@ -23,6 +23,9 @@ MEAN_START_X, MEAN_EPSILON = 0, 1
 ERR_INVALID, ERR_MISSING, ERR_HIP, ERR_UNSUPPORTED, ERR_INTERNAL = -1, -2, -3, -4, -5
 MAX_LANES = 16
 MESHSDF_MAX_PAIRS = 1 << 27           # S3D_MESHSDF_MAX_PAIRS (include/sin3dm_hip.h): 1.5 GiB of (cell, triangle) pairs
+RENDER_MAX_PAIRS = 1 << 27            # S3D_RENDER_MAX_PAIRS: 1 GiB of (tile, triangle) pairs
+RENDER_TILE, RENDER_SUBPIXEL, RENDER_MAX_COORD, RENDER_MAX_GRID = 16, 256, 1 << 20, 4096
+RENDER_AMBIENT, RENDER_DIFFUSE = 0.35, 0.65                    # S3D_RENDER_AMBIENT / S3D_RENDER_DIFFUSE
 
 
 class UNetCfg(C.Structure):
@@ -182,6 +185,17 @@ SIGNATURES = {
     "s3d_ssfid_features": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "s3d_ssfid_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "s3d_ssfid_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    # multi-view renders: project, bin, raster, shade
+    "s3d_render_project": (C.c_int, [C.c_void_p, C.c_int64, c_fp, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3d_render_bin_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "s3d_render_bin_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3d_render_raster": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                    C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3d_render_shade": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                   c_fp, c_fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                   C.c_void_p, C.c_void_p]),
     # torch's CPU noise stream on the device
     "s3d_rng_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "s3d_rng_destroy": (None, [C.c_void_p]),

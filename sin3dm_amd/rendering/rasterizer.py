@@ -1,0 +1,162 @@
+"""Multi-view renders of a triangle mesh on the device (s3d_render.hip): project, bin, raster, shade.
+Scan, sort and segment starts between the kernels are torch calls here, as in data/mesh_sampler.py."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from .. import _lib
+from . import camera
+
+TILE = _lib.RENDER_TILE
+
+
+def _f16(m):
+    return (C.c_float * 16)(*[float(x) for x in np.asarray(m, dtype=np.float64).reshape(16)])
+
+
+def _f3(v):
+    return (C.c_float * 3)(*[float(x) for x in np.asarray(v, dtype=np.float64).reshape(3)])
+
+
+def project(verts, matrix, Ws, Hs, near=camera.NEAR):
+    """(xy_fixed int32 [V, 2], inv_w float32 [V]) of float32 device vertices: sample coordinates snapped to 1 / 256; a vertex
+    with w <= near has inv_w = 0."""
+    _lib.require_gpu(verts)
+    v = verts.contiguous().float()
+    V = v.shape[0]
+    with torch.cuda.device(v.device):
+        xy = torch.empty((V, 2), device=v.device, dtype=torch.int32)
+        iw = torch.empty(V, device=v.device, dtype=torch.float32)
+        _lib.check(_lib.load().s3d_render_project(_lib.ptr(v), V, _f16(matrix), int(Ws), int(Hs), float(near), _lib.ptr(xy), _lib.ptr(iw),
+                                                  _lib.stream_ptr()))
+    return xy, iw
+
+
+def rasterize(xy_fixed, inv_w, faces, Ws, Hs, timer=None):
+    """The raster stage on given snapped coordinates: dict with face_id int32 [Hs, Ws] (-1: none), depth float32 [Hs, Ws] (1 / w),
+    count uint8 [Hs, Ws] (covering triangles, clamped at 255), status uint8 [F] (0 drawn, 1 a flagged corner, 2 out of range,
+    3 zero area) and info: dropped / degenerate / near counts, the number of (tile, triangle) pairs and the longest tile list.
+    timer(stage): called on the stream after every stage (tools/bench_render.py records a device event there)."""
+    timer = timer or (lambda stage: None)
+    _lib.require_gpu(xy_fixed)
+    lib = _lib.load()
+    Ws, Hs = int(Ws), int(Hs)
+    xy = xy_fixed.contiguous().to(torch.int32)
+    iw = inv_w.contiguous().float()
+    t = faces.contiguous().to(torch.int32).reshape(-1, 3)
+    V, F, dev = xy.shape[0], t.shape[0], xy.device
+    n_tiles = -(-Ws // TILE) * -(-Hs // TILE)
+    with torch.cuda.device(dev):
+        st = _lib.stream_ptr()
+        counts = torch.zeros(F, device=dev, dtype=torch.int64)
+        status = torch.zeros(F, device=dev, dtype=torch.uint8)
+        _lib.check(lib.s3d_render_bin_count(_lib.ptr(xy), _lib.ptr(iw), V, _lib.ptr(t), F, Ws, Hs, _lib.ptr(counts), _lib.ptr(status), st))
+        timer("bin count")
+        ends = torch.cumsum(counts, 0)
+        n_pairs = int(ends[-1]) if F else 0
+        if n_pairs > _lib.RENDER_MAX_PAIRS:
+            raise NotImplementedError(f"rasterize: {n_pairs} (tile, triangle) pairs on a {Ws} x {Hs} sample grid: {n_pairs * 8 / 2 ** 30:.2f} GiB "
+                                      f"of workspace, over the cap of {_lib.RENDER_MAX_PAIRS} pairs = 1 GiB")
+        offsets = (ends - counts).contiguous()
+        pair_tile = torch.empty(max(n_pairs, 1), device=dev, dtype=torch.int32)
+        pair_tri = torch.empty(max(n_pairs, 1), device=dev, dtype=torch.int32)
+        timer("scan")
+        _lib.check(lib.s3d_render_bin_fill(_lib.ptr(xy), _lib.ptr(iw), V, _lib.ptr(t), F, Ws, Hs, _lib.ptr(offsets), n_pairs, _lib.ptr(pair_tile),
+                                           _lib.ptr(pair_tri), st))
+        timer("bin fill")
+        keys, order = torch.sort(pair_tile[:n_pairs], stable=True)
+        seg_tri = pair_tri[:n_pairs][order].contiguous()
+        seg = torch.searchsorted(keys, torch.arange(n_tiles + 1, device=dev, dtype=torch.int32)).to(torch.int64).contiguous()
+        timer("sort and segments")
+        face_id = torch.empty((Hs, Ws), device=dev, dtype=torch.int32)
+        depth = torch.empty((Hs, Ws), device=dev, dtype=torch.float32)
+        count = torch.empty((Hs, Ws), device=dev, dtype=torch.uint8)
+        _lib.check(lib.s3d_render_raster(_lib.ptr(xy), _lib.ptr(iw), V, _lib.ptr(t), F, Ws, Hs, _lib.ptr(seg), _lib.ptr(seg_tri), n_pairs,
+                                         _lib.ptr(face_id), _lib.ptr(depth), _lib.ptr(count), st))
+        timer("raster")
+        hist = torch.bincount(status.long(), minlength=4).tolist() if F else [0, 0, 0, 0]
+        longest = int((seg[1:] - seg[:-1]).max())
+        torch.cuda.current_stream().synchronize()          # the temporaries above are done with
+    info = {"dropped": hist[1] + hist[2] + hist[3], "near": hist[1], "out_of_range": hist[2], "degenerate": hist[3], "n_pairs": n_pairs,
+            "longest_tile_list": longest}
+    return {"face_id": face_id, "depth": depth, "count": count, "status": status, "info": info}
+
+
+def pack_materials(materials, device):
+    """(mat_table int64 [M, 3] = {byte offset, W, H}, kd float32 [M, 3], images uint8, image_bytes): the layout of
+    s3d_meshsdf_texture.  materials: dicts with Kd and image (uint8 [H, W, 3+], array or tensor, top row first, or None)."""
+    table, blobs, kds, off = [], [], [], 0
+    for m in materials:
+        kds.append([float(x) for x in m.get("Kd", (1.0, 1.0, 1.0))])
+        img = m.get("image")
+        if img is None:
+            table.append([0, 0, 0])
+            continue
+        img = img if torch.is_tensor(img) else torch.from_numpy(np.array(img, dtype=np.uint8, order="C"))        # (a copy: PIL's is read-only)
+        img = img.to(device)[..., :3].contiguous()
+        table.append([off, img.shape[1], img.shape[0]])
+        blobs.append(img.reshape(-1))
+        off += img.numel()
+    images = torch.cat(blobs) if blobs else torch.zeros(1, device=device, dtype=torch.uint8)
+    return (torch.tensor(table, dtype=torch.int64, device=device).reshape(-1, 3).contiguous(),
+            torch.tensor(kds, dtype=torch.float32, device=device).reshape(-1, 3).contiguous(), images.contiguous(), off)
+
+
+def render_views(verts, faces, *, uvs=None, face_mat=None, materials=None, vertex_colors=None, views=None, resolution=(512, 512),
+                 supersample=2, return_buffers=False, timer=None):
+    """uint8 [n_views, H, W, 4] renders of a mesh given as device tensors: verts [V, 3], faces [F, 3].
+    Base colour: vertex_colors [V, 3] in [0, 1]; or materials (dicts with Kd and image, see pack_materials) with face_mat [F]
+    (None: material 0) and per-corner uvs [F, 3, 2]; or white.  views: camera.View objects (None: the reference's eight views of
+    the mesh normalised by its bounding box, camera.standard_views).  resolution: (W, H).  Alpha is the covered share of a pixel.
+    return_buffers: also a list with, per view, face_id / depth / count [H ss, W ss], xy_fixed, inv_w, status and info.
+    timer: see rasterize."""
+    timer = timer or (lambda stage: None)
+    _lib.require_gpu(verts)
+    lib = _lib.load()
+    W, H, ss = int(resolution[0]), int(resolution[1]), int(supersample)
+    if W < 1 or H < 1 or not 1 <= ss <= 8:
+        raise ValueError(f"render_views: resolution {W} x {H}, supersample {ss} (1 to 8)")
+    Ws, Hs = W * ss, H * ss
+    dev = verts.device
+    v = verts.contiguous().float().reshape(-1, 3)
+    t = faces.contiguous().to(torch.int32).reshape(-1, 3)
+    V, F = v.shape[0], t.shape[0]
+    if views is None:
+        if V:
+            lo, hi = v.min(0).values.double().cpu().numpy(), v.max(0).values.double().cpu().numpy()
+        else:
+            lo, hi = np.zeros(3), np.ones(3)
+        views = camera.standard_views(lo, hi, (W, H))
+    vcol = uv = fm = None
+    table = kd = images = None
+    n_mats = img_bytes = 0
+    if vertex_colors is not None:
+        vcol = vertex_colors.to(dev).contiguous().float().reshape(V, 3)
+    elif materials:
+        table, kd, images, img_bytes = pack_materials(materials, dev)
+        n_mats = table.shape[0]
+        if uvs is not None:
+            uv = uvs.to(dev).contiguous().float().reshape(F, 3, 2)
+        if face_mat is not None:
+            fm = face_mat.to(dev).contiguous().to(torch.int32).reshape(F)
+    out = torch.empty((len(views), H, W, 4), device=dev, dtype=torch.uint8)
+    buffers = []
+    for k, view in enumerate(views):
+        timer("start")
+        xy, iw = project(v, view.matrix, Ws, Hs, view.near)
+        timer("project")
+        r = rasterize(xy, iw, t, Ws, Hs, timer)
+        with torch.cuda.device(dev):
+            _lib.check(lib.s3d_render_shade(_lib.ptr(v), _lib.ptr(xy), _lib.ptr(iw), V, _lib.ptr(t), F, _lib.ptr(r["face_id"]), Ws, Hs, ss,
+                                            _f16(view.matrix), _f3(view.light), _lib.ptr(vcol), _lib.ptr(uv), _lib.ptr(fm), _lib.ptr(table),
+                                            _lib.ptr(kd), n_mats, _lib.ptr(images) if img_bytes else C.c_void_p(0), img_bytes,
+                                            _lib.ptr(out[k]), _lib.stream_ptr()))
+        timer("shade")
+        if return_buffers:
+            buffers.append(dict(r, xy_fixed=xy, inv_w=iw))
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream().synchronize()
+    return (out, buffers) if return_buffers else out

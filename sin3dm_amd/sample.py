@@ -16,6 +16,8 @@ S3D_DECIMATE=quadric beside it decimates by quadric-error edge collapse instead 
 An experiment of --data_type sdfpbr writes object.obj + object.mtl + textures/{albedo,metallic,roughness,normal}.png (or a
 metallic-roughness object.glb) there, one of --data_type sdf writes sdfgrid_r<reso>.npz + mesh_r<reso>_simple.obj; in the default mode
 they write object.obj coloured by the albedo / without colours.  The data type comes from EXP/encoding/args.json.
+S3D_RENDER=views beside any of these also writes renderings/000.png ... 007.png into every sample folder that gets a mesh: the
+reference's eight views, drawn on the device from the arrays the export holds (sin3dm_amd/rendering).
 """
 from __future__ import annotations
 
@@ -55,6 +57,38 @@ def decimation_mode(mode=None):
     if name not in ("cluster", "quadric"):
         raise ValueError(f"decimation {name!r}: expected 'cluster' or 'quadric'")
     return name
+
+
+def render_mode(mode=None):
+    """"" (off, the default) or "views": every sample folder that gets a mesh also gets renderings/000.png ... 007.png, the
+    reference's eight views drawn by the device rasteriser (sin3dm_amd/rendering) from the arrays the export
+    already holds on the device.  mode=None reads the environment variable S3D_RENDER."""
+    name = mode if mode is not None else (os.environ.get("S3D_RENDER") or "")
+    if name not in ("", "views"):
+        raise ValueError(f"render mode {name!r}: expected 'views' (or unset)")
+    return name
+
+
+def render_sample(save_dir, mesh):
+    """renderings/ beside a decoded mesh.  mesh: what decode_mesh (verts, tris, colours) or decode_texmesh (a dict, or None for an
+    empty iso-surface) returned.  Returns the paths written."""
+    from .rendering.rasterizer import render_views
+    from .rendering.render_multiview import write_views
+    if mesh is None:
+        return []
+    if isinstance(mesh, dict):
+        verts, tris, kw = mesh["verts"], mesh["tris"], {}
+        if mesh.get("image") is not None:
+            # the baked image has texel row 0 first, which the PNG shows as its bottom row: the rasteriser reads top row first
+            kw = dict(uvs=mesh["uvs"].reshape(-1, 3, 2), materials=[{"Kd": (1.0, 1.0, 1.0), "image": mesh["image"][..., :3].flip(0)}])
+    else:
+        verts, tris, cols = mesh
+        coloured = cols is not None and cols.dim() == 2 and cols.shape[1] >= 3           # (an sdf experiment decodes no colour)
+        kw = dict(vertex_colors=cols[:, :3].clamp(0, 1)) if coloured else {}
+    if tris.shape[0] == 0:
+        return []
+    images = render_views(verts, tris, **kw)
+    return write_views(images.cpu().numpy(), os.path.join(save_dir, "renderings"))
 
 
 def find_copy_mtl(args):
@@ -145,16 +179,20 @@ def decode(args, paths):
     decimate = {"decimation": "quadric"} if decimation_mode() == "quadric" else {}
     ae = ShapeAutoEncoder(encoding_log_dir(args.tag), args, device=dist_util.dev())
     ae.load_ckpt("final")
+    views = render_mode() == "views"
     for path in paths:
         fm = [f.unsqueeze(0) for f in load_triplane_data(path, device=dist_util.dev(), compose=False)]
         if args.vox:
             ae.decode_voxel(os.path.dirname(path), fm, args.reso)
-        elif textured:
-            ae.decode_texmesh(os.path.dirname(path), fm, args.reso, n_faces=args.n_faces, texture_reso=args.texreso,
-                              mtl_path=find_copy_mtl(args), file_format=args.file_format, **decimate)
+            continue
+        if textured:
+            mesh = ae.decode_texmesh(os.path.dirname(path), fm, args.reso, n_faces=args.n_faces, texture_reso=args.texreso,
+                                     mtl_path=find_copy_mtl(args), file_format=args.file_format, **decimate)
         else:
             # iso-surface on the device, vertex-coloured object.obj
-            ae.decode_mesh(os.path.dirname(path), fm, args.reso)
+            mesh = ae.decode_mesh(os.path.dirname(path), fm, args.reso)
+        if views:
+            render_sample(os.path.dirname(path), mesh)
 
 
 def main(argv=None):
