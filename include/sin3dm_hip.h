@@ -616,6 +616,46 @@ S3D_API int s3d_ssfid_profile(s3d_ssfid* h, int on);
 S3D_API int s3d_ssfid_profile_read(s3d_ssfid* h, double ms[5]);
 
 /* ------------------------------------------------------------------------------------------------
+ * Image features of the multi-view renders: what the reference's evaluation/sifid.py and evaluation/lpips.py
+ * take of a PNG.  S3D_IMGFEAT_INCEPTION is the stem of torchvision's inception_v3 (BasicConv2d = Conv2d(bias = False) +
+ * BatchNorm2d(eps = 1e-3, eval) + ReLU): Conv2d_1a_3x3, Conv2d_2a_3x3, Conv2d_2b_3x3 for dims 64, then MaxPool2d(3, 2),
+ * Conv2d_3b_1x1, Conv2d_4a_3x3 for dims 192, on 2 (u8 / 255) - 1.  S3D_IMGFEAT_ALEXNET is torchvision's alexnet `features` up to
+ * its fifth ReLU on ((u8 / 255. - 0.5) / 0.5 - mu) / sigma, with the five linear LPIPS layers.
+ * The handle owns the packed weights, the activations of the last s3d_imgfeat_features call and a workspace that grows on demand;
+ * calls on one handle must be ordered.  Growing the workspace may synchronise the device.  Every call only enqueues on `stream`.
+ * The same input gives the same bits on every call and handle.
+ * ------------------------------------------------------------------------------------------------ */
+#define S3D_IMGFEAT_INCEPTION 0
+#define S3D_IMGFEAT_ALEXNET 1
+typedef struct s3d_imgfeat s3d_imgfeat;
+S3D_API int s3d_imgfeat_create(int net, s3d_imgfeat** out);
+S3D_API void s3d_imgfeat_destroy(s3d_imgfeat* h);
+/* Host float32 by the torchvision state-dict names.  Inception: <unit>.conv.weight [Cout][Cin][k][k] and <unit>.bn.{weight, bias,
+ * running_mean, running_var} [Cout] for the five units above.  AlexNet: features.{0,3,6,8,10}.{weight, bias} and
+ * lpips_weights.{0..4}.main.1.weight [1][C][1][1].  One of these names with another shape is S3D_ERR_UNSUPPORTED; another name is
+ * S3D_ERR_INVALID. */
+S3D_API int s3d_imgfeat_set_param(s3d_imgfeat* h, const char* name, const float* data, const int64_t* shape, int ndim);
+/* Host only; the checks of s3d_imgfeat_features.  dims: 64 or 192 for the Inception stem (anything else: S3D_ERR_UNSUPPORTED),
+ * ignored for AlexNet.  nlayers = 3, 5 or 5; hw[l] = {rows, columns} and channels[l] of unit l's output (either may be null).  An
+ * image too small for the network is S3D_ERR_INVALID; for AlexNet that includes an empty final MaxPool2d(3, 2), where the
+ * reference raises although the pool's output is unused. */
+S3D_API int s3d_imgfeat_out_dims(int net, int H, int W, int dims, int* nlayers, int hw[5][2], int channels[5]);
+/* img: device uint8 [n][H][W][ch], ch = 3 or 4 (the fourth is not read).  acts: null, or a host array of nlayers device pointers,
+ * each null or float32 [n][rows][columns][C] (channels last, after the ReLU). */
+S3D_API int s3d_imgfeat_features(s3d_imgfeat* h, const uint8_t* img, int n, int H, int W, int ch, int dims, float* const* acts, void* stream);
+/* Inception: of the last unit of the last s3d_imgfeat_features call, per image, the rows' mean mu [n][C] and ddof = 1 covariance
+ * sigma [n][C][C], device float64; rows are pixels in row-major order.  One row gives the NaN covariance np.cov gives. */
+S3D_API int s3d_imgfeat_stats(s3d_imgfeat* h, double* mu, double* sigma, void* stream);
+/* AlexNet: of the n images of the last s3d_imgfeat_features call, total [n][n] = sum over the five maps of
+ * mean_pixels sum_c w_c (xh_i - xh_j)^2, xh = x rsqrt(sum_c x^2 + 1e-10), and layers (null or [5][n][n]) the five terms; device
+ * float64.  The diagonal is exactly 0 and the matrix exactly symmetric. */
+S3D_API int s3d_imgfeat_pairs(s3d_imgfeat* h, double* layers, double* total, void* stream);
+/* Stage timing for tools/bench_imgmetrics.py, as s3d_ssfid_profile: milliseconds of the last timed s3d_imgfeat_features, units
+ * 1..5 (a max-pool counts with the unit it feeds; 0 for units not run) and the unit normalisation (AlexNet). */
+S3D_API int s3d_imgfeat_profile(s3d_imgfeat* h, int on);
+S3D_API int s3d_imgfeat_profile_read(s3d_imgfeat* h, double ms[6]);
+
+/* ------------------------------------------------------------------------------------------------
  * Multi-view renders of triangle meshes: a tiled rasteriser, so that the views the reference's
  * evaluation/eval_full.py compares (rendering/blender_render_multiview.py makes them with Blender) can be made of an exported
  * mesh and of the input mesh.  Parity with Blender is not claimed: flat shading, one light, no shadows.

@@ -25,6 +25,7 @@ MAX_LANES = 16
 MESHSDF_MAX_PAIRS = 1 << 27           # S3D_MESHSDF_MAX_PAIRS (include/sin3dm_hip.h): 1.5 GiB of (cell, triangle) pairs
 RENDER_MAX_PAIRS = 1 << 27            # S3D_RENDER_MAX_PAIRS: 1 GiB of (tile, triangle) pairs
 RENDER_TILE, RENDER_SUBPIXEL, RENDER_MAX_COORD, RENDER_MAX_GRID = 16, 256, 1 << 20, 4096
+IMGFEAT_INCEPTION, IMGFEAT_ALEXNET = 0, 1          # S3D_IMGFEAT_*
 RENDER_AMBIENT, RENDER_DIFFUSE = 0.35, 0.65                    # S3D_RENDER_AMBIENT / S3D_RENDER_DIFFUSE
 
 
@@ -185,6 +186,17 @@ SIGNATURES = {
     "s3d_ssfid_features": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "s3d_ssfid_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "s3d_ssfid_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    # image features of the renders: Inception stem statistics (SIFID), AlexNet pair distances (LPIPS)
+    "s3d_imgfeat_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "s3d_imgfeat_destroy": (None, [C.c_void_p]),
+    "s3d_imgfeat_set_param": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, c_i64p, C.c_int]),
+    "s3d_imgfeat_out_dims": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "s3d_imgfeat_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                       C.c_void_p]),
+    "s3d_imgfeat_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3d_imgfeat_pairs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3d_imgfeat_profile": (C.c_int, [C.c_void_p, C.c_int]),
+    "s3d_imgfeat_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     # multi-view renders: project, bin, raster, shade
     "s3d_render_project": (C.c_int, [C.c_void_p, C.c_int64, c_fp, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "s3d_render_bin_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
