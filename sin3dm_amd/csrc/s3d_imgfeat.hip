@@ -8,23 +8,19 @@
 //                    uint8 sample with the roundings of sifid.py / lpips.py; out-of-range taps are staged as exact zeros.  The
 //                    epilogue applies scale * x + shift (BatchNorm folded in float64, or 1 and the bias), ReLU, and stores once.
 //   k_if_pool        MaxPool2d(3, 2), floor mode, no padding
-//   k_if_gram<C>     column sums and C x C Gram of the rows in float64 on v_mfma_f64_16x16x4_f64, 1024 rows per block
-//   k_if_cov         block partials -> mu, sigma, parts added in index order
+//   IfRows           the last unit's rows as the load of k_rows_gram: the column sums, the C x C Gram and k_rows_cov's mu, sigma
+//                    are s3d_rowstats.h's, 1024 rows per block
 //   k_if_unit        x * rsqrt(sum_c x^2 + 1e-10) per pixel
 //   k_if_pairs       sum over pixels and channels of w_c (xh - yh)^2 for every ordered pair of images of the batch, float64
 //   k_if_lpips       partials -> per-layer means and their sum over the five layers
 //
 // No float atomics; every sum has a fixed order that depends on the shapes alone, so the same input gives the same bits.
-#include "s3d_common.h"
+#include "s3d_rowstats.h"
 
 #include <algorithm>
 #include <cmath>
 
 namespace s3d {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kIfThreads = 256;
 constexpr int kIfTileM = 128;                         // output pixels per block: 4 waves x 32
@@ -32,9 +28,7 @@ constexpr int kIfTileN = 64;                          // output channels per blo
 constexpr int kIfChunk = 16;                          // k values per float32 MFMA chain and per LDS stage
 constexpr int kIfLd = 20;                             // floats per staged pixel row (16 + 4: 16-byte aligned, rows 20 banks apart)
 constexpr int kIfLayers = 5;
-constexpr int kIfGramRows = 64;                       // rows per LDS stage of k_if_gram
-constexpr int kIfGramSpan = 1024;                     // rows per block of k_if_gram
-constexpr int kIfGramPad = 16;                        // floats between staged rows: the four rows of an MFMA step hit distinct banks
+constexpr int kIfGramSpan = 1024;                     // rows per block of k_rows_gram
 constexpr int kIfPairSlices = 4;                      // blocks per pair of k_if_pairs
 constexpr double kIfBnEps = 1e-3;                     // torchvision BasicConv2d: BatchNorm2d(eps = 0.001)
 constexpr double kIfUnitEps = 1e-10;                  // lpips.py normalize()
@@ -197,79 +191,16 @@ __global__ void __launch_bounds__(kIfThreads) k_if_pool(const float* __restrict_
     *reinterpret_cast<f32x4*>(out + pix * C + c4 * 4) = best;
 }
 
-// ------------------------------------------------------------------ rows -> column sums, Gram
-// Block (bx, by, img) takes rows [1024 bx, 1024 bx + 1024) of image img in stages of 64 and the Gram columns [64 by, 64 by + 64):
-// wave w owns the 16 columns jb = 4 by + w and all C / 16 row blocks, one v_mfma_f64_16x16x4_f64 accumulator each.  An MFMA step
-// contracts four consecutive rows (lane l supplies row 4 s + l / 16, column l % 16 of its block); steps and stages run in row
-// order.  Result register r of lane l is G[16 ib + l / 16 + 4 r][16 jb + l % 16].  Rows past the end are staged as zeros.
+// ------------------------------------------------------------------ the rows of the last unit: the Load of k_rows_gram
 template <int C>
-__global__ void __launch_bounds__(kIfThreads) k_if_gram(const float* __restrict__ act, long long R, int nparts, double* __restrict__ gpart,
-                                                        double* __restrict__ mpart) {
-    constexpr int LD = C + kIfGramPad, NI = C / 16, Q = C / 4;
-    __shared__ float a[kIfGramRows * LD];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const long long img = blockIdx.z;
-    const float* rows = act + img * R * C;
-    const long long r_begin = (long long)blockIdx.x * kIfGramSpan;
-    const long long r_end = min(R, r_begin + kIfGramSpan);
-    const int jb = blockIdx.y * 4 + wave;
-    f64x4 g[NI];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) g[i] = f64x4{0.0, 0.0, 0.0, 0.0};
-    double colsum = 0.0;
-    for (long long r0 = r_begin; r0 < r_end; r0 += kIfGramRows) {
-        for (int i = t; i < kIfGramRows * Q; i += kIfThreads) {
-            const int row = i / Q, cq = i - row * Q;
-            f32x4 x = {0.f, 0.f, 0.f, 0.f};
-            if (r0 + row < r_end) x = *reinterpret_cast<const f32x4*>(rows + (r0 + row) * C + cq * 4);
-            *reinterpret_cast<f32x4*>(a + row * LD + cq * 4) = x;
-        }
-        __syncthreads();
-#pragma unroll 2
-        for (int s = 0; s < kIfGramRows / 4; ++s) {
-            const float* ar = a + (s * 4 + (lane >> 4)) * LD + (lane & 15);
-            const double bv = double(ar[jb * 16]);
-#pragma unroll
-            for (int ib = 0; ib < NI; ++ib) g[ib] = __builtin_amdgcn_mfma_f64_16x16x4f64(double(ar[ib * 16]), bv, g[ib], 0, 0, 0);
-        }
-        if (blockIdx.y == 0 && t < C)
-            for (int row = 0; row < kIfGramRows; ++row) colsum += double(a[row * LD + t]);
-        __syncthreads();
+struct IfRows {
+    const float* act;                                     // [n][R][C]
+    long long R;
+    __device__ void bind(int) {}
+    __device__ f32x4 operator()(long long img, long long row, int cq) const {
+        return *reinterpret_cast<const f32x4*>(act + (img * R + row) * C + cq * 4);
     }
-    double* gp = gpart + (img * nparts + blockIdx.x) * C * C;
-#pragma unroll
-    for (int ib = 0; ib < NI; ++ib)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) gp[(ib * 16 + (lane >> 4) + 4 * r) * C + jb * 16 + (lane & 15)] = g[ib][r];
-    if (blockIdx.y == 0 && t < C) mpart[(img * nparts + blockIdx.x) * C + t] = colsum;
-}
-
-// mu[i] = S_i / R; sigma[i][j] = (G_ij - S_i S_j / R) / (R - 1): np.cov(rowvar=False), ddof = 1.  Block (x, img) owns 16 entries;
-// lane pl = t % 16 of an entry adds parts pl, pl + 16, ... in order, then a fixed xor tree over the 16 lanes.
-__global__ void __launch_bounds__(kIfThreads) k_if_cov(const double* __restrict__ gpart, const double* __restrict__ mpart, int nparts, int C,
-                                                       double R, double* __restrict__ mu, double* __restrict__ sigma) {
-    const int e = blockIdx.x * 16 + (threadIdx.x >> 4), pl = threadIdx.x & 15;       // C * C is a multiple of 16
-    const long long img = blockIdx.y;
-    const int i = e / C, j = e % C;
-    const double* gp = gpart + img * nparts * C * C;
-    const double* mp = mpart + img * nparts * C;
-    double g = 0.0, si = 0.0, sj = 0.0;
-    for (int p = pl; p < nparts; p += 16) {
-        g += gp[(long long)p * C * C + e];
-        si += mp[(long long)p * C + i];
-        sj += mp[(long long)p * C + j];
-    }
-#pragma unroll
-    for (int off = 8; off >= 1; off >>= 1) {
-        g += __shfl_xor(g, off);
-        si += __shfl_xor(si, off);
-        sj += __shfl_xor(sj, off);
-    }
-    if (pl == 0) {
-        sigma[img * C * C + e] = (g - si * sj / R) / (R - 1.0);
-        if (j == 0) mu[img * C + i] = si / R;
-    }
-}
+};
 
 // ------------------------------------------------------------------ LPIPS head
 // One wave per pixel: lane l adds x_c^2 for c = l, l + 64, ... in float64, a fixed xor tree, then x * (s + 1e-10)^(-1/2).
@@ -362,17 +293,8 @@ struct s3d_imgfeat {
     DevBuf out[kIfLayers], unit[kIfLayers], pool, gpart, mpart, ppart;
     // the last s3d_imgfeat_features call: what the statistics and the pairs are taken of
     int n = 0, nlayers = 0, hw[kIfLayers][2] = {};
-    bool profile = false, timed = false;
-    hipEvent_t ev[kIfLayers + 2] = {};
-    ~s3d_imgfeat() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
+    StageTimer<kIfLayers + 1> timer;     // s3d_imgfeat_profile: the five units, the unit normalisation
 };
-#define IF_MARK(i)                                             \
-    do {                                                       \
-        if (h->profile) S3D_HIP(hipEventRecord(h->ev[i], st)); \
-    } while (0)
 
 static int imgfeat_pack(s3d_imgfeat* h) {
     for (int l = 0; l < kIfLayers; ++l) {
@@ -438,16 +360,10 @@ int s3d_imgfeat_set_param(s3d_imgfeat* h, const char* name, const float* data, c
             if (strcmp(name, lname) == 0) { slot = 5; wdim = 4; want[0] = 1; want[1] = d.cout; want[2] = want[3] = 1; }
         }
         if (slot < 0) continue;
-        bool ok = ndim == wdim;
-        size_t n = 1;
-        for (int k = 0; ok && k < ndim; ++k) { ok = shape[k] == want[k]; n *= size_t(shape[k]); }
-        if (!ok) {
-            std::string got;
-            for (int k = 0; k < ndim && k < 8; ++k) got += (k ? ", " : "") + std::to_string((long long)shape[k]);
-            set_error("imgfeat set_param: %s has shape [%s]; torchvision's %s is the network supported", name, got.c_str(),
-                      h->net == S3D_IMGFEAT_INCEPTION ? "inception_v3" : "alexnet");
-            return S3D_ERR_UNSUPPORTED;
-        }
+        size_t n;
+        S3D_TRY(check_param_shape("imgfeat", name, shape, ndim, want, wdim,
+                                  h->net == S3D_IMGFEAT_INCEPTION ? "torchvision's inception_v3 is the network supported"
+                                                                  : "torchvision's alexnet is the network supported", n));
         if (slot == 5) {
             h->lin[l].assign(data, data + n);
             h->have_lin[l] = true;
@@ -520,11 +436,12 @@ int s3d_imgfeat_features(s3d_imgfeat* h, const uint8_t* img, int n, int H, int W
         }
         if (pool_bytes) S3D_TRY(h->pool.reserve(pool_bytes));
     }
-    h->timed = false;
+    StageTimer<kIfLayers + 1>& tm = h->timer;
+    tm.timed = false;
     h->nlayers = 0;
     const void* cur = img;
     int e[2] = {H, W};
-    IF_MARK(0);
+    S3D_TRY(tm.mark(0, st));
     for (int l = 0; l < nl; ++l) {
         const IfLayerDef& d = kIfNets[h->net][l];
         if (d.pool_before) {
@@ -553,14 +470,14 @@ int s3d_imgfeat_features(s3d_imgfeat* h, const uint8_t* img, int n, int H, int W
         else if (h->net == S3D_IMGFEAT_INCEPTION) hipLaunchKernelGGL(k_if_conv<1>, grid, dim3(kIfThreads), 0, st, cur, c, wp, sc, sh, o);
         else hipLaunchKernelGGL(k_if_conv<2>, grid, dim3(kIfThreads), 0, st, cur, c, wp, sc, sh, o);
         S3D_HIP(hipGetLastError());
-        IF_MARK(l + 1);
+        S3D_TRY(tm.mark(l + 1, st));
         cur = o;
         e[0] = hw[l][0];
         e[1] = hw[l][1];
         if (acts && acts[l])
             S3D_HIP(hipMemcpyAsync(acts[l], o, size_t(n) * e[0] * e[1] * d.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
-    for (int l = nl; l < kIfLayers; ++l) IF_MARK(l + 1);
+    for (int l = nl; l < kIfLayers; ++l) S3D_TRY(tm.mark(l + 1, st));
     if (h->net == S3D_IMGFEAT_ALEXNET)
         for (int l = 0; l < nl; ++l) {
             const long long npix = (long long)n * hw[l][0] * hw[l][1];
@@ -568,8 +485,8 @@ int s3d_imgfeat_features(s3d_imgfeat* h, const uint8_t* img, int n, int H, int W
                                kIfNets[h->net][l].cout, static_cast<float*>(h->unit[l].p));
             S3D_HIP(hipGetLastError());
         }
-    IF_MARK(kIfLayers + 1);
-    h->timed = h->profile;
+    S3D_TRY(tm.mark(kIfLayers + 1, st));
+    tm.timed = tm.on;
     h->n = n;
     h->nlayers = nl;
     memcpy(h->hw, hw, sizeof hw);
@@ -583,19 +500,9 @@ int s3d_imgfeat_stats(s3d_imgfeat* h, double* mu, double* sigma, void* stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int l = h->nlayers - 1, C = kIfNets[h->net][l].cout;
     const long long R = (long long)h->hw[l][0] * h->hw[l][1];
-    const int nparts = int((R + kIfGramSpan - 1) / kIfGramSpan);
-    S3D_TRY(h->gpart.reserve(size_t(h->n) * nparts * C * C * sizeof(double)));
-    S3D_TRY(h->mpart.reserve(size_t(h->n) * nparts * C * sizeof(double)));
     const float* act = static_cast<const float*>(h->out[l].p);
-    double* gp = static_cast<double*>(h->gpart.p);
-    double* mp = static_cast<double*>(h->mpart.p);
-    const dim3 grid((unsigned)nparts, (unsigned)(C / 64), (unsigned)h->n);
-    if (C == 64) hipLaunchKernelGGL(k_if_gram<64>, grid, dim3(kIfThreads), 0, st, act, R, nparts, gp, mp);
-    else hipLaunchKernelGGL(k_if_gram<192>, grid, dim3(kIfThreads), 0, st, act, R, nparts, gp, mp);
-    S3D_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_if_cov, dim3((unsigned)(C * C / 16), (unsigned)h->n), dim3(kIfThreads), 0, st, gp, mp, nparts, C, double(R), mu, sigma);
-    S3D_HIP(hipGetLastError());
-    return 0;
+    if (C == 64) return launch_rows_stats<64>(IfRows<64>{act, R}, R, h->n, kIfGramSpan, h->gpart, h->mpart, mu, sigma, st);
+    return launch_rows_stats<192>(IfRows<192>{act, R}, R, h->n, kIfGramSpan, h->gpart, h->mpart, mu, sigma, st);
 }
 
 int s3d_imgfeat_pairs(s3d_imgfeat* h, double* layers, double* total, void* stream) {
@@ -629,24 +536,12 @@ int s3d_imgfeat_pairs(s3d_imgfeat* h, double* layers, double* total, void* strea
 
 int s3d_imgfeat_profile(s3d_imgfeat* h, int on) {
     S3D_CHECK(h, S3D_ERR_INVALID, "imgfeat_profile: null handle");
-    if (on)
-        for (hipEvent_t& e : h->ev)
-            if (!e) S3D_HIP(hipEventCreate(&e));
-    h->profile = on != 0;
-    h->timed = false;
-    return 0;
+    return h->timer.enable(on != 0);
 }
 
 int s3d_imgfeat_profile_read(s3d_imgfeat* h, double ms[6]) {
     S3D_CHECK(h && ms, S3D_ERR_INVALID, "imgfeat_profile_read: null argument");
-    S3D_CHECK(h->timed, S3D_ERR_INVALID, "imgfeat_profile_read: no call has been timed (s3d_imgfeat_profile(h, 1), then s3d_imgfeat_features)");
-    S3D_HIP(hipEventSynchronize(h->ev[kIfLayers + 1]));
-    for (int i = 0; i < kIfLayers + 1; ++i) {
-        float t = 0.f;
-        S3D_HIP(hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]));
-        ms[i] = double(t);
-    }
-    return 0;
+    return h->timer.read("imgfeat", ms);
 }
 
 }  // extern "C"

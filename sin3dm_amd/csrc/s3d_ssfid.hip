@@ -8,18 +8,15 @@
 //   k_ssfid_l2      implicit GEMM on mfma_f32_32x32x2f32: M = 4 x 4 x 8 output voxels per block, N = 64, K = 64 taps x 32 channels in
 //                   four 8-channel halo chunks; normalise + leaky_relu applied while staging the halo, out-of-range positions
 //                   staged as exact zeros; the epilogue leaves the second norm's partials
-//   k_ssfid_gram    normalise + leaky_relu of 128 rows, their activations (optional), column sums and C x C Gram in float64
-//   k_ssfid_cov     block partials -> mu, sigma (float64), parts added in index order
+//   SfRows          normalise + leaky_relu of the rows and their activations (optional), as the load of k_rows_gram: the column
+//                   sums, the C x C Gram and k_rows_cov's mu, sigma are s3d_rowstats.h's, 128 rows per block
 //
 // No float atomics; every sum has a fixed order that depends on the volume's shape alone, so the same input gives the same bits.
 // Statistics are taken about the channel's bias: a constant channel (an empty volume) has variance exactly 0 and normalises to
 // exactly 0, as in exact arithmetic.
-#include "s3d_common.h"
+#include "s3d_rowstats.h"
 
 namespace s3d {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kSfThreads = 256;
 constexpr int kSfC1 = 32, kSfC2 = 64, kSfTaps = 64;
@@ -33,7 +30,7 @@ constexpr int kSfChunk = 8, kSfChunks = kSfC1 / kSfChunk;
 constexpr int kSfHalo = kSfHx * kSfHy * kSfHz;        // 1800 positions
 constexpr int kSfStageBatch = 5;                      // halo loads in flight per thread while staging (15 per chunk)
 constexpr int kSfFlushTaps = 2;                       // taps per float32 MFMA chain of layer 2 (1, 2 or 4)
-constexpr int kSfGramRows = 128;                      // rows per block of k_ssfid_gram
+constexpr int kSfGramSpan = 128;                      // rows per block of k_rows_gram: 256 blocks at 128^3, one per CU
 
 __device__ static inline float sf_act(float x, double mean, double rstd) {
     const float v = float((double(x) - mean) * rstd);
@@ -284,86 +281,29 @@ __global__ void __launch_bounds__(kSfThreads) k_ssfid_l2(const float* __restrict
     }
 }
 
-// ------------------------------------------------------------------ rows -> activations, column sums, Gram
-// Block b takes rows [128 b, 128 b + 128): a = leaky_relu((x - mean) * rstd) as float32 (what the reference hands to np.cov), kept
-// in LDS and written to `act` when asked for; thread (ti, tj) = (t / 16, t % 16) owns the C/16 x C/16 block of sum a_i a_j at
-// (ti, tj) * C/16, accumulated over the rows in order in float64; threads < C add the columns.  Rows past the end are zeros.
+// ------------------------------------------------------------------ rows -> activations: the Load of k_rows_gram
+// a = leaky_relu((x - mean) * rstd) as float32 (what the reference hands to np.cov), written to `act` when asked for.  A thread
+// keeps its channel quad (kRsThreads is a multiple of C / 4), so bind fetches its four {mean, rstd} pairs once.
 template <int C>
-__global__ void __launch_bounds__(kSfThreads) k_ssfid_gram(const float* __restrict__ raw, long long R, const double* __restrict__ mr,
-                                                           float* __restrict__ act, double* __restrict__ gpart, double* __restrict__ mpart) {
-    constexpr int T = C / 16, LD = C + 4;
-    __shared__ float a[kSfGramRows * LD];
-    const int t = threadIdx.x;
-    const long long r0 = (long long)blockIdx.x * kSfGramRows;
-    const int rows = int(min((long long)kSfGramRows, R - r0));
-    {
-        constexpr int Q = C / 4;                                          // float4 per row; kSfThreads % Q == 0: a thread keeps its channels
-        const int cq = t % Q;
-        double mean[4], rstd[4];
+struct SfRows {
+    static_assert(kRsThreads % (C / 4) == 0, "a thread keeps its channel quad");
+    const float* raw;
+    const double* mr;
+    float* act;
+    double mean[4] = {}, rstd[4] = {};
+    __device__ void bind(int cq) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) { mean[e] = mr[(cq * 4 + e) * 2]; rstd[e] = mr[(cq * 4 + e) * 2 + 1]; }
-        for (int i = t; i < kSfGramRows * Q; i += kSfThreads) {
-            const int row = i / Q;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (row < rows) {
-                const f32x4 x = *reinterpret_cast<const f32x4*>(raw + (r0 + row) * C + cq * 4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = sf_act(x[e], mean[e], rstd[e]);
-                if (act) *reinterpret_cast<f32x4*>(act + (r0 + row) * C + cq * 4) = v;
-            }
-            *reinterpret_cast<f32x4*>(a + row * LD + cq * 4) = v;
-        }
     }
-    __syncthreads();
-    const int i0 = (t >> 4) * T, j0 = (t & 15) * T;
-    double g[T][T];
+    __device__ f32x4 operator()(long long, long long row, int cq) const {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(raw + row * C + cq * 4);
+        f32x4 v;
 #pragma unroll
-    for (int i = 0; i < T; ++i)
-#pragma unroll
-        for (int j = 0; j < T; ++j) g[i][j] = 0.0;
-    for (int row = 0; row < kSfGramRows; ++row) {
-        double ai[T], aj[T];
-#pragma unroll
-        for (int i = 0; i < T; ++i) { ai[i] = double(a[row * LD + i0 + i]); aj[i] = double(a[row * LD + j0 + i]); }
-#pragma unroll
-        for (int i = 0; i < T; ++i)
-#pragma unroll
-            for (int j = 0; j < T; ++j) g[i][j] = fma(ai[i], aj[j], g[i][j]);
+        for (int e = 0; e < 4; ++e) v[e] = sf_act(x[e], mean[e], rstd[e]);
+        if (act) *reinterpret_cast<f32x4*>(act + row * C + cq * 4) = v;
+        return v;
     }
-#pragma unroll
-    for (int i = 0; i < T; ++i)
-#pragma unroll
-        for (int j = 0; j < T; ++j) gpart[(long long)blockIdx.x * C * C + (i0 + i) * C + j0 + j] = g[i][j];
-    if (t < C) {
-        double s = 0.0;
-        for (int row = 0; row < kSfGramRows; ++row) s += double(a[row * LD + t]);
-        mpart[(long long)blockIdx.x * C + t] = s;
-    }
-}
-
-// mu[i] = S_i / R; sigma[i][j] = (G_ij - S_i S_j / R) / (R - 1): np.cov(rowvar=False), ddof = 1.  A block owns 16 entries (i, j);
-// lane pl = t % 16 of an entry adds parts pl, pl + 16, ... in order, then a fixed xor tree over the 16 lanes.
-__global__ void __launch_bounds__(kSfThreads) k_ssfid_cov(const double* __restrict__ gpart, const double* __restrict__ mpart, int nparts, int C,
-                                                          double R, double* __restrict__ mu, double* __restrict__ sigma) {
-    const int e = blockIdx.x * 16 + (threadIdx.x >> 4), pl = threadIdx.x & 15;       // C * C is a multiple of 16
-    const int i = e / C, j = e % C;
-    double g = 0.0, si = 0.0, sj = 0.0;
-    for (int p = pl; p < nparts; p += 16) {
-        g += gpart[(long long)p * C * C + e];
-        si += mpart[(long long)p * C + i];
-        sj += mpart[(long long)p * C + j];
-    }
-#pragma unroll
-    for (int off = 8; off >= 1; off >>= 1) {
-        g += __shfl_xor(g, off);
-        si += __shfl_xor(si, off);
-        sj += __shfl_xor(sj, off);
-    }
-    if (pl == 0) {
-        sigma[e] = (g - si * sj / R) / (R - 1.0);
-        if (j == 0) mu[i] = si / R;
-    }
-}
+};
 
 }  // namespace s3d
 
@@ -375,19 +315,9 @@ struct s3d_ssfid {
     bool packed = false;
     DevBuf w1T, b1, w2p, b2;             // [64][32]; [32]; fragment order (k_ssfid_l2); [64]
     DevBuf raw1, raw2, part1, part2, mr1, mr2, gpart, mpart;
-    // stage timing (s3d_ssfid_profile): events around layer 1, its statistics, layer 2, its statistics, the covariance
-    bool profile = false, timed = false;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    StageTimer<5> timer;                 // s3d_ssfid_profile: layer 1, its statistics, layer 2, its statistics, the covariance
     int last_layer = 0;
-    ~s3d_ssfid() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-    }
 };
-#define SF_MARK(i)                                             \
-    do {                                                       \
-        if (h->profile) S3D_HIP(hipEventRecord(h->ev[i], st)); \
-    } while (0)
 
 static const struct { const char* name; int ndim; int64_t shape[5]; } kSfParams[4] = {
     {"conv_1.weight", 5, {kSfC1, 1, 4, 4, 4}},
@@ -429,15 +359,9 @@ int s3d_ssfid_set_param(s3d_ssfid* h, const char* name, const float* data, const
     S3D_CHECK(h && name && data && shape, S3D_ERR_INVALID, "ssfid set_param: null argument");
     for (int p = 0; p < 4; ++p) {
         if (strcmp(kSfParams[p].name, name) != 0) continue;
-        bool ok = ndim == kSfParams[p].ndim;
-        size_t n = 1;
-        for (int k = 0; ok && k < ndim; ++k) { ok = shape[k] == kSfParams[p].shape[k]; n *= size_t(shape[k]); }
-        if (!ok) {
-            std::string got;
-            for (int k = 0; k < ndim && k < 8; ++k) got += (k ? ", " : "") + std::to_string((long long)shape[k]);
-            set_error("ssfid set_param: %s has shape [%s]; the classifier of ef_dim = 32 is the one supported", name, got.c_str());
-            return S3D_ERR_UNSUPPORTED;
-        }
+        size_t n;
+        S3D_TRY(check_param_shape("ssfid", name, shape, ndim, kSfParams[p].shape, kSfParams[p].ndim,
+                                  "the classifier of ef_dim = 32 is the one supported", n));
         h->host[p].assign(data, data + n);
         h->have[p] = true;
         h->packed = false;
@@ -474,85 +398,62 @@ int s3d_ssfid_features(s3d_ssfid* h, const uint8_t* vox, const int dims[3], int 
     const long long nb1 = (R1 + kSfThreads - 1) / kSfThreads;
     S3D_CHECK(nb1 < (1LL << 31), S3D_ERR_UNSUPPORTED, "ssfid_features: volume too large");
 
+    const int ntx = (X2 + kSfTx - 1) / kSfTx, nty = (Y2 + kSfTy - 1) / kSfTy, ntz = (Z2 + kSfTz - 1) / kSfTz;
+    const long long nb2 = (long long)ntx * nty * ntz;
+    // every allocation comes before the first launch
     S3D_TRY(h->raw1.reserve(size_t(R1) * kSfC1 * sizeof(float)));
     S3D_TRY(h->part1.reserve(size_t(nb1) * kSfC1 * 2 * sizeof(double)));
     S3D_TRY(h->mr1.reserve(kSfC1 * 2 * sizeof(double)));
-    if (out_layer == 2) {                                  // every allocation comes before the first launch
+    if (out_layer == 2) {
         S3D_TRY(h->raw2.reserve(size_t(R2) * kSfC2 * sizeof(float)));
+        S3D_TRY(h->part2.reserve(size_t(nb2) * kSfC2 * 2 * sizeof(double)));
         S3D_TRY(h->mr2.reserve(kSfC2 * 2 * sizeof(double)));
     }
-    h->timed = false;
-    SF_MARK(0);
+    S3D_TRY(reserve_rows_stats(out_layer == 2 ? kSfC2 : kSfC1, out_layer == 2 ? R2 : R1, 1, kSfGramSpan, h->gpart, h->mpart));
+    StageTimer<5>& tm = h->timer;
+    tm.timed = false;
+    S3D_TRY(tm.mark(0, st));
+    const float* raw1 = static_cast<const float*>(h->raw1.p);
+    const double* mr1 = static_cast<const double*>(h->mr1.p);
     hipLaunchKernelGGL(k_ssfid_l1, dim3((unsigned)nb1), dim3(kSfThreads), 0, st, vox, X, Y, Z, Y1, Z1, R1, static_cast<const float*>(h->w1T.p),
                        static_cast<const float*>(h->b1.p), static_cast<float*>(h->raw1.p), static_cast<double*>(h->part1.p));
     S3D_HIP(hipGetLastError());
-    SF_MARK(1);
+    S3D_TRY(tm.mark(1, st));
     hipLaunchKernelGGL(k_ssfid_mr, dim3(kSfC1), dim3(64), 0, st, static_cast<const double*>(h->part1.p), int(nb1), kSfC1,
                        static_cast<const float*>(h->b1.p), double(R1), static_cast<double*>(h->mr1.p));
     S3D_HIP(hipGetLastError());
-    SF_MARK(2);
-    SF_MARK(3);
-    SF_MARK(4);
-
-    const float* raw = static_cast<const float*>(h->raw1.p);
-    const double* mr = static_cast<const double*>(h->mr1.p);
-    long long R = R1;
-    int C = kSfC1;
+    for (int i = 2; i <= 4; ++i) S3D_TRY(tm.mark(i, st));                  // layer 1 alone: stages 2 and 3 are empty
     if (out_layer == 2) {
-        const int ntx = (X2 + kSfTx - 1) / kSfTx, nty = (Y2 + kSfTy - 1) / kSfTy, ntz = (Z2 + kSfTz - 1) / kSfTz;
-        const long long nb2 = (long long)ntx * nty * ntz;
-        S3D_TRY(h->part2.reserve(size_t(nb2) * kSfC2 * 2 * sizeof(double)));
-        hipLaunchKernelGGL(k_ssfid_l2, dim3((unsigned)nb2), dim3(kSfThreads), 0, st, raw, X1, Y1, Z1, mr, static_cast<const f32x4*>(h->w2p.p),
+        hipLaunchKernelGGL(k_ssfid_l2, dim3((unsigned)nb2), dim3(kSfThreads), 0, st, raw1, X1, Y1, Z1, mr1, static_cast<const f32x4*>(h->w2p.p),
                            static_cast<const float*>(h->b2.p), X2, Y2, Z2, nty, ntz, static_cast<float*>(h->raw2.p),
                            static_cast<double*>(h->part2.p));
         S3D_HIP(hipGetLastError());
-        SF_MARK(3);
+        S3D_TRY(tm.mark(3, st));
         hipLaunchKernelGGL(k_ssfid_mr, dim3(kSfC2), dim3(64), 0, st, static_cast<const double*>(h->part2.p), int(nb2), kSfC2,
                            static_cast<const float*>(h->b2.p), double(R2), static_cast<double*>(h->mr2.p));
         S3D_HIP(hipGetLastError());
-        SF_MARK(4);
-        raw = static_cast<const float*>(h->raw2.p);
-        mr = static_cast<const double*>(h->mr2.p);
-        R = R2;
-        C = kSfC2;
+        S3D_TRY(tm.mark(4, st));
+        const SfRows<kSfC2> rows{static_cast<const float*>(h->raw2.p), static_cast<const double*>(h->mr2.p), act};
+        S3D_TRY(launch_rows_stats<kSfC2>(rows, R2, 1, kSfGramSpan, h->gpart, h->mpart, mu, sigma, st));
+    } else {
+        const SfRows<kSfC1> rows{raw1, mr1, act};
+        S3D_TRY(launch_rows_stats<kSfC1>(rows, R1, 1, kSfGramSpan, h->gpart, h->mpart, mu, sigma, st));
     }
-    const long long nbg = (R + kSfGramRows - 1) / kSfGramRows;
-    S3D_TRY(h->gpart.reserve(size_t(nbg) * C * C * sizeof(double)));
-    S3D_TRY(h->mpart.reserve(size_t(nbg) * C * sizeof(double)));
-    double* gp = static_cast<double*>(h->gpart.p);
-    double* mp = static_cast<double*>(h->mpart.p);
-    if (C == kSfC1)
-        hipLaunchKernelGGL(k_ssfid_gram<kSfC1>, dim3((unsigned)nbg), dim3(kSfThreads), 0, st, raw, R, mr, act, gp, mp);
-    else
-        hipLaunchKernelGGL(k_ssfid_gram<kSfC2>, dim3((unsigned)nbg), dim3(kSfThreads), 0, st, raw, R, mr, act, gp, mp);
-    S3D_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_ssfid_cov, dim3(C * C / 16), dim3(kSfThreads), 0, st, gp, mp, int(nbg), C, double(R), mu, sigma);
-    S3D_HIP(hipGetLastError());
-    SF_MARK(5);
-    h->timed = h->profile;
+    S3D_TRY(tm.mark(5, st));
+    tm.timed = tm.on;
     h->last_layer = out_layer;
     return 0;
 }
 
 int s3d_ssfid_profile(s3d_ssfid* h, int on) {
     S3D_CHECK(h, S3D_ERR_INVALID, "ssfid_profile: null handle");
-    if (on)
-        for (hipEvent_t& e : h->ev)
-            if (!e) S3D_HIP(hipEventCreate(&e));
-    h->profile = on != 0;
-    h->timed = false;
-    return 0;
+    return h->timer.enable(on != 0);
 }
 
 int s3d_ssfid_profile_read(s3d_ssfid* h, double ms[5]) {
     S3D_CHECK(h && ms, S3D_ERR_INVALID, "ssfid_profile_read: null argument");
-    S3D_CHECK(h->timed, S3D_ERR_INVALID, "ssfid_profile_read: no call has been timed (s3d_ssfid_profile(h, 1), then s3d_ssfid_features)");
-    S3D_HIP(hipEventSynchronize(h->ev[5]));
-    for (int i = 0; i < 5; ++i) {
-        float t = 0.f;
-        S3D_HIP(hipEventElapsedTime(&t, h->ev[i], h->ev[i + 1]));
-        ms[i] = h->last_layer == 1 && (i == 2 || i == 3) ? 0.0 : double(t);
-    }
+    S3D_TRY(h->timer.read("ssfid", ms));
+    if (h->last_layer == 1) ms[2] = ms[3] = 0.0;
     return 0;
 }
 

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ._weights import FeatureHandle, check_weights, load_state  # noqa: F401  (lpips.py and the tests take them from here)
 from .ssfid import frechet_distance
 
 SIFID_DIMS = (64, 192)
@@ -24,30 +25,6 @@ for _n, _ci, _co, _k in _UNITS:
     INCEPTION_PARAM_SHAPES[f"{_n}.conv.weight"] = (_co, _ci, _k, _k)
     for _s in ("weight", "bias", "running_mean", "running_var"):
         INCEPTION_PARAM_SHAPES[f"{_n}.bn.{_s}"] = (_co,)
-
-
-def check_weights(state, shapes, what):
-    """The tensors of `shapes` out of a state dict as contiguous float32 on the host; every other key is ignored.  KeyError names a
-    missing key, ValueError a wrong shape."""
-    out = {}
-    for name, shape in shapes.items():
-        if name not in state:
-            raise KeyError(f"{what} weights: key '{name}' is missing")
-        t = torch.as_tensor(state[name]).detach().to("cpu", torch.float32).contiguous()
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{what} weights: '{name}' has shape {tuple(t.shape)}, expected {shape}")
-        out[name] = t
-    return out
-
-
-def load_state(weights):
-    """A state dict from a path (torch.load) or a mapping."""
-    if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__"):
-        state = torch.load(weights, map_location="cpu")
-        if not hasattr(state, "keys"):
-            raise ValueError(f"{weights}: a state dict is expected, got {type(state).__name__}")
-        return state
-    return weights
 
 
 def check_inception_weights(state):
@@ -87,30 +64,11 @@ def as_image_batch(images):
     return t.contiguous()
 
 
-class ImageFeatureNet:
+class ImageFeatureNet(FeatureHandle):
     """A handle of s3d_imgfeat: parameters by name, the features call, the stage timing."""
+    PREFIX, STAGES = "imgfeat", 6
     NET = None
-    SHAPES = None
-    WHAT = None
-
-    def __init__(self, weights=None):
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
-        _lib.check(self._lib.s3d_imgfeat_create(self.NET, C.byref(self._h)))
-        if weights is not None:
-            self.load_weights(weights)
-
-    def load_weights(self, weights, shapes=None, what=None):
-        for name, t in check_weights(load_state(weights), shapes or self.SHAPES, what or self.WHAT).items():
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            _lib.check(self._lib.s3d_imgfeat_set_param(self._h, name.encode(), C.c_void_p(t.data_ptr()), shape, t.dim()))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.s3d_imgfeat_destroy(self._h)
-            self._h = None
-
-    __del__ = close
+    CREATE_ARGS = property(lambda self: (self.NET,))
 
     def out_dims(self, H, W, dims=0):
         """[(rows, columns, channels)] per unit.  NotImplementedError for dims the stem does not have, ValueError for an image
@@ -135,13 +93,11 @@ class ImageFeatureNet:
 
     def profile(self, on=True):
         """Record device events between the units of every following features call (tools/bench_imgmetrics.py)."""
-        _lib.check(self._lib.s3d_imgfeat_profile(self._h, int(bool(on))))
+        super().profile(on)
 
     def stage_ms(self):
         """Milliseconds of the last timed features call: units 1..5 (a pool counts with the unit it feeds), the unit normalisation."""
-        ms = (C.c_double * 6)()
-        _lib.check(self._lib.s3d_imgfeat_profile_read(self._h, ms))
-        return tuple(ms)
+        return super().stage_ms()
 
 
 class InceptionStem(ImageFeatureNet):

@@ -13,55 +13,28 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ._weights import FeatureHandle, check_weights, load_state
 from .patch_utils import _as_occupancy, _dims, load_sdfgrid2vox, load_voxgrid
 
 PARAM_SHAPES = {"conv_1.weight": (32, 1, 4, 4, 4), "conv_1.bias": (32,), "conv_2.weight": (64, 32, 4, 4, 4), "conv_2.bias": (64,)}
+_HINT = " (the classifier of ef_dim = 32)"
 
 
 def check_classifier_weights(state):
     """The four tensors of PARAM_SHAPES out of a state dict of the reference's `classifier`, as contiguous float32 on the host;
     every other key (conv_3 ... linear1) is ignored.  KeyError names a missing key, ValueError a wrong shape."""
-    out = {}
-    for name, shape in PARAM_SHAPES.items():
-        if name not in state:
-            raise KeyError(f"classifier weights: key '{name}' is missing")
-        t = torch.as_tensor(state[name]).detach().to("cpu", torch.float32).contiguous()
-        if tuple(t.shape) != shape:
-            raise ValueError(f"classifier weights: '{name}' has shape {tuple(t.shape)}, expected {shape} (the classifier of ef_dim = 32)")
-        out[name] = t
-    return out
+    return check_weights(state, PARAM_SHAPES, "classifier", _HINT)
 
 
 def load_classifier_weights(path):
     """torch.load of the reference's Clsshapenet_128.pth (a state dict), reduced to the two layers SSFID reads."""
-    state = torch.load(path, map_location="cpu")
-    if not hasattr(state, "keys"):
-        raise ValueError(f"{path}: a state dict is expected, got {type(state).__name__}")
-    return check_classifier_weights(state)
+    return check_classifier_weights(load_state(path))
 
 
-class VoxelClassifier:
+class VoxelClassifier(FeatureHandle):
     """Layers 1 and 2 of the reference's classifier on the device.  weights: a path or a state dict."""
-
-    def __init__(self, weights=None):
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
-        _lib.check(self._lib.s3d_ssfid_create(C.byref(self._h)))
-        if weights is not None:
-            self.load_weights(weights)
-
-    def load_weights(self, weights):
-        w = load_classifier_weights(weights) if isinstance(weights, (str, bytes)) or hasattr(weights, "__fspath__") else check_classifier_weights(weights)
-        for name, t in w.items():
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            _lib.check(self._lib.s3d_ssfid_set_param(self._h, name.encode(), C.c_void_p(t.data_ptr()), shape, t.dim()))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.s3d_ssfid_destroy(self._h)
-            self._h = None
-
-    __del__ = close
+    PREFIX, STAGES = "ssfid", 5
+    SHAPES, WHAT, HINT = PARAM_SHAPES, "classifier", _HINT
 
     def features_device(self, vox, out_layer=2, return_activations=False):
         """(mu [C], sigma [C][C]) as float64 device tensors, and the activations [rows][C] (float32) when asked for."""
@@ -78,13 +51,11 @@ class VoxelClassifier:
 
     def profile(self, on=True):
         """Record device events between the stages of every following call (tools/bench_ssfid.py)."""
-        _lib.check(self._lib.s3d_ssfid_profile(self._h, int(bool(on))))
+        super().profile(on)
 
     def stage_ms(self):
         """Milliseconds of the last timed call: layer 1, its statistics, layer 2, its statistics, the covariance."""
-        ms = (C.c_double * 5)()
-        _lib.check(self._lib.s3d_ssfid_profile_read(self._h, ms))
-        return tuple(ms)
+        return super().stage_ms()
 
     def features(self, vox, out_layer=2, return_activations=False):
         """calculate_activation_statistics (:65): (mu, sigma) as float64 NumPy; with return_activations also the activations, rows

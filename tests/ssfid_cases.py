@@ -103,3 +103,18 @@ def bound(gap, value):
     """The tolerance of DESIGN.md §21: ten times the reference's own float32-versus-float64 gap on this input, and never below one
     float32 ulp of the statistic's largest magnitude."""
     return max(10.0 * float(gap), 2.0 ** -23 * float(np.max(np.abs(value))) if np.size(value) else 0.0)
+
+
+def check_tail(what, rows, mu, sigma):
+    """The statistics tail on its own (s3d_rowstats.h): a device mean and ddof = 1 covariance against np.mean / np.cov of the
+    float32 rows [R][C] the device itself returned, so that no convolution error enters.  The tolerance is the forward-error bound
+    of a float64 sum of R terms in any order, 8 R 2^-53 sum |terms|: for sigma[i][j] over the products and the product of the
+    column sums, (sum_r |a_ri a_rj| + |sum_r a_ri| |sum_r a_rj| / R) / (R - 1); for mu[i] over sum_r |a_ri| / R."""
+    a = np.asarray(rows, dtype=np.float64)
+    R = a.shape[0]
+    u, s, ab = 8.0 * R * 2.0 ** -53, np.abs(a.sum(axis=0)), np.abs(a)
+    mu_b, sigma_b = u * ab.sum(axis=0) / R, u * (ab.T @ ab + np.outer(s, s) / R) / (R - 1)
+    mu_e, sigma_e = np.abs(mu - a.mean(axis=0)), np.abs(sigma - np.cov(a, rowvar=False))
+    print(f"{what}: {R} rows, mu err {mu_e.max():.3e} bound there {mu_b.flat[mu_e.argmax()]:.3e}, "
+          f"sigma err {sigma_e.max():.3e} bound there {sigma_b.flat[sigma_e.argmax()]:.3e}")
+    assert mu.shape == mu_b.shape and sigma.shape == sigma_b.shape and np.all(mu_e <= mu_b) and np.all(sigma_e <= sigma_b), what

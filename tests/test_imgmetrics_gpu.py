@@ -94,6 +94,16 @@ def test_batch_of_three_is_the_images_singly(stem, stats, dims):
         assert np.array_equal(mu[k], stats[(name, dims)][0]) and np.array_equal(sigma[k], stats[(name, dims)][1])
 
 
+@pytest.mark.parametrize("names, dims", [(("a0",), 64), (("a0",), 192), (("d",), 64), (S.BATCH, 64), (S.BATCH, 192)])
+def test_statistics_tail_against_the_returned_activations(stem, names, dims):
+    """320 rows at dims 192, 6305 rows (six spans of 1024 and a ragged seventh) and a batch: the Gram and covariance alone, at the
+    bound of tests/ssfid_cases.check_tail."""
+    mu, sigma, acts = stem.statistics(np.stack([S.image(n) for n in names]), dims, return_activations=True)
+    rows = acts[-1].cpu().numpy()
+    for k, name in enumerate(names):
+        S.check_tail(f"{name}/{dims}", rows[k].reshape(-1, dims), mu[k], sigma[k])
+
+
 def test_same_bits_call_after_call_on_reused_and_fresh_handles(stem, stats):
     fresh = F.InceptionStem(S.inception_weights())
     for name in ("d", "s", "d"):                                            # one handle large -> small -> large

@@ -34,7 +34,7 @@ def _kernel_metadata(asm):
         sym = re.search(r"^\s+\.name:\s+(\S+)", entry, re.M)
         if not sym:                        # (the amdhsa.version list that follows the kernels)
             continue
-        name = re.match(r"_ZN3s3d\d+(k_\w+?)E", sym.group(1))
+        name = re.match(r"_ZN3s3dL?\d+(k_\w+?)E", sym.group(1))      # L: a static kernel of a shared header
         out[name.group(1) if name else sym.group(1)] = {k: int(v) for k, v in re.findall(r"^\s+\.(\w+):\s+(\d+)\s*$", entry, re.M)}
     return out
 

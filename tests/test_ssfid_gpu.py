@@ -57,6 +57,18 @@ def test_activations_and_statistics_against_the_restatement(layer, g, net):
             assert not act.any() and not mu.any() and not sigma.any()
 
 
+@pytest.mark.parametrize("layer", S.LAYERS)
+def test_statistics_tail_against_the_returned_activations(layer, net):
+    """Fewer rows than one 64-row stage (24), exactly one stage (64), a 128-row span plus a full and a partial stage (240), many
+    spans (2080, 8640): the Gram and covariance alone, at the bound of tests/ssfid_cases.check_tail."""
+    cases = {name: _vox(name) for name in ("rank_a", "ref32", "ref48")}
+    if layer == 1:
+        cases["ones 16 x 16 x 3"] = torch.ones(16, 16, 3, dtype=torch.bool, device="cuda")
+    for name, vox in cases.items():
+        mu, sigma, act = net.features(vox, layer, return_activations=True)
+        S.check_tail(f"{name}/{layer}", act.cpu().numpy(), mu, sigma)
+
+
 def test_same_bits_call_after_call_and_handle_after_handle(net):
     vox = _vox("ref40")
     for layer in S.LAYERS:
