@@ -711,6 +711,64 @@ S3D_API int s3d_render_shade(const float* verts, const int32_t* xy_fixed, const 
                              uint8_t* rgba, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PBR renders: smooth normals, normal maps, a GGX light model and the material passes of the reference's
+ * rendering/blender_render_pbr.py, on the raster stage above.  Parity with Blender is not claimed: directional lights, no shadows,
+ * no ambient occlusion, no tone curve, texel values taken as they are (no sRGB decoding).
+ * ------------------------------------------------------------------------------------------------ */
+#define S3D_RENDER_MAX_LIGHTS 4
+/* materials of one s3d_pbr_shade call: the PBR table is a host array and travels with the launch */
+#define S3D_RENDER_PBR_MAX_MATERIALS 16
+#define S3D_RENDER_MIN_ROUGHNESS 0.089f
+/* albedo of the geo pass: 134 / 255 (blender_render_pbr.py:207) */
+#define S3D_RENDER_GEO_GREY (134.0f / 255.0f)
+/* overall scale of rendering/pbr.py's three_light_rig (key : fill : rim = 1 : 0.5 : 0.1): a white Lambert surface (metallic 0,
+ * roughness 1) that faces all three lights squarely stays below 1 with the default ambient */
+#define S3D_RENDER_RIG_INTENSITY 0.5f
+#define S3D_RENDER_PBR_AMBIENT 0.1f
+#define S3D_RENDER_PASS_SHADED 0
+#define S3D_RENDER_PASS_ALBEDO 1
+#define S3D_RENDER_PASS_METALLIC 2
+#define S3D_RENDER_PASS_ROUGHNESS 3
+#define S3D_RENDER_PASS_NORMAL 4
+#define S3D_RENDER_PASS_GEO 5
+/* normals [n_verts][3]: the normalised sum of the unnormalised normals cross(b - a, c - a) of the faces at a vertex (area weights),
+ * summed in ascending corner order in float64.  corner_order [3 n_faces]: the corners (corner k = vertex k % 3 of face k / 3) sorted
+ * by vertex index, stably; vertex_start [n_verts + 1]: vertex v owns corner_order[vertex_start[v] .. vertex_start[v + 1]).  A vertex
+ * without faces, or whose sum has squared length 0 or is not finite: (0, 0, 0), "use the flat normal". */
+S3D_API int s3d_pbr_vertex_normals(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const int64_t* corner_order,
+                                      const int64_t* vertex_start, float* normals, void* stream);
+/* tangents [n_faces][2][3] = (T, B) of the uv map uv [n_faces][3][2] (v in the GL convention of the lookups): with e1 = b - a,
+ * e2 = c - a, (du1, dv1), (du2, dv2) and det = du1 dv2 - du2 dv1: T = (e1 dv2 - e2 dv1) / det, B = (e2 du1 - e1 du2) / det, in
+ * float64.  det == 0 or a result that is not finite: T = B = 0, and the normal map is ignored on that face. */
+S3D_API int s3d_pbr_face_tangents(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const float* uv,
+                                     float* tangents, void* stream);
+/* s3d_render_shade with another light model; rgba, the resolve and every argument up to image_bytes as there, without its light.
+ * normals [n_verts][3] (s3d_pbr_vertex_normals; null: flat): the shading normal is the barycentric mix of the corners' normals,
+ * normalised and turned like the flat normal; the flat normal where a corner's normal is zero or the mix points away from it.
+ * tangents [n_faces][2][3] (needs uv; null: no normal maps).
+ * pbr_table HOST int64 [n_mats][4][3] = {byte offset into images, W, H} of the albedo (3 channels), metallic (1), roughness (1)
+ * and normal (3) maps of a material, W = 0: absent — then the factor of pbr_factors HOST float [n_mats][5] = {Kd r, g, b,
+ * metallic, roughness} (the normal map has none).  n_mats <= S3D_RENDER_PBR_MAX_MATERIALS; mat_table / mat_kd are not read.
+ * pbr_table null: the base colour of s3d_render_shade (vertex colours, mat_table / mat_kd, white), metallic 0, roughness 0.5.
+ * Normal map: t = 2 texel / 255 - 1, T' = normalize(T - N (N . T)), B' = cross(N, T') sign(cross(N, T') . B),
+ * N <- normalize(t.x T' + t.y B' + t.z N).
+ * eye [3]: the camera position in the space of verts; lights [n_lights][4]: unit direction towards the light and intensity.
+ * With V to the eye, H = normalize(L + V), alpha = r^2 (r clamped to [S3D_RENDER_MIN_ROUGHNESS, 1]), k = alpha / 2,
+ * F0 = 0.04 (1 - m) + albedo m, F = F0 + (1 - F0)(1 - V.H)^5, D = alpha^2 / (pi ((N.H)^2 (alpha^2 - 1) + 1)^2),
+ * G = NL / (NL (1 - k) + k) NV / (NV (1 - k) + k), NL = max(N.L, 0), NV = max(N.V, 1e-4):
+ * out = ambient albedo + sum_k I_k NL ((1 - F)(1 - m) albedo + pi D G F / (4 NL NV + 1e-6)), clamped to [0, 1].
+ * pass: S3D_RENDER_PASS_SHADED; _ALBEDO / _METALLIC / _ROUGHNESS: the unlit value (the scalars as grey; roughness before the clamp);
+ * _NORMAL: 0.5 N + 0.5; _GEO: shaded with albedo S3D_RENDER_GEO_GREY, metallic 0, roughness 0.5 and no normal map.
+ * S3D_ERR_INVALID (nothing is launched): more than S3D_RENDER_MAX_LIGHTS lights, an unknown pass, a table entry that runs past
+ * image_bytes, tangents without uv, a value that is not finite.  More materials than the cap: S3D_ERR_UNSUPPORTED. */
+S3D_API int s3d_pbr_shade(const float* verts, const int32_t* xy_fixed, const float* inv_w, int64_t n_verts, const int32_t* faces,
+                                 int64_t n_faces, const int32_t* face_id, int ws, int hs, int supersample, const float view_proj[16],
+                                 const float* vertex_colors, const float* uv, const int32_t* face_mat, const int64_t* mat_table,
+                                 const float* mat_kd, int n_mats, const uint8_t* images, int64_t image_bytes, const float* normals,
+                                 const float* tangents, const int64_t* pbr_table, const float* pbr_factors, const float eye[3],
+                                 const float* lights, int n_lights, float ambient, int pass, uint8_t* rgba, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * torch's CPU noise stream on the device: the float32 values `torch.randn` / `torch.rand` draw from
  * torch's default CPU generator (MT19937), so that a sampling run consumes the stream the reference consumes on the CPU
  * (src/diffusion/gaussian_diffusion.py:514, 431, 591) without a host draw and an upload per step.

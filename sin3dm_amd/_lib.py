@@ -27,6 +27,9 @@ RENDER_MAX_PAIRS = 1 << 27            # S3D_RENDER_MAX_PAIRS: 1 GiB of (tile, tr
 RENDER_TILE, RENDER_SUBPIXEL, RENDER_MAX_COORD, RENDER_MAX_GRID = 16, 256, 1 << 20, 4096
 IMGFEAT_INCEPTION, IMGFEAT_ALEXNET = 0, 1          # S3D_IMGFEAT_*
 RENDER_AMBIENT, RENDER_DIFFUSE = 0.35, 0.65                    # S3D_RENDER_AMBIENT / S3D_RENDER_DIFFUSE
+RENDER_MAX_LIGHTS, RENDER_PBR_MAX_MATERIALS, RENDER_MIN_ROUGHNESS = 4, 16, 0.089      # S3D_RENDER_MAX_LIGHTS / _PBR_MAX_MATERIALS / _MIN_ROUGHNESS
+RENDER_RIG_INTENSITY, RENDER_PBR_AMBIENT = 0.5, 0.1            # S3D_RENDER_RIG_INTENSITY / S3D_RENDER_PBR_AMBIENT
+RENDER_PASSES = ("shaded", "albedo", "metallic", "roughness", "normal", "geo")         # S3D_RENDER_PASS_*: the index is the value
 
 
 class UNetCfg(C.Structure):
@@ -208,6 +211,12 @@ SIGNATURES = {
     "s3d_render_shade": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    c_fp, c_fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
                                    C.c_void_p, C.c_void_p]),
+    # PBR renders: vertex normals, face tangents, the shade kernel with the GGX light model and the material passes
+    "s3d_pbr_vertex_normals": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3d_pbr_face_tangents": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3d_pbr_shade": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                       c_fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                       C.c_void_p, C.c_void_p, c_i64p, c_fp, c_fp, c_fp, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
     # torch's CPU noise stream on the device
     "s3d_rng_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "s3d_rng_destroy": (None, [C.c_void_p]),

@@ -4,22 +4,17 @@
 // light, the supersamples of a pixel averaged in a fixed order).  Scan and sort between the calls stay with the caller (torch), as
 // for s3d_meshsdf.hip.  Every loop bound is known at launch; no float atomics, no communication between workgroups; every output
 // element is written by one thread, so the same input gives the same bits.
-#include "s3d_common.h"
-
-#include <cmath>
+#include "s3d_render_dev.h"
 
 namespace s3d {
 
 constexpr int kRenderThreads = 256;
 constexpr int kRasterTile = S3D_RENDER_TILE;           // samples per tile edge: 16 * 16 = one sample per thread
 constexpr int kRasterChunk = 128;                      // triangles staged in LDS per round of k_render_raster: 72 bytes each
-constexpr int kSub = S3D_RENDER_SUBPIXEL;              // fixed-point units per sample
-constexpr int kMaxCoord = S3D_RENDER_MAX_COORD;        // |snapped coordinate| of a drawn triangle: products of two differences fit 2^43
 static_assert(kRasterTile * kRasterTile == kRenderThreads, "one sample per thread");
 static inline unsigned render_blocks(long long n) { return (unsigned)((n + kRenderThreads - 1) / kRenderThreads); }
 
 struct ViewProj { float m[16]; };
-enum TriStatus { TRI_OK = 0, TRI_NEAR = 1, TRI_RANGE = 2, TRI_DEGENERATE = 3 };
 
 // ------------------------------------------------------------------ project: clip = M (x, y, z, 1); sample coordinates with row 0 on
 // top, sample (i, j) centred at (i + 0.5, j + 0.5); snapped to 1 / 256.  w <= near (or not a number): inv_w = 0, the flag.
@@ -45,50 +40,7 @@ __global__ void __launch_bounds__(kRenderThreads) k_render_project(const float* 
     inv_w[i] = iw;
 }
 
-// ------------------------------------------------------------------ a face on the screen.  The corners are ordered so that the doubled
-// area (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0) is positive (corners 1 and 2 exchanged when it was negative: `swapped`), so that the
-// inside of every edge is the positive side.
-struct ScreenTri { int x0, y0, x1, y1, x2, y2; float iw0, iw1, iw2; int v0, v1, v2; long long area2; bool swapped; };
-
-__device__ __forceinline__ int load_screen_tri(const int* __restrict__ xy, const float* __restrict__ inv_w, long long V,
-                                               const int* __restrict__ faces, long long f, ScreenTri& t) {
-    const int a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
-    if (a < 0 || b < 0 || c < 0 || a >= V || b >= V || c >= V) return TRI_RANGE;
-    t.iw0 = inv_w[a]; t.iw1 = inv_w[b]; t.iw2 = inv_w[c];
-    if (!(t.iw0 > 0.0f) || !(t.iw1 > 0.0f) || !(t.iw2 > 0.0f)) return TRI_NEAR;
-    t.x0 = xy[a * 2LL]; t.y0 = xy[a * 2LL + 1];
-    t.x1 = xy[b * 2LL]; t.y1 = xy[b * 2LL + 1];
-    t.x2 = xy[c * 2LL]; t.y2 = xy[c * 2LL + 1];
-    if (max(max(abs(t.x0), abs(t.x1)), max(max(abs(t.x2), abs(t.y0)), max(abs(t.y1), abs(t.y2)))) > kMaxCoord) return TRI_RANGE;
-    t.v0 = a; t.v1 = b; t.v2 = c;
-    t.area2 = (long long)(t.x1 - t.x0) * (t.y2 - t.y0) - (long long)(t.y1 - t.y0) * (t.x2 - t.x0);
-    if (t.area2 == 0) return TRI_DEGENERATE;
-    t.swapped = t.area2 < 0;
-    if (t.swapped) {
-        int s;
-        s = t.x1; t.x1 = t.x2; t.x2 = s;
-        s = t.y1; t.y1 = t.y2; t.y2 = s;
-        s = t.v1; t.v1 = t.v2; t.v2 = s;
-        const float w = t.iw1; t.iw1 = t.iw2; t.iw2 = w;
-        t.area2 = -t.area2;
-    }
-    return TRI_OK;
-}
-
-// One edge a -> b as E(p) = A px + B py + C with the inside positive, and whether a sample ON the edge belongs to the triangle:
-// the sample is tested as if it stood at p + (-eps, -eps^2), which moves E by dy eps - dx eps^2 — positive exactly when
-// dy > 0, or dy == 0 and dx < 0 (the top-left rule).  One displaced point lies in exactly one triangle of a tiling.
-struct Edge { int A, B; long long C; int tl; };
-__device__ __forceinline__ Edge make_edge(int xa, int ya, int xb, int yb) {
-    Edge e;
-    const int dx = xb - xa, dy = yb - ya;
-    e.A = -dy; e.B = dx;
-    e.C = -((long long)e.A * xa + (long long)e.B * ya);
-    e.tl = (dy > 0 || (dy == 0 && dx < 0)) ? 1 : 0;
-    return e;
-}
-__device__ __forceinline__ long long edge_at(int A, int B, long long C, int px, int py) { return (long long)A * px + (long long)B * py + C; }
-__device__ __forceinline__ bool edge_inside(long long E, int tl) { return E + tl > 0; }
+// (a face on the screen, its edges and the fill rule: s3d_render_dev.h)
 // 1 / w at a sample: the edge values are the (unnormalised) screen-space barycentric weights of the opposite corners
 __device__ __forceinline__ float depth_at(long long e12, long long e20, long long e01, float iw0, float iw1, float iw2, float area2) {
     return __fdiv_rn(float(e12) * iw0 + float(e20) * iw1 + float(e01) * iw2, area2);
@@ -210,37 +162,7 @@ __global__ void __launch_bounds__(kRenderThreads) k_render_raster(const int* __r
 // base colour (vertex colours, or the material's image at the interpolated uv, or its Kd, or white), times ambient + diffuse *
 // max(0, n . light) with n the flat normal turned towards the camera.  Which side faces the camera is the sign of the integer
 // screen area (times the handedness of the matrix, front_sign), so it is decided exactly.
-// Bilinear lookup, the GL / Blender convention: texel (i, j) is centred at u = (i + 0.5) / W, v = 1 - (j + 0.5) / H with row j = 0
-// the top row of the image; clamp to edge.
-__device__ __forceinline__ void texel(const unsigned char* __restrict__ img, long long off, long long W, int x, int y, float c[3]) {
-    const unsigned char* p = img + off + ((long long)y * W + x) * 3;
-    c[0] = float(p[0]); c[1] = float(p[1]); c[2] = float(p[2]);
-}
-__device__ __forceinline__ void tex_bilinear(const unsigned char* __restrict__ img, long long off, int W, int H, float u, float v, float c[3]) {
-    const float x = fminf(fmaxf(u * float(W) - 0.5f, -1.0f), float(W)), y = fminf(fmaxf((1.0f - v) * float(H) - 0.5f, -1.0f), float(H));
-    const float xf = floorf(x), yf = floorf(y), fx = x - xf, fy = y - yf;
-    const int x0 = min(max(int(xf), 0), W - 1), x1 = min(max(int(xf) + 1, 0), W - 1);
-    const int y0 = min(max(int(yf), 0), H - 1), y1 = min(max(int(yf) + 1, 0), H - 1);
-    float c00[3], c10[3], c01[3], c11[3];
-    texel(img, off, W, x0, y0, c00); texel(img, off, W, x1, y0, c10); texel(img, off, W, x0, y1, c01); texel(img, off, W, x1, y1, c11);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float top = c00[k] + fx * (c10[k] - c00[k]), bot = c01[k] + fx * (c11[k] - c01[k]);
-        c[k] = __fdiv_rn(top + fy * (bot - top), 255.0f);
-    }
-}
-
-struct ShadeArgs {
-    const float* verts; const int* xy; const float* inv_w; long long V;
-    const int* faces; long long F;
-    const int* face_id; int ws, hs, ss, W, H;
-    float light[3]; int front_sign;
-    const float* vcol; const float* uv; const int* face_mat;
-    const long long* mat; const float* kd; int M;
-    const unsigned char* img; long long img_bytes;
-    unsigned char* rgba;
-};
-
+// The shared pieces (barycentrics, bilinear lookup, base colour, face normal) are in s3d_render_dev.h.
 __global__ void __launch_bounds__(kRenderThreads) k_render_shade(ShadeArgs a) {
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= (long long)a.W * a.H) return;
@@ -253,43 +175,16 @@ __global__ void __launch_bounds__(kRenderThreads) k_render_shade(ShadeArgs a) {
             const int f = a.face_id[(long long)sy * a.ws + sx];
             ScreenTri t;
             if (f < 0 || f >= a.F || load_screen_tri(a.xy, a.inv_w, a.V, a.faces, f, t) != TRI_OK) continue;
-            const int px = sx * kSub + kSub / 2, py = sy * kSub + kSub / 2;
-            const Edge e01 = make_edge(t.x0, t.y0, t.x1, t.y1), e12 = make_edge(t.x1, t.y1, t.x2, t.y2), e20 = make_edge(t.x2, t.y2, t.x0, t.y0);
-            const float n0 = float(edge_at(e12.A, e12.B, e12.C, px, py)) * t.iw0, n1 = float(edge_at(e20.A, e20.B, e20.C, px, py)) * t.iw1,
-                        n2 = float(edge_at(e01.A, e01.B, e01.C, px, py)) * t.iw2;
-            const float sum = n0 + n1 + n2;
-            const float b0 = __fdiv_rn(n0, sum), b1 = __fdiv_rn(n1, sum), b2 = __fdiv_rn(n2, sum);
-            // base colour
-            float c[3] = {1.0f, 1.0f, 1.0f};
-            if (a.vcol) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) c[k] = b0 * a.vcol[t.v0 * 3LL + k] + b1 * a.vcol[t.v1 * 3LL + k] + b2 * a.vcol[t.v2 * 3LL + k];
-            } else if (a.M > 0) {
-                const int m = a.face_mat ? a.face_mat[f] : 0;
-                if (m >= 0 && m < a.M) {
-                    c[0] = a.kd[m * 3]; c[1] = a.kd[m * 3 + 1]; c[2] = a.kd[m * 3 + 2];
-                    const long long off = a.mat[m * 3], W = a.mat[m * 3 + 1], H = a.mat[m * 3 + 2];
-                    if (a.uv && W > 0 && H > 0 && off >= 0 && W <= 65536 && H <= 65536 && off + W * H * 3 <= a.img_bytes) {
-                        const float* q = a.uv + (long long)f * 6;                  // corners in the face's own order
-                        const int c1 = t.swapped ? 4 : 2, c2 = t.swapped ? 2 : 4;
-                        const float tu = b0 * q[0] + b1 * q[c1] + b2 * q[c2], tv = b0 * q[1] + b1 * q[c1 + 1] + b2 * q[c2 + 1];
-                        tex_bilinear(a.img, off, int(W), int(H), tu, tv, c);
-                    }
-                }
-            }
+            float b0, b1, b2, c[3] = {1.0f, 1.0f, 1.0f}, n[3];
+            sample_barycentrics(t, sx, sy, b0, b1, b2);
+            base_colour(a, t, f, b0, b1, b2, c);
             // the flat normal of the face in its own vertex order, towards the camera
-            const int o1 = t.swapped ? t.v2 : t.v1, o2 = t.swapped ? t.v1 : t.v2;
-            const float* A = a.verts + t.v0 * 3LL;
-            const float* B = a.verts + o1 * 3LL;
-            const float* Cc = a.verts + o2 * 3LL;
-            const float ux = B[0] - A[0], uy = B[1] - A[1], uz = B[2] - A[2], vx = Cc[0] - A[0], vy = Cc[1] - A[1], vz = Cc[2] - A[2];
-            float nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
+            bool front;
+            face_normal(a.verts, t, a.front_sign, n, front);
+            const float nx = n[0], ny = n[1], nz = n[2];
             const float len = sqrtf(nx * nx + ny * ny + nz * nz);
             float lambert = 0.0f;
             if (len > 0.0f) {
-                // own order: the screen area (rows downwards) is negative when `swapped`.  A right-handed camera (front_sign -1) sees
-                // a face whose normal points at it counter-clockwise, which is a negative area here: front when the product is positive
-                const bool front = (t.swapped ? -1 : 1) * a.front_sign > 0;
                 const float d = __fdiv_rn(nx * a.light[0] + ny * a.light[1] + nz * a.light[2], len);
                 lambert = fmaxf(front ? d : -d, 0.0f);
             }
@@ -307,18 +202,6 @@ __global__ void __launch_bounds__(kRenderThreads) k_render_shade(ShadeArgs a) {
     a.rgba[p * 4] = out[0]; a.rgba[p * 4 + 1] = out[1]; a.rgba[p * 4 + 2] = out[2]; a.rgba[p * 4 + 3] = out[3];
 }
 
-static int check_grid_size(const char* who, int ws, int hs) {
-    S3D_CHECK(ws >= 1 && hs >= 1 && ws <= S3D_RENDER_MAX_GRID && hs <= S3D_RENDER_MAX_GRID, S3D_ERR_INVALID,
-              "%s: sample grid %d x %d (1 to %d a side)", who, ws, hs, S3D_RENDER_MAX_GRID);
-    return 0;
-}
-static int check_mesh(const char* who, const void* xy, const void* inv_w, int64_t n_verts, const void* faces, int64_t n_faces) {
-    S3D_CHECK(n_verts >= 0 && n_verts <= INT32_MAX && n_faces >= 0 && n_faces <= INT32_MAX, S3D_ERR_INVALID, "%s: %lld vertices, %lld faces", who,
-              (long long)n_verts, (long long)n_faces);
-    S3D_CHECK(n_faces == 0 || faces, S3D_ERR_INVALID, "%s: null face table", who);
-    S3D_CHECK(n_verts == 0 || (xy && inv_w), S3D_ERR_INVALID, "%s: null vertex table", who);
-    return 0;
-}
 static inline int tiles_of(int n) { return (n + kRasterTile - 1) / kRasterTile; }
 
 }  // namespace s3d
@@ -391,27 +274,9 @@ int s3d_render_shade(const float* verts, const int32_t* xy_fixed, const float* i
                      const int32_t* face_id, int ws, int hs, int supersample, const float view_proj[16], const float light[3],
                      const float* vertex_colors, const float* uv, const int32_t* face_mat, const int64_t* mat_table, const float* mat_kd,
                      int n_mats, const uint8_t* images, int64_t image_bytes, uint8_t* rgba, void* stream) {
-    S3D_TRY(check_grid_size("render_shade", ws, hs));
-    S3D_TRY(check_mesh("render_shade", xy_fixed, inv_w, n_verts, faces, n_faces));
-    S3D_CHECK(supersample >= 1 && supersample <= 8 && ws % supersample == 0 && hs % supersample == 0, S3D_ERR_INVALID,
-              "render_shade: supersample %d (1 to 8, dividing the %d x %d sample grid)", supersample, ws, hs);
-    S3D_CHECK(view_proj && light, S3D_ERR_INVALID, "render_shade: null matrix or light");
-    for (int k = 0; k < 16; ++k) S3D_CHECK(std::isfinite(view_proj[k]), S3D_ERR_INVALID, "render_shade: matrix entry %d is not finite", k);
-    S3D_CHECK(std::isfinite(light[0]) && std::isfinite(light[1]) && std::isfinite(light[2]), S3D_ERR_INVALID, "render_shade: light is not finite");
-    S3D_CHECK(n_mats >= 0 && n_mats <= (1 << 20) && image_bytes >= 0, S3D_ERR_INVALID, "render_shade: bad material sizes");
-    S3D_CHECK(n_mats == 0 || (mat_table && mat_kd), S3D_ERR_INVALID, "render_shade: null material table");
-    S3D_CHECK(image_bytes == 0 || images, S3D_ERR_INVALID, "render_shade: null image buffer");
-    S3D_CHECK(face_id && rgba && (n_verts == 0 || verts), S3D_ERR_INVALID, "render_shade: null argument");
-    const float* m = view_proj;                               // handedness: the determinant of the x, y and w rows' linear parts
-    const double det = double(m[0]) * (double(m[5]) * m[14] - double(m[6]) * m[13]) - double(m[1]) * (double(m[4]) * m[14] - double(m[6]) * m[12]) +
-                       double(m[2]) * (double(m[4]) * m[13] - double(m[5]) * m[12]);
     ShadeArgs a;
-    a.verts = verts; a.xy = xy_fixed; a.inv_w = inv_w; a.V = n_verts; a.faces = faces; a.F = n_faces; a.face_id = face_id;
-    a.ws = ws; a.hs = hs; a.ss = supersample; a.W = ws / supersample; a.H = hs / supersample;
-    a.light[0] = light[0]; a.light[1] = light[1]; a.light[2] = light[2];
-    a.front_sign = det < 0.0 ? -1 : 1;
-    a.vcol = vertex_colors; a.uv = uv; a.face_mat = face_mat; a.mat = reinterpret_cast<const long long*>(mat_table); a.kd = mat_kd; a.M = n_mats;
-    a.img = images; a.img_bytes = image_bytes; a.rgba = rgba;
+    S3D_TRY(pack_shade_args("render_shade", verts, xy_fixed, inv_w, n_verts, faces, n_faces, face_id, ws, hs, supersample, view_proj, light,
+                            vertex_colors, uv, face_mat, mat_table, mat_kd, n_mats, images, image_bytes, rgba, a));
     hipLaunchKernelGGL(k_render_shade, dim3(render_blocks((long long)a.W * a.H)), dim3(kRenderThreads), 0, static_cast<hipStream_t>(stream), a);
     S3D_HIP(hipGetLastError());
     return 0;

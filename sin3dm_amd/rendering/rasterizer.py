@@ -1,5 +1,7 @@
 """Multi-view renders of a triangle mesh on the device (s3d_render.hip): project, bin, raster, shade.
-Scan, sort and segment starts between the kernels are torch calls here, as in data/mesh_sampler.py."""
+Scan, sort and segment starts between the kernels are torch calls here, as in data/mesh_sampler.py.
+Smooth normals, normal maps, the GGX light model and the material passes (s3d_render_pbr.hip) are the keyword
+arguments shading / passes / lights / ambient of render_views; without them a call is what it was."""
 from __future__ import annotations
 
 import ctypes as C
@@ -105,9 +107,124 @@ def pack_materials(materials, device):
             torch.tensor(kds, dtype=torch.float32, device=device).reshape(-1, 3).contiguous(), images.contiguous(), off)
 
 
+def vertex_normals(verts, faces):
+    """float32 [V, 3]: the area-weighted normal of every vertex (the normalised sum of cross(b - a, c - a) over its faces, in
+    ascending corner order, float64 on the device); (0, 0, 0) for a vertex no face references or whose sum vanishes."""
+    _lib.require_gpu(verts)
+    v = verts.contiguous().float().reshape(-1, 3)
+    t = faces.contiguous().to(torch.int32).reshape(-1, 3)
+    V, F, dev = v.shape[0], t.shape[0], v.device
+    with torch.cuda.device(dev):
+        keys, order = torch.sort(t.reshape(-1).to(torch.int64), stable=True)
+        start = torch.searchsorted(keys, torch.arange(V + 1, device=dev, dtype=torch.int64)).to(torch.int64).contiguous()
+        order = order.contiguous()
+        out = torch.empty((V, 3), device=dev, dtype=torch.float32)
+        _lib.check(_lib.load().s3d_pbr_vertex_normals(_lib.ptr(v), V, _lib.ptr(t), F, _lib.ptr(order), _lib.ptr(start), _lib.ptr(out),
+                                                         _lib.stream_ptr()))
+        torch.cuda.current_stream().synchronize()          # the temporaries above are done with
+    return out
+
+
+def face_tangents(verts, faces, uvs):
+    """float32 [F, 2, 3]: (T, B) = (d position / d u, d position / d v) of every face's uv map, uvs [F, 3, 2]; zeros where the
+    uv triangle has no area."""
+    _lib.require_gpu(verts)
+    v = verts.contiguous().float().reshape(-1, 3)
+    t = faces.contiguous().to(torch.int32).reshape(-1, 3)
+    V, F, dev = v.shape[0], t.shape[0], v.device
+    uv = uvs.to(dev).contiguous().float().reshape(F, 3, 2)
+    with torch.cuda.device(dev):
+        out = torch.empty((F, 2, 3), device=dev, dtype=torch.float32)
+        _lib.check(_lib.load().s3d_pbr_face_tangents(_lib.ptr(v), V, _lib.ptr(t), F, _lib.ptr(uv), _lib.ptr(out), _lib.stream_ptr()))
+        torch.cuda.current_stream().synchronize()
+    return out
+
+
+def eye_of(matrix):
+    """float64 [3]: the centre of projection of an object-to-clip matrix, the point its x, y and w rows all send to 0."""
+    m = np.asarray(matrix, dtype=np.float64).reshape(4, 4)[[0, 1, 3]]
+    return -np.linalg.solve(m[:, :3], m[:, 3])
+
+
+SHADINGS = ("flat", "smooth", "pbr", "pbr_flat")
+
+
+def _render_views_pbr(v, t, uvs, face_mat, materials, vertex_colors, views, W, H, ss, return_buffers, timer, shading, passes, lights, ambient):
+    """render_views with the light model of s3d_render_pbr.hip: one raster stage per view, one shade launch per pass."""
+    from . import pbr
+    lib = _lib.load()
+    dev, V, F = v.device, v.shape[0], t.shape[0]
+    Ws, Hs = W * ss, H * ss
+    single = isinstance(passes, str)
+    names = (passes,) if single else tuple(passes)
+    if not names or any(n not in _lib.RENDER_PASSES for n in names):
+        raise ValueError(f"render_views: passes {passes!r} (of {_lib.RENDER_PASSES})")
+    lights = pbr.three_light_rig() if lights is None else np.asarray(lights, dtype=np.float64).reshape(-1, 4)
+    if len(lights) > _lib.RENDER_MAX_LIGHTS:
+        raise ValueError(f"render_views: {len(lights)} lights (at most {_lib.RENDER_MAX_LIGHTS})")
+    ambient = _lib.RENDER_PBR_AMBIENT if ambient is None else float(ambient)
+    light_arr = (C.c_float * max(4 * len(lights), 1))(*[float(x) for x in lights.reshape(-1)])
+    vcol = uv = fm = tang = nrm = None
+    table = kd = images = None
+    ptab = pfac = None
+    n_mats = img_bytes = 0
+    if uvs is not None:
+        uv = uvs.to(dev).contiguous().float().reshape(F, 3, 2)
+    is_pbr = shading in ("pbr", "pbr_flat")
+    if vertex_colors is not None and not (is_pbr and materials):      # (pbr without materials: the colours are the albedo, as for smooth)
+        vcol = vertex_colors.to(dev).contiguous().float().reshape(V, 3)
+    elif materials:
+        if face_mat is not None:
+            fm = face_mat.to(dev).contiguous().to(torch.int32).reshape(F)
+        if is_pbr:
+            tab, fac, images, img_bytes = pbr.pack_pbr_materials(materials, dev)
+            n_mats = tab.shape[0]
+            if n_mats > _lib.RENDER_PBR_MAX_MATERIALS:
+                raise NotImplementedError(f"render_views: {n_mats} PBR materials (at most {_lib.RENDER_PBR_MAX_MATERIALS} in one call)")
+            ptab = (C.c_int64 * tab.size)(*[int(x) for x in tab.reshape(-1)])
+            pfac = (C.c_float * fac.size)(*[float(x) for x in fac.reshape(-1)])
+            if uv is not None and (tab[:, 3, 1] > 0).any():
+                tang = face_tangents(v, t, uv)
+        else:
+            table, kd, images, img_bytes = pack_materials(materials, dev)
+            n_mats = table.shape[0]
+    if shading in ("smooth", "pbr"):
+        nrm = vertex_normals(v, t)
+    out = {n: torch.empty((len(views), H, W, 4), device=dev, dtype=torch.uint8) for n in names}
+    buffers = []
+    for k, view in enumerate(views):
+        timer("start")
+        xy, iw = project(v, view.matrix, Ws, Hs, view.near)
+        timer("project")
+        r = rasterize(xy, iw, t, Ws, Hs, timer)
+        eye = _f3(eye_of(view.matrix))
+        with torch.cuda.device(dev):
+            for n in names:
+                _lib.check(lib.s3d_pbr_shade(_lib.ptr(v), _lib.ptr(xy), _lib.ptr(iw), V, _lib.ptr(t), F, _lib.ptr(r["face_id"]), Ws, Hs, ss,
+                                                    _f16(view.matrix), _lib.ptr(vcol), _lib.ptr(uv), _lib.ptr(fm), _lib.ptr(table), _lib.ptr(kd),
+                                                    n_mats, _lib.ptr(images) if img_bytes else C.c_void_p(0), img_bytes, _lib.ptr(nrm),
+                                                    _lib.ptr(tang), ptab, pfac, eye, light_arr, len(lights), ambient,
+                                                    _lib.RENDER_PASSES.index(n), _lib.ptr(out[n][k]), _lib.stream_ptr()))
+        timer("shade")
+        if return_buffers:
+            buffers.append(dict(r, xy_fixed=xy, inv_w=iw))
+    with torch.cuda.device(dev):
+        torch.cuda.current_stream().synchronize()
+    res = out[names[0]] if single or len(names) == 1 else out
+    return (res, buffers) if return_buffers else res
+
+
 def render_views(verts, faces, *, uvs=None, face_mat=None, materials=None, vertex_colors=None, views=None, resolution=(512, 512),
-                 supersample=2, return_buffers=False, timer=None):
+                 supersample=2, return_buffers=False, timer=None, shading="flat", passes=("shaded",), lights=None, ambient=None):
     """uint8 [n_views, H, W, 4] renders of a mesh given as device tensors: verts [V, 3], faces [F, 3].
+    shading / passes / lights / ambient (a call without them is the flat shader of §22, bit for bit):
+    shading "smooth": the same base colours under area-weighted vertex normals and the GGX light model (metallic 0, roughness
+    0.5); "pbr": the materials' further entries are used (rendering/pbr.py: metallic_image, roughness_image, normal_image, Pm,
+    Pr) on smooth normals, "pbr_flat" on flat ones — materials come before vertex colours there, and without materials the
+    vertex colours are the albedo, as for "smooth"; "flat" with any of the other three given: the light model on flat normals.
+    passes: names of _lib.RENDER_PASSES; one pass returns the array, several a dict of arrays by name (the raster stage runs once per view either way).  lights:
+    [n <= 4, 4] unit directions towards the light in the space of verts and intensities (None: pbr.three_light_rig());
+    ambient: scalar (None: _lib.RENDER_PBR_AMBIENT).
     Base colour: vertex_colors [V, 3] in [0, 1]; or materials (dicts with Kd and image, see pack_materials) with face_mat [F]
     (None: material 0) and per-corner uvs [F, 3, 2]; or white.  views: camera.View objects (None: the reference's eight views of
     the mesh normalised by its bounding box, camera.standard_views).  resolution: (W, H).  Alpha is the covered share of a pixel.
@@ -130,6 +247,11 @@ def render_views(verts, faces, *, uvs=None, face_mat=None, materials=None, verte
         else:
             lo, hi = np.zeros(3), np.ones(3)
         views = camera.standard_views(lo, hi, (W, H))
+    if shading not in SHADINGS:
+        raise ValueError(f"render_views: shading {shading!r} (of {SHADINGS})")
+    if shading != "flat" or tuple(passes) != ("shaded",) or isinstance(passes, str) or lights is not None or ambient is not None:
+        return _render_views_pbr(v, t, uvs, face_mat, materials, vertex_colors, views, W, H, ss, return_buffers, timer, shading, passes, lights,
+                                 ambient)
     vcol = uv = fm = None
     table = kd = images = None
     n_mats = img_bytes = 0

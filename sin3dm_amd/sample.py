@@ -18,6 +18,8 @@ metallic-roughness object.glb) there, one of --data_type sdf writes sdfgrid_r<re
 they write object.obj coloured by the albedo / without colours.  The data type comes from EXP/encoding/args.json.
 S3D_RENDER=views beside any of these also writes renderings/000.png ... 007.png into every sample folder that gets a mesh: the
 reference's eight views, drawn on the device from the arrays the export holds (sin3dm_amd/rendering).
+S3D_RENDER_SHADING=smooth or pbr beside it draws them with smooth normals and the three-light GGX model of DESIGN.md §24 (pbr: the
+metallic, roughness and normal channels of an sdfpbr sample's bake included); unset: the flat shader, as before.
 """
 from __future__ import annotations
 
@@ -69,16 +71,31 @@ def render_mode(mode=None):
     return name
 
 
-def render_sample(save_dir, mesh):
+def render_shading(mode=None):
+    """"" (the default: the flat shader the views always had), "flat", "smooth" or "pbr": the shading of the S3D_RENDER=views
+    renders (rendering/rasterizer.render_views).  mode=None reads the environment variable S3D_RENDER_SHADING."""
+    name = mode if mode is not None else (os.environ.get("S3D_RENDER_SHADING") or "")
+    if name not in ("", "flat", "smooth", "pbr"):
+        raise ValueError(f"render shading {name!r}: expected 'flat', 'smooth' or 'pbr' (or unset)")
+    return name
+
+
+def render_sample(save_dir, mesh, shading=None):
     """renderings/ beside a decoded mesh.  mesh: what decode_mesh (verts, tris, colours) or decode_texmesh (a dict, or None for an
-    empty iso-surface) returned.  Returns the paths written."""
+    empty iso-surface) returned.  shading: see render_shading; with "pbr" the 8-channel bake of an sdfpbr sample is used as it
+    lies on the device (albedo [..., :3], metallic [..., 3], roughness [..., 4], normal [..., 5:]).  Returns the paths written."""
     from .rendering.rasterizer import render_views
     from .rendering.render_multiview import write_views
+    shading = render_shading(shading)
     if mesh is None:
         return []
     if isinstance(mesh, dict):
         verts, tris, kw = mesh["verts"], mesh["tris"], {}
-        if mesh.get("image") is not None:
+        if mesh.get("image") is not None and shading == "pbr" and mesh["image"].shape[-1] == 8:
+            img = mesh["image"].flip(0)                         # (texel row 0 first: see below)
+            kw = dict(uvs=mesh["uvs"].reshape(-1, 3, 2), materials=[{"Kd": (1.0, 1.0, 1.0), "image": img[..., :3], "metallic_image": img[..., 3],
+                                                                     "roughness_image": img[..., 4], "normal_image": img[..., 5:8]}])
+        elif mesh.get("image") is not None:
             # the baked image has texel row 0 first, which the PNG shows as its bottom row: the rasteriser reads top row first
             kw = dict(uvs=mesh["uvs"].reshape(-1, 3, 2), materials=[{"Kd": (1.0, 1.0, 1.0), "image": mesh["image"][..., :3].flip(0)}])
     else:
@@ -87,6 +104,8 @@ def render_sample(save_dir, mesh):
         kw = dict(vertex_colors=cols[:, :3].clamp(0, 1)) if coloured else {}
     if tris.shape[0] == 0:
         return []
+    if shading not in ("", "flat"):                             # (unset: the call stays the one it always was)
+        kw["shading"] = shading
     images = render_views(verts, tris, **kw)
     return write_views(images.cpu().numpy(), os.path.join(save_dir, "renderings"))
 
@@ -180,6 +199,7 @@ def decode(args, paths):
     ae = ShapeAutoEncoder(encoding_log_dir(args.tag), args, device=dist_util.dev())
     ae.load_ckpt("final")
     views = render_mode() == "views"
+    shading = render_shading() if views else None              # (a mistyped value fails here, before the decoding)
     for path in paths:
         fm = [f.unsqueeze(0) for f in load_triplane_data(path, device=dist_util.dev(), compose=False)]
         if args.vox:
@@ -192,7 +212,7 @@ def decode(args, paths):
             # iso-surface on the device, vertex-coloured object.obj
             mesh = ae.decode_mesh(os.path.dirname(path), fm, args.reso)
         if views:
-            render_sample(os.path.dirname(path), mesh)
+            render_sample(os.path.dirname(path), mesh, shading)
 
 
 def main(argv=None):
