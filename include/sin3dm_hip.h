@@ -552,6 +552,20 @@ S3D_API int s3d_meshsdf_sample_surface(const float* tri9, int64_t n_faces, const
 S3D_API int s3d_meshsdf_texture(const int32_t* face, const float* bary, int64_t n, const float* uv, const int32_t* face_mat, int64_t n_faces,
                                 const int64_t* mat_table, const float* mat_kd, int n_mats, const uint8_t* images, int64_t image_bytes,
                                 float* colors, void* stream);
+/* The PBR variant (the reference's data/mesh_sampler_pbr.py; s3d_meshpbr.hip): out [n][8] = albedo rgb | metallic | roughness |
+ * normal xyz in [0, 1].  face, bary, uv, face_mat as above.  mat_table [n_mats][4][3] (device) = {byte offset into images, W, H} of
+ * the albedo, metallic, roughness and normal map of a material — albedo and normal tightly packed 8-bit RGB rows, metallic and
+ * roughness single 8-bit planes; W = 0: absent —, mat_factors [n_mats][5] (device) = Kd rgb, metallic, roughness: the table and
+ * factors of rendering.pbr.pack_pbr_materials.  The uv is interpolated once per query, by the expression of s3d_meshsdf_texture,
+ * and a NaN component of it is replaced by 0.  Per map, with that map's own W and H: texel x = round(u (W - 1)) mod W, y =
+ * round((1 - v) (H - 1)) mod H (half to even), value = byte / 255 (correctly rounded), so with the same albedo map columns 0..2
+ * equal s3d_meshsdf_texture's colours bit for bit.  Fallbacks: no albedo map: Kd; no metallic / roughness map: the factor; no
+ * normal map: (128, 128, 255) / 255, the flat tangent-space normal; a map whose texels would lie outside image_bytes, or a
+ * rounded coordinate that is not finite or >= 1e9 in magnitude: as if the map were absent; face -1: eight zeros.  A row is
+ * written as two 16-byte stores: `out` not 16-byte aligned is S3D_ERR_INVALID and launches nothing.  n == 0 does nothing. */
+S3D_API int s3d_meshsdf_texture_pbr(const int32_t* face, const float* bary, int64_t n, const float* uv, const int32_t* face_mat,
+                                    int64_t n_faces, const int64_t* mat_table, const float* mat_factors, int n_mats, const uint8_t* images,
+                                    int64_t image_bytes, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Geometry evaluation: the three metrics of the reference's evaluation/patch_utils.py that need nothing but

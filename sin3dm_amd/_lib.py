@@ -171,6 +171,8 @@ SIGNATURES = {
                                              C.c_void_p, C.c_void_p]),
     "s3d_meshsdf_texture": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                       C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "s3d_meshsdf_texture_pbr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     # geometry evaluation: occupancy pooling, patch validity and packing, LP maxima, pairwise counts
     "s3d_eval_pool_or": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
     "s3d_eval_patch_counts": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int)]),

@@ -212,9 +212,9 @@ class MeshSampler:
         return pts, face, bary
 
 
-def build_parser():
-    p = argparse.ArgumentParser(prog="python -m sin3dm_amd.data.mesh_sampler",
-                                description="OBJ/MTL -> the .npz that sin3dm_amd.train --data_path reads, on one MI355X")
+def build_parser(prog="python -m sin3dm_amd.data.mesh_sampler",
+                 description="OBJ/MTL -> the .npz that sin3dm_amd.train --data_path reads, on one MI355X"):
+    p = argparse.ArgumentParser(prog=prog, description=description)
     p.add_argument("-s", "--src", type=str, required=True)
     p.add_argument("-d", "--dst", type=str, required=True)
     p.add_argument("--reso", type=int, default=256)
@@ -231,15 +231,17 @@ def build_parser():
     return p
 
 
-def parse_args(argv=None):
-    args = build_parser().parse_args(argv)
+def parse_args(argv=None, parser=None):
+    args = (parser or build_parser()).parse_args(argv)
     if args.threshold is None:
         args.threshold = 2. / args.reso * 3
     return args
 
 
-def prepare(mesh, reso=256, n_surf=2_000_000, mult=8, threshold=None, enlarge_scale=1.03, only_vol=False, seed=0, timer=None):
-    """The dictionary the CLI saves (reference :152-222).  timer(name) is called at the start of every stage (tools/bench_prepare.py)."""
+def prepare_stages(mesh, texture, extra, reso=256, n_surf=2_000_000, mult=8, threshold=None, enlarge_scale=1.03, only_vol=False, seed=0,
+                   timer=None):
+    """The stages of prepare and of mesh_sampler_pbr.prepare_pbr.  texture(face, bary) -> float32 [n, C] on the device, 0 where
+    face is -1 (|sdf| = threshold); extra(mesh) -> the keys saved beside the grid keys."""
     import torch
     _lib.require_gpu()
     tick = timer or (lambda name: None)
@@ -259,9 +261,9 @@ def prepare(mesh, reso=256, n_surf=2_000_000, mult=8, threshold=None, enlarge_sc
     wn = mesh.winding_number(pts)
     tick("grid texture")
     vol_sdf = torch.where(wn.abs() >= 0.5, -dist, dist)
-    vol_tex = mesh.colors(face, bary)                       # face -1 (|sdf| = threshold) gives 0
-    out = {"pts_grid": vol_pts, "sdf_grid": vol_sdf.cpu().numpy().reshape(shape), "tex_grid": vol_tex.cpu().numpy().reshape(shape + (3,)),
-           "aabb": mesh.aabb, "threshold": thr, "Ka": mesh.Kas[0], "Kd": mesh.Kds[0], "Ks": mesh.Kss[0], "Ns": mesh.Nss[0]}
+    vol_tex = texture(face, bary)                           # face -1 (|sdf| = threshold) gives 0
+    out = {"pts_grid": vol_pts, "sdf_grid": vol_sdf.cpu().numpy().reshape(shape), "tex_grid": vol_tex.cpu().numpy().reshape(shape + (-1,)),
+           "aabb": mesh.aabb, "threshold": thr, **extra(mesh)}
     if only_vol:
         tick(None)
         return out
@@ -269,14 +271,14 @@ def prepare(mesh, reso=256, n_surf=2_000_000, mult=8, threshold=None, enlarge_sc
     gen = torch.Generator(device="cuda")
     gen.manual_seed(int(seed))
     on_pts, on_face, on_bary = mesh.sample_surf(n_surf, gen)
-    on_tex = mesh.colors(on_face, on_bary)
+    on_tex = texture(on_face, on_bary)
     tick("near-surface samples")
     lo = torch.from_numpy(mesh.aabb[:3].astype(np.float32)).to(on_pts.device)
     hi = torch.from_numpy(mesh.aabb[3:].astype(np.float32)).to(on_pts.device)
     noise = torch.randn(on_pts.shape, generator=gen, device=on_pts.device, dtype=torch.float32)
     near_pts = torch.minimum(torch.maximum(on_pts + noise * NEAR_SURF_SIGMA, lo), hi).contiguous()
     near_sdf, near_face, near_bary = mesh.query_sdf(near_pts, thr, with_closest=True)
-    near_tex = mesh.colors(near_face, near_bary)
+    near_tex = texture(near_face, near_bary)
     tick("download")
     out.update(pts_on_surf=on_pts.cpu().numpy(), tex_on_surf=on_tex.cpu().numpy(), pts_near_surf=near_pts.cpu().numpy(),
                sdf_near_surf=near_sdf.cpu().numpy(), tex_near_surf=near_tex.cpu().numpy())
@@ -284,18 +286,28 @@ def prepare(mesh, reso=256, n_surf=2_000_000, mult=8, threshold=None, enlarge_sc
     return out
 
 
-def main(argv=None):
-    args = parse_args(argv)
+def prepare(mesh, reso=256, n_surf=2_000_000, mult=8, threshold=None, enlarge_scale=1.03, only_vol=False, seed=0, timer=None):
+    """The dictionary the CLI saves (reference :152-222).  timer(name) is called at the start of every stage (tools/bench_prepare.py)."""
+    return prepare_stages(mesh, mesh.colors, lambda m: {"Ka": m.Kas[0], "Kd": m.Kds[0], "Ks": m.Kss[0], "Ns": m.Nss[0]}, reso=reso,
+                          n_surf=n_surf, mult=mult, threshold=threshold, enlarge_scale=enlarge_scale, only_vol=only_vol, seed=seed, timer=timer)
+
+
+def run_cli(args, sampler, prepare_fn):
+    """What main does after parsing: refuse without a GPU, read args.src with `sampler`, save prepare_fn's dictionary to args.dst."""
     _lib.require_gpu()                                     # before any work: no CPU fallback
     print("threshold:", args.threshold)
-    mesh = MeshSampler(args.src)
-    out = prepare(mesh, reso=args.reso, n_surf=args.n_surf, mult=args.mult, threshold=args.threshold, enlarge_scale=args.enlarge_scale,
-                  only_vol=args.only_vol, seed=args.seed)
+    mesh = sampler(args.src)
+    out = prepare_fn(mesh, reso=args.reso, n_surf=args.n_surf, mult=args.mult, threshold=args.threshold, enlarge_scale=args.enlarge_scale,
+                     only_vol=args.only_vol, seed=args.seed)
     os.makedirs(os.path.dirname(os.path.abspath(args.dst)), exist_ok=True)
     np.savez_compressed(args.dst, **out)
     for k in out:
         print(f"{k}: {np.asarray(out[k]).shape}")
     return 0
+
+
+def main(argv=None):
+    return run_cli(parse_args(argv), MeshSampler, prepare)
 
 
 if __name__ == "__main__":

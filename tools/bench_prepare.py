@@ -5,6 +5,7 @@ samples (the command line's defaults) on a procedural mesh of 24 000 faces: a bu
 warm-up run.  Writing the .npz (np.savez_compressed, host only) is timed once, separately.
 
     python tools/bench_prepare.py [--reso 256 --n_surf 2000000 --nu 120 --nv 100 --repeats 3] > profiles/prepare.txt
+    python tools/bench_prepare.py --pbr > profiles/prepare_pbr.txt         # prepare against mesh_sampler_pbr.prepare_pbr, interleaved
 """
 import argparse
 import collections
@@ -28,6 +29,8 @@ ap.add_argument("--nu", type=int, default=120)
 ap.add_argument("--nv", type=int, default=100)
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--no_save", action="store_true", help="skip timing np.savez_compressed")
+ap.add_argument("--pbr", action="store_true", help="the eight-channel prepare_pbr (four maps of different sizes) against the three-channel prepare, "
+                                                   "interleaved in one process, per stage and per texture launch by device events")
 args = ap.parse_args()
 
 _lib.require_gpu()                                   # no GPU: fail, there is nothing to measure
@@ -51,6 +54,86 @@ face_mat = (V[F].mean(1)[:, 1] < 0).astype(np.int32)
 materials = [{"Kd": (1.0, 1.0, 1.0), "image": image}, {"Kd": (0.3, 0.6, 0.2)}]
 
 stages = collections.OrderedDict()
+TEXTURE_CALLS = ("grid", "on-surface", "near-surface")          # the three texture calls of prepare, in order
+
+
+def pbr_materials():
+    """The two materials with four procedural maps of different sizes on the first: albedo 1024 x 1024 (the image above), metallic
+    512 x 512, roughness 256 x 512, normal 2048 x 1024."""
+    def plane(w, h, k):
+        y, x = np.mgrid[0:h, 0:w]
+        return ((x * k + y * (k + 2)) & 255).astype(np.uint8)
+    normal = np.stack([plane(2048, 1024, 1), plane(2048, 1024, 3), np.full((1024, 2048), 255, np.uint8)], -1)
+    return [dict(materials[0], metallic_image=plane(512, 512, 5), roughness_image=plane(256, 512, 7), normal_image=normal, Pm=0.0, Pr=1.0),
+            dict(materials[1], Pm=0.2, Pr=0.6)]
+
+
+def run_timed(pbr):
+    """One prepare (three channels) or prepare_pbr (eight): ({stage: ms} by device events recorded at every stage start, {texture
+    call: ms} by events around the three texture launches, the saved dictionary)."""
+    from sin3dm_amd.data.mesh_sampler_pbr import MeshSamplerPBR, prepare_pbr
+    if pbr:
+        mesh = MeshSamplerPBR(verts=V, faces=F, uvs=uvs, face_mat=face_mat, materials=pbr_materials())
+    else:
+        mesh = MeshSampler(verts=V, faces=F, uvs=uvs, face_mat=face_mat, materials=materials)
+    marks, calls = [], []
+    inner = mesh.materials8 if pbr else mesh.colors
+
+    def texture(face, bary):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = inner(face, bary)
+        b.record()
+        calls.append((a, b, int(face.shape[0]), face))
+        return out
+    setattr(mesh, "materials8" if pbr else "colors", texture)    # (prepare looks the method up on the instance)
+
+    def tick(name):
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record()
+        marks.append((name, ev))
+    out = (prepare_pbr if pbr else prepare)(mesh, reso=args.reso, n_surf=args.n_surf, timer=tick)
+    torch.cuda.synchronize()
+    cur = collections.OrderedDict()
+    for (name, ev), (_, nxt) in zip(marks[:-1], marks[1:]):
+        cur[name] = cur.get(name, 0.0) + ev.elapsed_time(nxt)
+    cur["TOTAL (without writing the file)"] = marks[0][1].elapsed_time(marks[-1][1])
+    tex =collections.OrderedDict((label, a.elapsed_time(b)) for label, (a, b, _, _) in zip(TEXTURE_CALLS, calls))
+    hits = collections.OrderedDict((label, (n, int((face >= 0).sum()))) for label, (_, _, n, face) in zip(TEXTURE_CALLS, calls))
+    return cur, tex, hits, out
+
+
+def run_pbr():
+    """The three-channel and the eight-channel prepare interleaved in one process."""
+    run_timed(False), run_timed(True)                    # warm-up: allocations, code objects
+    runs = {False: [], True: []}
+    for _ in range(args.repeats):
+        for pbr in (False, True):
+            runs[pbr].append(run_timed(pbr))
+    out = runs[True][-1][3]
+    grid = out["sdf_grid"].shape
+    assert out["tex_grid"].shape[-1] == 8 and runs[False][-1][3]["tex_grid"].shape[-1] == 3
+    assert all(np.array_equal(out[k], runs[False][-1][3][k]) for k in ("sdf_grid", "pts_on_surf", "sdf_near_surf"))
+    print(f"mesh preprocessing, three channels (prepare) against eight (prepare_pbr), one MI355X: {len(F)} faces, reso {args.reso} (grid "
+          f"{grid[0]} x {grid[1]} x {grid[2]} = {out['sdf_grid'].size} points), {args.n_surf} surface samples; the two interleaved in one process, "
+          f"median of {args.repeats} runs each after one warm-up [min .. max], ms by device events")
+
+    def row(label, a, b):
+        print(f"  {label:<34s} {statistics.median(a):9.3f} [{min(a):9.3f} .. {max(a):9.3f}]   {statistics.median(b):9.3f} [{min(b):9.3f} .. {max(b):9.3f}]"
+              f"   x {statistics.median(b) / max(statistics.median(a), 1e-9):.2f}")
+    print(f"  {'stage (with its host work and copies)':<34s} {'3 channels':^33s}   {'8 channels':^33s}")
+    for label in runs[False][0][0]:
+        row(label, [r[0][label] for r in runs[False]], [r[0][label] for r in runs[True]])
+    # nominal traffic of a query: face 4 B; on a hit bary 12, the face's uv 24, its material 4, the texels (3 | 3 + 1 + 1 + 3) and, per
+    # material, the table row; the row written (12 | 32)
+    miss, hit = (4 + 12, 4 + 32), (4 + 12 + 24 + 4 + 3 + 12, 4 + 12 + 24 + 4 + 8 + 32)
+    print(f"  {'texture launch alone':<34s} {'3 channels':^33s}   {'8 channels':^33s}        bytes moved, 8 : 3")
+    for label in TEXTURE_CALLS:
+        n, h = runs[True][-1][2][label]
+        b3, b8 = (n - h) * miss[0] + h * hit[0], (n - h) * miss[1] + h * hit[1]
+        row(f"{label} ({n} queries)", [r[1][label] for r in runs[False]], [r[1][label] for r in runs[True]])
+        print(f"      {h} hits at {hit[0]} | {hit[1]} B, {n - h} misses at {miss[0]} | {miss[1]} B: {b3 / 2 ** 20:.1f} | {b8 / 2 ** 20:.1f} MiB, ratio {b8 / b3:.2f}; "
+              f"{b3 / statistics.median([r[1][label] for r in runs[False]]) / 1e6:.0f} | {b8 / statistics.median([r[1][label] for r in runs[True]]) / 1e6:.0f} GB/s")
 
 
 def run():
@@ -70,8 +153,11 @@ def run():
     return cur, out, mesh
 
 
+if args.pbr:
+    run_pbr()
+    sys.exit(0)
 run()                                                # warm-up: allocations, code objects
-runs = [run() for _ in range(args.repeats)]
+runs =[run() for _ in range(args.repeats)]
 out, mesh = runs[-1][1], runs[-1][2]
 n_pairs = mesh._binned(mesh.band)[5]
 grid = out["sdf_grid"].shape
