@@ -142,6 +142,8 @@ def simplify_mesh(verts, tris, n_faces, attrs=None):
     longest bounding-box axis (cluster_grid); every occupied cell becomes one vertex, the mean of its members (added in ascending
     vertex order); faces are remapped, those with two equal indices dropped, of those with the same vertex set the first kept,
     the order preserved, unreferenced vertices dropped.  R is the result of a bisection: count(R) <= n_faces < count(R + 1).
+    Where no grid up to R = 2^20 is over the budget (faces that repeat a vertex set: the distinct sets fit the budget although the
+    faces do not), R = 2^20 is returned, the finest grid used, with count(R) <= n_faces alone: the deduplicated mesh.
     Returns (verts, tris, info); info: R and lo (the same number), s, origin, dims, keys (linear cell index of every input vertex,
     (ix * dims[1] + iy) * dims[2] + iz), vmap (cluster index of every input vertex, clusters numbered in ascending key), attrs (the attributes averaged like the positions, or None).  A mesh that already
     has at most n_faces faces is returned as it is (R = 0, vmap = arange)."""

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from test_texmesh_host import decode_png, parse_obj, rasterise
+from texmesh_cases import np_faces
 
 pytestmark = pytest.mark.gpu
 
@@ -45,16 +46,6 @@ def np_cluster_keys(v, R):
     dims = np.asarray([min(R, max(1, math.ceil(float(np.float32(e) / s)))) for e in ext], np.int64)
     idx = np.minimum(dims - 1, np.floor((v - lo) / s).astype(np.int64))
     return (idx[:, 0] * dims[1] + idx[:, 1]) * dims[2] + idx[:, 2], s, dims, lo, ext
-
-
-def np_faces(tris, vmap):
-    """remap, drop faces with two equal indices, keep the lowest-index face of every vertex set, preserve the order"""
-    m = vmap[tris].astype(np.int64)
-    ok = (m[:, 0] != m[:, 1]) & (m[:, 1] != m[:, 2]) & (m[:, 0] != m[:, 2])
-    if not ok.any():
-        return m[:0]
-    _, first = np.unique(np.sort(m[ok], 1), axis=0, return_index=True)
-    return m[np.flatnonzero(ok)[np.sort(first)]]
 
 
 def signed_volume(v, t):
