@@ -379,6 +379,12 @@ S3D_API int s3d_train_adamw_ema(float* params, const float* grads, float* exp_av
 /* ------------------------------------------------------------------------------------------------
  * Auto-encoder training tier: AutoEncoderGroupSkip encode / decode / losses and their
  * gradients (src/encoding/networks.py:122-220, src/encoding/model.py:178-237).  Reuses s3d_decoder_cfg.
+ * Variants (the numbers of s3d_decoder_create_variant):
+ *   0  the skip net with texture, tex_channels 1..8 (3: data_type sdftex; 8: sdfpbr with --enc_net_type skip);
+ *      volume 1 + tex_channels channels, pred = sdf | sigmoid(tex)
+ *   1  geometry only (use_tex=False of either class, data_type sdf): the tex_* fields are ignored, 1-channel volume,
+ *      pred = sdf, no tex group (tex_group_begin == the total size), tex may be null
+ *   2  the PBR net: S3D_ERR_UNSUPPORTED here (it decodes through s3d_decoder_* only)
  * Parameters: one caller-owned flat fp32 device vector, tensors in s3d_ae_param_info() order and PyTorch layouts:
  * [geo_encoder, geo_convs, geo_decoder | tex_encoder, tex_convs, tex_decoder] — the two halves are the reference's two
  * AdamW parameter groups (networks.py:146-150); use s3d_train_adamw_ema on each half with its learning rate.
@@ -395,7 +401,9 @@ typedef struct {
     float tex_weight;            /* 1.0 */
 } s3d_ae_loss_cfg;
 
-S3D_API int s3d_ae_create(const s3d_decoder_cfg* cfg, s3d_ae** out);
+S3D_API int s3d_ae_create(const s3d_decoder_cfg* cfg, s3d_ae** out);               /* variant 0 */
+S3D_API int s3d_ae_create_variant(const s3d_decoder_cfg* cfg, int variant, s3d_ae** out);
+S3D_API int s3d_ae_out_channels(const s3d_ae* a);               /* floats per row of pred: 1 + tex_channels, 1 for variant 1 */
 S3D_API void s3d_ae_destroy(s3d_ae* a);
 S3D_API int s3d_ae_num_params(const s3d_ae* a);
 S3D_API int s3d_ae_param_info(const s3d_ae* a, int i, const char** name, int64_t shape[5], int* ndim, int64_t* offset);
@@ -403,17 +411,23 @@ S3D_API int s3d_ae_param_info(const s3d_ae* a, int i, const char** name, int64_t
 S3D_API int64_t s3d_ae_param_numel(const s3d_ae* a, int64_t* tex_group_begin);
 S3D_API int s3d_ae_attach(s3d_ae* a, float* params, int64_t numel);
 S3D_API int s3d_ae_repack(s3d_ae* a, void* stream);              /* after every change of the attached vector */
-/* The training volume [1,C,2H,2W,2D] (device, C = 1 + tex_channels: sdf, texture): reduced once to the three
+/* The training volume [1,C,2H,2W,2D] (device, C = s3d_ae_out_channels: sdf, texture): reduced once to the three
  * projections the encoder needs; the volume itself is not kept. */
 S3D_API int s3d_ae_set_volume(s3d_ae* a, const float* vol, int C, int X2, int Y2, int Z2, void* stream);
 /* net.encode(vol): xy [1,Cg+Ct,H,W], xz [1,Cg+Ct,H,D], yz [1,Cg+Ct,W,D] */
 S3D_API int s3d_ae_encode(s3d_ae* a, float* xy, float* xz, float* yz, void* stream);
-/* net(vol, pts): pred [N, 1+tex_channels] (texture through the sigmoid) */
+/* net(vol, pts): pred [N, s3d_ae_out_channels] (texture through the sigmoid) */
 S3D_API int s3d_ae_forward(s3d_ae* a, const float* pts, int64_t N, const float aabb[6], float* pred, void* stream);
 /* _forward_batch + backward: losses[2] = {sdf_loss, tex_loss} (device), pred optional, grads = d(sdf_loss+tex_loss)/d params
  * (every element overwritten).  pts [N,3], sdf [N,1], tex [N,tex_channels] device. */
 S3D_API int s3d_ae_loss_grads(s3d_ae* a, const float* pts, const float* sdf, const float* tex, int64_t N, const float aabb[6],
                               const s3d_ae_loss_cfg* cfg, float* losses, float* pred, float* grads, void* stream);
+/* The same with the texture loss per column group: losses[4] = {sdf, rgb, mr, normal}, grads = the gradient of their sum.
+ * With 8 texture channels (data_type sdfpbr, model.py:226-233) rgb = columns 0-2, mr = 3-4 and normal = 5-7 are each their own
+ * mean over (points inside the band x its columns) times tex_weight; any other width is one group (losses[1], the sdftex
+ * loss; losses[2..3] = 0); variant 1 has no texture term (losses[1..3] = 0, tex may be null). */
+S3D_API int s3d_ae_loss_grads_groups(s3d_ae* a, const float* pts, const float* sdf, const float* tex, int64_t N, const float aabb[6],
+                                     const s3d_ae_loss_cfg* cfg, float* losses, float* pred, float* grads, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Iso-surface extraction: marching cubes on the device, replacing

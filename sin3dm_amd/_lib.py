@@ -229,6 +229,8 @@ SIGNATURES = {
     "s3d_rng_rand": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     # auto-encoder training tier
     "s3d_ae_create": (C.c_int, [C.POINTER(DecoderCfg), C.POINTER(C.c_void_p)]),
+    "s3d_ae_create_variant": (C.c_int, [C.POINTER(DecoderCfg), C.c_int32, C.POINTER(C.c_void_p)]),
+    "s3d_ae_out_channels": (C.c_int, [C.c_void_p]),
     "s3d_ae_destroy": (None, [C.c_void_p]),
     "s3d_ae_num_params": (C.c_int, [C.c_void_p]),
     "s3d_ae_param_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_char_p), c_i64p, C.POINTER(C.c_int), c_i64p]),
@@ -240,6 +242,8 @@ SIGNATURES = {
     "s3d_ae_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, c_fp, C.c_void_p, C.c_void_p]),
     "s3d_ae_loss_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, c_fp, C.POINTER(AeLossCfg),
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3d_ae_loss_grads_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, c_fp, C.POINTER(AeLossCfg),
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # training tier
     "s3d_unet_param_numel": (C.c_int64, [C.c_void_p]),
     "s3d_unet_param_offset": (C.c_int, [C.c_void_p, C.c_int, c_i64p]),

@@ -71,5 +71,11 @@ int launch_last_bwd(const float* dout, int dstride, int ooff, const float* W, co
 // losses[3] = {sdf_loss, tex_loss, #points inside the texture band}; dout [Np][1+TC] or null; ws: 192 floats
 int launch_ae_loss(const float* pred, const float* sdf, const float* tex, long long N, long long Np, int TC, int sdf_mode, int tex_mode,
                    float band, float tex_weight, float* ws, float* losses, float* dout, hipStream_t st);
+// the texture columns in ngroups (0..3) column groups [group_begin[q], group_begin[q+1]), each its own masked mean (sdfpbr: 3 | 2 | 3);
+// sigm: pred's texture columns are sigmoid outputs.  losses[5] = {sdf, group 0..2, #points inside the band}; ws: 320 floats;
+// ngroups 0 (TC 0, tex null) is data_type sdf
+int launch_ae_loss_groups(const float* pred, const float* sdf, const float* tex, long long N, long long Np, int TC, int ngroups,
+                          const int group_begin[4], int sigm, int sdf_mode, int tex_mode, float band, float tex_weight, float* ws,
+                          float* losses, float* dout, hipStream_t st);
 
 }  // namespace s3d

@@ -19,6 +19,9 @@
 //            gradient as a 2-D correlation with the projections.
 // Parameters: one flat fp32 device vector in the order [geo_encoder, geo_convs, geo_decoder | tex_encoder, tex_convs,
 // tex_decoder] — the reference's two AdamW parameter groups (networks.py:146-150) are the two halves.
+// Variants (s3d_ae_create_variant, the numbers of s3d_decoder_create_variant): 0 is the net above with 1..8 texture channels (a
+// volume of 1 + tex_channels channels; 3 is sdftex, 8 sdfpbr on the skip net), 1 the geometry net alone (use_tex=False: one net,
+// a 1-channel volume, no tex group), 2 — the PBR net — is refused.  Every loop over the nets below runs to a->nnets.
 #include <memory>
 
 #include "s3d_ae.h"
@@ -44,6 +47,7 @@ using namespace s3d;
 
 struct s3d_ae {
     s3d_decoder_cfg cfg;
+    int variant = 0;                    // s3d_decoder_create_variant's numbers: 0 skip net with texture, 1 geometry only (tex = TC = 0, C = 1, one net)
     int geo, tex, up, hid, TC, C, nnets = 2;
     std::vector<AeSpec> specs;
     std::vector<size_t> flat_off;
@@ -85,7 +89,7 @@ static void ae_specs(s3d_ae* a) {
     auto add = [&](const std::string& n, std::vector<int64_t> s) { a->specs.push_back({n, std::move(s)}); };
     const char* pre[2] = {"geo", "tex"};
     const int cin[2] = {a->geo, a->tex}, cout[2] = {1, a->TC}, encin[2] = {1, a->C};
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < a->nnets; ++k) {
         if (k == 1) { int64_t n = 0; for (auto& s : a->specs) n += int64_t(s.numel()); a->tex_begin = n; }
         const std::string e = std::string(pre[k]) + "_encoder", cv = std::string(pre[k]) + "_convs", ml = std::string(pre[k]) + "_decoder";
         add(e + ".weight", {cin[k], encin[k], 4, 4, 4}); add(e + ".bias", {cin[k]});
@@ -100,6 +104,7 @@ static void ae_specs(s3d_ae* a) {
     a->flat_off.resize(a->specs.size());
     size_t off = 0;
     for (size_t i = 0; i < a->specs.size(); ++i) { a->flat_off[i] = off; off += a->specs[i].numel(); }
+    if (a->nnets == 1) a->tex_begin = int64_t(off);          // no tex group: it begins where the vector ends
 }
 
 static int ae_plan(s3d_ae* a) {
@@ -116,7 +121,7 @@ static int ae_plan(s3d_ae* a) {
     const int cin[2] = {a->geo, a->tex}, cout[2] = {1, a->TC};
     a->encb_off = palloc(a->geo + a->tex);
     a->wp_off = palloc(size_t(3) * (a->geo + a->tex) * 16 * 4 * a->C);
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < a->nnets; ++k) {
         AeNet& N = a->net[k];
         N.cin = cin[k]; N.nout = cout[k];
         const std::string e = std::string(pre[k]) + "_encoder", cv = std::string(pre[k]) + "_convs", ml = std::string(pre[k]) + "_decoder";
@@ -206,14 +211,14 @@ struct AeRun {
 static int ae_encode(AeRun& R, float* pre[3], float* feat[3], float* mr) {
     s3d_ae* a = R.a;
     if (R.meas()) return 0;
-    S3D_TRY(launch_enc_pack(R.F(a->f_enc_w[0]), R.F(a->f_enc_w[1]), a->geo, a->tex, a->C, static_cast<float*>(a->pbuf.p) + a->wp_off, R.st));
+    S3D_TRY(launch_enc_pack(R.F(a->f_enc_w[0]), a->nnets == 2 ? R.F(a->f_enc_w[1]) : nullptr, a->geo, a->tex, a->C, static_cast<float*>(a->pbuf.p) + a->wp_off, R.st));
     S3D_TRY(launch_enc_fwd(a->enc, a->P(a->wp_off), a->P(a->encb_off), pre, R.st));
     return launch_enc_norm(false, pre, feat, mr, nullptr, nullptr, a->enc.g, a->enc.CO, nullptr, R.st);
 }
 
 // Forward + (when grads != null) backward of one batch of points.  pred: [N][1+TC] output.
 static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* tex, long long N, const float aabb[6],
-                   const s3d_ae_loss_cfg& lc, float* losses, float* pred_out, float* grads, hipStream_t st) {
+                   const s3d_ae_loss_cfg& lc, bool groups, float* losses, float* pred_out, float* grads, hipStream_t st) {
     AeRun R{a, st, grads};
     Arena& ar = a->arena;
     const bool meas = ar.measuring;
@@ -228,7 +233,8 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
         R.sw = a->side;
         R.side = true;
     }
-    const int up = a->up, hid = a->hid, CO = a->geo + a->tex, S = 1 + a->TC;
+    const int up = a->up, hid = a->hid, CO = a->geo + a->tex, S = 1 + a->TC, NN = a->nnets;
+    const bool two = NN == 2;                               // (the second chain exists with a second net only)
     const Geo g = a->enc.g;
     const long long Np = (N + 63) / 64 * 64;
     const bool bwd = grads != nullptr || meas;              // the measuring pass sizes the workspace for both
@@ -245,8 +251,8 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
     struct NetAct { float *x[3], *a1[3], *y[3], *s[3], *f[3], *mr; double* part[3]; } A[2];
     // (training with the side streams on: the texture net's plane blocks run as a second chain beside the geometry net's — they
     // share nothing but the encoder's feature planes — here, and again in the backward pass)
-    if (!meas && R.side) S3D_TRY(R.edge(st, a->chain2));
-    for (int n = 0; n < 2; ++n) {
+    if (!meas && R.side && two) S3D_TRY(R.edge(st, a->chain2));
+    for (int n = 0; n < NN; ++n) {
         const AeNet& N_ = a->net[n];
         NetAct& T = A[n];
         const bool second = n == 1 && R.side && !meas;
@@ -273,7 +279,7 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
         S3D_TRY(R.conv(CONV_1x1, 32, up, g, T.x, w_sc, b_sc, nullptr, T.s, 3, false, cs, true));
         S3D_TRY(R.conv(CONV_5x5, up, up, g, T.y, w_out, b_out, T.s, T.f, 3, false, cs, true));
     }
-    if (!meas && R.side) S3D_TRY(R.edge(a->chain2, st));          // the gather reads both nets' planes
+    if (!meas && R.side && two) S3D_TRY(R.edge(a->chain2, st));   // the gather reads both nets' planes
     // (measured and not kept: the backward scatter's point sort — 21 small dependent launches that depend on the points alone —
     // enqueued here on the second chain's stream, beside the MLPs' forward pass: every one of them waits for a slot behind the
     // 8192-block launches of that pass, the chain arrives late at its backward half, 5.00 -> 5.30 ms/iteration)
@@ -281,47 +287,54 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
     for (int k = 0; k < 6; ++k) ps.aabb[k] = aabb[k];
 
     // ---- points: gather, MLPs
-    float *X0[2], *H[2][5], *CAT[2];
-    for (int n = 0; n < 2; ++n) {
+    float *X0[2] = {nullptr, nullptr}, *H[2][5], *CAT[2];
+    for (int n = 0; n < NN; ++n) {
         X0[n] = ar.alloc<float>(size_t(Np) * up);
         for (int l = 0; l < 5; ++l) H[n][l] = ar.alloc<float>(size_t(Np) * hid);
         CAT[n] = ar.alloc<float>(size_t(Np) * (up + hid));
     }
     float* pred = ar.alloc<float>(size_t(Np) * S);
-    Geo gp; for (int p = 0; p < 3; ++p) { gp.h[p] = p < 2 ? int(Np / 64) : 0; gp.w[p] = p < 2 ? 64 : 0; }   // the point list as two "planes" (geo, tex)
+    Geo gp; for (int p = 0; p < 3; ++p) { gp.h[p] = p < NN ? int(Np / 64) : 0; gp.w[p] = p < NN ? 64 : 0; }   // the point list as two "planes" (geo, tex)
     auto lin = [&](int l, float* const in[2], float* const out[2]) -> int {       // both groups in one launch
         const float *w[3], *b[3];
         float *i3[3], *o3[3];
-        for (int n = 0; n < 2; ++n) { w[n] = R.F(a->net[n].f_mw[l]); b[n] = R.F(a->net[n].f_mb[l]); i3[n] = in[n]; o3[n] = out[n]; }
-        return R.conv(CONV_1x1, a->net[0].I[l], a->net[0].O[l], gp, i3, w, b, nullptr, o3, 2, /*relu=*/true);
+        for (int n = 0; n < NN; ++n) { w[n] = R.F(a->net[n].f_mw[l]); b[n] = R.F(a->net[n].f_mb[l]); i3[n] = in[n]; o3[n] = out[n]; }
+        return R.conv(CONV_1x1, a->net[0].I[l], a->net[0].O[l], gp, i3, w, b, nullptr, o3, NN, /*relu=*/true);
     };
     if (!meas) {
-        const float* fp[2][3];
-        for (int n = 0; n < 2; ++n) for (int p = 0; p < 3; ++p) fp[n][p] = A[n].f[p];
-        S3D_TRY(launch_gather(ps, fp, g.h, g.w, up, 2, X0, st));
+        const float* fp[2][3] = {};
+        for (int n = 0; n < NN; ++n) for (int p = 0; p < 3; ++p) fp[n][p] = A[n].f[p];
+        S3D_TRY(launch_gather(ps, fp, g.h, g.w, up, NN, X0, st));
     }
     {
-        float* h0[2] = {H[0][0], H[1][0]}; float* h1[2] = {H[0][1], H[1][1]}; float* h2[2] = {H[0][2], H[1][2]};
-        float* h3[2] = {H[0][3], H[1][3]}; float* h4[2] = {H[0][4], H[1][4]};
+        float *h0[2], *h1[2], *h2[2], *h3[2], *h4[2];
+        for (int n = 0; n < 2; ++n) { const int m = n < NN ? n : 0; h0[n] = H[m][0]; h1[n] = H[m][1]; h2[n] = H[m][2]; h3[n] = H[m][3]; h4[n] = H[m][4]; }
         S3D_TRY(lin(0, X0, h0)); S3D_TRY(lin(1, h0, h1)); S3D_TRY(lin(2, h1, h2));
         if (!meas)
-            for (int n = 0; n < 2; ++n) {
+            for (int n = 0; n < NN; ++n) {
                 S3D_TRY(launch_copy_slice(X0[n], 1, up, int(Np / 64), 64, CAT[n], up + hid, 0, st));
                 S3D_TRY(launch_copy_slice(H[n][2], 1, hid, int(Np / 64), 64, CAT[n], up + hid, up, st));
             }
         S3D_TRY(lin(3, CAT, h3)); S3D_TRY(lin(4, h3, h4));
         if (!meas)
-            for (int n = 0; n < 2; ++n)
+            for (int n = 0; n < NN; ++n)
                 S3D_TRY(launch_last_fwd(H[n][4], R.F(a->net[n].f_mw[5]), R.F(a->net[n].f_mb[5]), hid, a->net[n].nout, n == 1, pred, S,
                                         n == 0 ? 0 : 1, N, st));
     }
     if (!meas && pred_out) S3D_HIP(hipMemcpyAsync(pred_out, pred, size_t(N) * S * sizeof(float), hipMemcpyDeviceToDevice, st));
 
     // ---- losses and d loss / d (pre-activation outputs)
-    float* loss_ws = ar.alloc<float>(256);
-    float* loss3 = ar.alloc<float>(4);
+    float* loss_ws = ar.alloc<float>(512);
+    float* loss3 = ar.alloc<float>(8);
     float* dout = bwd ? ar.alloc<float>(size_t(Np) * S) : nullptr;
-    if (!meas && sdf) {
+    if (!meas && sdf && groups) {
+        // sdfpbr's eight material channels are three means (rgb | metallic-roughness | normal); any other width is one group, none is sdf
+        const int gb8[4] = {0, 3, 5, 8}, gb1[4] = {0, a->TC, 0, 0};
+        const int ng = a->TC == 8 ? 3 : (a->TC ? 1 : 0);
+        S3D_TRY(launch_ae_loss_groups(pred, sdf, tex, N, Np, a->TC, ng, a->TC == 8 ? gb8 : gb1, /*sigm=*/1, lc.sdf_loss, lc.tex_loss,
+                                      lc.sdf_threshold * lc.tex_threshold_ratio, lc.tex_weight, loss_ws, loss3, grads ? dout : nullptr, st));
+        if (losses) S3D_HIP(hipMemcpyAsync(losses, loss3, 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    } else if (!meas && sdf) {
         S3D_TRY(launch_ae_loss(pred, sdf, tex, N, Np, a->TC, lc.sdf_loss, lc.tex_loss, lc.sdf_threshold * lc.tex_threshold_ratio,
                                lc.tex_weight, loss_ws, loss3, grads ? dout : nullptr, st));
         if (losses) S3D_HIP(hipMemcpyAsync(losses, loss3, 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -337,13 +350,13 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
     // geometry net's (side-stream builds only) — each alternates a bandwidth-bound ReLU backward with an MFMA-bound 1x1 dgrad, so
     // the two chains want different things at most times.  Same kernels on the same operands: same bits.
     float* cws_n[2] = {cws, ar.alloc<float>(colsum_ws_floats(std::max(hid, up)))};
-    if (!meas && R.side) S3D_TRY(R.edge(st, a->chain2));
+    if (!meas && R.side && two) S3D_TRY(R.edge(st, a->chain2));
     // (issued layer by layer for BOTH nets, not net after net: the two chains then advance together however far the host is ahead)
     struct Step { int l; float* act; float* in; int in_stride; float* din; const float* dact; int dstride, coff; };
     Step steps[2][5];
     float *dXa_n[2], *dCAT_n[2];
     hipStream_t cs_n[2];
-    for (int n = 0; n < 2; ++n) {
+    for (int n = 0; n < NN; ++n) {
         const AeNet& N_ = a->net[n];
         cs_n[n] = n == 1 && R.side && !meas ? a->chain2 : st;      // this net's chain
         float* dH = ar.alloc<float>(size_t(Np) * hid);            // gradient of a hidden activation (reused)
@@ -361,8 +374,8 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
                              {0, H[n][0], X0[n], up, dXa, dH, hid, 0}};
         for (int k = 0; k < 5; ++k) steps[n][k] = st5[k];
     }
-    for (int kk = 0; kk < 10; ++kk) {
-            const int k = kk / 2, n = kk % 2;
+    for (int kk = 0; kk < 5 * NN; ++kk) {
+            const int k = kk / NN, n = kk % NN;
             const AeNet& N_ = a->net[n];
             const Step& s = steps[n][k];
             hipStream_t cs = cs_n[n];
@@ -378,22 +391,22 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
             float* o3[3] = {s.din, nullptr, nullptr};
             S3D_TRY(R.conv(CONV_1x1, O, I, g1, dy3, wT, nullptr, nullptr, o3, 1, false, cs, true));
         }
-    for (int n = 0; n < 2; ++n)
+    for (int n = 0; n < NN; ++n)
         if (!meas) S3D_TRY(launch_add_slice(dXa_n[n], dCAT_n[n], up + hid, 0, dX0[n], Np, up, cs_n[n]));
-    if (!meas && R.side) S3D_TRY(R.edge(a->chain2, st));          // the scatter reads both nets' point gradients
+    if (!meas && R.side && two) S3D_TRY(R.edge(a->chain2, st));   // the scatter reads both nets' point gradients
     // ---- scatter the point gradients onto the planes
-    float* dF[2][3];
-    for (int n = 0; n < 2; ++n) for (int p = 0; p < 3; ++p) dF[n][p] = ar.alloc<float>(hw[p] * up);
+    float* dF[2][3] = {};
+    for (int n = 0; n < NN; ++n) for (int p = 0; p < 3; ++p) dF[n][p] = ar.alloc<float>(hw[p] * up);
     char* sws = ar.alloc<char>(scatter_ws_bytes(Np, g.h, g.w));
     if (!meas) {
-        const float* dx[2] = {dX0[0], dX0[1]};
-        S3D_TRY(launch_scatter(ps, dF, g.h, g.w, up, 2, dx, sws, st));
+        const float* dx[2] = {dX0[0], two ? dX0[1] : nullptr};
+        S3D_TRY(launch_scatter(ps, dF, g.h, g.w, up, NN, dx, sws, st));
     }
     // ---- plane blocks
     float* dfeat[3];
     for (int p = 0; p < 3; ++p) dfeat[p] = ar.alloc<float>(hw[p] * CO);
-    if (!meas && R.side) S3D_TRY(R.edge(st, a->chain2));          // (the scatter's plane gradients are final)
-    for (int n = 0; n < 2; ++n) {
+    if (!meas && R.side && two) S3D_TRY(R.edge(st, a->chain2));   // (the scatter's plane gradients are final)
+    for (int n = 0; n < NN; ++n) {
         const AeNet& N_ = a->net[n];
         NetAct& T = A[n];
         const bool second = n == 1 && R.side && !meas;
@@ -445,15 +458,15 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
         if (!meas)
             S3D_TRY(launch_unslice_nhwc3(d_x, dfeat, hw, CO, n == 0 ? 0 : a->geo, N_.cin, cs));
     }
-    if (!meas && R.side) S3D_TRY(R.edge(a->chain2, st));          // the encoder's backward reads both nets' slices of dfeat
+    if (!meas && R.side && two) S3D_TRY(R.edge(a->chain2, st));   // the encoder's backward reads both nets' slices of dfeat
     // ---- encoder
     float* dpre[3];
     for (int p = 0; p < 3; ++p) dpre[p] = ar.alloc<float>(hw[p] * CO);
     float* ews = ar.alloc<float>(std::max(enc_wgrad_ws_floats(a->C, CO), enc_norm_bwd_ws_bytes(CO) / sizeof(float)));
     if (!meas) {
         S3D_TRY(launch_enc_norm(true, pre, feat, enc_mr, dfeat, dpre, g, CO, ews, st));        // (its chunk sums are consumed before the weight gradient reuses ews)
-        S3D_TRY(launch_enc_wgrad(a->enc, dpre, a->geo, a->tex, ews, R.G(a->f_enc_w[0]), R.G(a->f_enc_b[0]), R.G(a->f_enc_w[1]),
-                                 R.G(a->f_enc_b[1]), st));
+        S3D_TRY(launch_enc_wgrad(a->enc, dpre, a->geo, a->tex, ews, R.G(a->f_enc_w[0]), R.G(a->f_enc_b[0]), two ? R.G(a->f_enc_w[1]) : nullptr,
+                                 two ? R.G(a->f_enc_b[1]) : nullptr, st));
         S3D_TRY(R.tail.flush(R.side ? R.sw : st));        // the 16 weight-gradient reductions (they were 16 launches on the stream the iteration waits for)
         S3D_TRY(R.edge(R.sw, st));                        // every gradient of the pass is final in the order of the caller's stream (no-op in line)
     }
@@ -461,41 +474,51 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
 }
 
 static int ae_run(s3d_ae* a, const float* pts, const float* sdf, const float* tex, long long N, const float aabb[6],
-                  const s3d_ae_loss_cfg& lc, float* losses, float* pred, float* grads, hipStream_t st) {
+                  const s3d_ae_loss_cfg& lc, bool groups, float* losses, float* pred, float* grads, hipStream_t st) {
     a->arena.measuring = true; a->arena.high = 0;
-    int rc = ae_step(a, pts, sdf, tex, N, aabb, lc, losses, pred, grads, st);
+    int rc = ae_step(a, pts, sdf, tex, N, aabb, lc, groups, losses, pred, grads, st);
     a->arena.measuring = false;
     if (rc) return rc;
     if (a->arena.high > a->arena.buf.cap) {
         S3D_HIP(hipStreamSynchronize(st));
         S3D_TRY(a->arena.buf.reserve(a->arena.high + (a->arena.high >> 3)));
     }
-    return ae_step(a, pts, sdf, tex, N, aabb, lc, losses, pred, grads, st);
+    return ae_step(a, pts, sdf, tex, N, aabb, lc, groups, losses, pred, grads, st);
 }
 
 }  // namespace s3d
 
 extern "C" {
 
-int s3d_ae_create(const s3d_decoder_cfg* cfg, s3d_ae** out) {
+int s3d_ae_create(const s3d_decoder_cfg* cfg, s3d_ae** out) { return s3d_ae_create_variant(cfg, 0, out); }
+int s3d_ae_create_variant(const s3d_decoder_cfg* cfg, int variant, s3d_ae** out) {
     S3D_CHECK(cfg && out, S3D_ERR_INVALID, "ae_create: null argument");
+    S3D_CHECK(variant >= 0 && variant <= 2, S3D_ERR_INVALID, "ae_create: variant %d (0 skip net, 1 geometry only, 2 PBR net)", variant);
+    S3D_CHECK(variant != 2 || cfg->tex_channels == 8, S3D_ERR_UNSUPPORTED, "ae: the PBR net has 8 material channels, got tex_channels=%d",
+              cfg->tex_channels);
+    S3D_CHECK(variant != 2, S3D_ERR_UNSUPPORTED, "ae training: the PBR net (variant 2) is not built; it decodes only");
+    const bool tex = variant != 1;
     S3D_CHECK(cfg->mlp_hidden_layers == 4, S3D_ERR_UNSUPPORTED, "ae: mlp_hidden_layers=%d (only the default 4 is built)", cfg->mlp_hidden_layers);
     S3D_CHECK(cfg->feat_channel_up % 32 == 0 && cfg->mlp_hidden_channels % 32 == 0 && cfg->feat_channel_up > 0 && cfg->mlp_hidden_channels > 0,
               S3D_ERR_UNSUPPORTED, "ae training: feat_channel_up=%d and mlp_hidden_channels=%d must be multiples of 32",
               cfg->feat_channel_up, cfg->mlp_hidden_channels);
-    S3D_CHECK(cfg->geo_feat_channels >= 1 && cfg->tex_feat_channels >= 1 && cfg->geo_feat_channels + cfg->tex_feat_channels <= 12 &&
-              cfg->geo_feat_channels % 4 == 0 && cfg->tex_feat_channels % 4 == 0,
+    const int tfc = tex ? cfg->tex_feat_channels : 0;           // (the geometry-only net ignores the tex_* fields)
+    S3D_CHECK(cfg->geo_feat_channels >= 1 && (!tex || tfc >= 1) && cfg->geo_feat_channels + tfc <= 12 &&
+              cfg->geo_feat_channels % 4 == 0 && tfc % 4 == 0,
               S3D_ERR_UNSUPPORTED, "ae training: feature groups must be multiples of 4 channels, at most 12 together");
-    S3D_CHECK(cfg->tex_channels >= 1 && cfg->tex_channels <= 3, S3D_ERR_UNSUPPORTED, "ae: tex_channels must be 1..3");
+    S3D_CHECK(!tex || (cfg->tex_channels >= 1 && cfg->tex_channels <= 8), S3D_ERR_UNSUPPORTED, "ae: tex_channels must be 1..8, got %d",
+              cfg->tex_channels);
     std::unique_ptr<s3d_ae> a(new s3d_ae());
     a->cfg = *cfg;
-    a->geo = cfg->geo_feat_channels; a->tex = cfg->tex_feat_channels; a->up = cfg->feat_channel_up; a->hid = cfg->mlp_hidden_channels;
-    a->TC = cfg->tex_channels; a->C = 1 + cfg->tex_channels;
+    a->variant = variant; a->nnets = tex ? 2 : 1;
+    a->geo = cfg->geo_feat_channels; a->tex = tfc; a->up = cfg->feat_channel_up; a->hid = cfg->mlp_hidden_channels;
+    a->TC = tex ? cfg->tex_channels : 0; a->C = 1 + a->TC;
     ae_specs(a.get());
     *out = a.release();
     return 0;
 }
 void s3d_ae_destroy(s3d_ae* a) { delete a; }
+int s3d_ae_out_channels(const s3d_ae* a) { return a ? 1 + a->TC : S3D_ERR_INVALID; }
 int s3d_ae_num_params(const s3d_ae* a) { return a ? int(a->specs.size()) : S3D_ERR_INVALID; }
 int s3d_ae_param_info(const s3d_ae* a, int i, const char** name, int64_t shape[5], int* ndim, int64_t* offset) {
     S3D_CHECK(a && i >= 0 && i < int(a->specs.size()), S3D_ERR_INVALID, "ae param_info: index %d out of range", i);
@@ -524,7 +547,7 @@ int s3d_ae_repack(s3d_ae* a, void* stream) {
 }
 int s3d_ae_set_volume(s3d_ae* a, const float* vol, int C, int X2, int Y2, int Z2, void* stream) {
     S3D_CHECK(a && vol, S3D_ERR_INVALID, "ae_set_volume: null argument");
-    S3D_CHECK(C == a->C, S3D_ERR_INVALID, "ae_set_volume: %d channels, the encoder takes %d (sdf + texture)", C, a->C);
+    S3D_CHECK(C == a->C, S3D_ERR_INVALID, "ae_set_volume: %d channels, the encoder takes %d (sdf, then the texture channels)", C, a->C);
     S3D_CHECK(X2 >= 2 && Y2 >= 2 && Z2 >= 2 && X2 % 2 == 0 && Y2 % 2 == 0 && Z2 % 2 == 0, S3D_ERR_INVALID,
               "ae_set_volume: the volume must be twice the feature-map size, got (%d,%d,%d)", X2, Y2, Z2);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -567,14 +590,21 @@ int s3d_ae_forward(s3d_ae* a, const float* pts, int64_t N, const float aabb[6], 
     S3D_CHECK(a && pts && aabb && pred && N >= 1, S3D_ERR_INVALID, "ae_forward: bad argument");
     S3D_CHECK(a->flat && a->has_volume, S3D_ERR_INVALID, "ae_forward: attach parameters and set the volume first");
     s3d_ae_loss_cfg lc{};
-    return ae_run(a, pts, nullptr, nullptr, N, aabb, lc, nullptr, pred, nullptr, static_cast<hipStream_t>(stream));
+    return ae_run(a, pts, nullptr, nullptr, N, aabb, lc, false, nullptr, pred, nullptr, static_cast<hipStream_t>(stream));
 }
 int s3d_ae_loss_grads(s3d_ae* a, const float* pts, const float* sdf, const float* tex, int64_t N, const float aabb[6],
                       const s3d_ae_loss_cfg* cfg, float* losses, float* pred, float* grads, void* stream) {
-    S3D_CHECK(a && pts && sdf && tex && aabb && cfg && losses && grads && N >= 1, S3D_ERR_INVALID, "ae_loss_grads: bad argument");
+    S3D_CHECK(a && pts && sdf && (tex || a->TC == 0) && aabb && cfg && losses && grads && N >= 1, S3D_ERR_INVALID, "ae_loss_grads: bad argument");
     S3D_CHECK(a->flat && a->has_volume, S3D_ERR_INVALID, "ae_loss_grads: attach parameters and set the volume first");
     S3D_CHECK(cfg->sdf_loss >= 0 && cfg->sdf_loss <= 1 && cfg->tex_loss >= 0 && cfg->tex_loss <= 2, S3D_ERR_INVALID, "ae_loss_grads: unknown loss type");
-    return ae_run(a, pts, sdf, tex, N, aabb, *cfg, losses, pred, grads, static_cast<hipStream_t>(stream));
+    return ae_run(a, pts, sdf, tex, N, aabb, *cfg, false, losses, pred, grads, static_cast<hipStream_t>(stream));
+}
+int s3d_ae_loss_grads_groups(s3d_ae* a, const float* pts, const float* sdf, const float* tex, int64_t N, const float aabb[6],
+                             const s3d_ae_loss_cfg* cfg, float* losses, float* pred, float* grads, void* stream) {
+    S3D_CHECK(a && pts && sdf && (tex || a->TC == 0) && aabb && cfg && losses && grads && N >= 1, S3D_ERR_INVALID, "ae_loss_grads_groups: bad argument");
+    S3D_CHECK(a->flat && a->has_volume, S3D_ERR_INVALID, "ae_loss_grads_groups: attach parameters and set the volume first");
+    S3D_CHECK(cfg->sdf_loss >= 0 && cfg->sdf_loss <= 1 && cfg->tex_loss >= 0 && cfg->tex_loss <= 2, S3D_ERR_INVALID, "ae_loss_grads_groups: unknown loss type");
+    return ae_run(a, pts, sdf, tex, N, aabb, *cfg, true, losses, pred, grads, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

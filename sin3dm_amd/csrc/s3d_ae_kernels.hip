@@ -69,7 +69,11 @@ struct EncArgs {
 // multiply-adds on 512 scalar loads each, 300 us for 0.3 GFLOP): the wave first copies its plane's weights into LDS as
 // [tap][k/4][co][4] (12 KB for CO = 12, C = 4), then every pixel's 4x4 taps x 4C projection values are read once as float4 and
 // feed all CO accumulators from broadcast LDS reads.  Same order of the multiply-adds as before.
-constexpr int kEncFwdMaxCO = 12, kEncFwdMaxK4 = 4;
+// MAXK4 input channels x MAXCO feature channels is the size of the arrays: <4, 12> is the sdftex net (and every smaller one),
+// <9, 12> the 9-channel sdfpbr volume (16 x 36 floats of taps per pixel, 16 x 9 x 12 float4 of weights = 27 KB of LDS) and
+// <1, 4> the geometry-only net.
+constexpr int kEncFwdMaxCO = 12, kEncFwdMaxK4 = 9;
+template <int kEncFwdMaxK4, int kEncFwdMaxCO>
 __global__ __launch_bounds__(64) void k_enc_fwd(EncArgs a) {
     __shared__ float4 sw[16 * kEncFwdMaxK4 * kEncFwdMaxCO];
     const int p = blockIdx.y;
@@ -150,11 +154,14 @@ int launch_enc_fwd(const EncDesc& e, const float* Wp, const float* bias, float* 
         a.P[p] = e.P[p]; a.pre[p] = pre[p]; a.h[p] = e.g.h[p]; a.w[p] = e.g.w[p]; a.inv_len[p] = e.inv_len[p];
         a.begin[p + 1] = a.begin[p] + (long long)e.g.h[p] * e.g.w[p] * e.CO;
     }
-    S3D_CHECK(e.CO <= kEncFwdMaxCO && e.C <= kEncFwdMaxK4, S3D_ERR_UNSUPPORTED, "encoder: %d feature channels (max %d), %d input channels (max %d)",
+    S3D_CHECK(e.CO >= 1 && e.CO <= kEncFwdMaxCO && e.C >= 1 && e.C <= kEncFwdMaxK4, S3D_ERR_UNSUPPORTED, "encoder: %d feature channels (max %d), %d input channels (max %d)",
               e.CO, kEncFwdMaxCO, e.C, kEncFwdMaxK4);
     int maxpix = 0;
     for (int p = 0; p < 3; ++p) maxpix = std::max(maxpix, e.g.h[p] * e.g.w[p]);
-    hipLaunchKernelGGL(k_enc_fwd, dim3(cdiv(maxpix, 64), 3), dim3(64), 0, st, a);
+    const dim3 grid(cdiv(maxpix, 64), 3);
+    if (e.C == 1 && e.CO <= 4) hipLaunchKernelGGL((k_enc_fwd<1, 4>), grid, dim3(64), 0, st, a);
+    else if (e.C <= 4) hipLaunchKernelGGL((k_enc_fwd<4, 12>), grid, dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((k_enc_fwd<9, 12>), grid, dim3(64), 0, st, a);
     S3D_HIP(hipGetLastError());
     return 0;
 }
@@ -787,7 +794,7 @@ int launch_colsum3(const float* const x[3], const size_t rows[3], int C, float* 
     return 0;
 }
 
-// ------------------------------------------------------------------ the last MLP layer (hid -> 1 or 3 outputs)
+// ------------------------------------------------------------------ the last MLP layer (hid -> 1..8 outputs)
 // forward: out[n][o] = b[o] + sum_i W[o][i] * h[n][i]  (+ sigmoid), written into pred[n][ooff + o] (row stride 4-ish)
 // one wave per point: lanes stride the hidden units, shuffle-reduce
 __global__ __launch_bounds__(256) void k_last_fwd(const float* __restrict__ h, const float* __restrict__ W, const float* __restrict__ b,
@@ -815,22 +822,28 @@ int launch_last_fwd(const float* h, const float* W, const float* b, int I, int O
 }
 // backward: dh[n][i] = sum_o dout[n][o] * W[o][i] ; dW[o][i] = sum_n dout[n][o] * h[n][i] ; db[o] = sum_n dout[n][o]
 // dout [Np][4-wide rows: column ooff + o]; rows >= N carry zero.  dW/db: per-chunk partials then ordered sum.
+// (MAXO: 3 for the sdf and rgb outputs, 8 for the eight material channels of sdfpbr)
 constexpr int kLastChunks = 512;
+template <int MAXO>
 __global__ __launch_bounds__(256) void k_last_bwd(const float* __restrict__ dout, int dstride, int ooff, const float* __restrict__ W,
                                                   const float* __restrict__ h, int I, int O, long long Np, float* __restrict__ dh,
                                                   float* __restrict__ part) {
     const long long r0 = Np * blockIdx.x / kLastChunks, r1 = Np * (blockIdx.x + 1) / kLastChunks;
     for (int i = threadIdx.x; i < I; i += 256) {
-        float w[3] = {0, 0, 0}, acc[3] = {0, 0, 0};
-        for (int o = 0; o < O; ++o) w[o] = W[size_t(o) * I + i];
+        float w[MAXO], acc[MAXO];
+#pragma unroll
+        for (int o = 0; o < MAXO; ++o) { w[o] = o < O ? W[size_t(o) * I + i] : 0.f; acc[o] = 0.f; }
 #pragma unroll 8
         for (long long n = r0; n < r1; ++n) {                // (unrolled: eight rows of loads in flight per thread)
             const float hv = h[n * I + i];
             float d = 0.f;
-            for (int o = 0; o < O; ++o) { const float g = dout[n * dstride + ooff + o]; d = fmaf(g, w[o], d); acc[o] = fmaf(g, hv, acc[o]); }
+#pragma unroll
+            for (int o = 0; o < MAXO; ++o)
+                if (o < O) { const float g = dout[n * dstride + ooff + o]; d = fmaf(g, w[o], d); acc[o] = fmaf(g, hv, acc[o]); }
             dh[n * I + i] = d;
         }
-        for (int o = 0; o < O; ++o) part[(size_t(blockIdx.x) * O + o) * (I + 1) + i] = acc[o];
+#pragma unroll
+        for (int o = 0; o < MAXO; ++o) if (o < O) part[(size_t(blockIdx.x) * O + o) * (I + 1) + i] = acc[o];
     }
     if (int(threadIdx.x) < O) {
         float s = 0.f;
@@ -856,8 +869,9 @@ __global__ __launch_bounds__(256) void k_last_bwd_fin(const float* __restrict__ 
 size_t last_bwd_ws_floats(int I, int O) { return size_t(kLastChunks) * O * (I + 1); }
 int launch_last_bwd(const float* dout, int dstride, int ooff, const float* W, const float* h, int I, int O, long long Np, float* dh,
                     float* ws, float* dW, float* db, hipStream_t st) {
-    S3D_CHECK(O >= 1 && O <= 3, S3D_ERR_UNSUPPORTED, "last layer: %d outputs", O);
-    hipLaunchKernelGGL(k_last_bwd, dim3(kLastChunks), dim3(256), 0, st, dout, dstride, ooff, W, h, I, O, Np, dh, ws);
+    S3D_CHECK(O >= 1 && O <= 8, S3D_ERR_UNSUPPORTED, "last layer: %d outputs (1..8)", O);
+    if (O <= 3) hipLaunchKernelGGL(k_last_bwd<3>, dim3(kLastChunks), dim3(256), 0, st, dout, dstride, ooff, W, h, I, O, Np, dh, ws);
+    else hipLaunchKernelGGL(k_last_bwd<8>, dim3(kLastChunks), dim3(256), 0, st, dout, dstride, ooff, W, h, I, O, Np, dh, ws);
     S3D_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_last_bwd_fin, dim3(cdiv(O * (I + 1), 8)), dim3(256), 0, st, ws, I, O, dW, db);
     S3D_HIP(hipGetLastError());
@@ -866,6 +880,7 @@ int launch_last_bwd(const float* dout, int dstride, int ooff, const float* W, co
 
 // ------------------------------------------------------------------ losses (src/encoding/model.py:186-237) and d loss / d pre-activation
 // sdf: weightedl1  mean(|p - g| * (1 + 0.5 sign(g) sign(g - p))) or l1 ; tex (on rows with |g_sdf| < band): l1 | l2 | huber(0.1), * tex_weight
+// (k_loss_*: one mean over all TC texture columns, none for TC = 0 — the two-loss call; k_loss_groups_*: one mean per column group)
 // pred [N][1+TC] holds sdf and SIGMOID-ed texture; dout gets d(sdf_loss + tex_loss)/d(pre-activation) (through the sigmoid)
 struct LossArgs {
     const float* pred; const float* sdf; const float* tex; float* dout; float* part; float* losses;
@@ -936,6 +951,86 @@ int launch_ae_loss(const float* pred, const float* sdf, const float* tex, long l
     S3D_HIP(hipGetLastError());
     if (dout) {
         hipLaunchKernelGGL(k_loss_grad, dim3(cdivll(Np, 256)), dim3(256), 0, st, a);
+        S3D_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+// The same with the texture columns in up to three GROUPS, each its own mean over (points inside the band x its columns) times
+// tex_weight (model.py:226-233: rgb = columns 0-2, mr = 3-4, normal = 5-7 of sdfpbr; one group of all columns is the sdftex loss;
+// no group is data_type sdf, and tex may then be null).  sigm: the texture columns of pred went through a sigmoid (the skip net)
+// and dout is the gradient in front of it.  losses[5] = {sdf, group 0, group 1, group 2, #points inside the band}.
+struct LossGroupArgs {
+    const float* pred; const float* sdf; const float* tex; float* dout; float* part; float* losses;
+    long long N, Np; int TC, ng, gb[4], sdf_mode, tex_mode, sigm; float band, tex_weight;
+};
+__global__ __launch_bounds__(256) void k_loss_groups_part(LossGroupArgs a) {
+    __shared__ double red[5][256];
+    const long long r0 = a.N * blockIdx.x / kLossChunks, r1 = a.N * (blockIdx.x + 1) / kLossChunks;
+    double s_sdf = 0, s_g[3] = {0, 0, 0}, cnt = 0;
+    const int S = 1 + a.TC;
+    for (long long n = r0 + threadIdx.x; n < r1; n += 256) {
+        const float g = a.sdf[n], p = a.pred[n * S];
+        const float wgt = a.sdf_mode == 1 ? 1.f + 0.5f * sgn(g) * sgn(g - p) : 1.f;
+        s_sdf += fabsf(p - g) * wgt;
+        if (a.ng && fabsf(g) < a.band) {
+            cnt += 1;
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                if (q < a.ng)
+                    for (int k = a.gb[q]; k < a.gb[q + 1]; ++k) s_g[q] += tex_term(a.tex_mode, a.pred[n * S + 1 + k] - a.tex[n * a.TC + k]);
+        }
+    }
+    red[0][threadIdx.x] = s_sdf; red[1][threadIdx.x] = s_g[0]; red[2][threadIdx.x] = s_g[1]; red[3][threadIdx.x] = s_g[2]; red[4][threadIdx.x] = cnt;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (int(threadIdx.x) < o) for (int k = 0; k < 5; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x < 5) a.part[blockIdx.x * 5 + threadIdx.x] = float(red[threadIdx.x][0]);
+}
+__global__ void k_loss_groups_fin(LossGroupArgs a) {
+    double s[5] = {0, 0, 0, 0, 0};
+    for (int k = 0; k < kLossChunks; ++k) for (int j = 0; j < 5; ++j) s[j] += a.part[k * 5 + j];
+    a.losses[0] = float(s[0] / double(a.N));
+    for (int q = 0; q < 3; ++q)                                  // 0/0 = nan like F.l1_loss on an empty selection
+        a.losses[1 + q] = q < a.ng ? float(s[1 + q] / (s[4] * (a.gb[q + 1] - a.gb[q])) * a.tex_weight) : 0.f;
+    a.losses[4] = float(s[4]);
+}
+__global__ void k_loss_groups_grad(LossGroupArgs a) {
+    const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= a.Np) return;
+    const int S = 1 + a.TC;
+    if (n >= a.N) { for (int k = 0; k < S; ++k) a.dout[n * S + k] = 0.f; return; }
+    const float g = a.sdf[n], p = a.pred[n * S];
+    const float wgt = a.sdf_mode == 1 ? 1.f + 0.5f * sgn(g) * sgn(g - p) : 1.f;
+    a.dout[n * S] = sgn(p - g) * wgt / float(a.N);
+    const bool in = a.ng && fabsf(g) < a.band;
+    for (int q = 0; q < a.ng; ++q) {
+        const float scale = in ? a.tex_weight / (a.losses[4] * float(a.gb[q + 1] - a.gb[q])) : 0.f;
+        for (int k = a.gb[q]; k < a.gb[q + 1]; ++k) {
+            const float s = a.pred[n * S + 1 + k];
+            float d = in ? tex_dterm(a.tex_mode, s - a.tex[n * a.TC + k]) * scale : 0.f;
+            if (in && a.sigm) d = d * s * (1.f - s);            // (the products in k_loss_grad's order: one group gives its bits)
+            a.dout[n * S + 1 + k] = d;
+        }
+    }
+}
+int launch_ae_loss_groups(const float* pred, const float* sdf, const float* tex, long long N, long long Np, int TC, int ngroups,
+                          const int group_begin[4], int sigm, int sdf_mode, int tex_mode, float band, float tex_weight, float* ws,
+                          float* losses, float* dout, hipStream_t st) {
+    S3D_CHECK(ngroups >= 0 && ngroups <= 3 && (ngroups == 0) == (TC == 0) && (ngroups == 0 || tex), S3D_ERR_INVALID,
+              "ae loss: %d column groups over %d texture channels", ngroups, TC);
+    LossGroupArgs a{pred, sdf, tex, dout, ws, losses, N, Np, TC, ngroups, {0, 0, 0, 0}, sdf_mode, tex_mode, sigm, band, tex_weight};
+    for (int q = 0; q <= ngroups; ++q) a.gb[q] = group_begin[q];
+    S3D_CHECK(a.gb[0] == 0 && a.gb[ngroups] == TC, S3D_ERR_INVALID, "ae loss: the column groups must cover the %d texture channels", TC);
+    for (int q = 0; q < ngroups; ++q) S3D_CHECK(a.gb[q + 1] > a.gb[q], S3D_ERR_INVALID, "ae loss: empty column group %d", q);
+    hipLaunchKernelGGL(k_loss_groups_part, dim3(kLossChunks), dim3(256), 0, st, a);
+    S3D_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_loss_groups_fin, dim3(1), dim3(1), 0, st, a);
+    S3D_HIP(hipGetLastError());
+    if (dout) {
+        hipLaunchKernelGGL(k_loss_groups_grad, dim3(cdivll(Np, 256)), dim3(256), 0, st, a);
         S3D_HIP(hipGetLastError());
     }
     return 0;

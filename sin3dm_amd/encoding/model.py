@@ -32,14 +32,16 @@ def ae_loss_cfg(sdf_loss, tex_loss, sdf_threshold, tex_threshold_ratio=0.999, te
 class FlatGroupAdamW:
     """torch.optim.AdamW over the auto-encoder's two parameter groups (geo: lr*split, tex: lr; betas 0.9/0.999, eps 1e-8,
     weight_decay 0.01 = torch's default, which the reference inherits at model.py:131-137) followed by ExponentialLR,
-    on the flat parameter vector: two launches of the fused Adam kernel per step."""
+    on the flat parameter vector: two launches of the fused Adam kernel per step.  The geometry-only net (data_type sdf) has no
+    tex group: one group at the geometry group's rate, lr*split when split > 0 (the reference crashes there in
+    tex_parameters())."""
 
     def __init__(self, net, lr, lr_split=-1.0, lr_decay=1.0, weight_decay=0.01):
         self.net = net
         flat = net.flat_parameters
         tb = net.tex_group_begin
-        self.ranges = ((0, tb), (tb, flat.numel()))
-        self.lrs = [lr * lr_split if lr_split > 0 else lr, lr]
+        self.ranges = tuple(r for r in ((0, tb), (tb, flat.numel())) if r[1] > r[0])
+        self.lrs = [lr * lr_split if lr_split > 0 else lr, lr][:len(self.ranges)]
         self.lr_decay, self.weight_decay = float(lr_decay), float(weight_decay)
         self.exp_avg, self.exp_avg_sq = torch.zeros_like(flat), torch.zeros_like(flat)
         self.steps = 0
@@ -71,6 +73,10 @@ class ShapeAutoEncoder:
     experiment directory trained by either side loads on the other; trains, encodes and decodes on the MI355X."""
 
     def __init__(self, log_dir, cfg, device=None):
+        if getattr(cfg, "data_type", "sdftex") == "sdfpbr" and getattr(cfg, "tex_loss", "l1") != "l1":
+            # the reference defines only l1 for sdfpbr (:226-233) and silently trains without any material loss otherwise
+            raise ValueError(f"--tex_loss {cfg.tex_loss} with --data_type sdfpbr: the material losses (rgb, mr, normal) are "
+                             "defined for l1 only")
         self.log_dir = log_dir
         self.device = device or torch.device(f"cuda:{getattr(cfg, 'gpu_id', 0)}")
         self.net = get_networks(cfg).to(self.device)
@@ -219,20 +225,26 @@ class ShapeAutoEncoder:
 
     # ------------------------------------------------------------------ training (reference :51-139, 178-258)
     def _load_data(self, path, sdf_renorm=False):
-        """The preprocessed .npz of one shape: grid + near-surface samples (reference :51-112)."""
-        if self.data_type != "sdftex":
-            raise NotImplementedError(f"auto-encoder training is built for data_type sdftex only; {self.data_type} experiments "
-                                      "are sampled and decoded here (DESIGN.md §18)")
+        """The preprocessed .npz of one shape: grid + near-surface samples (reference :51-112).  data_type sdf has no tex_*
+        arrays and a 1-channel volume; sdfpbr has 8 material channels."""
+        if self.net.variant == 2:
+            raise NotImplementedError("auto-encoder training is not built for the PBR network with texture (--enc_net_type pbr "
+                                      "--data_type sdfpbr): train it with --enc_net_type skip; it is sampled and decoded here "
+                                      "(DESIGN.md §18)")
+        self.net.build_training_tier()
         data = np.load(path)
+        has_tex = self.data_type != "sdf"
         dev = self.device
         self.aabb = torch.from_numpy(data["aabb"]).float().to(dev)
         self.sdf_threshold = float(data["threshold"])
         self.material = {"Ka": data["Ka"].tolist() if "Ka" in data else [0, 0, 0], "Kd": data["Kd"].tolist() if "Kd" in data else [1, 1, 1],
                          "Ks": data["Ks"].tolist() if "Ks" in data else [0.4, 0.4, 0.4], "Ns": data["Ns"].tolist() if "Ns" in data else 10}
-        pts_grid, sdf_grid, tex_grid = data["pts_grid"], data["sdf_grid"], data["tex_grid"]
+        pts_grid, sdf_grid = data["pts_grid"], data["sdf_grid"]
+        tex_grid = data["tex_grid"] if has_tex else None
         fs = (torch.tensor(pts_grid.shape[:3]).float() * (self.fm_reso / max(pts_grid.shape[:3]))).long().tolist()
         self.featmap_size = [int(x // 2 * 2) for x in fs]
-        grid = torch.from_numpy(np.concatenate([sdf_grid[np.newaxis], tex_grid.transpose(3, 0, 1, 2)], axis=0)).float().to(dev)
+        grid = np.concatenate([sdf_grid[np.newaxis], tex_grid.transpose(3, 0, 1, 2)], axis=0) if has_tex else sdf_grid[np.newaxis]
+        grid = torch.from_numpy(grid).float().to(dev)
         want = [x * 2 for x in self.featmap_size]
         if list(grid.shape[1:]) != want:
             grid = F.interpolate(grid.unsqueeze(0), size=want, mode="trilinear", align_corners=False).squeeze(0)
@@ -242,10 +254,13 @@ class ShapeAutoEncoder:
         self.sdf_grid = torch.from_numpy(sdf_grid).float().to(dev).view(-1, 1).clamp_(-thr, thr)
         self.pts_near_surf = torch.from_numpy(data["pts_near_surf"]).float().to(dev).view(-1, 3)
         self.sdf_near_surf = torch.from_numpy(data["sdf_near_surf"]).float().to(dev).view(-1, 1).clamp_(-thr, thr)
-        tc = tex_grid.shape[-1]
-        self.tex_grid = torch.from_numpy(tex_grid).float().to(dev).view(-1, tc)
-        self.tex_near_surf = torch.from_numpy(data["tex_near_surf"]).float().to(dev).view(-1, tc)
-        if "pts_on_surf" in data:
+        if has_tex:
+            tc = tex_grid.shape[-1]
+            if tc != self.net.cfg[5]:
+                raise ValueError(f"{path}: tex_grid has {tc} channels, --data_type {self.data_type} takes {self.net.cfg[5]}")
+            self.tex_grid = torch.from_numpy(tex_grid).float().to(dev).view(-1, tc)
+            self.tex_near_surf = torch.from_numpy(data["tex_near_surf"]).float().to(dev).view(-1, tc)
+        if has_tex and "pts_on_surf" in data:
             self.pts_on_surf = torch.from_numpy(data["pts_on_surf"]).float().to(dev).view(-1, 3)
             self.tex_on_surf = torch.from_numpy(data["tex_on_surf"]).float().to(dev).view(-1, tc)
         if sdf_renorm:
@@ -257,9 +272,11 @@ class ShapeAutoEncoder:
         n_grid = int(batch_size * self.vol_ratio)
         gi = torch.randint(0, self.pts_grid.shape[0], (n_grid,), device=self.device)
         si = torch.randint(0, self.pts_near_surf.shape[0], (batch_size - n_grid,), device=self.device)
-        return {"pts": torch.cat([self.pts_grid[gi], self.pts_near_surf[si]], dim=0),
-                "sdf": torch.cat([self.sdf_grid[gi], self.sdf_near_surf[si]], dim=0),
-                "tex": torch.cat([self.tex_grid[gi], self.tex_near_surf[si]], dim=0)}
+        batch = {"pts": torch.cat([self.pts_grid[gi], self.pts_near_surf[si]], dim=0),
+                 "sdf": torch.cat([self.sdf_grid[gi], self.sdf_near_surf[si]], dim=0)}
+        if self.data_type != "sdf":
+            batch["tex"] = torch.cat([self.tex_grid[gi], self.tex_near_surf[si]], dim=0)
+        return batch
 
     def _loss_cfg(self):
         return ae_loss_cfg(self.sdf_loss_type, self.tex_loss_type, self.sdf_threshold, self.tex_threshold_ratio, self.tex_weight,
@@ -270,12 +287,13 @@ class ShapeAutoEncoder:
         self.optimizer = FlatGroupAdamW(self.net, lr, self.lr_split, lr_decay=min_lr_ratio ** (1 / self.n_iters))
 
     def train_step(self, data):
-        """_forward_batch + update_network (reference :178-237) -> {"sdf_loss", "tex_loss"} device scalars."""
-        losses, _, grads = self.net.loss_and_grads(self.input_grid, data["pts"], data["sdf"], data["tex"], self._loss_cfg(),
+        """_forward_batch + update_network (reference :178-237) -> device scalars {"sdf_loss"} (sdf), {"sdf_loss", "tex_loss"}
+        (sdftex) or {"sdf_loss", "rgb_loss", "mr_loss", "normal_loss"} (sdfpbr)."""
+        losses, _, grads = self.net.loss_and_grads(self.input_grid, data["pts"], data["sdf"], data.get("tex"), self._loss_cfg(),
                                                    aabb=self.aabb, grad_out=getattr(self, "_grad", None))
         self._grad = grads
         self.optimizer.step(grads)
-        return {"sdf_loss": losses[0], "tex_loss": losses[1]}
+        return {k: losses[i] for i, k in enumerate(self.net.loss_names)}
 
     def train(self, data_path, log_every=100):
         self._load_data(data_path, sdf_renorm=bool(self.sdf_renorm))
@@ -314,6 +332,8 @@ class ShapeAutoEncoder:
     @torch.no_grad()
     def encode(self, vol=None):
         """reference :309-317"""
+        if self.net.variant != 2:
+            self.net.build_training_tier()
         return self.net.encode(self.input_grid if vol is None else vol)
 
     def save_ckpt(self, name):

@@ -3,8 +3,11 @@
 
 The decode side covers the reference's three data types: sdftex (skip net, 1+3 columns), sdf (use_tex=False: the geo network
 alone, 1 column, feature maps of fdim_geo channels) and sdfpbr (skip net with 8 sigmoid channels, or the PBR net: sdf | rgb 3 |
-metallic-roughness 2 | normal 3, no sigmoid).  The training tier below is built for the skip net with up to 3 texture channels
-only; on the other nets `encode`, `forward`, `loss_and_grads` and training raise NotImplementedError.
+metallic-roughness 2 | normal 3, no sigmoid).  The training tier below is built for the skip net with 1..8 texture channels
+(sdftex, and sdfpbr with --enc_net_type skip) and for the geometry-only net of either class (sdf).  The sdftex net has it from
+construction; the other two keep their earlier decode-only contract (`encode`, `forward`, `loss_and_grads` raise
+NotImplementedError) until `build_training_tier()` is called, which ShapeAutoEncoder does for training; the PBR net with texture
+has none.
 
 `decode(x, feat_maps, aabb)` keeps the reference semantics (sdf, sigmoid(rgb)); the per-plane conv blocks are
 evaluated once per distinct triplane and cached (the reference recomputes them on every call with identical
@@ -12,8 +15,10 @@ results).
 
 Training tier: `encode(vol)`, `forward(vol, x)` and `loss_and_grads(...)` run on the s3d_ae_*
 entry points.  The parameters are then views of one flat device vector laid out [geo group | tex group] (the reference's
-two AdamW parameter groups, :146-150); the input volume is reduced once to three 2-D projections (`set_volume`), which
-is all the Conv3d-then-mean encoder needs.
+two AdamW parameter groups, :146-150; the geometry-only net has the geo group alone and `tex_group_begin` is the vector's
+size); the input volume (1 + tex_channels channels, 1 for sdf) is reduced once to three 2-D projections (`set_volume`),
+which is all the Conv3d-then-mean encoder needs.  The texture loss of 8 channels is the reference's three means (rgb, mr,
+normal; model.py:226-233), of any other width one mean.
 """
 from __future__ import annotations
 
@@ -91,6 +96,9 @@ class AutoEncoderGroupSkip(nn.Module):
         self._ae_dirty = False
         self._ae_volume = None
         self.tex_group_begin = None
+        # the sdftex skip net has its training tier from construction, as it always had; the geometry-only net and the skip net
+        # with more than 3 texture channels keep their documented decode-only contract until build_training_tier() is called
+        self._tier_built = self.variant == 0 and tex_channels <= 3
 
     _TEX_VARIANT = 0
     _TEX_PREFIXES = ("tex_encoder", "tex_convs", "tex_decoder")
@@ -100,8 +108,28 @@ class AutoEncoderGroupSkip(nn.Module):
 
     @property
     def training_tier_built(self):
-        """The s3d_ae_* tier covers the skip net with texture of up to 3 channels (sdftex)."""
-        return self.variant == 0 and self.cfg[5] <= 3
+        """Whether encode, forward(vol, x), loss_and_grads and flat_parameters run: always for the skip net with up to 3 texture
+        channels (sdftex); for the geometry-only net of either class (sdf) and the skip net with up to 8 channels (sdfpbr with
+        --enc_net_type skip) once build_training_tier() was called; never for the PBR net with texture."""
+        return self._tier_built
+
+    def build_training_tier(self):
+        """Switch the s3d_ae_* tier on for this network (ShapeAutoEncoder does before it loads training data).  A network as
+        constructed keeps what it did before this tier covered it: the geometry-only and the 8-channel nets decode only and
+        say so.  The PBR net with texture has no training tier: NotImplementedError."""
+        if self.variant not in (0, 1):
+            raise NotImplementedError(
+                f"{type(self).__name__}(use_tex={self.use_tex}, tex_channels={self.cfg[5]}): the training tier is not built for the "
+                "PBR network with texture; it decodes only (DESIGN.md §18)")
+        self._tier_built = True
+        return self
+
+    @property
+    def loss_names(self):
+        """The entries of `loss_and_grads`' losses: the reference's loss_dict keys of this network's data type."""
+        if self.variant == 1:
+            return ("sdf_loss",)
+        return ("sdf_loss", "rgb_loss", "mr_loss", "normal_loss") if self.cfg[5] == 8 else ("sdf_loss", "tex_loss")
 
     def geo_parameters(self):
         """reference :146-147"""
@@ -120,14 +148,17 @@ class AutoEncoderGroupSkip(nn.Module):
     def _ensure_ae(self):
         if not self.training_tier_built:
             raise NotImplementedError(
-                f"{type(self).__name__}(use_tex={self.use_tex}, tex_channels={self.cfg[5]}): encode, forward(vol, x), loss_and_grads "
-                "and training are not built for geometry-only, PBR and 8-channel networks; they decode only (DESIGN.md §18)")
+                f"{type(self).__name__}(use_tex={self.use_tex}, tex_channels={self.cfg[5]}): the training tier (encode, "
+                "forward(vol, x), loss_and_grads, flat_parameters) of this network is not built yet: call build_training_tier() "
+                "first, as ShapeAutoEncoder does for training; the PBR network with texture has none and decodes only "
+                "(DESIGN.md §18)")
         lib = _lib.load()
         params = dict(self.named_parameters())
         if self._ae is None:
             h = C.c_void_p()
             cfg = _lib.DecoderCfg(*self.cfg)
-            _lib.check(lib.s3d_ae_create(C.byref(cfg), C.byref(h)))
+            _lib.check(lib.s3d_ae_create_variant(C.byref(cfg), self.variant, C.byref(h)))
+            assert lib.s3d_ae_out_channels(h) == self.out_channels
             self._ae = h
         intact = self._ae_flat is not None and all(
             params[n].data_ptr() == self._ae_flat.data_ptr() + 4 * off and params[n].device == self._ae_flat.device
@@ -183,7 +214,8 @@ class AutoEncoderGroupSkip(nn.Module):
         return {name: flat[off:off + numel].view(shp) for name, off, numel, shp in self._ae_layout}
 
     def set_volume(self, vol):
-        """vol [1, 1+tex_channels, 2H, 2W, 2D]: reduce it to the encoder's three projections (done once per volume)."""
+        """vol [1, out_channels, 2H, 2W, 2D] (sdf, then the texture channels): reduce it to the encoder's three projections
+        (done once per volume)."""
         lib = self._ensure_ae()
         _lib.require_gpu(vol)
         v = vol.contiguous().float()
@@ -202,7 +234,7 @@ class AutoEncoderGroupSkip(nn.Module):
         """reference :164-180 -> [xy [1,C,H,W], xz [1,C,H,D], yz [1,C,W,D]]"""
         lib = self.set_volume(vol)
         H, W, D = self._feat_size
-        Cc = self.geo_feat_dim + self.tex_feat_dim
+        Cc = self.in_feat_channels
         dev = vol.device
         out = [torch.empty((1, Cc, a, b), device=dev, dtype=torch.float32) for a, b in ((H, W), (H, D), (W, D))]
         with torch.cuda.device(dev):
@@ -211,17 +243,26 @@ class AutoEncoderGroupSkip(nn.Module):
 
     def loss_and_grads(self, vol, pts, sdf, tex, loss_cfg, aabb=None, grad_out=None, want_pred=False):
         """One ShapeAutoEncoder iteration without the optimizer (model.py:186-237 + loss.backward()): returns
-        (losses [2] = (sdf_loss, tex_loss) on the device, pred or None, flat gradient of sdf_loss + tex_loss)."""
+        (losses on the device, pred or None, flat gradient of their sum).  losses is [2] = (sdf_loss, tex_loss) for sdftex and
+        for sdf (tex=None, tex_loss 0), and [4] = (sdf_loss, rgb_loss, mr_loss, normal_loss) for the 8 channels of sdfpbr."""
         lib = self.set_volume(vol)
-        pts, sdf, tex = pts.contiguous().float(), sdf.contiguous().float(), tex.contiguous().float()
+        pts, sdf = pts.contiguous().float(), sdf.contiguous().float()
         N = pts.shape[0]
         dev = pts.device
-        losses = torch.empty(2, device=dev, dtype=torch.float32)
-        pred = torch.empty((N, 1 + self.cfg[5]), device=dev, dtype=torch.float32) if want_pred else None
+        if self.variant == 1:
+            tex = None
+        else:
+            tex = tex.contiguous().float()
+            assert tuple(tex.shape) == (N, self.cfg[5]), (tuple(tex.shape), N, self.cfg[5])
+        assert sdf.numel() == N, (tuple(sdf.shape), N)
+        groups = len(self.loss_names) == 4
+        losses = torch.empty(4 if groups else 2, device=dev, dtype=torch.float32)
+        pred = torch.empty((N, self.out_channels), device=dev, dtype=torch.float32) if want_pred else None
         g = grad_out if grad_out is not None else torch.empty_like(self._ae_flat)
+        fn = lib.s3d_ae_loss_grads_groups if groups else lib.s3d_ae_loss_grads
         with torch.cuda.device(dev):
-            _lib.check(lib.s3d_ae_loss_grads(self._ae, _lib.ptr(pts), _lib.ptr(sdf), _lib.ptr(tex), N, self._aabb6(aabb),
-                                             C.byref(loss_cfg), _lib.ptr(losses), _lib.ptr(pred), _lib.ptr(g), _lib.stream_ptr()))
+            _lib.check(fn(self._ae, _lib.ptr(pts), _lib.ptr(sdf), _lib.ptr(tex), N, self._aabb6(aabb),
+                          C.byref(loss_cfg), _lib.ptr(losses), _lib.ptr(pred), _lib.ptr(g), _lib.stream_ptr()))
         return losses, pred, g
 
     # ------------------------------------------------------------------ HIP handle
@@ -323,7 +364,7 @@ class AutoEncoderGroupSkip(nn.Module):
         """net(vol, x) (reference :222-224) through the training-tier forward (no gradient)."""
         lib = self.set_volume(vol)
         pts = x.contiguous().float()
-        pred = torch.empty((pts.shape[0], 1 + self.cfg[5]), device=pts.device, dtype=torch.float32)
+        pred = torch.empty((pts.shape[0], self.out_channels), device=pts.device, dtype=torch.float32)
         with torch.cuda.device(pts.device):
             _lib.check(lib.s3d_ae_forward(self._ae, _lib.ptr(pts), pts.shape[0], self._aabb6(aabb), _lib.ptr(pred), _lib.stream_ptr()))
         return pred
@@ -331,8 +372,9 @@ class AutoEncoderGroupSkip(nn.Module):
 
 class AutoEncoderGroupPBR(AutoEncoderGroupSkip):
     """Reference :227-316: the geo side of the skip net; tex_convs = two 3x3 blocks (the second normalises its input and adds
-    that normalised input back); rgb / mr / normal heads on one gathered feature, no sigmoid.  Decode only: the handle, the
-    triplane cache, `decode`, `decode_grid`, `prepare`, `reset_aabb` and the parameter groups are the base class's."""
+    that normalised input back); rgb / mr / normal heads on one gathered feature, no sigmoid.  With texture it decodes only; with
+    use_tex=False it is the base class's geometry-only net and trains like it.  The handle, the triplane cache, `decode`,
+    `decode_grid`, `prepare`, `reset_aabb` and the parameter groups are the base class's."""
     _TEX_VARIANT = 2
     _TEX_PREFIXES = ("tex_encoder", "tex_convs", "rgb_decoder", "mr_decoder", "normal_decoder")
 
