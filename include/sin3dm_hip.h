@@ -321,6 +321,18 @@ S3D_API int s3d_decoder_decode_points(s3d_decoder* d, const float* pts, int64_t 
  * out [res0,res1,res2, 1+tex_channels] and the three resolutions. */
 S3D_API int s3d_decoder_grid_dims(const float aabb[6], int reso, int dims[3]);
 S3D_API int s3d_decoder_decode_grid(s3d_decoder* d, int reso, const float aabb[6], float* out, void* stream);
+/* The sdf of the geometry head and its exact gradient with respect to the point, in world units: pts [N,3] device ->
+ * sdf [N] (the bits of decode_points' column 0), grad [N,3] = d sdf / d p with F.grid_sample's autograd conventions for
+ * padding_mode='border', align_corners=False (0 beyond a border, the floor cell at a texel centre) and relu'(0) = 0.
+ * iters > 0 first runs that many Newton steps onto the zero level set, p <- p - clamp(sdf g / |g|^2, +-max_step) per
+ * component (no move where |g|^2 < 1e-20), the displacement from the start clamped to +-max_move per component; pts_out
+ * [N,3] receives the final points, and sdf and grad belong to them: iters + 1 evaluations, each two launches on `stream`
+ * (the geometry head through the decode kernel for the sdf, then the gradient kernel), no host synchronisation.
+ * Needs a prepared triplane; every variant (the texture group is not touched).  S3D_ERR_INVALID for iters < 0, a null
+ * pts_out with iters > 0, non-positive max_step / max_move with iters > 0; S3D_ERR_UNSUPPORTED for the widths decode_points
+ * refuses; all checked before any device call.  N == 0 is a no-op. */
+S3D_API int s3d_decoder_sdf_grad(s3d_decoder* d, const float* pts, int64_t N, const float aabb[6], int iters, float max_step,
+                         float max_move, float* pts_out, float* sdf, float* grad, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training tier: what the reference gets from autograd + torch.optim for

@@ -129,6 +129,8 @@ SIGNATURES = {
                                                C.c_int, C.c_void_p]),
     "s3d_decoder_decode_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, c_fp, C.c_int, C.c_void_p,
                                             C.c_void_p]),
+    "s3d_decoder_sdf_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, c_fp, C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "s3d_decoder_grid_dims": (C.c_int, [c_fp, C.c_int, C.POINTER(C.c_int)]),
     "s3d_decoder_decode_grid": (C.c_int, [C.c_void_p, C.c_int, c_fp, C.c_void_p, C.c_void_p]),
     # iso-surface extraction

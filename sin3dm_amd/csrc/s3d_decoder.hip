@@ -175,7 +175,9 @@ constexpr int kSlabLd = 36;   // padded slab row (floats)
 
 // One layer on the matrix cores: hout[m] (MT tiles of 32 rows) = W[MT*32][K] x [in0 | in1] + bias, optional ReLU.
 // in0 has KT0 tiles of 32 rows, in1 KT1.  All four waves run it in lockstep (they share the LDS weight slabs).
-template <int KT0, int KT1, int MT>
+// BIAS = false starts the accumulators at zero and never reads `bias` (the transposed layers of k_decode_grad).  GRAD only tells
+// k_decode_grad's instances from k_decode's: sharing them reordered k_decode's instructions, and k_decode is to compile as it did.
+template <int KT0, int KT1, int MT, bool BIAS = true, bool GRAD = false>
 __device__ __forceinline__ void mlp_layer(const float* __restrict__ Wg, const float* __restrict__ bias,
                                           const f32x16* in0, const f32x16* in1, f32x16* hout, float* lds, bool relu) {
     constexpr int KT = KT0 + KT1, K = KT * 32, M = MT * 32;
@@ -185,7 +187,7 @@ __device__ __forceinline__ void mlp_layer(const float* __restrict__ Wg, const fl
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) hout[m][r] = bias[m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
+        for (int r = 0; r < 16; ++r) hout[m][r] = BIAS ? bias[m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half] : 0.f;
     // slab staging descriptors: item -> (row, float4 q)
     gf4p src[NI]; int dst[NI];
 #pragma unroll
@@ -347,6 +349,169 @@ __global__ __launch_bounds__(256, 1) void k_decode(DecodeArgs a) {
     }
 }
 
+// ------------------------------------------------------------------ sdf and its gradient with respect to the point
+// k_decode_grad: the geometry group's chain of k_decode with each hidden layer's ReLU pattern kept as bit words, then the chain in
+// reverse mode on transposed weight packs: the accumulator of G_prev = W^T G is again the next B operand, so mlp_layer runs it
+// with zero-started accumulators and no ReLU.  dL/dx (UPT tiles) is dotted with the planes' bilinear derivative.
+// The sdf it reports is NOT its own forward's: gather_plane's sums are left to the compiler's contraction, which picks other
+// fused products in this kernel than in k_decode (1..4 units in the last place of the sdf, measured), so k_decode itself, run
+// on the geometry head alone, writes sdf[N] first and this kernel reads it.  That is what makes the sdf bit-identical to
+// decode_points' column 0.  A Newton step (step != 0) moves the point with that sdf and this gradient.
+struct GradArgs {
+    const float* pts;                               // [N][3] the points to evaluate (pts0 or pts_out of the previous step)
+    const float* pts0;                              // [N][3] the start points (the total move is clamped around them)
+    long long N;
+    float amin[3], gsize[3];
+    const float* feat[3]; int ph[3], pw[3];
+    const float* w[6]; const float* b[6];           // the geometry head's forward packs
+    const float* wt4; const float* wt3x; const float* wt3h; const float* wt2; const float* wt1; const float* wt0;   // transposed
+    int step; float max_step, max_move;
+    const float* sdf;                               // [N] k_decode's sdf at pts
+    float* pts_out; float* grad;                    // pts_out: written when step != 0 (may alias pts), or a copy when non-null
+};
+
+// bit (m & 1) * 16 + r of word m >> 1: unit r of tile m is active
+template <int HIDT>
+__device__ __forceinline__ void relu_pattern(const f32x16* h, unsigned* mk) {
+#pragma unroll
+    for (int w = 0; w < (HIDT + 1) / 2; ++w) mk[w] = 0u;
+#pragma unroll
+    for (int m = 0; m < HIDT; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mk[m >> 1] |= (h[m][r] > 0.f ? 1u : 0u) << ((m & 1) * 16 + r);
+    // the words are opaque from here on: seen through, relu_mask would select on the compares themselves, one lane mask in a
+    // scalar register pair per unit and layer
+#pragma unroll
+    for (int w = 0; w < (HIDT + 1) / 2; ++w) asm volatile("" : "+v"(mk[w]));
+}
+template <int HIDT>
+__device__ __forceinline__ void relu_mask(f32x16* g, const unsigned* mk) {
+#pragma unroll
+    for (int m = 0; m < HIDT; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) g[m][r] = ((mk[m >> 1] >> ((m & 1) * 16 + r)) & 1u) ? g[m][r] : 0.f;
+}
+
+// d(sum over channels of dx * sample)/d(fy, fx) of one plane at gather_plane's cell, over the channels this lane half holds.
+// F.grid_sample's backward for padding_mode='border': the factor of a clamped coordinate is 0 (on = false), the cell at an
+// integer position is the one floor selects.  One deviation, on a set of measure zero: exactly ON the last texel centre (fy == h - 1, not
+// clamped) floor selects a cell whose second row is clamped onto the first, so the factor is 0, where autograd keeps the in-bounds
+// corners' term -(c00 (1 - tx) + c01 tx).
+template <int UPT>
+__device__ __forceinline__ void plane_grad(const float* __restrict__ fm, int h, int w, float u, float v, int half,
+                                           const f32x16* dx, float& dfy, float& dfx, bool& on_y, bool& on_x) {
+    constexpr int C = UPT * 32;
+    float fy = __fmul_rn(__fmaf_rn(__fadd_rn(u, 1.f), float(h), -1.f), 0.5f), fx = __fmul_rn(__fmaf_rn(__fadd_rn(v, 1.f), float(w), -1.f), 0.5f);
+    on_y = !(fy < 0.f) && !(fy > float(h - 1)); on_x = !(fx < 0.f) && !(fx > float(w - 1));
+    fy = fminf(fmaxf(fy, 0.f), float(h - 1)); fx = fminf(fmaxf(fx, 0.f), float(w - 1));
+    const int y0 = int(floorf(fy)), x0 = int(floorf(fx));
+    const float ty = fy - float(y0), tx = fx - float(x0);
+    const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
+    const float* p00 = fm + (size_t(y0) * w + x0) * C + half * 4;
+    const float* p01 = fm + (size_t(y0) * w + x1) * C + half * 4;
+    const float* p10 = fm + (size_t(y1) * w + x0) * C + half * 4;
+    const float* p11 = fm + (size_t(y1) * w + x1) * C + half * 4;
+    float sy = 0.f, sx = 0.f;
+#pragma unroll
+    for (int t = 0; t < UPT; ++t)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int c = t * 32 + q * 8;
+            const f32x4 a = g4(p00 + c)[0], b = g4(p01 + c)[0], cc = g4(p10 + c)[0], d = g4(p11 + c)[0];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float g = dx[t][q * 4 + e];
+                sy += g * ((cc[e] - a[e]) * (1.f - tx) + (d[e] - b[e]) * tx);
+                sx += g * ((b[e] - a[e]) * (1.f - ty) + (d[e] - cc[e]) * ty);
+            }
+        }
+    dfy = sy + __shfl_xor(sy, 32);                  // lanes j and j + 32 hold the two halves of a point's channels
+    dfx = sx + __shfl_xor(sx, 32);
+}
+
+template <int UPT, int HIDT>
+__global__ __launch_bounds__(256, 1) void k_decode_grad(GradArgs a) {
+    __shared__ __attribute__((aligned(16))) float lds[2 * HIDT * 32 * kSlabLd];
+    constexpr int MW = (HIDT + 1) / 2;
+    static_assert(UPT <= HIDT, "the slabs of the dL/dx layers (UPT * 32 rows) must fit the hidden layers' LDS");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, half = lane >> 5;
+    const long long pt = (long long)blockIdx.x * 128 + wave * 32 + j;
+    const bool live = pt < a.N;
+    float p[3] = {0.f, 0.f, 0.f};
+    if (live) { p[0] = a.pts[pt * 3]; p[1] = a.pts[pt * 3 + 1]; p[2] = a.pts[pt * 3 + 2]; }
+    float qn[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) qn[k] = __fsub_rn(__fdiv_rn(2.f * __fsub_rn(p[k], a.amin[k]), a.gsize[k]), 1.f);
+    const float uu[3] = {qn[0], qn[0], qn[1]}, vv[3] = {qn[1], qn[2], qn[2]};
+    unsigned mk[5][MW];
+    f32x16 hA[HIDT], hB[HIDT], dx[UPT];
+    {   // forward, for the ReLU patterns
+        f32x16 x[UPT];
+#pragma unroll
+        for (int t = 0; t < UPT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) x[t][r] = 0.f;
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) gather_plane<UPT>(a.feat[pl], a.ph[pl], a.pw[pl], uu[pl], vv[pl], half, x);
+        mlp_layer<UPT, 0, HIDT, true, true>(a.w[0], a.b[0], x, x, hA, lds, true);      relu_pattern<HIDT>(hA, mk[0]);
+        mlp_layer<HIDT, 0, HIDT, true, true>(a.w[1], a.b[1], hA, hA, hB, lds, true);   relu_pattern<HIDT>(hB, mk[1]);
+        mlp_layer<HIDT, 0, HIDT, true, true>(a.w[2], a.b[2], hB, hB, hA, lds, true);   relu_pattern<HIDT>(hA, mk[2]);
+        mlp_layer<UPT, HIDT, HIDT, true, true>(a.w[3], a.b[3], x, hA, hB, lds, true);  relu_pattern<HIDT>(hB, mk[3]);
+        mlp_layer<HIDT, 0, HIDT, true, true>(a.w[4], a.b[4], hB, hB, hA, lds, true);   relu_pattern<HIDT>(hA, mk[4]);
+    }
+    // backward: seed = the sdf row of the last layer, then the hidden layers transposed
+#pragma unroll
+    for (int m = 0; m < HIDT; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) hA[m][r] = a.w[5][m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half];
+    relu_mask<HIDT>(hA, mk[4]);
+    mlp_layer<HIDT, 0, HIDT, false, true>(a.wt4, nullptr, hA, hA, hB, lds, false);       relu_mask<HIDT>(hB, mk[3]);
+    mlp_layer<HIDT, 0, UPT, false, true>(a.wt3x, nullptr, hB, hB, dx, lds, false);       // layer 3 takes [x | h]: dL/dx ...
+    mlp_layer<HIDT, 0, HIDT, false, true>(a.wt3h, nullptr, hB, hB, hA, lds, false);      relu_mask<HIDT>(hA, mk[2]);   // ... and dL/dh
+    mlp_layer<HIDT, 0, HIDT, false, true>(a.wt2, nullptr, hA, hA, hB, lds, false);       relu_mask<HIDT>(hB, mk[1]);
+    mlp_layer<HIDT, 0, HIDT, false, true>(a.wt1, nullptr, hB, hB, hA, lds, false);       relu_mask<HIDT>(hA, mk[0]);
+    {
+        f32x16 dx0[UPT];
+        mlp_layer<HIDT, 0, UPT, false, true>(a.wt0, nullptr, hA, hA, dx0, lds, false);
+#pragma unroll
+        for (int t = 0; t < UPT; ++t) dx[t] += dx0[t];
+    }
+    // planes: coords_list [[0,1],[0,2],[1,2]]; d fy / d u = h / 2, d u / d p_k = 2 / gsize[k]
+    float gn[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+        const int au = pl == 2 ? 1 : 0, av = pl == 0 ? 1 : 2;
+        float dfy, dfx; bool on_y, on_x;
+        plane_grad<UPT>(a.feat[pl], a.ph[pl], a.pw[pl], uu[pl], vv[pl], half, dx, dfy, dfx, on_y, on_x);
+        gn[au] += on_y ? dfy * (0.5f * float(a.ph[pl])) : 0.f;
+        gn[av] += on_x ? dfx * (0.5f * float(a.pw[pl])) : 0.f;
+    }
+    if (!live || half) return;
+    float gr[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { gr[k] = gn[k] * (2.f / a.gsize[k]); a.grad[pt * 3 + k] = gr[k]; }
+    if (a.step) {
+        // Newton step onto the level set, every operation rounded once (a float32 restatement reproduces it)
+        const float sdf = a.sdf[pt];
+        const float g2 = __fadd_rn(__fadd_rn(__fmul_rn(gr[0], gr[0]), __fmul_rn(gr[1], gr[1])), __fmul_rn(gr[2], gr[2]));
+        if (g2 >= 1e-20f) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float p0 = a.pts0[pt * 3 + k];
+                float s = __fdiv_rn(__fmul_rn(sdf, gr[k]), g2);
+                s = fminf(fmaxf(s, -a.max_step), a.max_step);
+                float dm = __fsub_rn(__fsub_rn(p[k], s), p0);
+                dm = fminf(fmaxf(dm, -a.max_move), a.max_move);
+                p[k] = __fadd_rn(p0, dm);
+            }
+        }
+    }
+    if (a.pts_out) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) a.pts_out[pt * 3 + k] = p[k];
+    }
+}
+
 }  // namespace s3d
 
 using namespace s3d;
@@ -373,6 +538,10 @@ struct s3d_decoder {
     int ph[3] = {0, 0, 0}, pw[3] = {0, 0, 0};
     bool prepared = false;
     Arena arena;
+    // transposed packs of the geometry head (s3d_decoder_sdf_grad), built on a handle's first gradient call
+    DevBuf gbuf;
+    bool gpacked = false;
+    size_t gwt[6] = {0, 0, 0, 0, 0, 0};                  // wt4, wt3x, wt3h, wt2, wt1, wt0
     const float* dev(size_t off) const { return static_cast<const float*>(wbuf.p) + off; }
     int out_channels() const { int c = 0; for (const auto& h : heads) c += h.nout; return c; }
 };
@@ -541,6 +710,34 @@ static int run_decode(s3d_decoder* d, const float* pts, long long N, const float
     return S3D_ERR_UNSUPPORTED;
 }
 
+// columns [c0, c0+n) of dense W [out][in], transposed and zero-padded: [np][outp]
+static size_t pack_transposed(std::vector<float>& st, const std::vector<float>& W, int out, int in, int c0, int n, int np, int outp) {
+    std::vector<float> t(size_t(n) * out);
+    for (int o = 0; o < out; ++o)
+        for (int i = 0; i < n; ++i) t[size_t(i) * out + o] = W[size_t(o) * in + c0 + i];
+    return pack_linear(st, t, n, out, 0, np, outp, 0);
+}
+static int dec_pack_grad(s3d_decoder* d) {
+    const int up = d->cfg.feat_channel_up, hid = d->cfg.mlp_hidden_channels, upp = d->up_p, hidp = d->hid_p;
+    const std::string ml = d->heads[0].name;             // geo_decoder
+    auto W = [&](const char* layer) -> const std::vector<float>& { return d->host.at(ml + layer + ".weight"); };
+    std::vector<float> st;
+    d->gwt[0] = pack_transposed(st, W(".second_layers.2"), hid, hid, 0, hid, hidp, hidp);
+    d->gwt[1] = pack_transposed(st, W(".second_layers.0"), hid, up + hid, 0, up, upp, hidp);
+    d->gwt[2] = pack_transposed(st, W(".second_layers.0"), hid, up + hid, up, hid, hidp, hidp);
+    d->gwt[3] = pack_transposed(st, W(".first_layers.4"), hid, hid, 0, hid, hidp, hidp);
+    d->gwt[4] = pack_transposed(st, W(".first_layers.2"), hid, hid, 0, hid, hidp, hidp);
+    d->gwt[5] = pack_transposed(st, W(".first_layers.0"), hid, up, 0, up, upp, hidp);
+    S3D_TRY(upload(d->gbuf, st.data(), st.size() * sizeof(float)));
+    d->gpacked = true;
+    return 0;
+}
+template <int UPT, int HIDT>
+static int launch_decode_grad(const GradArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL((k_decode_grad<UPT, HIDT>), dim3((unsigned)((a.N + 127) / 128)), dim3(256), 0, st, a);
+    S3D_HIP(hipGetLastError());
+    return 0;
+}
 
 }  // namespace s3d
 
@@ -588,6 +785,7 @@ int s3d_decoder_set_param(s3d_decoder* d, const char* name, const float* data, c
         S3D_CHECK(ok, S3D_ERR_INVALID, "size mismatch for %s", name);
         d->host[sp.name].assign(data, data + n);
         d->packed = false;
+        d->gpacked = false;
         return 0;
     }
     set_error("unexpected key '%s' in decoder state_dict", name);
@@ -708,6 +906,56 @@ int s3d_decoder_decode_points(s3d_decoder* d, const float* pts, int64_t N, const
     S3D_CHECK(d && aabb && N >= 0 && (N == 0 || (pts && out)), S3D_ERR_INVALID, "decode_points: bad argument");
     if (N == 0) return 0;                                   // decoding no points is a no-op (empty tensors have null pointers)
     return run_decode(d, pts, N, aabb, nullptr, clamp_color, out, static_cast<hipStream_t>(stream));
+}
+
+int s3d_decoder_sdf_grad(s3d_decoder* d, const float* pts, int64_t N, const float aabb[6], int iters, float max_step, float max_move,
+                         float* pts_out, float* sdf, float* grad, void* stream) {
+    S3D_CHECK(d && aabb && N >= 0 && (N == 0 || (pts && sdf && grad)), S3D_ERR_INVALID, "sdf_grad: bad argument");
+    S3D_CHECK(iters >= 0, S3D_ERR_INVALID, "sdf_grad: iters=%d", iters);
+    S3D_CHECK(iters == 0 || N == 0 || pts_out, S3D_ERR_INVALID, "sdf_grad: iters=%d needs pts_out", iters);
+    S3D_CHECK(iters == 0 || (max_step > 0.f && max_move > 0.f), S3D_ERR_INVALID, "sdf_grad: max_step=%g, max_move=%g must be positive", double(max_step), double(max_move));
+    const int upt = d->up_p / 32, hidt = d->hid_p / 32;
+    const bool built = (upt == 2 && hidt == 8) || (upt == 1 && (hidt == 1 || hidt == 2 || hidt == 8)) || (upt == 3 && hidt == 4);
+    if (!built) {
+        set_error("decoder: feat_channel_up=%d / mlp_hidden_channels=%d has no compiled kernel (supported after padding to 32: "
+                  "up<=64 with hidden 256, up<=32 with hidden 32 or 64, up 96 with hidden 128)", d->cfg.feat_channel_up,
+                  d->cfg.mlp_hidden_channels);
+        return S3D_ERR_UNSUPPORTED;
+    }
+    if (N == 0) return 0;
+    S3D_CHECK(d->prepared, S3D_ERR_INVALID, "decoder: call s3d_decoder_prepare_triplane first");
+    S3D_CHECK(d->packed, S3D_ERR_INVALID, "decoder: parameters changed since s3d_decoder_prepare_triplane; prepare again");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (!d->gpacked) {
+        S3D_HIP(hipStreamSynchronize(st));               // an earlier gradient call may still read the packs
+        S3D_TRY(dec_pack_grad(d));
+    }
+    // the geometry head alone through k_decode: sdf[N] with the bits of decode_points' column 0
+    DecodeArgs da; memset(&da, 0, sizeof da);
+    da.N = N; da.out = sdf; da.out_stride = 1; da.ngroups = 1;
+    GradArgs a; memset(&a, 0, sizeof a);
+    a.pts0 = pts; a.N = N; a.max_step = max_step; a.max_move = max_move; a.sdf = sdf; a.grad = grad;
+    for (int k = 0; k < 3; ++k) {
+        da.amin[k] = a.amin[k] = aabb[k]; da.gsize[k] = a.gsize[k] = aabb[3 + k] - aabb[k];
+        da.feat[0][k] = a.feat[k] = d->featp[0][k]; da.ph[k] = a.ph[k] = d->ph[k]; da.pw[k] = a.pw[k] = d->pw[k];
+        da.gdim[k] = 1;
+    }
+    const auto& H = d->heads[0];
+    for (int l = 0; l < 6; ++l) { da.mlp[0].w[l] = a.w[l] = d->dev(H.mw[l]); da.mlp[0].b[l] = a.b[l] = d->dev(H.mb[l]); }
+    da.hbeg[0] = 0; da.hbeg[1] = da.hbeg[2] = 1; da.col0[0] = 0; da.ncol[0] = 1;
+    const float* g = static_cast<const float*>(d->gbuf.p);
+    a.wt4 = g + d->gwt[0]; a.wt3x = g + d->gwt[1]; a.wt3h = g + d->gwt[2]; a.wt2 = g + d->gwt[3]; a.wt1 = g + d->gwt[4]; a.wt0 = g + d->gwt[5];
+    for (int it = 0; it <= iters; ++it) {                // iters + 1 evaluations: sdf and grad belong to the returned point
+        da.pts = a.pts = it == 0 ? pts : pts_out;
+        a.step = it < iters;
+        a.pts_out = (a.step || iters == 0) ? pts_out : nullptr;
+        if (upt == 2 && hidt == 8) { S3D_TRY((launch_decode<2, 8>(da, st))); S3D_TRY((launch_decode_grad<2, 8>(a, st))); }
+        else if (upt == 1 && hidt == 1) { S3D_TRY((launch_decode<1, 1>(da, st))); S3D_TRY((launch_decode_grad<1, 1>(a, st))); }
+        else if (upt == 1 && hidt == 8) { S3D_TRY((launch_decode<1, 8>(da, st))); S3D_TRY((launch_decode_grad<1, 8>(a, st))); }
+        else if (upt == 1 && hidt == 2) { S3D_TRY((launch_decode<1, 2>(da, st))); S3D_TRY((launch_decode_grad<1, 2>(a, st))); }
+        else { S3D_TRY((launch_decode<3, 4>(da, st))); S3D_TRY((launch_decode_grad<3, 4>(a, st))); }
+    }
+    return 0;
 }
 
 int s3d_decoder_grid_dims(const float aabb[6], int reso, int dims[3]) {

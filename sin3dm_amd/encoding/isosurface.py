@@ -89,10 +89,22 @@ def largest_component(verts, tris, attrs=None):
     return verts[keep_v], new_tris.contiguous(), (attrs[keep_v] if attrs is not None else None)
 
 
-def export_obj(path, verts, tris, colors=None):
-    """Wavefront OBJ with optional per-vertex colours (`v x y z r g b`)."""
+def _unit_normals(normals, n_verts, who):
+    """[V,3] float numpy of one normal per vertex, or None"""
+    if normals is None:
+        return None
+    vn = _np(normals).astype(np.float64).reshape(-1, 3)
+    if vn.shape[0] != n_verts:
+        raise ValueError(f"{who}: {vn.shape[0]} normals for {n_verts} vertices")
+    return vn
+
+
+def export_obj(path, verts, tris, colors=None, normals=None):
+    """Wavefront OBJ with optional per-vertex colours (`v x y z r g b`) and optional per-vertex normals [V,3] (`vn` lines after
+    the vertices, faces `f v//vn`; without them the file is what it always was)."""
     v = verts.detach().cpu().numpy()
     f = tris.detach().cpu().numpy().astype(np.int64) + 1
+    vn = _unit_normals(normals, v.shape[0], "export_obj")
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as fh:
         if colors is not None:
@@ -100,7 +112,11 @@ def export_obj(path, verts, tris, colors=None):
             np.savetxt(fh, np.concatenate([v, c], 1), fmt="v %.6f %.6f %.6f %.4f %.4f %.4f")
         else:
             np.savetxt(fh, v, fmt="v %.6f %.6f %.6f")
-        np.savetxt(fh, f, fmt="f %d %d %d")
+        if vn is not None:
+            np.savetxt(fh, vn, fmt="vn %.6f %.6f %.6f")
+            np.savetxt(fh, np.repeat(f, 2, axis=1), fmt="f %d//%d %d//%d %d//%d")
+        else:
+            np.savetxt(fh, f, fmt="f %d %d %d")
 
 
 # ------------------------------------------------------------------ decimation to a face budget: vertex clustering on a grid
@@ -483,11 +499,11 @@ def read_material_params_from_mtl(path):
 _MATERIAL_DEFAULTS = {"Kd": [1, 1, 1], "Ka": [0, 0, 0], "Ks": [0.4, 0.4, 0.4], "Ns": 10}
 
 
-def export_textured_obj(path, verts, tris, uvs, image, material=None, mtl_str=None):
+def export_textured_obj(path, verts, tris, uvs, image, material=None, mtl_str=None, normals=None):
     """`path` (x.obj) plus x.mtl and x.png beside it.  image [T,T,C] uint8 with row 0 = texel row y = 0 (written as the BOTTOM row of
     the PNG, so that vt = texel / T); uvs [3F,2], three per face in the face's vertex order.  The material block is `mtl_str`
     (read_material_params_from_mtl) when given, else Kd/Ka/Ks/Ns of `material` (missing or None entries: Kd 1 1 1, Ka 0 0 0,
-    Ks 0.4 0.4 0.4, Ns 10) and illum 2."""
+    Ks 0.4 0.4 0.4, Ns 10) and illum 2.  normals [V,3]: `vn` lines and faces `f v/vt/vn` (None: the file as it always was)."""
     if not path.endswith(".obj"):
         raise ValueError(f"export_textured_obj: {path!r} does not end in .obj")
     v, f, vt = _np(verts), _np(tris).astype(np.int64), _np(uvs)
@@ -508,18 +524,24 @@ def export_textured_obj(path, verts, tris, uvs, image, material=None, mtl_str=No
         fh.write(f"map_Kd {stem}.png\n")
     with open(path[:-4] + ".png", "wb") as fh:
         fh.write(png_bytes(_np(image)[::-1]))
-    _write_uv_obj(path, stem, v, vt, f)
+    _write_uv_obj(path, stem, v, vt, f, _unit_normals(normals, v.shape[0], "export_textured_obj"))
 
 
-def _write_uv_obj(path, stem, v, vt, f):
-    """The .obj of the textured writers: mtllib, v, vt (three per face, in the face's vertex order), usemtl material_0, f v/vt."""
+def _write_uv_obj(path, stem, v, vt, f, vn=None):
+    """The .obj of the textured writers: mtllib, v, vt (three per face, in the face's vertex order), usemtl material_0, f v/vt;
+    with per-vertex normals vn [V,3]: `vn` lines after the `vt` lines and f v/vt/vn."""
     ft = np.arange(3 * f.shape[0], dtype=np.int64).reshape(-1, 3) + 1
     with open(path, "w") as fh:
         fh.write(f"mtllib {stem}.mtl\n")
         np.savetxt(fh, v, fmt="v %.6f %.6f %.6f")
         np.savetxt(fh, vt, fmt="vt %.6f %.6f")
+        if vn is not None:
+            np.savetxt(fh, vn, fmt="vn %.6f %.6f %.6f")
         fh.write("usemtl material_0\n")
-        np.savetxt(fh, np.stack([f + 1, ft], 2).reshape(-1, 6), fmt="f %d/%d %d/%d %d/%d")
+        if vn is not None:
+            np.savetxt(fh, np.stack([f + 1, ft, f + 1], 2).reshape(-1, 9), fmt="f %d/%d/%d %d/%d/%d %d/%d/%d")
+        else:
+            np.savetxt(fh, np.stack([f + 1, ft], 2).reshape(-1, 6), fmt="f %d/%d %d/%d %d/%d")
 
 
 def split_pbr_image(image):
@@ -536,11 +558,12 @@ _PBR_MTL_DEFAULTS = (("Ns", 250), ("Ks", [0.5, 0.5, 0.5]), ("Ke", [0, 0, 0]), ("
 PBR_MAPS = (("map_Kd", "albedo"), ("map_Pm", "metallic"), ("map_Pr", "roughness"), ("map_Bump -bm 1.000000", "normal"))
 
 
-def export_pbr_obj(path, verts, tris, uvs, albedo, metallic, roughness, normal, **material):
+def export_pbr_obj(path, verts, tris, uvs, albedo, metallic, roughness, normal, normals=None, **material):
     """`path` (x.obj), x.mtl and textures/{albedo,metallic,roughness,normal}.png beside it: the files, the material block and
     its defaults of the reference's save_mesh_with_pbr (src/encoding/utils3d.py:137-166; keyword arguments Ns, Ks, Ke, Ni, d,
     illum, Ps, Pc, Pcr, aniso, anisor override them).  albedo / normal [T,T,3], metallic / roughness [T,T] uint8 (written as
-    single-channel PNGs), row 0 = texel row y = 0 = the BOTTOM row of each PNG, as in export_textured_obj."""
+    single-channel PNGs), row 0 = texel row y = 0 = the BOTTOM row of each PNG, as in export_textured_obj.  normals [V,3]: per-vertex
+    geometric normals as `vn` lines (not the `normal` map), as in export_textured_obj."""
     if not path.endswith(".obj"):
         raise ValueError(f"export_pbr_obj: {path!r} does not end in .obj")
     v, f, vt = _np(verts), _np(tris).astype(np.int64), _np(uvs)
@@ -567,23 +590,23 @@ def export_pbr_obj(path, verts, tris, uvs, albedo, metallic, roughness, normal, 
     for name, m in maps.items():
         with open(os.path.join(root, "textures", name + ".png"), "wb") as fh:
             fh.write(png_bytes(m[::-1]))
-    _write_uv_obj(path, stem, v, vt, f)
+    _write_uv_obj(path, stem, v, vt, f, _unit_normals(normals, v.shape[0], "export_pbr_obj"))
 
 
-def export_glb(path, verts, tris, uvs, image):
+def export_glb(path, verts, tris, uvs, image, normals=None):
     """Binary glTF 2.0: one un-indexed triangle primitive of 3F vertices (POSITION, TEXCOORD_0 with v_gltf = 1 - v_obj), the PNG of
-    export_textured_obj embedded as a bufferView, base colour factor 1, metallic 0, roughness 1, double sided."""
+    export_textured_obj embedded as a bufferView, base colour factor 1, metallic 0, roughness 1, double sided.  normals [V,3]: a NORMAL accessor (None: the file as it always was)."""
     material = {"pbrMetallicRoughness": {"baseColorFactor": [1.0, 1.0, 1.0, 1.0], "baseColorTexture": {"index": 0},
                                          "metallicFactor": 0.0, "roughnessFactor": 1.0}, "doubleSided": True}
-    _write_glb(path, verts, tris, uvs, [png_bytes(_np(image)[::-1])], material, "export_glb")
+    _write_glb(path, verts, tris, uvs, [png_bytes(_np(image)[::-1])], material, "export_glb", normals)
 
 
-def export_pbr_glb(path, verts, tris, uvs, albedo, metallic, roughness, normal):
+def export_pbr_glb(path, verts, tris, uvs, albedo, metallic, roughness, normal, normals=None):
     """Binary glTF 2.0 with one metallic-roughness material (an own design: the reference has no PBR GLB): baseColorTexture =
     albedo, metallicRoughnessTexture = ONE RGB image with G = roughness, B = metallic (glTF's channel assignment) and R = 0,
     normalTexture = normal; three embedded PNGs, the albedo's bytes equal to export_pbr_obj's.  metallicFactor and
     roughnessFactor are 1.0: glTF multiplies the texture by them, so export_glb's 0.0 / 1.0 would cancel the metallic map.
-    Double sided.  Arrays as in export_pbr_obj."""
+    Double sided.  Arrays as in export_pbr_obj; normals [V,3]: per-vertex geometric normals as a NORMAL accessor."""
     al, me, ro, no = _np(albedo), _np(metallic), _np(roughness), _np(normal)
     if me.shape != ro.shape or me.ndim != 2 or al.shape != me.shape + (3,) or no.shape != al.shape:
         raise ValueError(f"export_pbr_glb: albedo {al.shape}, metallic {me.shape}, roughness {ro.shape}, normal {no.shape}")
@@ -591,22 +614,28 @@ def export_pbr_glb(path, verts, tris, uvs, albedo, metallic, roughness, normal):
     material = {"pbrMetallicRoughness": {"baseColorFactor": [1.0, 1.0, 1.0, 1.0], "baseColorTexture": {"index": 0},
                                          "metallicRoughnessTexture": {"index": 1}, "metallicFactor": 1.0, "roughnessFactor": 1.0},
                 "normalTexture": {"index": 2}, "doubleSided": True}
-    _write_glb(path, verts, tris, uvs, [png_bytes(m[::-1]) for m in (al, packed, no)], material, "export_pbr_glb")
+    _write_glb(path, verts, tris, uvs, [png_bytes(m[::-1]) for m in (al, packed, no)], material, "export_pbr_glb", normals)
 
 
-def _write_glb(path, verts, tris, uvs, pngs, material, who):
-    """The GLB container of export_glb / export_pbr_glb: texture i = image i = pngs[i]."""
+def _write_glb(path, verts, tris, uvs, pngs, material, who, normals=None):
+    """The GLB container of export_glb / export_pbr_glb: texture i = image i = pngs[i].  normals [V,3] (per vertex, expanded to the
+    3F corners like the positions): accessor 2 = NORMAL, its bufferView after the images so that every other index stays."""
     v, f, vt = _np(verts).astype(np.float32), _np(tris).astype(np.int64), _np(uvs).astype(np.float32)
     if vt.shape[0] != 3 * f.shape[0]:
         raise ValueError(f"{who}: {vt.shape[0]} texture coordinates for {f.shape[0]} faces")
     pos = np.ascontiguousarray(v[f.reshape(-1)], dtype="<f4").reshape(-1, 3)
     uv = np.ascontiguousarray(np.stack([vt[:, 0], 1.0 - vt[:, 1]], 1), dtype="<f4")
     parts = [pos.tobytes(), uv.tobytes(), *pngs]
+    vn = _unit_normals(normals, v.shape[0], who)
+    if vn is not None:
+        parts.append(np.ascontiguousarray(vn[f.reshape(-1)], dtype="<f4").reshape(-1, 3).tobytes())
     views, blob = [], b""
     for p in parts:
         views.append({"buffer": 0, "byteOffset": len(blob), "byteLength": len(p)})
         blob += p + b"\0" * (-len(p) % 4)
     views[0]["target"] = views[1]["target"] = 34962                                        # ARRAY_BUFFER
+    if vn is not None:
+        views[-1]["target"] = 34962
     n = pos.shape[0]
     bounds = {"min": pos.min(0).tolist(), "max": pos.max(0).tolist()} if n else {"min": [0.0] * 3, "max": [0.0] * 3}
     gltf = {
@@ -621,6 +650,9 @@ def _write_glb(path, verts, tris, uvs, pngs, material, who):
                       {"bufferView": 1, "componentType": 5126, "count": n, "type": "VEC2"}],
         "bufferViews": views, "buffers": [{"byteLength": len(blob)}],
     }
+    if vn is not None:
+        gltf["meshes"][0]["primitives"][0]["attributes"]["NORMAL"] = 2
+        gltf["accessors"].append({"bufferView": len(views) - 1, "componentType": 5126, "count": n, "type": "VEC3"})
     js = json.dumps(gltf, separators=(",", ":")).encode()
     js += b" " * (-len(js) % 4)
     total = 12 + 8 + len(js) + 8 + len(blob)

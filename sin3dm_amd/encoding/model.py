@@ -140,13 +140,43 @@ class ShapeAutoEncoder:
         np.savez_compressed(os.path.join(save_dir, f"r{reso}_voxel.npz"), voxel=vox)
         return vox
 
+    def _refine_and_normals(self, triplane_feat, aabb, verts, tris, reso, box_size, refine, refine_max_move, normals):
+        """The field's part of the mesh exports: `refine` Newton steps of the vertices onto the decoded zero level
+        set, each step and the total move clamped to refine_max_move cells of the decode grid (box_size / reso, world units) per
+        component, and with normals="field" the unit gradient at the final vertices (sdf < 0 is inside: +g points outward), the
+        area-weighted normal where the gradient vanishes.  -> (verts, normals or None); faces are never changed."""
+        if normals not in (None, "field"):
+            raise ValueError(f"normals {normals!r}: expected 'field' (or None)")
+        refine = int(refine)
+        if refine < 0 or not refine_max_move > 0:
+            raise ValueError(f"refine={refine}, refine_max_move={refine_max_move}: expected refine >= 0 and a positive move")
+        if (refine == 0 and normals is None) or verts.shape[0] == 0:
+            return verts, (verts.new_zeros((0, 3)) if normals is not None else None)
+        self.net.eval()
+        limit = float(refine_max_move) * float(box_size) / float(reso)
+        verts, _, grad = self.net.project_to_surface(verts, triplane_feat, aabb=aabb, iters=refine, max_step=limit, max_move=limit)
+        if normals is None:
+            return verts, None
+        from ..rendering.rasterizer import vertex_normals
+        g2 = (grad * grad).sum(1, keepdim=True)
+        flat = g2[:, 0] < 1e-20
+        n = grad / g2.clamp_min(1e-20).sqrt()
+        if bool(flat.any()):
+            n = torch.where(flat[:, None], vertex_normals(verts, tris), n)
+        return verts, n
+
     @torch.no_grad()
-    def decode_mesh(self, save_dir, triplane_feat, reso, name="object.obj", only_largest_cc=True, save_voxel=True):
+    def decode_mesh(self, save_dir, triplane_feat, reso, name="object.obj", only_largest_cc=True, save_voxel=True, refine=0,
+                    refine_max_move=0.5, normals=None, return_normals=False):
         """The geometry half of decode_texmesh (reference :362-390): decode_grid -> voxel.npz -> iso-surface of the
         padded SDF grid at level 0 -> largest connected component -> `v / reso * box_size + box_min`, all on the device
         (sdfgrid_to_mesh, utils3d.py:196-208, used PyMCubes + point_cloud_utils on the CPU).  The decoded colour is
         interpolated onto the vertices and written as a vertex-coloured OBJ (sdfpbr: the albedo; sdf: an OBJ without
-        colours); decimation, UV atlas and the baked texture that follow in the reference are decode_texmesh."""
+        colours); decimation, UV atlas and the baked texture that follow in the reference are decode_texmesh.
+        refine=K > 0 projects the vertices onto the decoded zero level set after the re-normalisation (K Newton steps, at most
+        refine_max_move cells per axis; the colours stay the interpolated ones); normals="field" writes the unit gradient there as
+        `vn` lines (_refine_and_normals).  return_normals: a fourth entry, the normals [V,3] (None without them).  With the
+        defaults the file and the returned tuple are what they always were."""
         from .isosurface import export_obj, largest_component, marching_cubes
         H, W = triplane_feat[0].shape[-2:]
         D = triplane_feat[1].shape[-1]
@@ -162,12 +192,13 @@ class ShapeAutoEncoder:
         box_min = aabb[:3]
         box_size = aabb[3:].max() - aabb[:3].min()                               # the reference's re-normalisation (:385-387)
         verts = verts / float(reso) * box_size + box_min
-        export_obj(os.path.join(save_dir, name), verts, tris, cols)
-        return verts, tris, cols
+        verts, vn = self._refine_and_normals(triplane_feat, aabb, verts, tris, reso, box_size, refine, refine_max_move, normals)
+        export_obj(os.path.join(save_dir, name), verts, tris, cols, **({"normals": vn} if vn is not None else {}))
+        return (verts, tris, cols, vn) if return_normals else (verts, tris, cols)
 
     @torch.no_grad()
     def decode_texmesh(self, save_dir, triplane_feat, reso, n_faces=10000, texture_reso=2048, only_largest_cc=True, save_voxel=True,
-                       mtl_path=None, file_format="obj", decimation="cluster"):
+                       mtl_path=None, file_format="obj", decimation="cluster", refine=0, refine_max_move=0.5, normals=None):
         """Reference :362-473 for data_type sdftex: decode_grid -> voxel.npz -> iso-surface -> largest component -> the re-normalisation
         of decode_mesh -> decimation to n_faces (isosurface.simplify_mesh) -> UV atlas at texture_reso and ONE decode_batch call over
         its covered texels, quantised and dilated on the device (isosurface.bake_texture) -> object.obj + object.mtl + object.png, or
@@ -178,6 +209,9 @@ class ShapeAutoEncoder:
         data_type sdfpbr (:459-471): ONE bake of all 8 channels, split into albedo [..., :3], metallic [..., 3], roughness [..., 4]
         and normal [..., 5:] -> object.obj + object.mtl + textures/{albedo,metallic,roughness,normal}.png (export_pbr_obj), or
         object.glb with one metallic-roughness material (export_pbr_glb).
+        refine=K > 0 projects the DECIMATED vertices onto the decoded zero level set (_refine_and_normals) before the atlas, so the
+        texel positions are taken on the refined mesh; normals="field" writes the field's unit normals (`vn`, or NORMAL in the GLB)
+        and returns them as "normals".  With the defaults every file is what it always was.
         Returns a dict of what was written (verts, tris, info, and with a texture uvs, image, mask, gb_pos, corner0), or None for
         an empty iso-surface (no mesh file is written then)."""
         import warnings
@@ -205,23 +239,25 @@ class ShapeAutoEncoder:
         box_size = aabb[3:].max() - aabb[:3].min()
         verts = verts / float(reso) * box_size + box_min
         verts, tris, info = (iso.simplify_mesh_quadric if decimation == "quadric" else iso.simplify_mesh)(verts, tris, n_faces)
+        verts, vn = self._refine_and_normals(triplane_feat, aabb, verts, tris, reso, box_size, refine, refine_max_move, normals)
+        nk = {"normals": vn} if vn is not None else {}
         if self.data_type == "sdf":
-            iso.export_obj(os.path.join(save_dir, f"mesh_r{reso}_simple.obj"), verts, tris)
-            return {"verts": verts, "tris": tris, "info": info}
+            iso.export_obj(os.path.join(save_dir, f"mesh_r{reso}_simple.obj"), verts, tris, **nk)
+            return {"verts": verts, "tris": tris, "info": info, **nk}
         image, mask, gb_pos, uvs, corner0 = iso.bake_texture(
             verts, tris, texture_reso, lambda p: self.decode_batch(triplane_feat, p, aabb=aabb)[..., 1:])
         if self.data_type == "sdfpbr":
             maps = iso.split_pbr_image(image)
             if file_format == "obj":
-                iso.export_pbr_obj(os.path.join(save_dir, "object.obj"), verts, tris, uvs, *maps)
+                iso.export_pbr_obj(os.path.join(save_dir, "object.obj"), verts, tris, uvs, *maps, **nk)
             else:
-                iso.export_pbr_glb(os.path.join(save_dir, "object.glb"), verts, tris, uvs, *maps)
+                iso.export_pbr_glb(os.path.join(save_dir, "object.glb"), verts, tris, uvs, *maps, **nk)
         elif file_format == "obj":
             mtl_str = iso.read_material_params_from_mtl(mtl_path) if mtl_path is not None else None
-            iso.export_textured_obj(os.path.join(save_dir, "object.obj"), verts, tris, uvs, image, material=self.material, mtl_str=mtl_str)
+            iso.export_textured_obj(os.path.join(save_dir, "object.obj"), verts, tris, uvs, image, material=self.material, mtl_str=mtl_str, **nk)
         else:
-            iso.export_glb(os.path.join(save_dir, "object.glb"), verts, tris, uvs, image)
-        return {"verts": verts, "tris": tris, "uvs": uvs, "image": image, "mask": mask, "gb_pos": gb_pos, "corner0": corner0, "info": info}
+            iso.export_glb(os.path.join(save_dir, "object.glb"), verts, tris, uvs, image, **nk)
+        return {"verts": verts, "tris": tris, "uvs": uvs, "image": image, "mask": mask, "gb_pos": gb_pos, "corner0": corner0, "info": info, **nk}
 
     # ------------------------------------------------------------------ training (reference :51-139, 178-258)
     def _load_data(self, path, sdf_renorm=False):

@@ -334,6 +334,34 @@ class AutoEncoderGroupSkip(nn.Module):
                                                      int(bool(clamp_color)), _lib.ptr(out), _lib.stream_ptr()))
         return out
 
+    def _sdf_grad(self, x, feat_maps, aabb, iters, max_step, max_move):
+        lib = self.prepare(feat_maps)
+        _lib.require_gpu(x)
+        pts = x.contiguous().float()
+        n, dev = pts.shape[0], pts.device
+        sdf = torch.empty((n,), device=dev, dtype=torch.float32)
+        grad = torch.empty((n, 3), device=dev, dtype=torch.float32)
+        moved = torch.empty((n, 3), device=dev, dtype=torch.float32) if iters > 0 else None
+        with torch.cuda.device(dev):
+            _lib.check(lib.s3d_decoder_sdf_grad(self._handle, _lib.ptr(pts), n, self._aabb6(aabb), int(iters), float(max_step),
+                                                float(max_move), _lib.ptr(moved), _lib.ptr(sdf), _lib.ptr(grad), _lib.stream_ptr()))
+        return moved, sdf, grad
+
+    def sdf_and_grad(self, x, feat_maps, aabb=None):
+        """x [N,3] -> (sdf [N], d sdf / d x [N,3] in world units): the geometry head and its exact gradient with respect to the
+        point, with F.grid_sample's autograd conventions (0 beyond a plane's border, the floor cell at a texel centre).  sdf has
+        the bits of decode(...)[:, 0]."""
+        _, sdf, grad = self._sdf_grad(x, feat_maps, aabb, 0, 0.0, 0.0)
+        return sdf, grad
+
+    def project_to_surface(self, x, feat_maps, aabb=None, iters=2, max_step=0.05, max_move=0.1):
+        """`iters` Newton steps of x onto the zero level set, x <- x - clamp(sdf g / |g|^2, +-max_step) per component, the
+        displacement from the start clamped to +-max_move per component (world units) -> (x', sdf(x'), grad(x'))."""
+        if iters == 0:
+            sdf, grad = self.sdf_and_grad(x, feat_maps, aabb)
+            return x.contiguous().float().clone(), sdf, grad
+        return self._sdf_grad(x, feat_maps, aabb, iters, max_step, max_move)
+
     def decode_grid(self, feat_maps, reso, aabb=None):
         """Cell-centred grid over aabb, colours clamped to [0,1] (decode_grid + decode_batch, model.py:319-349)."""
         lib = self.prepare(feat_maps)

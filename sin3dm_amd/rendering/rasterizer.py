@@ -149,7 +149,8 @@ def eye_of(matrix):
 SHADINGS = ("flat", "smooth", "pbr", "pbr_flat")
 
 
-def _render_views_pbr(v, t, uvs, face_mat, materials, vertex_colors, views, W, H, ss, return_buffers, timer, shading, passes, lights, ambient):
+def _render_views_pbr(v, t, uvs, face_mat, materials, vertex_colors, views, W, H, ss, return_buffers, timer, shading, passes, lights, ambient,
+                      normals=None):
     """render_views with the light model of s3d_render_pbr.hip: one raster stage per view, one shade launch per pass."""
     from . import pbr
     lib = _lib.load()
@@ -189,7 +190,12 @@ def _render_views_pbr(v, t, uvs, face_mat, materials, vertex_colors, views, W, H
             table, kd, images, img_bytes = pack_materials(materials, dev)
             n_mats = table.shape[0]
     if shading in ("smooth", "pbr"):
-        nrm = vertex_normals(v, t)
+        if normals is not None:
+            nrm = normals.to(dev).contiguous().float().reshape(-1, 3)
+            if nrm.shape[0] != V:
+                raise ValueError(f"render_views: {nrm.shape[0]} normals for {V} vertices")
+        else:
+            nrm = vertex_normals(v, t)
     out = {n: torch.empty((len(views), H, W, 4), device=dev, dtype=torch.uint8) for n in names}
     buffers = []
     for k, view in enumerate(views):
@@ -215,7 +221,7 @@ def _render_views_pbr(v, t, uvs, face_mat, materials, vertex_colors, views, W, H
 
 
 def render_views(verts, faces, *, uvs=None, face_mat=None, materials=None, vertex_colors=None, views=None, resolution=(512, 512),
-                 supersample=2, return_buffers=False, timer=None, shading="flat", passes=("shaded",), lights=None, ambient=None):
+                 supersample=2, return_buffers=False, timer=None, shading="flat", passes=("shaded",), lights=None, ambient=None, normals=None):
     """uint8 [n_views, H, W, 4] renders of a mesh given as device tensors: verts [V, 3], faces [F, 3].
     shading / passes / lights / ambient (a call without them is the flat shader of §22, bit for bit):
     shading "smooth": the same base colours under area-weighted vertex normals and the GGX light model (metallic 0, roughness
@@ -224,7 +230,8 @@ def render_views(verts, faces, *, uvs=None, face_mat=None, materials=None, verte
     vertex colours are the albedo, as for "smooth"; "flat" with any of the other three given: the light model on flat normals.
     passes: names of _lib.RENDER_PASSES; one pass returns the array, several a dict of arrays by name (the raster stage runs once per view either way).  lights:
     [n <= 4, 4] unit directions towards the light in the space of verts and intensities (None: pbr.three_light_rig());
-    ambient: scalar (None: _lib.RENDER_PBR_AMBIENT).
+    ambient: scalar (None: _lib.RENDER_PBR_AMBIENT).  normals [V, 3]: vertex normals that replace the area-weighted ones under
+    "smooth" and "pbr" (the field normals of decode_mesh(normals="field"), say); the flat shadings do not read them.
     Base colour: vertex_colors [V, 3] in [0, 1]; or materials (dicts with Kd and image, see pack_materials) with face_mat [F]
     (None: material 0) and per-corner uvs [F, 3, 2]; or white.  views: camera.View objects (None: the reference's eight views of
     the mesh normalised by its bounding box, camera.standard_views).  resolution: (W, H).  Alpha is the covered share of a pixel.
@@ -251,7 +258,7 @@ def render_views(verts, faces, *, uvs=None, face_mat=None, materials=None, verte
         raise ValueError(f"render_views: shading {shading!r} (of {SHADINGS})")
     if shading != "flat" or tuple(passes) != ("shaded",) or isinstance(passes, str) or lights is not None or ambient is not None:
         return _render_views_pbr(v, t, uvs, face_mat, materials, vertex_colors, views, W, H, ss, return_buffers, timer, shading, passes, lights,
-                                 ambient)
+                                 ambient, normals)
     vcol = uv = fm = None
     table = kd = images = None
     n_mats = img_bytes = 0

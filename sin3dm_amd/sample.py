@@ -16,6 +16,8 @@ S3D_DECIMATE=quadric beside it decimates by quadric-error edge collapse instead 
 An experiment of --data_type sdfpbr writes object.obj + object.mtl + textures/{albedo,metallic,roughness,normal}.png (or a
 metallic-roughness object.glb) there, one of --data_type sdf writes sdfgrid_r<reso>.npz + mesh_r<reso>_simple.obj; in the default mode
 they write object.obj coloured by the albedo / without colours.  The data type comes from EXP/encoding/args.json.
+S3D_MESH_REFINE=K (default 0) projects the exported vertices onto the decoded zero level set in K Newton steps, and
+S3D_MESH_NORMALS=field writes the field's unit normals into the mesh files; edit.py reads both as well.
 S3D_RENDER=views beside any of these also writes renderings/000.png ... 007.png into every sample folder that gets a mesh: the
 reference's eight views, drawn on the device from the arrays the export holds (sin3dm_amd/rendering).
 S3D_RENDER_SHADING=smooth or pbr beside it draws them with smooth normals and the three-light GGX model of DESIGN.md §24 (pbr: the
@@ -71,6 +73,28 @@ def render_mode(mode=None):
     return name
 
 
+def mesh_refine(value=None):
+    """K >= 0 (default 0): Newton steps of the exported mesh's vertices onto the decoded zero level set (decode_mesh /
+    decode_texmesh refine=K).  value=None reads the environment variable S3D_MESH_REFINE."""
+    raw = value if value is not None else (os.environ.get("S3D_MESH_REFINE") or "0")
+    try:
+        k = int(raw)
+    except (TypeError, ValueError):
+        k = -1
+    if k < 0:
+        raise ValueError(f"mesh refine {raw!r}: expected a number of steps >= 0")
+    return k
+
+
+def mesh_normals(mode=None):
+    """"" (the default: no normals in the mesh files) or "field": the decoded field's unit gradient at every vertex, written as
+    `vn` lines or the GLB's NORMAL (normals="field").  mode=None reads the environment variable S3D_MESH_NORMALS."""
+    name = mode if mode is not None else (os.environ.get("S3D_MESH_NORMALS") or "")
+    if name not in ("", "field"):
+        raise ValueError(f"mesh normals {name!r}: expected 'field' (or unset)")
+    return name
+
+
 def render_shading(mode=None):
     """"" (the default: the flat shader the views always had), "flat", "smooth" or "pbr": the shading of the S3D_RENDER=views
     renders (rendering/rasterizer.render_views).  mode=None reads the environment variable S3D_RENDER_SHADING."""
@@ -83,7 +107,9 @@ def render_shading(mode=None):
 def render_sample(save_dir, mesh, shading=None):
     """renderings/ beside a decoded mesh.  mesh: what decode_mesh (verts, tris, colours) or decode_texmesh (a dict, or None for an
     empty iso-surface) returned.  shading: see render_shading; with "pbr" the 8-channel bake of an sdfpbr sample is used as it
-    lies on the device (albedo [..., :3], metallic [..., 3], roughness [..., 4], normal [..., 5:]).  Returns the paths written."""
+    lies on the device (albedo [..., :3], metallic [..., 3], roughness [..., 4], normal [..., 5:]).  Field normals in the mesh (a
+    dict's "normals", a fourth tuple entry) are passed on to render_views, which uses them under "smooth" and "pbr".  Returns the
+    paths written."""
     from .rendering.rasterizer import render_views
     from .rendering.render_multiview import write_views
     shading = render_shading(shading)
@@ -91,6 +117,7 @@ def render_sample(save_dir, mesh, shading=None):
         return []
     if isinstance(mesh, dict):
         verts, tris, kw = mesh["verts"], mesh["tris"], {}
+        vn = mesh.get("normals")
         if mesh.get("image") is not None and shading == "pbr" and mesh["image"].shape[-1] == 8:
             img = mesh["image"].flip(0)                         # (texel row 0 first: see below)
             kw = dict(uvs=mesh["uvs"].reshape(-1, 3, 2), materials=[{"Kd": (1.0, 1.0, 1.0), "image": img[..., :3], "metallic_image": img[..., 3],
@@ -99,13 +126,16 @@ def render_sample(save_dir, mesh, shading=None):
             # the baked image has texel row 0 first, which the PNG shows as its bottom row: the rasteriser reads top row first
             kw = dict(uvs=mesh["uvs"].reshape(-1, 3, 2), materials=[{"Kd": (1.0, 1.0, 1.0), "image": mesh["image"][..., :3].flip(0)}])
     else:
-        verts, tris, cols = mesh
+        verts, tris, cols = mesh[:3]
+        vn = mesh[3] if len(mesh) > 3 else None
         coloured = cols is not None and cols.dim() == 2 and cols.shape[1] >= 3           # (an sdf experiment decodes no colour)
         kw = dict(vertex_colors=cols[:, :3].clamp(0, 1)) if coloured else {}
     if tris.shape[0] == 0:
         return []
     if shading not in ("", "flat"):                             # (unset: the call stays the one it always was)
         kw["shading"] = shading
+        if vn is not None:
+            kw["normals"] = vn
     images = render_views(verts, tris, **kw)
     return write_views(images.cpu().numpy(), os.path.join(save_dir, "renderings"))
 
@@ -196,6 +226,11 @@ def decode(args, paths):
     textured = mesh_mode() == "textured"
     # only a choice other than the default is passed on: the default call is the one it always was
     decimate = {"decimation": "quadric"} if decimation_mode() == "quadric" else {}
+    field = {}
+    if mesh_refine():
+        field["refine"] = mesh_refine()
+    if mesh_normals():
+        field["normals"] = mesh_normals()
     ae = ShapeAutoEncoder(encoding_log_dir(args.tag), args, device=dist_util.dev())
     ae.load_ckpt("final")
     views = render_mode() == "views"
@@ -207,10 +242,10 @@ def decode(args, paths):
             continue
         if textured:
             mesh = ae.decode_texmesh(os.path.dirname(path), fm, args.reso, n_faces=args.n_faces, texture_reso=args.texreso,
-                                     mtl_path=find_copy_mtl(args), file_format=args.file_format, **decimate)
+                                     mtl_path=find_copy_mtl(args), file_format=args.file_format, **decimate, **field)
         else:
             # iso-surface on the device, vertex-coloured object.obj
-            mesh = ae.decode_mesh(os.path.dirname(path), fm, args.reso)
+            mesh = ae.decode_mesh(os.path.dirname(path), fm, args.reso, **field, **({"return_normals": True} if "normals" in field else {}))
         if views:
             render_sample(os.path.dirname(path), mesh, shading)
 
