@@ -74,6 +74,7 @@ struct SmallOuter {
     float* ws;                      // small_outer_ws_floats(S, C)
     int H, W, D, C, B;
 };
+constexpr int kSmallMaxS = 12;     // the widest composed map: k_small_outer's register arrays; s3d_unet_train_attach refuses more
 size_t small_outer_ws_floats(int S, int C);
 int launch_small_outer(const SmallOuter& s, hipStream_t st);
 

@@ -1060,7 +1060,7 @@ int launch_gn_act_bwd(const GnActBwd& s, hipStream_t st) {
 //   optional dv[px][c] = sum_o Wt[p][o][c]*s[px][o]                                      (out.2's dgrad)
 // Two-stage: per-chunk partials (a thread owns a float4 of channels and every pl-th pixel of the chunk; the pixel
 // lanes are added through LDS in lane order), then k_small_reduce adds the chunks in order.
-constexpr int kSmallChunks = 256, kSmallMaxS = 12;
+constexpr int kSmallChunks = 256;                // (kSmallMaxS: s3d_bwd.h)
 struct SmallArgs {
     const float* s;                 // composed [B][S][H+D][W+D]
     const float* v[3];              // NHWC [B][h][w][C]

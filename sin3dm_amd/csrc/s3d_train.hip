@@ -444,6 +444,10 @@ int s3d_unet_train_attach(s3d_unet* m, float* params, int64_t numel) {
     S3D_CHECK(numel == s3d_unet_param_numel(m), S3D_ERR_INVALID, "train_attach: %lld floats given, the model has %lld",
               (long long)numel, (long long)s3d_unet_param_numel(m));
     S3D_CHECK(m->cfg.model_channels * 2 * m->cfg.channel_mult[0] <= 1024, S3D_ERR_UNSUPPORTED, "training: model too wide");
+    // launch_small_outer would refuse the width from the middle of the first backward pass (the measuring pass launches nothing)
+    const int wide = std::max(m->cfg.in_channels, m->cfg.out_channels);
+    S3D_CHECK(wide <= kSmallMaxS, S3D_ERR_UNSUPPORTED,
+              "training supports in/out_channels <= %d (the Sin3DM triplane feature width), got %d", kSmallMaxS, wide);
     m->flat_off.resize(m->specs.size());
     m->flat_index.clear();
     size_t off = 0;

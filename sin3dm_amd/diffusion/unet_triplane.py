@@ -209,12 +209,13 @@ class _TriplaneUNetBase(nn.Module):
             for name, off, numel, shp in layout:
                 p = params[name]
                 assert tuple(p.shape) == shp, (name, tuple(p.shape), shp)
-                view = flat[off:off + numel].view(shp)
-                view.copy_(p.detach().to(dev, th.float32))
-                p.data = view
+                flat[off:off + numel].view(shp).copy_(p.detach().to(dev, th.float32))
         with th.cuda.device(dev):
+            # (a refused attach, e.g. a width the training kernels do not take, leaves the parameters and the handle as they were)
             _lib.check(lib.s3d_unet_train_attach(self._handle, _lib.ptr(flat), total))
             _lib.check(lib.s3d_unet_repack(self._handle, _lib.stream_ptr()))
+        for name, off, numel, shp in layout:
+            params[name].data = flat[off:off + numel].view(shp)
         self._flat, self._flat_layout = flat, layout
         self._plist = None
         named = dict(self.named_parameters())

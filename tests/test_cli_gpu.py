@@ -85,6 +85,35 @@ def test_train_cli_then_sample(tmp_path):
     assert torch.isfinite(y).all()
 
 
+def test_train_cli_then_sample_sdf(tmp_path):
+    """--data_type sdf: the diffusion stage on a geometry-only encoding (a 4-channel feat.npz; parser_util.train_args sets
+    in_channels = out_channels = fdim_geo), then sample.py --vox from the checkpoint it wrote."""
+    from test_pbr_gpu import make_experiment as make_typed_experiment
+    from sin3dm_amd import sample, train
+    from sin3dm_amd.utils import parser_util as pu
+    hwd = (12, 16, 10)
+    enc = make_typed_experiment(str(tmp_path / "src"), "sdf", "skip", hwd=hwd, mc=32)
+    assert np.load(pu.encoding_feat_path(enc))["feat_xy"].shape == (4, 12, 16)
+    tag = str(tmp_path / "run")
+    train.main(["--tag", tag, "--enc_log", pu.encoding_log_dir(enc), "--model_channels", "32", "--diff_batch_size", "2",
+                "--diff_n_iters", "6", "--save_interval", "3", "--log_interval", "2", "--ema_rate", "0.9"], confirm=lambda _: "y")
+    ddir = pu.diffusion_log_dir(tag)
+    sd = torch.load(os.path.join(ddir, "ema_0.9_000006.pt"))
+    assert {k: tuple(v.shape) for k, v in sd.items()} == dict(T.unet_param_shapes(in_channels=4, model_channels=32, out_channels=4))
+    assert tuple(sd["in_conv.0.conv_xy.weight"].shape) == (32, 4, 1, 1) and tuple(sd["out.2.conv_yz.weight"].shape) == (4, 32, 1, 1)
+    assert all(torch.isfinite(v).all() for v in sd.values())
+    dargs = json.load(open(os.path.join(ddir, "args.json")))
+    assert (dargs["in_channels"], dargs["out_channels"]) == (4, 4), dargs
+    logs = [json.loads(l) for l in open(os.path.join(ddir, "progress.jsonl"))]
+    losses = [l["loss"] for l in logs if "loss" in l]
+    assert losses and all(np.isfinite(v) and v > 0 for v in losses), logs
+    paths = sample.main(["--tag", tag, "--n_samples", "1", "--use_ddim", "True", "--timestep_respacing", "5", "--vox", "--reso", "32"])
+    d = np.load(paths[0])
+    assert d["feat_xy"].shape == (4, 12, 16) and d["feat_xz"].shape == (4, 12, 10) and d["feat_yz"].shape == (4, 16, 10)
+    assert all(np.isfinite(d[k]).all() for k in d.files)
+    assert os.path.exists(os.path.join(os.path.dirname(paths[0]), "r32_voxel.npz"))
+
+
 def test_train_cli_autoencoder_stage(tmp_path):
     """train.py --only_enc on a synthetic preprocessed shape: writes the encoding/ folder sample.py and the diffusion
     stage read (args.json, feat.npz, ckpt_final.pth)."""

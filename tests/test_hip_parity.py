@@ -26,11 +26,11 @@ def cu(a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev())
 
 
-def make_model(mc, raw=False, ssn=True, cm=(1, 2)):
+def make_model(mc, raw=False, ssn=True, cm=(1, 2), ch=12):
     from sin3dm_amd.diffusion.unet_triplane import TriplaneUNetModelSmall, TriplaneUNetModelSmallRaw
     cls = TriplaneUNetModelSmallRaw if raw else TriplaneUNetModelSmall
-    m = cls(12, mc, 12, channel_mult=cm, use_scale_shift_norm=ssn)
-    m.load_state_dict(T.synthetic_state_dict(T.unet_param_shapes(model_channels=mc, rollout=not raw,
+    m = cls(ch, mc, ch, channel_mult=cm, use_scale_shift_norm=ssn)
+    m.load_state_dict(T.synthetic_state_dict(T.unet_param_shapes(in_channels=ch, model_channels=mc, out_channels=ch, rollout=not raw,
                                                                  use_scale_shift_norm=ssn, channel_mult=cm), 0))
     return m.to(dev()).eval()
 
@@ -403,20 +403,24 @@ def test_trajectories_branches_golden(tag, px, resp, ddim, clip):
         assert np.abs(ref_corner).max() > 0.5 and relerr(corner, ref_corner) < 2e-4
 
 
-@pytest.mark.parametrize("mc,B", [(32, 2), (64, 1), (64, 2)])
-def test_fused_denoise_step_equals_forward_plus_sampler_kernel(mc, B):
+# (the latent width C: 12, or fdim_geo = 4 for --data_type sdf; the pixel-chunk head and the LDS in_conv take C <= 16)
+@pytest.mark.parametrize("mc,B,C", [pytest.param(32, 2, 12, id="32-2"), pytest.param(64, 1, 12, id="64-1"), pytest.param(64, 2, 12, id="64-2"),
+                                    (64, 1, 4), (64, 2, 16), (64, 1, 1), (64, 1, 20), (32, 2, 4), (128, 1, 8)])
+def test_fused_denoise_step_equals_forward_plus_sampler_kernel(mc, B, C):
     """The sampling loops' step (s3d_unet_step_film: ONE library call; SURVEY section 2b K8 + K9) against the single-step API
     (forward, then s3d_sampler_step), bit for bit: DDPM, DDIM with eta, the in-painting branch, EPSILON and unclipped, t = 0
     included.  mc = 64, batch 1: the pixel-chunk output head applies the update in its own launch and the model output is never
     stored; batch 2: the same head writes to the workspace and the sampler kernel follows (bandwidth-bound regime); mc = 32: the
-    generic head.  And the loops draw their eps ahead from the device generator."""
+    generic head.  Widths other than 12: 4, 1, 8 and 16 in the pixel-chunk head (its weight staging, its `co < Cout` masks and its
+    corner count follow the width); at 20 and at mc = 32 the generic head and the sampler kernel run either way and the equality is
+    trivial.  And the loops draw their eps ahead from the device generator (width 12, and the first of the other widths)."""
     from sin3dm_amd import _lib
     from sin3dm_amd.diffusion.gaussian_diffusion import HostTimesteps
     from sin3dm_amd.diffusion.script_util import create_gaussian_diffusion
     H, W, D = 12, 9, 7
     kw = dict(H=H, W=W, D=D)
-    model = make_model(mc)
-    shape = (B, 12, H + D, W + D)
+    model = make_model(mc, ch=C)
+    shape = (B, C, H + D, W + D)
     x, eps = cu(T.synthetic_noise(shape, 91)), cu(T.synthetic_noise(shape, 92))
     y0 = cu(T.synthetic_noise(shape, 93))
     mask = (cu(T.synthetic_noise(shape, 94)) > 0).float()
@@ -431,7 +435,9 @@ def test_fused_denoise_step_equals_forward_plus_sampler_kernel(mc, B):
                     with torch.no_grad():
                         a = diff._step(mode, model, x, ht, clip, None, kw, fuse=False, noise=eps, **extra)
                         b = diff._step(mode, model, x, ht, clip, None, kw, fuse=True, noise=eps, **extra)
-                    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), (mc, B, px, ti, mode, extra.keys(), clip)
+                    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), (mc, B, C, px, ti, mode, extra.keys(), clip)
+    if C != 12 and (mc, B, C) != (64, 1, 4):
+        return
     # device-generator loops: reproducible under a seed, finite, corner at zero
     diff = create_gaussian_diffusion(steps=1000, noise_schedule="linear", predict_xstart=True, timestep_respacing="10")
     outs = []
@@ -445,8 +451,11 @@ def test_fused_denoise_step_equals_forward_plus_sampler_kernel(mc, B):
     assert torch.isfinite(z).all() and float(z[..., H:, W:].abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("mc,B,hwd,ddim", [(64, 1, (40, 24, 56), False), (64, 2, (12, 9, 7), True), (128, 1, (64, 48, 32), False), (32, 2, (10, 14, 6), False)])
-def test_next_steps_in_conv_carried_by_the_output_head_is_the_same_bits(mc, B, hwd, ddim):
+@pytest.mark.parametrize("mc,B,hwd,ddim,C", [pytest.param(64, 1, (40, 24, 56), False, 12, id="64-1-hwd0-False"), pytest.param(64, 2, (12, 9, 7), True, 12, id="64-2-hwd1-True"),
+                                             pytest.param(128, 1, (64, 48, 32), False, 12, id="128-1-hwd2-False"), pytest.param(32, 2, (10, 14, 6), False, 12, id="32-2-hwd3-False"),
+                                             (64, 2, (12, 9, 7), True, 4), (128, 1, (12, 9, 7), False, 16), (64, 1, (12, 9, 7), False, 1),
+                                             (64, 1, (12, 9, 7), False, 8), (64, 1, (12, 9, 7), False, 20)])
+def test_next_steps_in_conv_carried_by_the_output_head_is_the_same_bits(mc, B, hwd, ddim, C):
     """in_conv is TriplaneConv(in, ch, 1, padding=0, is_rollout=False) (src/diffusion/unet_triplane.py:378, 482): a pointwise map of x_t
     with no timestep in it, and in a sampling loop x_t IS the previous step's sample (gaussian_diffusion.py:533-534).  The loops let the
     output head of step n also evaluate step n + 1's in_conv and its GroupNorm partial sums on the x_{t-1} it has just formed
@@ -454,17 +463,32 @@ def test_next_steps_in_conv_carried_by_the_output_head_is_the_same_bits(mc, B, h
     mapping.  Every step's sample and pred_xstart equal the loop that launches in_conv each step, bit for bit: ragged planes whose
     rows are not multiples of the head's 64-pixel or in_conv's 32-pixel segments, batch 2, DDPM and DDIM, the widths of the
     pixel-chunk head (64 / 128; at 32 channels the generic head takes the step and nothing is carried).  A consumer of the
-    progressive loop that edits out["sample"] in place switches the carry off for that step (version counter): still equal."""
+    progressive loop that edits out["sample"] in place switches the carry off for that step (version counter): still equal.
+    Latent widths C other than 12: the tail's weight registers (wA[ci < Cin]: input channels 0..7, wB[8 + ci < Cin]: 8..15) and its
+    staged x_{t-1} (sxn[e][co < Cin]) follow the width; 8 fills wA exactly, 16 both, 1 and 4 part of wA; at 20 nothing is carried
+    (out_head_can_carry: Cin == Cout <= 16).  That the carry was ASKED of every step but the last and OFFERED to every step but the
+    first is seen in the flags denoise_step receives; whether the library then skipped its in_conv launch cannot be seen from
+    Python (s3d_unet_profile brackets the convolution classes, and in_conv is none of them; tests/test_hip_handle_state.py)."""
+    from sin3dm_amd import _lib
     from sin3dm_amd.diffusion.script_util import create_gaussian_diffusion
     H, W, D = hwd
     kw = dict(H=H, W=W, D=D)
-    shape = (B, 12, H + D, W + D)
+    shape = (B, C, H + D, W + D)
     diff = create_gaussian_diffusion(steps=1000, noise_schedule="linear", predict_xstart=True, timestep_respacing="ddim6" if ddim else "6")
     loop = diff.ddim_sample_loop_progressive if ddim else diff.p_sample_loop_progressive
 
+    flags = []
+
     def run(carry, edit_at=None):
-        model = make_model(mc)
+        model = make_model(mc, ch=C)
         model.carries_in_conv = carry
+        step_fn = model.denoise_step
+        del flags[:]
+
+        def denoise_step(*a, carry=0, **k):
+            flags.append(carry)
+            return step_fn(*a, carry=carry, **k)
+        model.denoise_step = denoise_step
         torch.manual_seed(17)
         outs = []
         for n, out in enumerate(loop(model, shape, model_kwargs=kw)):
@@ -473,10 +497,14 @@ def test_next_steps_in_conv_carried_by_the_output_head_is_the_same_bits(mc, B, h
                 out["sample"].mul_(0.5)                    # the reference's loop continues from whatever the consumer left in out["sample"]
         return outs
 
-    a, b = run(False), run(True)
+    a = run(False)
+    assert flags == [0] * 6, flags
+    b = run(True)
+    O, I = _lib.CARRY_OUT, _lib.CARRY_IN
+    assert flags == [O] + [O | I] * 4 + [I], flags
     assert len(a) == 6
     for n, (x, y) in enumerate(zip(a, b)):
-        assert torch.equal(x[0], y[0]) and torch.equal(x[1], y[1]), (mc, B, hwd, ddim, n)
+        assert torch.equal(x[0], y[0]) and torch.equal(x[1], y[1]), (mc, B, hwd, ddim, C, n)
     assert torch.isfinite(a[-1][0]).all()
     a, b = run(False, edit_at=2), run(True, edit_at=2)
     for n, (x, y) in enumerate(zip(a, b)):

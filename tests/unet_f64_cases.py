@@ -24,10 +24,16 @@ ZERO_GRAD_REL = 1e-9                       # max|g64_k| < ZERO_GRAD_REL * G: a z
 EPS32 = 2.0 ** -23
 
 
-def _case(mc, hwd, B, t, cm=(1, 2), ssn=True, rollout=True, predict_xstart=True, w=None, refused=None):
+TRAIN_MAX_CH = 12                          # kSmallMaxS (s3d_bwd.h): s3d_unet_train_attach refuses a wider in/out_channels
+TRAIN_REFUSED = "in/out_channels <= 12"
+
+
+def _case(mc, hwd, B, t, cm=(1, 2), ssn=True, rollout=True, predict_xstart=True, w=None, refused=None, ch=12):
+    """ch: the latent width, in_channels = out_channels (fdim_geo for --data_type sdf, fdim_geo + fdim_tex otherwise).
+    refused: the message with which the library refuses the model's forward and training step; train_refused: the training step alone."""
     assert len(t) == B and (w is None or len(w) == B)
     return dict(mc=mc, hwd=hwd, B=B, t=tuple(t), cm=cm, ssn=ssn, rollout=rollout, predict_xstart=predict_xstart, w=w,
-                large_t=max(t) > 3, refused=refused)
+                large_t=max(t) > 3, refused=refused, ch=ch, train_refused=TRAIN_REFUSED if ch > TRAIN_MAX_CH else None)
 
 
 CASES = {
@@ -49,6 +55,19 @@ CASES = {
     "G3": _case(32, (12, 20, 8), 2, (1, 3), cm=(1, 2, 2)),
     "G4": _case(64, (9, 13, 7), 2, (1, 3), cm=(1, 2, 2)),
     "H": _case(64, (9, 13, 7), 3, (3, 0, 1), predict_xstart=False, w=(1.0, 0.25, 2.0)),
+    # Latent widths other than 12 (parser_util.train_args: fdim_geo for --data_type sdf, both options of the command line).  The
+    # inference side changes form at 16 | 17 (k_in_conv_lds: Cin <= 16 at 64 / 128 / 256 channels; k_out_head_px: Cout <= 16; the
+    # carried in_conv: Cin == Cout <= 16), the training side refuses above 12 (TRAIN_MAX_CH).
+    "W4": _case(64, (9, 13, 7), 2, (1, 3), ch=4),                         # the sdf width: LDS in_conv, pixel-chunk head
+    "W4n": _case(32, (9, 13, 7), 2, (1, 3), ch=4),                        # width 4 in k_in_conv / k_out_head
+    "W4w": _case(128, (9, 12, 5), 1, (2,), ch=4),
+    "W4e": _case(64, (9, 13, 7), 3, (3, 0, 1), predict_xstart=False, w=(1.0, 0.25, 2.0), ch=4),
+    "W1": _case(64, (9, 13, 7), 2, (1, 3), ch=1),
+    "W8": _case(64, (17, 33, 9), 1, (2,), ch=8),                          # the head's first weight-register half exactly, none of the second
+    "W11": _case(128, (9, 12, 5), 2, (0, 3), ch=11),                      # an odd width just under the training limit
+    "W16": _case(64, (9, 13, 7), 2, (1, 3), ch=16),                       # the last width of the fast forms; training refused
+    "W20": _case(64, (9, 13, 7), 2, (1, 3), ch=20),                       # k_in_conv / k_out_head + k_sampler at 64 channels
+    "W20n": _case(32, (9, 13, 7), 2, (1, 3), ch=20),
 }
 
 # What the float32 port must stay under on every case (conditions on the inputs, about twice its worst error over the cases as
@@ -72,7 +91,7 @@ def _port_modules():
 
 def param_shapes(case):
     c = CASES[case]
-    return T.unet_param_shapes(model_channels=c["mc"], rollout=c["rollout"], use_scale_shift_norm=c["ssn"], channel_mult=c["cm"])
+    return T.unet_param_shapes(in_channels=c["ch"], model_channels=c["mc"], out_channels=c["ch"], rollout=c["rollout"], use_scale_shift_norm=c["ssn"], channel_mult=c["cm"])
 
 
 def state_dict(case):
@@ -84,7 +103,7 @@ def inputs(case):
     import torch
     c = CASES[case]
     H, W, D = c["hwd"]
-    shape = (c["B"], 12, H + D, W + D)
+    shape = (c["B"], c["ch"], H + D, W + D)
     x0 = torch.from_numpy(T.synthetic_noise(shape, X0_SEED)).clamp(-1, 1)
     noise = torch.from_numpy(T.synthetic_noise(shape, NOISE_SEED))
     w = torch.tensor(c["w"] if c["w"] is not None else [1.0] * c["B"], dtype=torch.float32)
@@ -131,16 +150,21 @@ def planes(c, H, W, D):
     return c[..., :H, :W], c[..., :H, W:], c[..., H:, :W]
 
 
-def forward_error(y, y64, hwd):
+def forward_error(y, y64, hwd, zero_corner=True):
     """(worst, (sample, plane)): max|y - y64| / max|y64| over each plane of each sample, the worst of them and where it is.
-    The padding corner y[..., H:, W:] must be exactly zero."""
+    The padding corner y[..., H:, W:] must be exactly zero; with zero_corner=False (a sampler step's x_{t-1}, whose corner is the
+    update of a model output of 0) it is a fourth region, "corner", compared like the planes."""
     H, W, D = hwd
     y, y64 = np.asarray(y, np.float64), np.asarray(y64, np.float64)
     assert y.shape == y64.shape, (y.shape, y64.shape)
-    assert not np.any(y[..., H:, W:]), "the padding corner of the output is not zero"
+    if zero_corner:
+        assert not np.any(y[..., H:, W:]), "the padding corner of the output is not zero"
     worst = (-1.0, None)
     for b in range(y.shape[0]):
-        for name, a, r in zip(PLANE_NAMES, planes(y[b], H, W, D), planes(y64[b], H, W, D)):
+        regions = list(zip(PLANE_NAMES, planes(y[b], H, W, D), planes(y64[b], H, W, D)))
+        if not zero_corner:
+            regions.append(("corner", y[b][..., H:, W:], y64[b][..., H:, W:]))
+        for name, a, r in regions:
             worst = max(worst, (float(np.max(np.abs(a - r)) / np.max(np.abs(r))), (b, name)))
     return worst
 
@@ -196,7 +220,7 @@ def device_model(case):
     from sin3dm_amd.diffusion.unet_triplane import TriplaneUNetModelSmall, TriplaneUNetModelSmallRaw
     c = CASES[case]
     cls = TriplaneUNetModelSmall if c["rollout"] else TriplaneUNetModelSmallRaw
-    m = cls(12, c["mc"], 12, channel_mult=c["cm"], use_scale_shift_norm=c["ssn"])
+    m = cls(c["ch"], c["mc"], c["ch"], channel_mult=c["cm"], use_scale_shift_norm=c["ssn"])
     m.load_state_dict(state_dict(case))
     return m.to(torch.device("cuda:0"))
 
@@ -280,14 +304,88 @@ def device_errors(case, y=None, step=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------------ one sampler step
+# One fused denoising step at the case's timesteps on the float32 port's x_t, eps = T.synthetic_noise(.., STEP_EPS_SEED): the DDPM
+# update and the DDIM update with eta = 0 (gaussian_diffusion.py:396-440, 538-600; x0 prediction, clipped, no respacing).
+STEP_EPS_SEED = 402
+STEP_MODES = ("ddpm", "ddim")
+STEP_CASES = ("W4", "W1", "W16", "W20")
+
+
+def step_eps(case):
+    return T.synthetic_noise(port(case, False)["x_t"].shape, STEP_EPS_SEED)
+
+
+@functools.lru_cache(maxsize=None)
+def step_reference(case):
+    """{mode: {"f64": (sample, pred_xstart), "f32": (sample, pred_xstart)}}.  f64: the port's forward in float64 on the float32 x_t
+    promoted, then the update in float64 from the float64 tables; f32: the float32 port's forward, then the C oracle's updates."""
+    import torch
+    orc, tp = _port_modules()
+    c = CASES[case]
+    assert c["predict_xstart"] and min(c["t"]) > 0
+    H, W, D = c["hwd"]
+    p32 = port(case, False)
+    x, eps = p32["x_t"].copy(), step_eps(case)
+    tab, _ = orc.schedule_tables()
+    sd = {k: v.double() for k, v in state_dict(case).items()}
+    n = torch.get_num_threads()
+    torch.set_num_threads(min(16, n))
+    try:
+        with torch.no_grad():
+            y64 = tp.unet_forward(sd, torch.from_numpy(x).double(), torch.tensor(c["t"], dtype=torch.float64), H, W, D,
+                                  model_channels=c["mc"], channel_mult=c["cm"], use_scale_shift_norm=c["ssn"], rollout=c["rollout"])
+    finally:
+        torch.set_num_threads(n)
+    out = {m: {"f64": ([], []), "f32": ([], [])} for m in STEP_MODES}
+    for b, t in enumerate(c["t"]):
+        xb, eb = torch.from_numpy(x[b]).double(), torch.from_numpy(eps[b]).double()
+        s, p = tp.p_sample_update(y64[b], xb, eb, tab, t)
+        out["ddpm"]["f64"][0].append(s.numpy()), out["ddpm"]["f64"][1].append(p.numpy())
+        # DDIM, eta = 0 (:538-600): eps from the clipped x0, then the deterministic step to alphas_cumprod_prev
+        e = (float(tab[3][t]) * xb - p) / float(tab[4][t])
+        s = p * float(np.sqrt(tab[2][t])) + float(np.sqrt(1.0 - tab[2][t])) * e
+        out["ddim"]["f64"][0].append(s.numpy()), out["ddim"]["f64"][1].append(p.numpy())
+        for m, fn in (("ddpm", orc.p_sample_update), ("ddim", orc.ddim_update)):
+            s, p = fn(p32["y"][b], x[b], eps[b], tab, t)
+            out[m]["f32"][0].append(s), out[m]["f32"][1].append(p)
+    return {m: {k: tuple(np.stack(a) for a in v) for k, v in d.items()} for m, d in out.items()}
+
+
+def step_errors(case, mode, sample, pred):
+    """(sample, pred_xstart) errors against the float64 step: forward_error's measure; x_{t-1}'s corner is a region of its own
+    and pred_xstart's is exactly zero."""
+    s64, p64 = step_reference(case)[mode]["f64"]
+    hwd = CASES[case]["hwd"]
+    return forward_error(sample, s64, hwd, zero_corner=False), forward_error(pred, p64, hwd)
+
+
+def device_fused_step(case, mode):
+    """One fused step (the sampling loops' one-call form) of a fresh model: (sample, pred_xstart) as numpy arrays."""
+    import torch
+    from sin3dm_amd import _lib
+    from sin3dm_amd.diffusion.gaussian_diffusion import HostTimesteps
+    c = CASES[case]
+    H, W, D = c["hwd"]
+    dev = torch.device("cuda:0")
+    m = device_model(case).eval()
+    x = torch.from_numpy(port(case, False)["x_t"].copy()).to(dev)
+    eps = torch.from_numpy(step_eps(case)).to(dev)
+    t = HostTimesteps(torch.tensor(c["t"], dtype=torch.int64, device=dev), c["t"])
+    with torch.no_grad():
+        s, p, _ = device_diffusion(case)._step(_lib.STEP_DDPM if mode == "ddpm" else _lib.STEP_DDIM, m, x, t, True, None,
+                                               dict(H=H, W=W, D=D), eta=0.0, fuse=True, noise=eps)
+    return s.cpu().numpy(), p.cpu().numpy()
+
+
 # ------------------------------------------------------------------------------------------------------------ kernel forms
 # Forms the library takes by launch size or by option (include/sin3dm_hip.h: s3d_set_option), forced so that they run at test
 # sizes.  CONV_IMPL=naive is the control: one thread per output, plain summation order.
 FORWARD_FORMS = (("WINO", 0), ("WINO", 4), ("WINO24W", 1), ("VCAT", 0), ("GN_FUSED", 0), ("CONV1X1_T", 1), ("RANK1_BATCH", 0),
                  ("RANK1_SLICES", 0), ("CONV_IMPL", "naive"))
-FORWARD_FORM_CASES = ("A", "B", "Be", "C", "D")
+FORWARD_FORM_CASES = ("A", "B", "Be", "C", "D", "W4", "W16")
 TRAINING_FORMS = (("WGRAD_WINO", 0), ("GNB_FUSED", 0), ("BWD_SIDE", 0), ("EDGE_SIGNAL", 0), ("WINO", 4))
-TRAINING_FORM_CASES = ("A", "B", "D", "H")
+TRAINING_FORM_CASES = ("A", "B", "D", "H", "W4")
 
 # How a forced form shows that it ran.  By name: (launch class, a string the library's kernel names must hold, strings they must
 # not hold).  By result: the cases on which the form's summation order differs from the default's, so the output bits must.

@@ -7,7 +7,10 @@ metrics; tests/test_hip_unet_f64.py asserts bounds chosen from this table).
     python tools/unet_f64_report.py --cases A B --forms default WINO=4
 
 Columns: error of the device / of the float32 port / their ratio (the port's error floored at 2^-23), for the forward (worst
-plane of any sample), the loss terms, the worst gradient tensor E_k (with its name) and the zero-gradient noise Z_k; for a forced form, how it showed that it ran."""
+plane of any sample), the loss terms, the worst gradient tensor E_k (with its name) and the zero-gradient noise Z_k; for a forced form, how it showed that it ran.
+A case whose width the training kernels do not take (U.CASES[..]["train_refused"]) has its forward columns and the library's
+refusal of the step.  Then one fused sampler step per width (U.STEP_CASES; tests/test_hip_unet_widths.py): x_{t-1} and pred_xstart
+of the DDPM and the DDIM update against float64, device / float32 port and oracle / ratio."""
 import argparse
 import os
 import sys
@@ -24,7 +27,7 @@ def _cell(dev, prt, rat, key):
 
 def line(case, form, dev, prt):
     rat = U.ratios(dev, prt)
-    return (f"{case:<4}{form:<18}| {_cell(dev, prt, rat, 'fwd')} | {_cell(dev, prt, rat, 'loss')} | {_cell(dev, prt, rat, 'grad')} "
+    return (f"{case:<5}{form:<18}| {_cell(dev, prt, rat, 'fwd')} | {_cell(dev, prt, rat, 'loss')} | {_cell(dev, prt, rat, 'grad')} "
             f"{dev.get('grad_name', '-'):<48} | {_cell(dev, prt, rat, 'zero')}" + (f" | {dev['ran']}" if "ran" in dev else ""))
 
 
@@ -59,10 +62,36 @@ def refusal(case):
     raise AssertionError(f"case {case} ran; the library should refuse it ({U.CASES[case]['refused']})")
 
 
+def train_refusal(case):
+    """What the library answers to a training step at a width it does not train."""
+    try:
+        U.device_step(case)
+    except NotImplementedError as e:
+        assert U.CASES[case]["train_refused"] in str(e), e
+        return f"step refused: {e}"
+    raise AssertionError(f"case {case} trained; the library should refuse the step ({U.CASES[case]['train_refused']})")
+
+
+def step_lines(cases):
+    print("# one fused sampler step  | x_{t-1}: device port32 ratio, where            | pred_xstart: device port32 ratio, where")
+    worst = (0.0, "")
+    for case in cases:
+        for mode in U.STEP_MODES:
+            dev = U.step_errors(case, mode, *U.device_fused_step(case, mode))
+            prt = U.step_errors(case, mode, *U.step_reference(case)[mode]["f32"])
+            cells = []
+            for d, p in zip(dev, prt):
+                r = d[0] / max(p[0], U.EPS32)
+                worst = max(worst, (r, f"{case} {mode}"))
+                cells.append(f"{d[0]:.2e} {p[0]:.2e} {r:6.2f} {str(d[1]):<14}")
+            print(f"{case:<5}{mode:<18}| " + " | ".join(cells), flush=True)
+    print(f"# worst ratio, fused step: {worst[0]:.2f} ({worst[1]})")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--cases", nargs="*", default=list(U.CASES))
-    ap.add_argument("--forms", nargs="*", default=None, help="default, autograd, or NAME=VALUE; all of them when not given")
+    ap.add_argument("--forms", nargs="*", default=None, help="default, autograd, step (the fused sampler step) or NAME=VALUE; all of them when not given")
     a = ap.parse_args()
     print(f"# {'case form':<21}| forward: device port32 ratio | loss: device port32 ratio   | worst E_k: device port32 ratio, tensor"
           f"{'':<43} | Z_k: device port32 ratio")
@@ -78,15 +107,18 @@ def main():
             if a.forms is not None and form.split()[0] not in a.forms:
                 continue
             if U.CASES[case]["refused"]:
-                print(f"{case:<4}{form:<18}| {refusal(case)}", flush=True)
+                print(f"{case:<5}{form:<18}| {refusal(case)}", flush=True)
                 continue
-            dev = run(case, n, v, fwd, trn, ag)
-            print(line(case, form, dev, prt), flush=True)
+            refused = U.CASES[case]["train_refused"] and trn
+            dev = run(case, n, v, fwd, trn and not refused, ag)
+            print(line(case, form, dev, prt) + (f" | {train_refusal(case)}" if refused else ""), flush=True)
             kind = "default forms" if n is None else "forced forms"
             for k, r in U.ratios(dev, prt).items():
                 worst[kind, k] = max(worst.get((kind, k), (0.0, "")), (r, f"{case} {form}"))
     for (kind, k), (r, where) in sorted(worst.items()):
         print(f"# worst ratio, {kind}, {k}: {r:.2f} ({where})")
+    if a.forms is None or "step" in a.forms:
+        step_lines([c for c in U.STEP_CASES if c in a.cases])
 
 
 if __name__ == "__main__":
