@@ -250,6 +250,37 @@ S3D_API int s3d_unet_step_film_known(s3d_unet* m, const float* film, int film_st
 S3D_API int s3d_sampler_renoise(const float* x_prev, const float* noise, const float* known_tables, const int64_t* t, int32_t T,
                        int64_t batch, int64_t per_sample, float* x_t, void* stream);
 
+/* Few-step sampling: the DPM-Solver++ multistep update, data prediction, orders 1 and 2M (DESIGN.md section 26 — no counterpart in
+ * the reference, whose samplers are first order).  At schedule index i = t[b], with x0 formed as in s3d_sampler_step (the model output,
+ * or (sr * x_t) - (srm1 * model_out) for S3D_MEAN_EPSILON; clamped to [-1, 1] when clip_denoised):
+ *     s = (cx[i] * x_t) + (c0[i] * x0)
+ *     s = s + (c1[i] * x0_prev)                order == 2; x0_prev: the previous step's pred_xstart
+ *     s = s + (cn[i] * noise)                  noise != NULL (the SDE form)
+ *     sample = s;  pred_xstart = x0
+ * every product and sum its own fp32 round-to-nearest operation in this order.  `tables` is a device fp32 array [S3D_MTAB_ROWS][T] of
+ * float64 values cast to fp32 (GaussianDiffusion.multistep_tables: they depend on the spacing of the kept steps); the step's own
+ * `tables` serve sr / srm1 only.  `order` is 1 or 2, the same for the whole batch; with order == 1 x0_prev is not read and may be NULL.
+ * x0_prev may not alias pred_xstart (a loop alternates two buffers).  Of s3d_sampler_args, mean_type, clip_denoised, T, batch,
+ * per_sample, model_out, x, noise, t, tables, sample and pred_xstart are used; y0, mask and mean must be NULL and mode S3D_STEP_DDIM. */
+enum { S3D_MTAB_CX = 0, S3D_MTAB_C0, S3D_MTAB_C1, S3D_MTAB_CN, S3D_MTAB_ROWS };
+typedef struct {
+    const float* x0_prev;        /* [B, per_sample] the previous step's pred_xstart (order 2)        */
+    const float* tables;         /* [S3D_MTAB_ROWS][T] device fp32                                   */
+    int32_t order;               /* 1 or 2                                                           */
+} s3d_multistep;
+/* The stand-alone kernel; known != NULL: the known-region blend (s3d_known_region) follows the update, `sample` is stored once. */
+S3D_API int s3d_sampler_step_multistep(const s3d_sampler_args* a, const s3d_multistep* ms, const s3d_known_region* known /* may be NULL */,
+                       void* stream);
+/* s3d_unet_step_film_carry with the multistep update applied in the output head's launch (k_out_head_px_ms); with S3D_CARRY_OUT the
+ * next step's in_conv is evaluated on the sample just formed.  Identical bits to s3d_unet_forward_film followed by
+ * s3d_sampler_step_multistep.  The in-head form stores no model output: with model_out != NULL (and at widths the pixel-chunk head
+ * does not take) the step runs as output head + the stand-alone kernel, and S3D_CARRY_OUT then leaves nothing behind.
+ * The known-region blend is NOT fused into the head with this update (the known-region instantiations of the head already sit at the
+ * scalar-register limit): such a step is s3d_unet_forward_film (model output stored) followed by s3d_sampler_step_multistep with
+ * known != NULL, which is what the sampling loops do. */
+S3D_API int s3d_unet_step_film_multistep(s3d_unet* m, const float* film, int film_stride, int B, int H, int W, int D,
+                       const s3d_sampler_args* step, const s3d_multistep* ms, float* model_out, void* stream, int carry_flags);
+
 /* ------------------------------------------------------------------------------------------
  * Leaf operators, exported so the parity tests can pin each kernel to the reference op it replaces
  * (SURVEY.md §8c item 3).  Planes are NCHW device tensors xy[B,C,H,W], xz[B,C,H,D], yz[B,C,W,D].

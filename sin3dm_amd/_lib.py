@@ -17,6 +17,7 @@ c_i64p = C.POINTER(C.c_int64)
 ABI_VERSION = 13
 TAB_ROWS = ("sqrt_recip", "sqrt_recipm1", "coef1", "coef2", "logvar", "acp", "acp_prev")
 KTAB_ROWS = ("sqrt_acp_prev", "sqrt_1m_acp_prev", "sqrt_1m_beta", "sqrt_beta")     # s3d_known_region.tables (S3D_KTAB_*)
+MTAB_ROWS = ("cx", "c0", "c1", "cn")                                                # s3d_multistep.tables (S3D_MTAB_*)
 STEP_DDPM, STEP_DDIM, STEP_MEAN_ONLY = 0, 1, 2
 CARRY_OUT, CARRY_IN = 1, 2               # s3d_unet_step_film_carry flags (include/sin3dm_hip.h)
 MEAN_START_X, MEAN_EPSILON = 0, 1
@@ -49,6 +50,11 @@ class SamplerArgs(C.Structure):
 class KnownRegionArgs(C.Structure):
     """s3d_known_region: the known-region blend of a step (include/sin3dm_hip.h)."""
     _fields_ = [("y0", C.c_void_p), ("mask", C.c_void_p), ("noise", C.c_void_p), ("tables", C.c_void_p)]
+
+
+class MultistepArgs(C.Structure):
+    """s3d_multistep: the DPM-Solver++ multistep update of a step (include/sin3dm_hip.h)."""
+    _fields_ = [("x0_prev", C.c_void_p), ("tables", C.c_void_p), ("order", C.c_int32)]
 
 
 PROF_CLASSES = 4
@@ -102,6 +108,9 @@ SIGNATURES = {
     "s3d_sampler_step_known": (C.c_int, [C.POINTER(SamplerArgs), C.POINTER(KnownRegionArgs), C.c_void_p]),
     "s3d_unet_step_film_known": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                            C.POINTER(SamplerArgs), C.POINTER(KnownRegionArgs), C.c_void_p, C.c_void_p, C.c_int]),
+    "s3d_sampler_step_multistep": (C.c_int, [C.POINTER(SamplerArgs), C.POINTER(MultistepArgs), C.POINTER(KnownRegionArgs), C.c_void_p]),
+    "s3d_unet_step_film_multistep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.POINTER(SamplerArgs), C.POINTER(MultistepArgs), C.c_void_p, C.c_void_p, C.c_int]),
     "s3d_sampler_renoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p,
                                       C.c_void_p]),
     "s3d_op_triplane_conv": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int,

@@ -382,7 +382,8 @@ struct InConvCarry { const float* wT; const float* bias; float* out[3]; double* 
 int launch_out_head(const Tri& x, int B, GnStats stats, const ActArgs& a, const float* w /*[3][Cout][C]*/,
                     const float* bias /*[3][Cout]*/, int Cout, int H, int W, int D, float* out, hipStream_t st,
                     const s3d_sampler_args* fuse = nullptr, const GnPartials* part = nullptr, const InConvCarry* carry = nullptr,
-                    const s3d_known_region* known = nullptr);          // known: the step's known-region blend (fuse != null)
+                    const s3d_known_region* known = nullptr,           // known: the step's known-region blend (fuse != null)
+                    const s3d_multistep* ms = nullptr);                // ms: the step's update is the multistep one (fuse != null, no known region)
 bool out_head_can_carry(int C, int Cin, int Cout_head);  // the pixel-chunk head of this width can run the in_conv tail
 bool out_head_fuses_sampler(int C, int Cout, int B);     // the update happens inside the head's launch (else: head, then k_sampler)
 bool out_head_px_takes(int C, int Cout);                 // the pixel-chunk head serves this width (it can add GroupNorm partials itself)
@@ -397,6 +398,9 @@ int launch_linear(const float* in, int B, int I, const float* W, const float* bi
 
 int launch_sampler(const s3d_sampler_args& a, hipStream_t st);
 int launch_sampler_known(const s3d_sampler_args& a, const s3d_known_region& kr, hipStream_t st);
+// the argument rules of s3d_sampler_step_multistep / s3d_unet_step_film_multistep (need_model_out: the stand-alone entry)
+int check_multistep_args(const char* who, const s3d_sampler_args* a, const s3d_multistep* ms, bool need_model_out);
+int launch_sampler_multistep(const s3d_sampler_args& a, const s3d_multistep& ms, const s3d_known_region* known, hipStream_t st);
 int launch_renoise(const float* xprev, const float* er, const float* ktab, const int64_t* t, int T, long long batch, long long per_sample,
                    float* xt, hipStream_t st);
 

@@ -210,7 +210,7 @@ int launch_repack_generic(const PackDesc* descs_dev, int ndesc, int blocks, cons
 // null (the model output is not stored)
 int run_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, hipStream_t st,
                 Tape* tape, const float* ext_film = nullptr, int ext_film_stride = 0, const s3d_sampler_args* fuse = nullptr,
-                int carry_flags = 0, const s3d_known_region* known = nullptr);
+                int carry_flags = 0, const s3d_known_region* known = nullptr, const s3d_multistep* ms = nullptr);
 
 struct Fwd {
     s3d_unet* m;

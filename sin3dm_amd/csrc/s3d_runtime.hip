@@ -97,6 +97,20 @@ int device_cus() {
     return n;
 }
 
+// the argument rules of the two multistep entry points
+int check_multistep_args(const char* who, const s3d_sampler_args* a, const s3d_multistep* ms, bool need_model_out) {
+    S3D_CHECK(a->x && a->t && a->tables && a->sample && a->pred_xstart && (!need_model_out || a->model_out), S3D_ERR_INVALID,
+              "%s: %sx, t, tables, sample and pred_xstart are required", who, need_model_out ? "model_out, " : "");
+    S3D_CHECK(a->mode == S3D_STEP_DDIM, S3D_ERR_INVALID, "%s: the step's mode must be S3D_STEP_DDIM, not %d", who, a->mode);
+    S3D_CHECK(!a->y0 && !a->mask && !a->mean, S3D_ERR_INVALID, "%s: y0, mask and mean must be NULL (no x0 replacement, no posterior mean)", who);
+    S3D_CHECK(ms->tables, S3D_ERR_INVALID, "%s: the coefficient tables are required", who);
+    S3D_CHECK(ms->order == 1 || ms->order == 2, S3D_ERR_INVALID, "%s: order must be 1 or 2, not %d", who, ms->order);
+    S3D_CHECK(ms->order == 1 || ms->x0_prev, S3D_ERR_INVALID, "%s: order 2 needs x0_prev", who);
+    S3D_CHECK(ms->order == 1 || ms->x0_prev != a->pred_xstart, S3D_ERR_INVALID, "%s: x0_prev may not alias pred_xstart", who);
+    S3D_CHECK(a->T > 0 && a->batch >= 0 && a->per_sample >= 0, S3D_ERR_INVALID, "%s: bad sizes", who);
+    return 0;
+}
+
 }  // namespace s3d
 
 extern "C" {
@@ -167,6 +181,14 @@ int s3d_sampler_step_known(const s3d_sampler_args* a, const s3d_known_region* kn
     S3D_CHECK(known->y0 && known->mask && known->noise && known->tables, S3D_ERR_INVALID, "sampler_step_known: y0, mask, noise and tables are required");
     S3D_CHECK(a->T > 0 && a->batch >= 0 && a->per_sample >= 0, S3D_ERR_INVALID, "sampler_step_known: bad sizes");
     return launch_sampler_known(*a, *known, static_cast<hipStream_t>(stream));
+}
+
+int s3d_sampler_step_multistep(const s3d_sampler_args* a, const s3d_multistep* ms, const s3d_known_region* known, void* stream) {
+    using namespace s3d;
+    S3D_CHECK(a != nullptr && ms != nullptr, S3D_ERR_INVALID, "sampler_step_multistep: null args");
+    S3D_TRY(check_multistep_args("sampler_step_multistep", a, ms, true));
+    if (known) S3D_CHECK(known->y0 && known->mask && known->noise && known->tables, S3D_ERR_INVALID, "sampler_step_multistep: y0, mask, noise and tables of the known region are required");
+    return launch_sampler_multistep(*a, *ms, known, static_cast<hipStream_t>(stream));
 }
 
 int s3d_sampler_renoise(const float* x_prev, const float* noise, const float* known_tables, const int64_t* t, int32_t T, int64_t batch,

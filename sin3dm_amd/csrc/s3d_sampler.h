@@ -113,6 +113,46 @@ __device__ __forceinline__ float sampler_element_known(const s3d_sampler_args& a
                                                        const KnownCoef& kc, long long i, float mo) {
     return sampler_element_known<LEAN>(a, c, kr, kc, i, mo, a.x[i], a.noise ? a.noise[i] : 0.f);
 }
+// DPM-Solver++ multistep update (data prediction, orders 1 and 2M; DESIGN.md section 26 — our own addition, the reference samples
+// with DDPM / DDIM only).  The front is sampler_element's: x0 = the model output (START_X) or (sr * x_t) - (srm1 * model_out)
+// (EPSILON), clamped when clip_denoised.  Then
+//     s = (cx * x_t) + (c0 * x0)              order 1
+//     s = s + (c1 * x0_prev)                  order 2: the previous step's pred_xstart
+//     s = s + (cn * eps)                      a.noise != null (the SDE form)
+// every product and sum rounded on its own, in this order; sample = s, pred_xstart = x0.  cx / c0 / c1 / cn are fp32 casts of float64
+// values computed on the host for the schedule's spacing (s3d_multistep.tables); a.tables serves sr / srm1 only.
+struct MultistepCoef { float sr, srm1, cx, c0, c1, cn; };
+__device__ __forceinline__ MultistepCoef multistep_coef(const s3d_sampler_args& a, const s3d_multistep& ms, int t) {
+    MultistepCoef c;
+    c.sr = a.tables[S3D_TAB_SQRT_RECIP * a.T + t]; c.srm1 = a.tables[S3D_TAB_SQRT_RECIPM1 * a.T + t];
+    c.cx = ms.tables[S3D_MTAB_CX * a.T + t]; c.c0 = ms.tables[S3D_MTAB_C0 * a.T + t];
+    c.c1 = ms.tables[S3D_MTAB_C1 * a.T + t]; c.cn = ms.tables[S3D_MTAB_CN * a.T + t];
+    return c;
+}
+// element i of the step: mo / xt / nv as in sampler_element, xp = x0_prev[i] (anything when ms.order == 1: not used).  Writes
+// pred_xstart and, with STORE, sample; returns the sample.  STORE = false: the caller stores the (blended) value once.
+template <bool STORE = true>
+__device__ __forceinline__ float multistep_element(const s3d_sampler_args& a, const s3d_multistep& ms, const MultistepCoef& c, long long i,
+                                                   float mo, float xt, float nv, float xp) {
+#pragma clang fp contract(off)
+    float x0 = mo;
+    if (a.mean_type == S3D_MEAN_EPSILON) {
+        const float p1 = c.sr * xt, p2 = c.srm1 * mo;
+        x0 = p1 - p2;
+    }
+    if (a.clip_denoised) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+    const float q1 = c.cx * xt, q2 = c.c0 * x0;
+    float s = q1 + q2;
+    if (ms.order == 2) { const float q3 = c.c1 * xp; s = s + q3; }
+    if (a.noise) { const float q4 = c.cn * nv; s = s + q4; }
+    if (STORE) a.sample[i] = s;
+    a.pred_xstart[i] = x0;
+    return s;
+}
+template <bool STORE = true>
+__device__ __forceinline__ float multistep_element(const s3d_sampler_args& a, const s3d_multistep& ms, const MultistepCoef& c, long long i, float mo) {
+    return multistep_element<STORE>(a, ms, c, i, mo, a.x[i], a.noise ? a.noise[i] : 0.f, ms.order == 2 ? ms.x0_prev[i] : 0.f);
+}
 // one level of re-noising between two repeats of a step: x_t = (sqrt(1 - beta_t) * x_prev) + (sqrt(beta_t) * er)
 __device__ __forceinline__ float renoise_element(float c1mb, float cb, float xprev, float er) {
 #pragma clang fp contract(off)

@@ -236,7 +236,7 @@ int pack_all(s3d_unet* m) {
 
 int run_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, hipStream_t st,
                 Tape* tape, const float* ext_film, int ext_film_stride, const s3d_sampler_args* fuse, int carry_flags,
-                const s3d_known_region* known) {
+                const s3d_known_region* known, const s3d_multistep* ms) {
     const s3d_unet_cfg& c = m->cfg;
     const int mc = c.model_channels, ted = 4 * mc;
     Fwd f{m, B, st, nullptr};
@@ -382,14 +382,14 @@ int run_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W
         // S3D_CARRY_OUT: the head also runs the NEXT step's in_conv on the x_{t-1} it forms (unet_triplane.py:378, 482: a pointwise
         // TriplaneConv) into h0 / part0 — dead since this step's first block consumed them
         InConvCarry cy;
-        const bool give = (carry_flags & S3D_CARRY_OUT) && fuse && !(known && out) && fuse->sample && fuse->mode != S3D_STEP_MEAN_ONLY && !tape && part0.p &&
+        const bool give = (carry_flags & S3D_CARRY_OUT) && fuse && !(known && out) && !(ms && out) && fuse->sample && fuse->mode != S3D_STEP_MEAN_ONLY && !tape && part0.p &&
                           h.C == h0.C && out_head_fuses_sampler(h.C, c.out_channels, B) && out_head_can_carry(h.C, c.in_channels, c.out_channels);
         if (give) {
             cy.wT = m->dev(m->in_wT); cy.bias = m->dev(m->in_b); cy.part = part0.p; cy.maxparts = part0.maxparts; cy.Cin = c.in_channels;
             for (int p = 0; p < 3; ++p) cy.out[p] = h0.p[p];
         }
         S3D_TRY(launch_out_head(h, B, stats, aa, m->dev(m->out_w), m->dev(m->out_b), c.out_channels, H, W, D, out, st, fuse, head_adds ? &h.part : nullptr,
-                                give ? &cy : nullptr, known));
+                                give ? &cy : nullptr, known, ms));
         if (give) { m->carry.valid = true; m->carry.sample = fuse->sample; memcpy(m->carry.key, ckey, sizeof ckey); }
     }
     return 0;
@@ -445,7 +445,7 @@ int s3d_unet_set_param(s3d_unet* m, const char* name, const float* data, const i
 
 static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, void* stream,
                         const float* ext_film, int ext_film_stride, const s3d_sampler_args* fuse = nullptr, int carry_flags = 0,
-                        const s3d_known_region* known = nullptr);
+                        const s3d_known_region* known = nullptr, const s3d_multistep* ms = nullptr);
 
 int s3d_unet_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, void* stream) {
     S3D_CHECK(m && x && t && out, S3D_ERR_INVALID, "unet_forward: null argument");
@@ -531,11 +531,22 @@ int s3d_unet_step_film_known(s3d_unet* m, const float* film, int film_stride, in
     return forward_impl(m, step->x, nullptr, B, H, W, D, model_out, stream, film, film_stride, step, carry_flags, known);
 }
 
+int s3d_unet_step_film_multistep(s3d_unet* m, const float* film, int film_stride, int B, int H, int W, int D, const s3d_sampler_args* step,
+                                 const s3d_multistep* ms, float* model_out, void* stream, int carry_flags) {
+    S3D_CHECK(m && film && step && ms, S3D_ERR_INVALID, "unet_step_film_multistep: null argument");
+    S3D_CHECK((carry_flags & ~(S3D_CARRY_OUT | S3D_CARRY_IN)) == 0, S3D_ERR_INVALID, "unet_step_film_multistep: unknown flag bits %d", carry_flags);
+    S3D_CHECK(film_stride == 0 || film_stride == m->film_total, S3D_ERR_INVALID, "unet_step_film_multistep: film_stride must be 0 or %d", m->film_total);
+    S3D_TRY(check_multistep_args("unet_step_film_multistep", step, ms, false));
+    S3D_CHECK(step->batch == B && step->per_sample == (long long)m->cfg.out_channels * (H + D) * (W + D) && m->cfg.in_channels == m->cfg.out_channels,
+              S3D_ERR_INVALID, "unet_step_film_multistep: the step's shape is not the model's");
+    return forward_impl(m, step->x, nullptr, B, H, W, D, model_out, stream, film, film_stride, step, carry_flags, nullptr, ms);
+}
+
 }  // extern "C"
 
 static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, void* stream,
                         const float* ext_film, int ext_film_stride, const s3d_sampler_args* fuse, int carry_flags,
-                        const s3d_known_region* known) {
+                        const s3d_known_region* known, const s3d_multistep* ms) {
     S3D_CHECK(B >= 1 && H >= 1 && W >= 1 && D >= 1, S3D_ERR_INVALID, "unet_forward: B,H,W,D must be >= 1");
     if (!m->packed) S3D_TRY(pack_all(m));                             // (drops a carried in_conv: it was formed with the old weights)
     m->tape.valid = false;                    // the workspace is shared with the training tape
@@ -549,7 +560,7 @@ static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int 
     if (!same || m->inf_high > m->arena.buf.cap) {
         m->arena.measuring = true;
         m->arena.high = 0;
-        rc = run_forward(m, x, t, B, H, W, D, out, st, nullptr, ext_film, ext_film_stride, fuse, 0, known);
+        rc = run_forward(m, x, t, B, H, W, D, out, st, nullptr, ext_film, ext_film_stride, fuse, 0, known, ms);
         m->arena.measuring = false;
         if (rc) return rc;
         m->inf_high = m->arena.high;
@@ -564,7 +575,7 @@ static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int 
     ++m->fwd_count;
     if (m->prof_now) ++m->prof_forwards;
     m->arena.peak = 0;
-    rc = run_forward(m, x, t, B, H, W, D, out, st, nullptr, ext_film, ext_film_stride, fuse, carry_flags, known);
+    rc = run_forward(m, x, t, B, H, W, D, out, st, nullptr, ext_film, ext_film_stride, fuse, carry_flags, known, ms);
     m->prof_now = false;
     if (rc) return rc;
     return workspace_overrun("unet_forward", m->arena.peak, m->inf_high);

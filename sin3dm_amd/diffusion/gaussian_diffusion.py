@@ -105,6 +105,18 @@ def known_region_schedule(num_timesteps, resample=1):
             yield i, r < reps - 1
 
 
+# the few-step samplers of multistep_sample_loop by name: (order, sde)
+MULTISTEP_SAMPLERS = {"dpmpp1": (1, False), "dpmpp2m": (2, False), "dpmpp2m_sde": (2, True)}
+
+
+def multistep_sampler(name):
+    """(order, sde) of a sampler name; ValueError for anything else."""
+    try:
+        return MULTISTEP_SAMPLERS[name]
+    except (KeyError, TypeError):
+        raise ValueError(f"sampler {name!r}: expected one of {', '.join(sorted(MULTISTEP_SAMPLERS))}") from None
+
+
 def host_values_of(t):
     return getattr(t, "host_values", None) if isinstance(t, HostTimesteps) else None
 
@@ -181,6 +193,51 @@ class GaussianDiffusion:
             tab = th.from_numpy(rows.astype(np.float32)).contiguous().to(device)
             self._dev_tables[key] = tab
         return tab
+
+    def multistep_tables(self, order=2, sde=False):
+        """Coefficients of the DPM-Solver++ multistep update (data prediction) for every index of this
+        (respaced) schedule: (float64 [4][T] rows cx, c0, c1, cn — _lib.MTAB_ROWS —, int array [T] of the order each index runs at).
+        With alpha = sqrt(abar), sigma = sqrt(1 - abar), lambda = log(abar / (1 - abar)) / 2, s the level of index i, t the level
+        below it (alphas_cumprod_prev[i]) and h = lambda_t - lambda_s:
+            ODE (sde=False)   cx = sigma_t / sigma_s              g = alpha_t (1 - exp(-h))      cn = 0
+            SDE               cx = (sigma_t / sigma_s) exp(-h)    g = alpha_t (1 - exp(-2h))     cn = sigma_t sqrt(1 - exp(-2h))
+            order 1           c0 = g, c1 = 0
+            order 2           r = (lambda_s - lambda_{s+1}) / h (the previous step's width over this one's);
+                              c0 = g (1 + 1 / (2r)), c1 = -g / (2r)
+        x_{i-1} = cx x_i + c0 x0 + c1 x0_prev + cn eps.  Index T - 1 has no history and runs at order 1; index 0 returns the model's
+        x0: (0, 1, 0, 0), order 1 (lambda_t is infinite there)."""
+        order = int(order)
+        if order not in (1, 2):
+            raise ValueError(f"multistep order {order!r}: expected 1 or 2")
+        ac, acp = self.alphas_cumprod, self.alphas_cumprod_prev
+        T = self.num_timesteps
+        lam = 0.5 * np.log(ac / (1.0 - ac))
+        tab = np.zeros((4, T), dtype=np.float64)
+        orders = np.ones(T, dtype=np.int64)
+        tab[:, 0] = (0.0, 1.0, 0.0, 0.0)
+        for i in range(1, T):
+            alpha_t, sigma_t, sigma_s = np.sqrt(acp[i]), np.sqrt(1.0 - acp[i]), np.sqrt(1.0 - ac[i])
+            h = 0.5 * np.log(acp[i] / (1.0 - acp[i])) - lam[i]
+            if sde:
+                cx, g, cn = (sigma_t / sigma_s) * np.exp(-h), alpha_t * (1.0 - np.exp(-2.0 * h)), sigma_t * np.sqrt(1.0 - np.exp(-2.0 * h))
+            else:
+                cx, g, cn = sigma_t / sigma_s, alpha_t * (1.0 - np.exp(-h)), 0.0
+            if order == 2 and i < T - 1:
+                r = (lam[i] - lam[i + 1]) / h
+                tab[:, i] = (cx, g * (1.0 + 1.0 / (2.0 * r)), -g / (2.0 * r), cn)
+                orders[i] = 2
+            else:
+                tab[:, i] = (cx, g, 0.0, cn)
+        return tab, orders
+
+    def _multistep_tables(self, device, order=2, sde=False):
+        """(fp32 device image [S3D_MTAB_ROWS][T] of multistep_tables: float64 values cast once; the per-index orders, on the host)."""
+        key = f"multistep/{int(order)}/{int(bool(sde))}/{device}"
+        ent = self._dev_tables.get(key)
+        if ent is None:
+            tab, orders = self.multistep_tables(order, sde)
+            ent = self._dev_tables[key] = (th.from_numpy(tab.astype(np.float32)).contiguous().to(device), orders)
+        return ent
 
     def _mean_type_code(self):
         if self.model_mean_type == ModelMeanType.START_X:
@@ -294,6 +351,58 @@ class GaussianDiffusion:
                 _lib.check(_lib.load().s3d_sampler_step(a, _lib.stream_ptr()))
         return sample, pred, mean
 
+    def _multistep_step(self, model, x, t, clip_denoised, model_kwargs, order=1, x0_prev=None, sde=False, noise=None, carry=0,
+                        known=None, fuse=True, tables=None):
+        """One DPM-Solver++ multistep update (s3d_sampler.h multistep_element) -> (sample, pred_xstart).
+        order: what this call runs at (1, or 2 with x0_prev = the previous step's pred_xstart, which may not be the tensor this
+        call returns).  noise: the step's eps (the SDE form) or None.  tables: the fp32 device image [4][T] of the coefficients;
+        None = this schedule's own for (2, sde) — order-1 rows of a schedule whose other indices run at order 2 are the same
+        values as an all-order-1 table's.  fuse / carry / known: as in _step; the update happens in the output head's launch
+        (s3d_unet_step_film_multistep) unless there is a known region: that blend is not fused with this update, the step is then
+        the forward (model output stored) + s3d_sampler_step_multistep."""
+        _lib.require_gpu(x)
+        if model_kwargs is None:
+            model_kwargs = {}
+        B = x.shape[0]
+        assert t.shape == (B,) and order in (1, 2)
+        x = x.contiguous().float()
+        if tables is None:
+            tables = self._multistep_tables(x.device, 2, sde)[0]
+        assert tables.shape == (4, self.num_timesteps) and tables.dtype == th.float32 and tables.is_contiguous() and tables.device == x.device
+        if order == 2:
+            assert x0_prev is not None and x0_prev.shape == x.shape and x0_prev.dtype == th.float32 and x0_prev.is_contiguous() and x0_prev.device == x.device
+        if noise is not None:
+            assert noise.shape == x.shape and noise.is_contiguous() and noise.dtype == th.float32
+        step_fn = getattr(model, "denoise_step", None) if fuse else None
+        ts = self._scale_timesteps(t)
+        fused = step_fn is not None and known is None and host_values_of(ts) is not None and set(model_kwargs) == {"H", "W", "D"}
+        model_output = None
+        if not fused:
+            model_output = model(x, ts, **model_kwargs)
+            assert model_output.shape == x.shape, "learned-variance outputs are not supported on this path"
+            model_output = model_output.contiguous()
+        sample, pred = th.empty_like(x), th.empty_like(x)
+        kr = None
+        if known is not None:
+            for k in known:
+                assert k.shape == x.shape and k.dtype == th.float32 and k.is_contiguous() and k.device == x.device
+            kr = _lib.KnownRegionArgs(y0=known[0].data_ptr(), mask=known[1].data_ptr(), noise=known[2].data_ptr(),
+                                      tables=self._known_tables(x.device).data_ptr())
+        t64 = t.to(device=x.device, dtype=th.int64).contiguous()
+        a = _lib.SamplerArgs(mode=_lib.STEP_DDIM, mean_type=self._mean_type_code(), clip_denoised=int(bool(clip_denoised)), is_mask_t0=0,
+                             eta=0.0, T=self.num_timesteps, batch=B, per_sample=x[0].numel(),
+                             model_out=model_output.data_ptr() if model_output is not None else None, x=x.data_ptr(),
+                             noise=noise.data_ptr() if noise is not None else None, t=t64.data_ptr(),
+                             tables=self._tables(x.device).data_ptr(), y0=None, mask=None, sample=sample.data_ptr(),
+                             pred_xstart=pred.data_ptr(), mean=None)
+        ms = _lib.MultistepArgs(x0_prev=x0_prev.data_ptr() if order == 2 else None, tables=tables.data_ptr(), order=int(order))
+        if fused:
+            step_fn(x, ts, a, carry=carry if getattr(model, "carries_in_conv", False) else 0, multistep=ms, **model_kwargs)
+            return sample, pred
+        with th.cuda.device(x.device):
+            _lib.check(_lib.load().s3d_sampler_step_multistep(a, ms, kr, _lib.stream_ptr()))
+        return sample, pred
+
     def renoise(self, x_prev, t, noise):
         """One level of re-noising, x_t = sqrt(1 - beta_t) * x_{t-1} + sqrt(beta_t) * noise (t: [B] indices into this schedule):
         what the loops run between two repeats of a step (`resample`).  One element-wise kernel, every operation rounded."""
@@ -364,7 +473,7 @@ class GaussianDiffusion:
         return per[0].unsqueeze(len(pre)) if len(per) == 1 else th.stack(per, dim=len(pre))
 
     def _loop(self, mode, model, shape, noise, device, progress, clip_denoised=True, denoised_fn=None, cond_fn=None,
-              model_kwargs=None, generator=None, known=None, resample=1, **kw):
+              model_kwargs=None, generator=None, known=None, resample=1, multistep=None, **kw):
         """Shared body of p_sample_loop_progressive / ddim_sample_loop_progressive (:488-536, 687-734).  Every step is ONE call
         into the library when the denoiser is the HIP UNet (`_step(fuse=True)`); the per-step eps comes from the device
         generator like the reference's randn_like on a GPU, drawn for many steps at a time (`noise_fn`, if set, is asked every
@@ -384,7 +493,10 @@ class GaussianDiffusion:
         re-noising between two repeats (known_region_schedule) and every evaluation is yielded.  Draws, each of x's shape and all from
         the loop's one source (generator / noise_fn) in this order: the step's eps, the blend's eps_known, then the re-noising's eps
         when one follows.  A step that a re-noising follows leaves no in_conv behind (no CARRY_OUT) and the repeated step reads a
-        tensor no step wrote (no CARRY_IN).  Defaults: today's launches and bits."""
+        tensor no step wrote (no CARRY_IN).  Defaults: today's launches and bits.
+        multistep ((order, sde); multistep_sample_loop_progressive): every step is the DPM-Solver++ multistep update instead of
+        `mode`'s, at the order multistep_tables gives its index, with the previous step's pred_xstart as history.  The step's eps is
+        drawn only when `sde`, eps_known only with `known`: the ODE form without a known region draws nothing after x_T."""
         if cond_fn is not None:
             raise NotImplementedError("cond_fn guidance is out of scope (no caller in the reference)")
         if device is None:
@@ -398,9 +510,19 @@ class GaussianDiffusion:
         cpu_noise = is_cpu_stream(generator) and self.noise_fn is None
         if known is not None and (kw.get("y0") is not None or kw.get("mask") is not None):
             raise ValueError("known= cannot be combined with the DDIM x0 replacement (y0= / mask=)")
+        ms_tab = ms_orders = None
+        if multistep is not None:
+            if int(resample) != 1:
+                raise ValueError("resample > 1 with a multistep sampler: a re-noised step would need the history restarted")
+            if denoised_fn is not None:
+                raise NotImplementedError("denoised_fn with a multistep sampler")
+            if kw.get("y0") is not None or kw.get("mask") is not None:
+                raise ValueError("the DDIM x0 replacement (y0= / mask=) cannot be combined with a multistep sampler")
+            ms_tab, ms_orders = self._multistep_tables(device, multistep[0], multistep[1])
+        step_eps = multistep is None or bool(multistep[1])                      # (the multistep ODE form has no eps)
         img = noise if noise is not None else self._randn(shape, device, generator)
         evals = list(known_region_schedule(self.num_timesteps, resample))
-        n_draws = sum(1 + (known is not None) + int(rn) for _, rn in evals)     # x-shaped N(0,1) tensors this loop consumes after x_T
+        n_draws = sum(int(step_eps) + (known is not None) + int(rn) for _, rn in evals)     # x-shaped N(0,1) tensors this loop consumes after x_T
         if known is not None:
             # y0 / mask given for one sample are expanded over the batch here, once per loop
             known = tuple(_expand_known(k, shape, device) for k in (known.y0, known.mask))
@@ -443,16 +565,26 @@ class GaussianDiffusion:
         # between: CARRY_OUT on every step but the last; CARRY_IN when `img` still IS the tensor the previous step wrote — same
         # object, same version counter (a consumer of this generator that replaces or edits out["sample"] switches it off).
         prev_sample, prev_version = None, -1
+        x0_prev = None                                                          # multistep: the previous step's pred_xstart
         for n, (i, renoise_follows) in enumerate(evals):
             t = HostTimesteps(all_t[i], (i,) * shape[0])
             carry = ((_lib.CARRY_OUT if n < last and not renoise_follows else 0)
                      | (_lib.CARRY_IN if img is prev_sample and img._version == prev_version else 0))
             # (noise_fn without a known region: _step asks it, as ever)
-            eps = draw(img) if self.noise_fn is None or known is not None else None
+            if multistep is not None:
+                eps = draw(img) if step_eps else None
+            else:
+                eps = draw(img) if self.noise_fn is None or known is not None else None
             kn = known + (draw(img),) if known is not None else None
             with th.no_grad():
-                sample, pred, _ = self._step(mode, model, img, t, clip_denoised, denoised_fn, model_kwargs, fuse=True,
-                                             noise=eps, carry=carry, known=kn, **kw)
+                if multistep is not None:
+                    # (a fresh pred_xstart every step: x0_prev, which the caller of this generator may also hold, is never written)
+                    sample, pred = self._multistep_step(model, img, t, clip_denoised, model_kwargs, order=int(ms_orders[i]) if x0_prev is not None else 1,
+                                                        x0_prev=x0_prev, sde=bool(multistep[1]), noise=eps, carry=carry, known=kn, tables=ms_tab)
+                    x0_prev = pred
+                else:
+                    sample, pred, _ = self._step(mode, model, img, t, clip_denoised, denoised_fn, model_kwargs, fuse=True,
+                                                 noise=eps, carry=carry, known=kn, **kw)
             prev_sample, prev_version = sample, (sample._version if sample is not None else -1)
             out = {"sample": sample, "pred_xstart": pred}
             yield out                 # (outside the no_grad block: a generator abandoned mid-loop must not unwind a context manager at interpreter exit)
@@ -500,9 +632,32 @@ class GaussianDiffusion:
             pass
         return final["sample"]
 
+    def multistep_sample_loop_progressive(self, model, shape, order=2, sde=False, noise=None, clip_denoised=True, model_kwargs=None,
+                                          device=None, progress=False, generator=None, known=None, resample=1, denoised_fn=None,
+                                          cond_fn=None, y0=None, mask=None):
+        """Generator over the per-step dicts of a DPM-Solver++ multistep run (data prediction; DESIGN.md section 26 — not in the
+        reference): order 1 is DDIM with eta = 0 in other rounding, order 2 (2M) adds the previous step's pred_xstart — no further
+        model evaluation — and wants steps spaced evenly in logSNR (--timestep_respacing logsnrN).  sde: the stochastic form, one
+        eps per step.  Built on _loop: one library call per step on the HIP UNet, chunked draws, the carried in_conv.
+        `generator`, `known`: see _loop.  resample > 1, denoised_fn, cond_fn and y0 / mask are refused."""
+        yield from self._loop(_lib.STEP_DDIM, model, shape, noise, device, progress, clip_denoised=clip_denoised, denoised_fn=denoised_fn,
+                              cond_fn=cond_fn, model_kwargs=model_kwargs, generator=generator, known=known, resample=resample,
+                              multistep=(int(order), bool(sde)), y0=y0, mask=mask)
+
+    def multistep_sample_loop(self, model, shape, order=2, sde=False, noise=None, clip_denoised=True, model_kwargs=None, device=None,
+                              progress=False, generator=None, known=None, resample=1, denoised_fn=None, cond_fn=None, y0=None, mask=None):
+        """Full multistep run, returns the final sample (multistep_sample_loop_progressive)."""
+        final = None
+        for final in self.multistep_sample_loop_progressive(model, shape, order=order, sde=sde, noise=noise, clip_denoised=clip_denoised,
+                                                            model_kwargs=model_kwargs, device=device, progress=progress,
+                                                            generator=generator, known=known, resample=resample,
+                                                            denoised_fn=denoised_fn, cond_fn=cond_fn, y0=y0, mask=mask):
+            pass
+        return final["sample"]
+
     # ------------------------------------------------------------------ several independent runs at once
     def sample_loop_chains_progressive(self, model, shape, n_runs, chains=2, ddim=False, generators=None, noises=None, device=None,
-                                       streams=None, **loop_kw):
+                                       streams=None, sampler=None, **loop_kw):
         """`n_runs` independent p_sample_loop (ddim=False) / ddim_sample_loop (ddim=True) runs of batch shape `shape`, up to
         `chains` of them in flight at once: chain c owns HIP stream c and workspace lane c of the denoiser (`model.lane`), its
         steps are issued round-robin with the other chains' from this one host thread.  The reference produces many samples by
@@ -512,12 +667,17 @@ class GaussianDiffusion:
         generator per run every result is bit-identical to the same run alone on the current stream.
         A generator: yields {chain: (run, that run's latest step dict)} after every ROUND (each chain in flight advanced by one
         step; the tensors live on their chain's stream) and returns the list of final samples, ordered by run, valid on the
-        caller's current stream.  chains <= 1, or a denoiser without lanes: the runs follow each other on the current stream."""
+        caller's current stream.  chains <= 1, or a denoiser without lanes: the runs follow each other on the current stream.
+        sampler (a name of MULTISTEP_SAMPLERS, for every chain): multistep_sample_loop runs instead, `ddim` is then not looked at."""
         import collections
         import contextlib
         if device is None:
             device = next(model.parameters()).device
         loop = self.ddim_sample_loop_progressive if ddim else self.p_sample_loop_progressive
+        if sampler is not None:
+            import functools
+            ms_order, ms_sde = multistep_sampler(sampler)
+            loop = functools.partial(self.multistep_sample_loop_progressive, order=ms_order, sde=ms_sde)
         n_runs = int(n_runs)
         nch = max(1, min(int(chains), n_runs, _lib.MAX_LANES))
         lane = getattr(model, "lane", None)
@@ -571,10 +731,10 @@ class GaussianDiffusion:
         return [results[r] for r in range(n_runs)]
 
     def sample_loop_chains(self, model, shape, n_runs, chains=2, ddim=False, generators=None, noises=None, device=None,
-                           streams=None, **loop_kw):
+                           streams=None, sampler=None, **loop_kw):
         """The final samples of sample_loop_chains_progressive (a list ordered by run)."""
         it = self.sample_loop_chains_progressive(model, shape, n_runs, chains=chains, ddim=ddim, generators=generators,
-                                                 noises=noises, device=device, streams=streams, **loop_kw)
+                                                 noises=noises, device=device, streams=streams, sampler=sampler, **loop_kw)
         while True:
             try:
                 next(it)

@@ -7,13 +7,35 @@ import torch as th
 from .gaussian_diffusion import GaussianDiffusion, HostTimesteps, host_values_of
 
 
-def space_timesteps(num_timesteps, section_counts):
+def logsnr_timesteps(alphas_cumprod, n):
+    """The base steps nearest to `n` targets spaced evenly in logSNR (lambda = log(abar / (1 - abar)) / 2) between the last and the
+    first base step: target k is lambda_{T-1} + k (lambda_0 - lambda_{T-1}) / (n - 1), the kept index the j with the smallest
+    |lambda_j - target| (the lowest j on a tie).  Nearest indices can coincide, so the set may have fewer than `n` members (linear
+    T = 1000: 40 -> 39, 80 -> 76).  The spacing a multistep solver wants: its step ratios stay near 1, where
+    steps even in t end with one interval that spans most of the logSNR range."""
+    ac = np.asarray(alphas_cumprod, dtype=np.float64)
+    n = int(n)
+    if n < 2 or n > ac.shape[0]:
+        raise ValueError(f"cannot space {n} steps evenly in logSNR over {ac.shape[0]} base steps")
+    lam = 0.5 * np.log(ac / (1.0 - ac))
+    targets = lam[-1] + np.arange(n) * (lam[0] - lam[-1]) / (n - 1)
+    return {int(np.argmin(np.abs(lam - v))) for v in targets}           # (argmin: the first, i.e. lowest, index of a tie)
+
+
+def space_timesteps(num_timesteps, section_counts, alphas_cumprod=None):
     """Which original steps to keep (reference: src/diffusion/respace.py:7-60).
 
     `section_counts`: "ddimN" (fixed integer stride giving exactly N steps), a comma-separated string or a
     list of per-section counts; each equally sized section is covered by evenly spaced, rounded indices
-    that include its first and last step.
+    that include its first and last step.  "logsnrN" (not in the reference): logsnr_timesteps of the base
+    schedule's `alphas_cumprod`, which this form needs.
     """
+    if isinstance(section_counts, str) and section_counts.startswith("logsnr"):
+        if alphas_cumprod is None:
+            raise ValueError(f"timestep respacing {section_counts!r} needs the base schedule's alphas_cumprod")
+        if len(alphas_cumprod) != num_timesteps:
+            raise ValueError(f"alphas_cumprod has {len(alphas_cumprod)} entries for {num_timesteps} timesteps")
+        return logsnr_timesteps(alphas_cumprod, int(section_counts[6:]))
     if isinstance(section_counts, str):
         if section_counts.startswith("ddim"):
             want = int(section_counts[4:])
@@ -72,6 +94,9 @@ class SpacedDiffusion(GaussianDiffusion):
 
     def _step(self, mode, model, *args, **kwargs):
         return super()._step(mode, self._wrap_model(model), *args, **kwargs)
+
+    def _multistep_step(self, model, *args, **kwargs):
+        return super()._multistep_step(self._wrap_model(model), *args, **kwargs)
 
     def training_losses(self, model, *args, **kwargs):
         """Reference :93-96: training conditions the denoiser on ORIGINAL step indices too."""

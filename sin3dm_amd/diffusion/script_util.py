@@ -2,6 +2,8 @@
 `diffusion` group of args.json into the HIP-backed UNet module and its (respaced) Gaussian diffusion."""
 from __future__ import annotations
 
+import numpy as np
+
 from ..utils.parser_util import args_to_dict, diffusion_defaults, diffusion_model_defaults
 from . import gaussian_diffusion as gd
 from .respace import SpacedDiffusion, space_timesteps
@@ -26,9 +28,11 @@ def create_gaussian_diffusion(*, steps=1000, learn_sigma=False, sigma_small=Fals
                               use_kl=False, predict_xstart=False, rescale_timesteps=False,
                               rescale_learned_sigmas=False, timestep_respacing=""):
     """A SpacedDiffusion over `steps` base timesteps; `timestep_respacing` "" keeps all of them."""
-    kept = space_timesteps(steps, timestep_respacing if timestep_respacing else [steps])
+    betas = gd.get_named_beta_schedule(noise_schedule, steps)
+    # ("logsnrN" spaces the kept steps by the base schedule's logSNR)
+    kept = space_timesteps(steps, timestep_respacing if timestep_respacing else [steps], alphas_cumprod=np.cumprod(1.0 - betas, axis=0))
     mean_type = gd.ModelMeanType.START_X if predict_xstart else gd.ModelMeanType.EPSILON
-    return SpacedDiffusion(use_timesteps=kept, betas=gd.get_named_beta_schedule(noise_schedule, steps),
+    return SpacedDiffusion(use_timesteps=kept, betas=betas,
                            model_mean_type=mean_type, model_var_type=_var_type(learn_sigma, sigma_small),
                            loss_type=_loss_type(use_kl, rescale_learned_sigmas), rescale_timesteps=rescale_timesteps)
 

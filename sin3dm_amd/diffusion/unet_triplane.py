@@ -341,7 +341,7 @@ class _TriplaneUNetBase(nn.Module):
     # denoise_step takes `carry` (GaussianDiffusion._loop asks); S3D_CARRY_IN_CONV=0: every step launches its own in_conv (A/B)
     carries_in_conv = os.environ.get("S3D_CARRY_IN_CONV", "1") != "0"
 
-    def denoise_step(self, x, timesteps, step, H=None, W=None, D=None, carry=0, known=None):
+    def denoise_step(self, x, timesteps, step, H=None, W=None, D=None, carry=0, known=None, multistep=None):
         """One step of a sampling loop in one library call: this forward (host-known `timesteps`) with the sampler update
         `step` (_lib.SamplerArgs with x / noise / tables / outputs set; its model_out is ignored) applied by the output
         head's launch — src/diffusion/unet_triplane.py:465-510 + gaussian_diffusion.py:396-440 / 538-600.  The model output
@@ -350,7 +350,8 @@ class _TriplaneUNetBase(nn.Module):
         the head also leaves the next step's in_conv (a pointwise TriplaneConv, :378, 482) in the workspace; CARRY_IN — `x` is the
         previous step's sample, untouched since: that in_conv is used instead of launching the kernel.  Same bits either way.
         known (_lib.KnownRegionArgs, s3d_unet_step_film_known): the known-region blend follows the update in the same launch; a
-        carried in_conv is then the blended sample's."""
+        carried in_conv is then the blended sample's.
+        multistep (_lib.MultistepArgs, s3d_unet_step_film_multistep): the update is the DPM-Solver++ multistep one (`step` in DDIM mode)."""
         assert H is not None and W is not None and D is not None
         _lib.require_gpu(x)
         hv = getattr(timesteps, "host_values", None)
@@ -362,7 +363,11 @@ class _TriplaneUNetBase(nn.Module):
         t = timesteps.to(device=x.device, dtype=th.float32).contiguous()
         with th.cuda.device(x.device):
             film, stride = self._film_for(lib, hv, t)
-            if known is not None:
+            if multistep is not None:
+                assert known is None, "the known-region blend is not fused with the multistep update (forward + s3d_sampler_step_multistep)"
+                _lib.check(lib.s3d_unet_step_film_multistep(self._handle, _lib.ptr(film), stride, B, int(H), int(W), int(D), C.byref(step),
+                                                            C.byref(multistep), None, _lib.stream_ptr(), int(carry)))
+            elif known is not None:
                 _lib.check(lib.s3d_unet_step_film_known(self._handle, _lib.ptr(film), stride, B, int(H), int(W), int(D), C.byref(step),
                                                         C.byref(known), None, _lib.stream_ptr(), int(carry)))
             elif carry:

@@ -14,8 +14,8 @@
 --resample R                 every step but the last runs R times with a re-noising in between (RePaint's resampling)
 
 --resize sets the canvas for --keep / --paste (as for sample.py); --outpaint sets its own.  Everything else — flags, lanes and
-chains at batch 1 and 2, S3D_NOISE / S3D_MESH / S3D_DECIMATE, the per-sample feat.npz and mesh files, the aabb scaled with the
-canvas — is sin3dm_amd.sample's.  A box marks its projection on each plane, and a plane pixel stands for a whole column of the
+chains at batch 1 and 2, S3D_NOISE / S3D_MESH / S3D_DECIMATE, S3D_SAMPLER (the few-step samplers of DESIGN.md section 26; not with
+--resample > 1), the per-sample feat.npz and mesh files, the aabb scaled with the canvas — is sin3dm_amd.sample's.  A box marks its projection on each plane, and a plane pixel stands for a whole column of the
 volume (sin3dm_amd/utils/region_util.py).
 """
 from __future__ import annotations
@@ -48,6 +48,8 @@ def edit_args(argv=None):
         raise ValueError("--outpaint sets its own canvas and cannot be combined with --keep / --paste")
     if ed.resample < 1 or ed.feather < 0:
         raise ValueError("--resample must be >= 1 and --feather >= 0")
+    if ed.resample > 1 and sample.sampler_choice():
+        raise ValueError(f"--resample {ed.resample} with S3D_SAMPLER={sample.sampler_choice()}: a re-noised step would need the multistep history restarted")
     return ed, sample_args(rest)
 
 

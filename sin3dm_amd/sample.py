@@ -2,6 +2,11 @@
 
     python -m sin3dm_amd.sample --tag EXP --n_samples N [--use_ddim True --timestep_respacing 100] [--resize a b c] [--vox]
     python -m torch.distributed.run --nproc-per-node 8 -m sin3dm_amd.sample --tag EXP --n_samples 64 ...
+    S3D_SAMPLER=dpmpp2m python -m sin3dm_amd.sample --tag EXP --n_samples N --timestep_respacing logsnr20
+
+S3D_SAMPLER=dpmpp1 | dpmpp2m | dpmpp2m_sde samples with the DPM-Solver++ multistep update instead of DDPM / DDIM: the
+same number of model evaluations as --timestep_respacing keeps steps, second order with dpmpp2m; logsnrN spaces the steps evenly in
+logSNR (it may keep fewer than N: the count is printed).  edit.py reads it as well (not with --resample > 1).
 
 Reads EXP/encoding/{args.json,feat.npz}, EXP/diffusion/{args.json,ema_<rate>_<iters>.pt} and the AE checkpoint
 EXP/encoding/ckpt_final.pth written by the reference's train.py; writes EXP/<output>/NNN/feat.npz (and
@@ -41,6 +46,17 @@ def noise_source(noise=None):
     name = noise if noise is not None else (os.environ.get("S3D_NOISE") or "device")
     if name not in ("device", "torch_cpu"):
         raise ValueError(f"noise source {name!r}: expected 'device' or 'torch_cpu'")
+    return name
+
+
+def sampler_choice(name=None):
+    """"" (the default: DDPM, or DDIM with --use_ddim, as ever) or a few-step sampler of diffusion.gaussian_diffusion.MULTISTEP_SAMPLERS:
+    "dpmpp1", "dpmpp2m" or "dpmpp2m_sde" (DPM-Solver++ multistep; --use_ddim is then not looked at, and
+    --timestep_respacing logsnrN is the spacing they are meant for).  name=None reads the environment variable S3D_SAMPLER."""
+    from .diffusion.gaussian_diffusion import MULTISTEP_SAMPLERS
+    name = name if name is not None else (os.environ.get("S3D_SAMPLER") or "")
+    if name != "" and name not in MULTISTEP_SAMPLERS:
+        raise ValueError(f"sampler {name!r}: expected one of {', '.join(sorted(MULTISTEP_SAMPLERS))} (or unset)")
     return name
 
 
@@ -171,6 +187,16 @@ def sample_diffusion(args, rank=0, world=1, base_seed=1000, noise=None, hwd=None
                                                     map_location="cpu"))
     model.to(dev).eval()
     sample_fn = diffusion.ddim_sample_loop if args.use_ddim else diffusion.p_sample_loop
+    sampler = sampler_choice()
+    chain_kw = {}
+    if sampler:                                                # (unset: the calls below are the ones they always were)
+        import functools
+        from .diffusion.gaussian_diffusion import multistep_sampler
+        order, sde = multistep_sampler(sampler)
+        sample_fn = functools.partial(diffusion.multistep_sample_loop, order=order, sde=sde)
+        chain_kw = {"sampler": sampler}
+        if rank == 0:
+            print(f"sampler {sampler}: {diffusion.num_timesteps} model evaluations per sample")
 
     result_dir = os.path.join(args.tag, args.output)
     os.makedirs(result_dir, exist_ok=True)
@@ -195,7 +221,7 @@ def sample_diffusion(args, rank=0, world=1, base_seed=1000, noise=None, hwd=None
         # workspace lane each) instead of one after the other (src/sample.py:33-47)
         res = diffusion.sample_loop_chains(model, [args.diff_batch_size, C, H + D, W + D], len(full), chains=nch,
                                            ddim=bool(args.use_ddim), generators=[gens[g] for g in full], device=dev, model_kwargs=kw,
-                                           **loop_kw)
+                                           **chain_kw, **loop_kw)
         outs = dict(zip(full, res))
     for g, idx in enumerate(groups):
         samples = outs[g] if g in outs else sample_fn(model, [len(idx), C, H + D, W + D], progress=rank == 0, model_kwargs=kw,
