@@ -427,7 +427,7 @@ S3D_API int s3d_train_adamw_ema(float* params, const float* grads, float* exp_av
  *      volume 1 + tex_channels channels, pred = sdf | sigmoid(tex)
  *   1  geometry only (use_tex=False of either class, data_type sdf): the tex_* fields are ignored, 1-channel volume,
  *      pred = sdf, no tex group (tex_group_begin == the total size), tex may be null
- *   2  the PBR net: S3D_ERR_UNSUPPORTED here (it decodes through s3d_decoder_* only)
+ *   2  the PBR net: S3D_ERR_UNSUPPORTED from s3d_ae_create_variant; s3d_ae_create_pbr makes it (see there)
  * Parameters: one caller-owned flat fp32 device vector, tensors in s3d_ae_param_info() order and PyTorch layouts:
  * [geo_encoder, geo_convs, geo_decoder | tex_encoder, tex_convs, tex_decoder] — the two halves are the reference's two
  * AdamW parameter groups (networks.py:146-150); use s3d_train_adamw_ema on each half with its learning rate.
@@ -446,7 +446,14 @@ typedef struct {
 
 S3D_API int s3d_ae_create(const s3d_decoder_cfg* cfg, s3d_ae** out);               /* variant 0 */
 S3D_API int s3d_ae_create_variant(const s3d_decoder_cfg* cfg, int variant, s3d_ae** out);
-S3D_API int s3d_ae_out_channels(const s3d_ae* a);               /* floats per row of pred: 1 + tex_channels, 1 for variant 1 */
+/* AutoEncoderGroupPBR with texture (networks.py:227-333; data_type sdfpbr with --enc_net_type pbr): tex_convs = two 3x3 blocks,
+ * the second normalising its input with the norm_p it also applies to its hidden maps; rgb / mr / normal heads on one gathered
+ * feature; a 9-channel volume, pred = sdf | rgb 3 | mr 2 | normal 3 with NO sigmoid.  The handle is taken by every s3d_ae_* call
+ * but s3d_ae_loss_grads (four losses: s3d_ae_loss_grads_groups).  The tex group is [tex_encoder, tex_convs.0, tex_convs.1,
+ * rgb_decoder, mr_decoder, normal_decoder] (networks.py:260-262).  S3D_ERR_UNSUPPORTED unless tex_channels == 8, the widths
+ * are multiples of 32, mlp_hidden_layers == 4 and the feature groups are multiples of 4 channels, at most 12 together. */
+S3D_API int s3d_ae_create_pbr(const s3d_decoder_cfg* cfg, s3d_ae** out);
+S3D_API int s3d_ae_out_channels(const s3d_ae* a);               /* floats per row of pred: 1 + tex_channels, 1 for variant 1, 9 for the PBR net */
 S3D_API void s3d_ae_destroy(s3d_ae* a);
 S3D_API int s3d_ae_num_params(const s3d_ae* a);
 S3D_API int s3d_ae_param_info(const s3d_ae* a, int i, const char** name, int64_t shape[5], int* ndim, int64_t* offset);

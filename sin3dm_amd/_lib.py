@@ -241,6 +241,7 @@ SIGNATURES = {
     # auto-encoder training tier
     "s3d_ae_create": (C.c_int, [C.POINTER(DecoderCfg), C.POINTER(C.c_void_p)]),
     "s3d_ae_create_variant": (C.c_int, [C.POINTER(DecoderCfg), C.c_int32, C.POINTER(C.c_void_p)]),
+    "s3d_ae_create_pbr": (C.c_int, [C.POINTER(DecoderCfg), C.POINTER(C.c_void_p)]),
     "s3d_ae_out_channels": (C.c_int, [C.c_void_p]),
     "s3d_ae_destroy": (None, [C.c_void_p]),
     "s3d_ae_num_params": (C.c_int, [C.c_void_p]),

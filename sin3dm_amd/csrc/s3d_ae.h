@@ -28,6 +28,14 @@ int launch_mr_from_partials3(double* const part[3], int nchunks, int C, const si
 // InstanceNorm2d(affine) + SiLU of a net's three planes + their {mean, rstd} (mr [3][C][2]): partials, statistics, apply — three launches
 int launch_inorm_silu3(float* const x[3], double* const part[3], const float* const gamma[3], const float* const beta[3], float* const y[3],
                        const size_t hw[3], int C, float eps, float* mr, hipStream_t st);
+// the same with both results kept — xn = IN(x) and y = SiLU(xn) — for a block that normalises its INPUT (the PBR net's tex_convs.1)
+int launch_inorm_keep3(float* const x[3], double* const part[3], const float* const gamma[3], const float* const beta[3], float* const xn[3],
+                       float* const y[3], const size_t hw[3], int C, float eps, float* mr, hipStream_t st);
+// backward of that input norm: dx from (dres, du) — see s3d_ae_kernels.hip — and dgamma / dbeta ADDED to what is there
+size_t in_norm_bwd_ws_bytes(int C);
+int launch_in_norm_bwd3(const float* const x[3], const float* mr, const float* const gamma[3], const float* const beta[3],
+                        const float* const dres[3], const float* const du[3], float* const dx[3], float* const dgamma[3],
+                        float* const dbeta[3], const size_t hw[3], int C, void* ws, hipStream_t st);
 int launch_colsum3(const float* const x[3], const size_t rows[3], int C, float* ws, float* const out[3], float* const out2[3], hipStream_t st);   // ws: 3 * colsum_ws_floats(C)
 // pixel chunks of the InstanceNorm partial sums (s3d_decoder.hip); part: kInNormChunks*C*2 doubles per plane
 constexpr int kInNormChunks = 64;
@@ -61,6 +69,9 @@ int launch_scatter_apply(ScatterPlan& plan, float* const dfeat[2][3], const floa
 int launch_relu_bwd(const float* dact, int dstride, int coff, const float* act, float* dpre, long long rows, int C, float* ws,
                     float* colsum, hipStream_t st);
 int launch_add_slice(const float* a, const float* b, int bstride, int coff, float* out, long long rows, int C, hipStream_t st);
+// out = ((a[0] + b[0]) + (a[1] + b[1])) + (a[2] + b[2]), b[j] the column slice [coff, coff + C) of rows bstride apart
+int launch_add_slices3(const float* const a[3], const float* const b[3], int bstride, int coff, float* out, long long rows, int C,
+                       hipStream_t st);
 size_t colsum_ws_floats(int C);
 int launch_colsum(const float* x, long long rows, int C, float* ws, float* out, hipStream_t st, float* out2 = nullptr);   // out2: a second parameter with the same gradient
 int launch_last_fwd(const float* h, const float* W, const float* b, int I, int O, int sigm, float* pred, int pstride, int ooff,

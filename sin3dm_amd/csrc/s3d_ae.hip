@@ -21,7 +21,9 @@
 // tex_decoder] — the reference's two AdamW parameter groups (networks.py:146-150) are the two halves.
 // Variants (s3d_ae_create_variant, the numbers of s3d_decoder_create_variant): 0 is the net above with 1..8 texture channels (a
 // volume of 1 + tex_channels channels; 3 is sdftex, 8 sdfpbr on the skip net), 1 the geometry net alone (use_tex=False: one net,
-// a 1-channel volume, no tex group), 2 — the PBR net — is refused.  Every loop over the nets below runs to a->nnets.
+// a 1-channel volume, no tex group), 2 — the PBR net — is refused there and made by s3d_ae_create_pbr: its iteration is ae_step_pbr
+// (two 3x3 texture blocks, the second with an input norm that shares its parameters with the hidden norm, three heads on one gather).
+// Every loop over the nets in ae_step runs to a->nnets.
 #include <memory>
 
 #include "s3d_ae.h"
@@ -39,6 +41,13 @@ struct AeNet {
     size_t f_in_w, f_in_b, f_out_w, f_out_b, f_sc_w, f_sc_b, f_gamma[3], f_beta[3], f_mw[6], f_mb[6];   // flat offsets
     size_t in_dense[3], out_dense[3], sc_dense[3], in_T[3], out_T[3], sc_T[3], mT[5];                   // packed offsets
     int I[6], O[6];
+    int ks = 5;                                              // plane-block kernel size (3 for the PBR net's texture blocks)
+};
+// the PBR net's texture side beyond its first block (which is net[1] at 3x3): tex_convs.1 and the three heads
+struct AePbr {
+    size_t f_in_w, f_in_b, f_out_w, f_out_b, f_gamma[3], f_beta[3];      // tex_convs.1 (no shortcut parameters)
+    size_t in_dense[3], in_T[3], out_dense[3], out_T[3];
+    struct Head { size_t f_mw[6], f_mb[6], mT[5]; int nout, ooff; } head[3];   // rgb | mr | normal: pred columns ooff .. ooff + nout
 };
 
 }  // namespace s3d
@@ -54,6 +63,7 @@ struct s3d_ae {
     int64_t tex_begin = 0;
     float* flat = nullptr;
     AeNet net[2];
+    AePbr pbr;                          // variant 2 only
     size_t f_enc_w[2], f_enc_b[2];
     // packed image
     DevBuf pbuf, descs_dev;
@@ -89,17 +99,27 @@ static void ae_specs(s3d_ae* a) {
     auto add = [&](const std::string& n, std::vector<int64_t> s) { a->specs.push_back({n, std::move(s)}); };
     const char* pre[2] = {"geo", "tex"};
     const int cin[2] = {a->geo, a->tex}, cout[2] = {1, a->TC}, encin[2] = {1, a->C};
+    const char* ln[6] = {".first_layers.0", ".first_layers.2", ".first_layers.4", ".second_layers.0", ".second_layers.2", ".second_layers.4"};
+    auto mlp = [&](const std::string& ml, int nout) {
+        const int I[6] = {up, hid, hid, up + hid, hid, hid}, O[6] = {hid, hid, hid, hid, hid, nout};
+        for (int l = 0; l < 6; ++l) { add(ml + ln[l] + ".weight", {O[l], I[l]}); add(ml + ln[l] + ".bias", {O[l]}); }
+    };
     for (int k = 0; k < a->nnets; ++k) {
         if (k == 1) { int64_t n = 0; for (auto& s : a->specs) n += int64_t(s.numel()); a->tex_begin = n; }
-        const std::string e = std::string(pre[k]) + "_encoder", cv = std::string(pre[k]) + "_convs", ml = std::string(pre[k]) + "_decoder";
+        const bool pbr = a->variant == 2 && k == 1;          // the PBR net's texture side: two 3x3 blocks, three heads
+        const int ks = pbr ? 3 : 5;
+        const std::string e = std::string(pre[k]) + "_encoder", cv = std::string(pre[k]) + (pbr ? "_convs.0" : "_convs"), ml = std::string(pre[k]) + "_decoder";
         add(e + ".weight", {cin[k], encin[k], 4, 4, 4}); add(e + ".bias", {cin[k]});
-        add(cv + ".in_layers.0.weight", {3 * up, cin[k], 5, 5}); add(cv + ".in_layers.0.bias", {3 * up});
+        add(cv + ".in_layers.0.weight", {3 * up, cin[k], ks, ks}); add(cv + ".in_layers.0.bias", {3 * up});
         for (int p = 0; p < 3; ++p) { add(cv + ".norm_" + kAePl[p] + ".weight", {up}); add(cv + ".norm_" + kAePl[p] + ".bias", {up}); }
-        add(cv + ".out_layers.1.weight", {3 * up, up, 5, 5}); add(cv + ".out_layers.1.bias", {3 * up});
+        add(cv + ".out_layers.1.weight", {3 * up, up, ks, ks}); add(cv + ".out_layers.1.bias", {3 * up});
         add(cv + ".shortcut.weight", {3 * up, cin[k], 1, 1}); add(cv + ".shortcut.bias", {3 * up});
-        const char* ln[6] = {".first_layers.0", ".first_layers.2", ".first_layers.4", ".second_layers.0", ".second_layers.2", ".second_layers.4"};
-        const int I[6] = {up, hid, hid, up + hid, hid, hid}, O[6] = {hid, hid, hid, hid, hid, cout[k]};
-        for (int l = 0; l < 6; ++l) { add(ml + ln[l] + ".weight", {O[l], I[l]}); add(ml + ln[l] + ".bias", {O[l]}); }
+        if (!pbr) { mlp(ml, cout[k]); continue; }
+        const std::string c1 = "tex_convs.1";
+        add(c1 + ".in_layers.1.weight", {3 * up, up, 3, 3}); add(c1 + ".in_layers.1.bias", {3 * up});
+        for (int p = 0; p < 3; ++p) { add(c1 + ".norm_" + kAePl[p] + ".weight", {up}); add(c1 + ".norm_" + kAePl[p] + ".bias", {up}); }
+        add(c1 + ".out_layers.1.weight", {3 * up, up, 3, 3}); add(c1 + ".out_layers.1.bias", {3 * up});
+        mlp("rgb_decoder", 3); mlp("mr_decoder", 2); mlp("normal_decoder", 3);
     }
     a->flat_off.resize(a->specs.size());
     size_t off = 0;
@@ -121,10 +141,14 @@ static int ae_plan(s3d_ae* a) {
     const int cin[2] = {a->geo, a->tex}, cout[2] = {1, a->TC};
     a->encb_off = palloc(a->geo + a->tex);
     a->wp_off = palloc(size_t(3) * (a->geo + a->tex) * 16 * 4 * a->C);
+    const char* ln[6] = {".first_layers.0", ".first_layers.2", ".first_layers.4", ".second_layers.0", ".second_layers.2", ".second_layers.4"};
     for (int k = 0; k < a->nnets; ++k) {
         AeNet& N = a->net[k];
         N.cin = cin[k]; N.nout = cout[k];
-        const std::string e = std::string(pre[k]) + "_encoder", cv = std::string(pre[k]) + "_convs", ml = std::string(pre[k]) + "_decoder";
+        const bool pbr = a->variant == 2 && k == 1;
+        const int T = pbr ? 9 : 25;
+        N.ks = pbr ? 3 : 5;
+        const std::string e = std::string(pre[k]) + "_encoder", cv = std::string(pre[k]) + (pbr ? "_convs.0" : "_convs"), ml = std::string(pre[k]) + "_decoder";
         a->f_enc_w[k] = a->off_of(e + ".weight"); a->f_enc_b[k] = a->off_of(e + ".bias");
         add(PK_COPY, a->f_enc_b[k], a->encb_off + (k == 0 ? 0 : a->geo), cin[k]);
         N.f_in_w = a->off_of(cv + ".in_layers.0.weight"); N.f_in_b = a->off_of(cv + ".in_layers.0.bias");
@@ -132,20 +156,44 @@ static int ae_plan(s3d_ae* a) {
         N.f_sc_w = a->off_of(cv + ".shortcut.weight"); N.f_sc_b = a->off_of(cv + ".shortcut.bias");
         for (int p = 0; p < 3; ++p) {
             N.f_gamma[p] = a->off_of(cv + ".norm_" + kAePl[p] + ".weight"); N.f_beta[p] = a->off_of(cv + ".norm_" + kAePl[p] + ".bias");
-            const size_t win = N.f_in_w + size_t(p) * up * cin[k] * 25, wout = N.f_out_w + size_t(p) * up * up * 25, wsc = N.f_sc_w + size_t(p) * up * cin[k];
-            N.in_dense[p] = palloc(size_t(25) * up * 32); add(PK_DENSE_PAD, win, N.in_dense[p], (long long)25 * up * cin[k], up, cin[k], cin[k], 25, 32);
-            N.in_T[p] = palloc(size_t(25) * 32 * up);     add(PK_DENSE_T_PAD, win, N.in_T[p], (long long)25 * up * cin[k], up, cin[k], cin[k], 25, 32);
-            N.out_dense[p] = palloc(size_t(25) * up * up); add(PK_DENSE, wout, N.out_dense[p], (long long)up * up, up, up, up, 25);
-            N.out_T[p] = palloc(size_t(25) * up * up);    add(PK_DENSE_T, wout, N.out_T[p], (long long)up * up, up, up, up, 25);
+            const size_t win = N.f_in_w + size_t(p) * up * cin[k] * T, wout = N.f_out_w + size_t(p) * up * up * T, wsc = N.f_sc_w + size_t(p) * up * cin[k];
+            N.in_dense[p] = palloc(size_t(T) * up * 32); add(PK_DENSE_PAD, win, N.in_dense[p], (long long)T * up * cin[k], up, cin[k], cin[k], T, 32);
+            N.in_T[p] = palloc(size_t(T) * 32 * up);     add(PK_DENSE_T_PAD, win, N.in_T[p], (long long)T * up * cin[k], up, cin[k], cin[k], T, 32);
+            N.out_dense[p] = palloc(size_t(T) * up * up); add(PK_DENSE, wout, N.out_dense[p], (long long)up * up, up, up, up, T);
+            N.out_T[p] = palloc(size_t(T) * up * up);    add(PK_DENSE_T, wout, N.out_T[p], (long long)up * up, up, up, up, T);
             N.sc_dense[p] = palloc(size_t(up) * 32);      add(PK_DENSE_PAD, wsc, N.sc_dense[p], (long long)up * cin[k], up, cin[k], cin[k], 1, 32);
             N.sc_T[p] = palloc(size_t(32) * up);          add(PK_DENSE_T_PAD, wsc, N.sc_T[p], (long long)up * cin[k], up, cin[k], cin[k], 1, 32);
         }
-        const char* ln[6] = {".first_layers.0", ".first_layers.2", ".first_layers.4", ".second_layers.0", ".second_layers.2", ".second_layers.4"};
         const int I[6] = {up, hid, hid, up + hid, hid, hid}, O[6] = {hid, hid, hid, hid, hid, cout[k]};
-        for (int l = 0; l < 6; ++l) {
-            N.I[l] = I[l]; N.O[l] = O[l];
-            N.f_mw[l] = a->off_of(ml + ln[l] + ".weight"); N.f_mb[l] = a->off_of(ml + ln[l] + ".bias");
-            if (l < 5) { N.mT[l] = palloc(size_t(I[l]) * O[l]); add(PK_TRANS2D, N.f_mw[l], N.mT[l], (long long)I[l] * O[l], O[l], 0, I[l]); }
+        for (int l = 0; l < 6; ++l) { N.I[l] = I[l]; N.O[l] = O[l]; }
+        if (!pbr) {
+            for (int l = 0; l < 6; ++l) {
+                N.f_mw[l] = a->off_of(ml + ln[l] + ".weight"); N.f_mb[l] = a->off_of(ml + ln[l] + ".bias");
+                if (l < 5) { N.mT[l] = palloc(size_t(I[l]) * O[l]); add(PK_TRANS2D, N.f_mw[l], N.mT[l], (long long)I[l] * O[l], O[l], 0, I[l]); }
+            }
+            continue;
+        }
+        AePbr& Q = a->pbr;
+        const std::string c1 = "tex_convs.1";
+        Q.f_in_w = a->off_of(c1 + ".in_layers.1.weight"); Q.f_in_b = a->off_of(c1 + ".in_layers.1.bias");
+        Q.f_out_w = a->off_of(c1 + ".out_layers.1.weight"); Q.f_out_b = a->off_of(c1 + ".out_layers.1.bias");
+        for (int p = 0; p < 3; ++p) {
+            Q.f_gamma[p] = a->off_of(c1 + ".norm_" + kAePl[p] + ".weight"); Q.f_beta[p] = a->off_of(c1 + ".norm_" + kAePl[p] + ".bias");
+            const size_t win = Q.f_in_w + size_t(p) * up * up * 9, wout = Q.f_out_w + size_t(p) * up * up * 9;
+            Q.in_dense[p] = palloc(size_t(9) * up * up);  add(PK_DENSE, win, Q.in_dense[p], (long long)up * up, up, up, up, 9);
+            Q.in_T[p] = palloc(size_t(9) * up * up);      add(PK_DENSE_T, win, Q.in_T[p], (long long)up * up, up, up, up, 9);
+            Q.out_dense[p] = palloc(size_t(9) * up * up); add(PK_DENSE, wout, Q.out_dense[p], (long long)up * up, up, up, up, 9);
+            Q.out_T[p] = palloc(size_t(9) * up * up);     add(PK_DENSE_T, wout, Q.out_T[p], (long long)up * up, up, up, up, 9);
+        }
+        const char* hn[3] = {"rgb_decoder", "mr_decoder", "normal_decoder"};
+        const int hout[3] = {3, 2, 3}, hoff[3] = {1, 4, 6};
+        for (int j = 0; j < 3; ++j) {
+            AePbr::Head& Hd = Q.head[j];
+            Hd.nout = hout[j]; Hd.ooff = hoff[j];
+            for (int l = 0; l < 6; ++l) {
+                Hd.f_mw[l] = a->off_of(std::string(hn[j]) + ln[l] + ".weight"); Hd.f_mb[l] = a->off_of(std::string(hn[j]) + ln[l] + ".bias");
+                if (l < 5) { Hd.mT[l] = palloc(size_t(I[l]) * O[l]); add(PK_TRANS2D, Hd.f_mw[l], Hd.mT[l], (long long)I[l] * O[l], O[l], 0, I[l]); }
+            }
         }
     }
     a->psize = ps;
@@ -188,6 +236,19 @@ struct AeRun {
             J.h = g.h[p]; J.w = g.w[p];
         }
         return launch_conv(kind, ca, use_on ? on : st);
+    }
+    // the point list as up to kMaxConvJobs 1x1 jobs of one launch (the PBR net's four MLPs advance a layer per launch; Geo has three slots)
+    int lin_jobs(int cin, int cout, long long Np, int njobs, float* const in[], const float* const wgt[], const float* const bias[],
+                 float* const out[], bool relu, hipStream_t on) {
+        if (meas()) return 0;
+        ConvArgs ca; memset(&ca, 0, sizeof ca);
+        ca.B = 1; ca.cin = cin; ca.cout = cout; ca.njobs = njobs; ca.relu = relu ? 1 : 0;
+        for (int j = 0; j < njobs; ++j) {
+            ConvJob& J = ca.job[j];
+            J.in = in[j]; J.wgt = wgt[j]; J.bias = bias ? bias[j] : nullptr; J.out = out[j];
+            J.h = int(Np / 64); J.w = 64;
+        }
+        return launch_conv(CONV_1x1, ca, on);
     }
     // from / use_from: the stream dy was produced on when it is not the caller's (the second MLP chain)
     int wgrad(int taps, int cin, int cin_store, int cout, const Geo& g, float* const dy[3], int a_cstride, float* const act[3],
@@ -473,8 +534,291 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
     return 0;
 }
 
+// The PBR net's iteration (variant 2; AutoEncoderGroupPBR, networks.py:227-333).  A function of its own: variants 0 and 1 keep
+// ae_step's launches.  Geometry side: ae_step's, on the caller's stream.  Texture side on chain2: tex_convs.0 (the plane block at
+// 3x3), tex_convs.1 (input norm kept, the same norm_p again on the hidden maps, identity shortcut on the NORMALISED input), ONE
+// gather, three heads.  The four MLPs advance a layer per launch in the forward pass (four jobs); in the backward pass the three
+// heads share chain2: per layer three ReLU backwards, three weight gradients (side stream) and ONE three-job 1x1 dgrad launch.
+// The gradient of the gathered feature is ((rgb) + (mr)) + (normal), each term dXa + dCAT[:, :up], in one launch.  norm_p of
+// tex_convs.1 receives its hidden-map gradient first (written) and its input-norm gradient second (added), both on chain2.
+static int ae_step_pbr(s3d_ae* a, const float* pts, const float* sdf, const float* tex, long long N, const float aabb[6],
+                       const s3d_ae_loss_cfg& lc, float* losses, float* pred_out, float* grads, hipStream_t st) {
+    AeRun R{a, st, grads};
+    Arena& ar = a->arena;
+    const bool meas = ar.measuring;
+    ar.reset();
+    if (!meas && grads && opt_on(OPT_BWD_SIDE)) {
+        if (!a->side) {
+            int least = 0, greatest = 0;
+            (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+            S3D_HIP(hipStreamCreateWithPriority(&a->side, hipStreamNonBlocking, least));
+        }
+        if (!a->chain2) S3D_HIP(hipStreamCreateWithFlags(&a->chain2, hipStreamNonBlocking));
+        R.sw = a->side;
+        R.side = true;
+    }
+    const int up = a->up, hid = a->hid, CO = a->geo + a->tex, S = 9;
+    const Geo g = a->enc.g;
+    const long long Np = (N + 63) / 64 * 64;
+    const bool bwd = grads != nullptr || meas;
+    const AePbr& Q = a->pbr;
+    hipStream_t c2 = R.side && !meas ? a->chain2 : st;      // the texture side's chain
+    hipStream_t sb = R.side ? R.sw : st;                    // bias column sums: nobody inside the pass reads them
+    size_t hw[3];
+    for (int p = 0; p < 3; ++p) hw[p] = size_t(g.h[p]) * g.w[p];
+    auto planes = [&](float* o[3], int C) { for (int p = 0; p < 3; ++p) o[p] = ar.alloc<float>(hw[p] * C); };
+    auto conv3 = [&](ConvKind kind, int cin, int cout, float* const in[3], const size_t w[3], size_t fb, float* const res[3], float* const out[3],
+                     hipStream_t on) -> int {                 // fb: flat offset of the [3 * cout] bias, size_t(-1) none
+        const float *wp[3], *bp[3];
+        for (int p = 0; p < 3; ++p) { wp[p] = a->P(w[p]); bp[p] = fb == size_t(-1) ? nullptr : R.F(fb + size_t(p) * cout); }
+        return R.conv(kind, cin, cout, g, in, wp, fb == size_t(-1) ? nullptr : bp, res, out, 3, false, on, true);
+    };
+
+    // ---- encode
+    float *pre[3], *feat[3];
+    for (int p = 0; p < 3; ++p) { pre[p] = ar.alloc<float>(hw[p] * CO); feat[p] = ar.alloc<float>(hw[p] * CO); }
+    float* enc_mr = ar.alloc<float>(size_t(3) * CO * 2);
+    S3D_TRY(ae_encode(R, pre, feat, enc_mr));
+
+    // ---- plane blocks: geo_convs (5x5) and tex_convs.0 (3x3) are the same block
+    struct BlockAct { float *x[3], *a1[3], *y[3], *s[3], *f[3], *mr; double* part[3]; } A[2];
+    auto block_fwd = [&](int n, hipStream_t cs) -> int {
+        const AeNet& N_ = a->net[n];
+        BlockAct& T = A[n];
+        const ConvKind kind = N_.ks == 3 ? CONV_3x3 : CONV_5x5;
+        planes(T.x, 32); planes(T.a1, up); planes(T.y, up); planes(T.s, up); planes(T.f, up);
+        for (int p = 0; p < 3; ++p) T.part[p] = ar.alloc<double>(size_t(kInNormChunks) * up * 2);
+        T.mr = ar.alloc<float>(size_t(3) * up * 2);
+        if (!meas) S3D_TRY(launch_slice_pad_nhwc3(feat, T.x, hw, CO, n == 0 ? 0 : a->geo, N_.cin, cs));
+        S3D_TRY(conv3(kind, 32, up, T.x, N_.in_dense, N_.f_in_b, nullptr, T.a1, cs));
+        if (!meas) {
+            const float *gam[3], *bet[3];
+            for (int p = 0; p < 3; ++p) { gam[p] = R.F(N_.f_gamma[p]); bet[p] = R.F(N_.f_beta[p]); }
+            S3D_TRY(launch_inorm_silu3(T.a1, T.part, gam, bet, T.y, hw, up, 1e-6f, T.mr, cs));
+        }
+        S3D_TRY(conv3(CONV_1x1, 32, up, T.x, N_.sc_dense, N_.f_sc_b, nullptr, T.s, cs));
+        return conv3(kind, up, up, T.y, N_.out_dense, N_.f_out_b, T.s, T.f, cs);
+    };
+    if (!meas && R.side) S3D_TRY(R.edge(st, c2));
+    S3D_TRY(block_fwd(0, st));
+    S3D_TRY(block_fwd(1, c2));
+    // tex_convs.1 on f0 = A[1].f
+    float *xn[3], *v[3], *a2[3], *y2[3], *f1[3];
+    double* part1[3];
+    planes(xn, up); planes(v, up); planes(a2, up); planes(y2, up); planes(f1, up);
+    for (int p = 0; p < 3; ++p) part1[p] = ar.alloc<double>(size_t(kInNormChunks) * up * 2);
+    float* mr_in = ar.alloc<float>(size_t(3) * up * 2);      // {mean, rstd} of f0 (the input norm) and of a2 (the hidden norm)
+    float* mr_hid = ar.alloc<float>(size_t(3) * up * 2);
+    const float *gam1[3], *bet1[3];
+    for (int p = 0; p < 3; ++p) { gam1[p] = R.F(Q.f_gamma[p]); bet1[p] = R.F(Q.f_beta[p]); }
+    if (!meas) S3D_TRY(launch_inorm_keep3(A[1].f, part1, gam1, bet1, xn, v, hw, up, 1e-6f, mr_in, c2));
+    S3D_TRY(conv3(CONV_3x3, up, up, v, Q.in_dense, Q.f_in_b, nullptr, a2, c2));
+    if (!meas) S3D_TRY(launch_inorm_silu3(a2, part1, gam1, bet1, y2, hw, up, 1e-6f, mr_hid, c2));
+    S3D_TRY(conv3(CONV_3x3, up, up, y2, Q.out_dense, Q.f_out_b, xn, f1, c2));
+    if (!meas && R.side) S3D_TRY(R.edge(c2, st));           // the gather reads both sides' planes
+    PointSet ps; ps.pts = pts; ps.N = N; ps.Np = Np;
+    for (int k = 0; k < 6; ++k) ps.aabb[k] = aabb[k];
+
+    // ---- points: ONE gather per side, four MLPs (0 geo, 1 rgb, 2 mr, 3 normal)
+    constexpr int M = 4;
+    const int I[6] = {up, hid, hid, up + hid, hid, hid};
+    const size_t* f_mw[M] = {a->net[0].f_mw, Q.head[0].f_mw, Q.head[1].f_mw, Q.head[2].f_mw};
+    const size_t* f_mb[M] = {a->net[0].f_mb, Q.head[0].f_mb, Q.head[1].f_mb, Q.head[2].f_mb};
+    const size_t* mT[M] = {a->net[0].mT, Q.head[0].mT, Q.head[1].mT, Q.head[2].mT};
+    const int nout[M] = {1, Q.head[0].nout, Q.head[1].nout, Q.head[2].nout}, ooff[M] = {0, Q.head[0].ooff, Q.head[1].ooff, Q.head[2].ooff};
+    float *X0[2], *Xm[M], *H[M][5], *CAT[M];
+    for (int n = 0; n < 2; ++n) X0[n] = ar.alloc<float>(size_t(Np) * up);
+    for (int m = 0; m < M; ++m) {
+        Xm[m] = X0[m ? 1 : 0];
+        for (int l = 0; l < 5; ++l) H[m][l] = ar.alloc<float>(size_t(Np) * hid);
+        CAT[m] = ar.alloc<float>(size_t(Np) * (up + hid));
+    }
+    float* pred = ar.alloc<float>(size_t(Np) * S);
+    if (!meas) {
+        const float* fp[2][3];
+        for (int p = 0; p < 3; ++p) { fp[0][p] = A[0].f[p]; fp[1][p] = f1[p]; }
+        S3D_TRY(launch_gather(ps, fp, g.h, g.w, up, 2, X0, st));
+    }
+    auto lin = [&](int l, float* const in[M], int lo) -> int {
+        const float *w[M], *b[M];
+        float* out[M];
+        for (int m = 0; m < M; ++m) { w[m] = R.F(f_mw[m][l]); b[m] = R.F(f_mb[m][l]); out[m] = H[m][lo]; }
+        return R.lin_jobs(I[l], hid, Np, M, in, w, b, out, true, st);
+    };
+    {
+        float *h0[M], *h1[M], *h3[M];
+        for (int m = 0; m < M; ++m) { h0[m] = H[m][0]; h1[m] = H[m][1]; h3[m] = H[m][3]; }
+        S3D_TRY(lin(0, Xm, 0)); S3D_TRY(lin(1, h0, 1)); S3D_TRY(lin(2, h1, 2));
+        if (!meas)
+            for (int m = 0; m < M; ++m) {
+                S3D_TRY(launch_copy_slice(Xm[m], 1, up, int(Np / 64), 64, CAT[m], up + hid, 0, st));
+                S3D_TRY(launch_copy_slice(H[m][2], 1, hid, int(Np / 64), 64, CAT[m], up + hid, up, st));
+            }
+        S3D_TRY(lin(3, CAT, 3)); S3D_TRY(lin(4, h3, 4));
+        if (!meas)
+            for (int m = 0; m < M; ++m)                       // pred = sdf | rgb | mr | normal, no sigmoid on the material columns
+                S3D_TRY(launch_last_fwd(H[m][4], R.F(f_mw[m][5]), R.F(f_mb[m][5]), hid, nout[m], /*sigm=*/0, pred, S, ooff[m], N, st));
+    }
+    if (!meas && pred_out) S3D_HIP(hipMemcpyAsync(pred_out, pred, size_t(N) * S * sizeof(float), hipMemcpyDeviceToDevice, st));
+
+    // ---- losses (sdfpbr's three masked means) and d loss / d pred
+    float* loss_ws = ar.alloc<float>(512);
+    float* loss3 = ar.alloc<float>(8);
+    float* dout = bwd ? ar.alloc<float>(size_t(Np) * S) : nullptr;
+    if (!meas && sdf) {
+        const int gb8[4] = {0, 3, 5, 8};
+        S3D_TRY(launch_ae_loss_groups(pred, sdf, tex, N, Np, 8, 3, gb8, /*sigm=*/0, lc.sdf_loss, lc.tex_loss,
+                                      lc.sdf_threshold * lc.tex_threshold_ratio, lc.tex_weight, loss_ws, loss3, grads ? dout : nullptr, st));
+        if (losses) S3D_HIP(hipMemcpyAsync(losses, loss3, 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    if (!bwd) return 0;
+
+    // ================================================================= backward
+    // ---- MLPs: the geometry net's chain on the caller's stream, the three heads' on chain2
+    float* cws2 = ar.alloc<float>(3 * colsum_ws_floats(up));
+    float* cws_c[2] = {ar.alloc<float>(colsum_ws_floats(std::max(hid, up))), ar.alloc<float>(colsum_ws_floats(std::max(hid, up)))};
+    if (!meas && R.side) S3D_TRY(R.edge(st, c2));
+    struct Step { int l; float* act; float* in; int in_stride; float* din; const float* dact; int dstride, coff; };
+    Step steps[M][5];
+    float *dXa[M], *dCAT[M];
+    for (int m = 0; m < M; ++m) {
+        hipStream_t cs = m ? c2 : st;
+        float* dH = ar.alloc<float>(size_t(Np) * hid);
+        dCAT[m] = ar.alloc<float>(size_t(Np) * (up + hid));
+        dXa[m] = ar.alloc<float>(size_t(Np) * up);
+        float* lws = ar.alloc<float>(last_bwd_ws_floats(hid, nout[m]));
+        if (!meas) S3D_TRY(launch_last_bwd(dout, S, ooff[m], R.F(f_mw[m][5]), H[m][4], hid, nout[m], Np, dH, lws, R.G(f_mw[m][5]), R.G(f_mb[m][5]), cs));
+        const Step st5[5] = {{4, H[m][4], H[m][3], hid, dH, dH, hid, 0},
+                             {3, H[m][3], CAT[m], up + hid, dCAT[m], dH, hid, 0},
+                             {2, H[m][2], H[m][1], hid, dH, dCAT[m], up + hid, up},
+                             {1, H[m][1], H[m][0], hid, dH, dH, hid, 0},
+                             {0, H[m][0], Xm[m], up, dXa[m], dH, hid, 0}};
+        for (int k = 0; k < 5; ++k) steps[m][k] = st5[k];
+    }
+    Geo g1; for (int p = 0; p < 3; ++p) { g1.h[p] = p == 0 ? int(Np / 64) : 0; g1.w[p] = p == 0 ? 64 : 0; }
+    for (int k = 0; k < 5; ++k) {
+        const int l = steps[0][k].l, Il = I[l];
+        float* dP[M];
+        for (int m = 0; m < M; ++m) {
+            const Step& s = steps[m][k];
+            hipStream_t cs = m ? c2 : st;
+            dP[m] = ar.alloc<float>(size_t(Np) * hid);
+            if (!meas) S3D_TRY(launch_relu_bwd(s.dact, s.dstride, s.coff, s.act, dP[m], Np, hid, cws_c[m ? 1 : 0], R.G(f_mb[m][l]), cs));
+            float* dy3[3] = {dP[m], nullptr, nullptr}; float* a3[3] = {s.in, nullptr, nullptr}; float* dw3[3] = {R.G(f_mw[m][l]), nullptr, nullptr};
+            S3D_TRY(R.wgrad(1, Il, Il, hid, g1, dy3, s.in_stride, a3, dw3, 1, cs, true));
+        }
+        {   // geometry net's dgrad, then the heads' as three jobs of one launch
+            const float* wT[1] = {a->P(mT[0][l])};
+            float* o[1] = {steps[0][k].din};
+            S3D_TRY(R.lin_jobs(hid, Il, Np, 1, dP, wT, nullptr, o, false, st));
+            const float* wT3[3] = {a->P(mT[1][l]), a->P(mT[2][l]), a->P(mT[3][l])};
+            float* o3[3] = {steps[1][k].din, steps[2][k].din, steps[3][k].din};
+            S3D_TRY(R.lin_jobs(hid, Il, Np, 3, dP + 1, wT3, nullptr, o3, false, c2));
+        }
+    }
+    float* dX0[2] = {ar.alloc<float>(size_t(Np) * up), ar.alloc<float>(size_t(Np) * up)};
+    if (!meas) {
+        S3D_TRY(launch_add_slice(dXa[0], dCAT[0], up + hid, 0, dX0[0], Np, up, st));
+        S3D_TRY(launch_add_slices3(dXa + 1, dCAT + 1, up + hid, 0, dX0[1], Np, up, c2));
+    }
+    if (!meas && R.side) S3D_TRY(R.edge(c2, st));            // the scatter reads both sides' point gradients
+    // ---- scatter
+    float* dF[2][3] = {};
+    for (int n = 0; n < 2; ++n) planes(dF[n], up);
+    char* sws = ar.alloc<char>(scatter_ws_bytes(Np, g.h, g.w));
+    if (!meas) S3D_TRY(launch_scatter(ps, dF, g.h, g.w, up, 2, dX0, sws, st));
+    // ---- plane blocks
+    float* dfeat[3];
+    planes(dfeat, CO);
+    if (!meas && R.side) S3D_TRY(R.edge(st, c2));
+    auto gn_bwd = [&](float* const x[3], float* const dy[3], float* const dx[3], const size_t fg[3], const size_t fbeta[3], float* mr,
+                      hipStream_t cs) -> int {              // InstanceNorm(affine) + SiLU backward; WRITES dgamma / dbeta
+        GnActBwd s;
+        s.x.C = s.dy.C = s.dx.C = up; s.x.g = s.dy.g = s.dx.g = g;
+        for (int p = 0; p < 3; ++p) {
+            s.x.p[p] = x[p]; s.dy.p[p] = dy[p]; s.dx.p[p] = dx[p];
+            s.gamma[p] = R.F(fg[p]); s.beta[p] = R.F(fbeta[p]); s.dgamma[p] = R.G(fg[p]); s.dbeta[p] = R.G(fbeta[p]);
+        }
+        s.rowadd = nullptr; s.coladd = nullptr; s.add = nullptr; s.stats.mr = mr; s.film = nullptr; s.dfilm = nullptr; s.film_stride = 0;
+        s.B = 1; s.ngroups = up;
+        s.ws = ar.alloc<float>(gn_bwd_ws_floats(1, up));
+        return meas ? 0 : launch_gn_act_bwd(s, cs);
+    };
+    auto colsum_side = [&](float* const x[3], size_t fb, size_t fb2, hipStream_t cs) -> int {
+        if (meas) return 0;
+        S3D_TRY(R.edge(cs, sb));
+        float *o[3], *o2[3];
+        for (int p = 0; p < 3; ++p) { o[p] = R.G(fb + size_t(p) * up); o2[p] = fb2 == size_t(-1) ? nullptr : R.G(fb2 + size_t(p) * up); }
+        return launch_colsum3(x, hw, up, cws2, o, fb2 == size_t(-1) ? nullptr : o2, sb);
+    };
+    auto dw3 = [&](size_t f, size_t per, float* o[3]) { for (int p = 0; p < 3; ++p) o[p] = R.G(f + size_t(p) * per); };
+    // the block of block_fwd: its output gradient dFn -> its slice of dfeat
+    auto block_bwd = [&](int n, float* const dFn[3], hipStream_t cs) -> int {
+        const AeNet& N_ = a->net[n];
+        BlockAct& T = A[n];
+        const int taps = N_.ks * N_.ks;
+        const ConvKind kind = N_.ks == 3 ? CONV_3x3 : CONV_5x5;
+        float *d_y[3], *d_xs[3], *d_a1[3], *d_x[3], *dw_out[3], *dw_sc[3], *dw_in[3];
+        planes(d_y, up); planes(d_xs, 32); planes(d_a1, up); planes(d_x, 32);
+        dw3(N_.f_out_w, size_t(up) * up * taps, dw_out); dw3(N_.f_sc_w, size_t(up) * N_.cin, dw_sc); dw3(N_.f_in_w, size_t(up) * N_.cin * taps, dw_in);
+        S3D_TRY(colsum_side(dFn, N_.f_out_b, N_.f_sc_b, cs));
+        S3D_TRY(conv3(kind, up, up, dFn, N_.out_T, size_t(-1), nullptr, d_y, cs));
+        S3D_TRY(R.wgrad(taps, up, up, up, g, dFn, up, T.y, dw_out, 3, cs, true));
+        S3D_TRY(conv3(CONV_1x1, up, 32, dFn, N_.sc_T, size_t(-1), nullptr, d_xs, cs));
+        S3D_TRY(R.wgrad(1, 32, N_.cin, up, g, dFn, 32, T.x, dw_sc, 3, cs, true));
+        S3D_TRY(gn_bwd(T.a1, d_y, d_a1, N_.f_gamma, N_.f_beta, T.mr, cs));
+        S3D_TRY(colsum_side(d_a1, N_.f_in_b, size_t(-1), cs));
+        S3D_TRY(R.wgrad(taps, 32, N_.cin, up, g, d_a1, 32, T.x, dw_in, 3, cs, true));
+        S3D_TRY(conv3(kind, up, 32, d_a1, N_.in_T, size_t(-1), d_xs, d_x, cs));
+        return meas ? 0 : launch_unslice_nhwc3(d_x, dfeat, hw, CO, n == 0 ? 0 : a->geo, N_.cin, cs);
+    };
+    S3D_TRY(block_bwd(0, dF[0], st));
+    {   // tex_convs.1: dF1 = dF[1]
+        float *d_y2[3], *d_a2[3], *d_u[3], *d_f0[3], *dw_out[3], *dw_in[3];
+        planes(d_y2, up); planes(d_a2, up); planes(d_u, up); planes(d_f0, up);
+        dw3(Q.f_out_w, size_t(up) * up * 9, dw_out); dw3(Q.f_in_w, size_t(up) * up * 9, dw_in);
+        void* iws = ar.alloc<char>(in_norm_bwd_ws_bytes(up));
+        S3D_TRY(colsum_side(dF[1], Q.f_out_b, size_t(-1), c2));
+        S3D_TRY(conv3(CONV_3x3, up, up, dF[1], Q.out_T, size_t(-1), nullptr, d_y2, c2));
+        S3D_TRY(R.wgrad(9, up, up, up, g, dF[1], up, y2, dw_out, 3, c2, true));
+        S3D_TRY(gn_bwd(a2, d_y2, d_a2, Q.f_gamma, Q.f_beta, mr_hid, c2));          // first use of norm_p: dgamma / dbeta written
+        S3D_TRY(colsum_side(d_a2, Q.f_in_b, size_t(-1), c2));
+        S3D_TRY(R.wgrad(9, up, up, up, g, d_a2, up, v, dw_in, 3, c2, true));
+        S3D_TRY(conv3(CONV_3x3, up, up, d_a2, Q.in_T, size_t(-1), nullptr, d_u, c2));
+        if (!meas) {
+            float *dg[3], *db[3];
+            for (int p = 0; p < 3; ++p) { dg[p] = R.G(Q.f_gamma[p]); db[p] = R.G(Q.f_beta[p]); }
+            S3D_TRY(launch_in_norm_bwd3(A[1].f, mr_in, gam1, bet1, dF[1], d_u, d_f0, dg, db, hw, up, iws, c2));   // second use: added
+        }
+        S3D_TRY(block_bwd(1, d_f0, c2));
+    }
+    if (!meas && R.side) S3D_TRY(R.edge(c2, st));            // the encoder's backward reads both slices of dfeat
+    // ---- encoder
+    float* dpre[3];
+    planes(dpre, CO);
+    float* ews = ar.alloc<float>(std::max(enc_wgrad_ws_floats(a->C, CO), enc_norm_bwd_ws_bytes(CO) / sizeof(float)));
+    if (!meas) {
+        S3D_TRY(launch_enc_norm(true, pre, feat, enc_mr, dfeat, dpre, g, CO, ews, st));
+        S3D_TRY(launch_enc_wgrad(a->enc, dpre, a->geo, a->tex, ews, R.G(a->f_enc_w[0]), R.G(a->f_enc_b[0]), R.G(a->f_enc_w[1]), R.G(a->f_enc_b[1]), st));
+        S3D_TRY(R.tail.flush(R.side ? R.sw : st));
+        S3D_TRY(R.edge(R.sw, st));
+    }
+    return 0;
+}
+
 static int ae_run(s3d_ae* a, const float* pts, const float* sdf, const float* tex, long long N, const float aabb[6],
                   const s3d_ae_loss_cfg& lc, bool groups, float* losses, float* pred, float* grads, hipStream_t st) {
+    if (a->variant == 2) {                                  // the PBR net: its own iteration, always the grouped losses
+        a->arena.measuring = true; a->arena.high = 0;
+        int rc = ae_step_pbr(a, pts, sdf, tex, N, aabb, lc, losses, pred, grads, st);
+        a->arena.measuring = false;
+        if (rc) return rc;
+        if (a->arena.high > a->arena.buf.cap) {
+            S3D_HIP(hipStreamSynchronize(st));
+            S3D_TRY(a->arena.buf.reserve(a->arena.high + (a->arena.high >> 3)));
+        }
+        return ae_step_pbr(a, pts, sdf, tex, N, aabb, lc, losses, pred, grads, st);
+    }
     a->arena.measuring = true; a->arena.high = 0;
     int rc = ae_step(a, pts, sdf, tex, N, aabb, lc, groups, losses, pred, grads, st);
     a->arena.measuring = false;
@@ -496,7 +840,7 @@ int s3d_ae_create_variant(const s3d_decoder_cfg* cfg, int variant, s3d_ae** out)
     S3D_CHECK(variant >= 0 && variant <= 2, S3D_ERR_INVALID, "ae_create: variant %d (0 skip net, 1 geometry only, 2 PBR net)", variant);
     S3D_CHECK(variant != 2 || cfg->tex_channels == 8, S3D_ERR_UNSUPPORTED, "ae: the PBR net has 8 material channels, got tex_channels=%d",
               cfg->tex_channels);
-    S3D_CHECK(variant != 2, S3D_ERR_UNSUPPORTED, "ae training: the PBR net (variant 2) is not built; it decodes only");
+    S3D_CHECK(variant != 2, S3D_ERR_UNSUPPORTED, "ae training: the PBR net (variant 2) is not built by this call; use s3d_ae_create_pbr");
     const bool tex = variant != 1;
     S3D_CHECK(cfg->mlp_hidden_layers == 4, S3D_ERR_UNSUPPORTED, "ae: mlp_hidden_layers=%d (only the default 4 is built)", cfg->mlp_hidden_layers);
     S3D_CHECK(cfg->feat_channel_up % 32 == 0 && cfg->mlp_hidden_channels % 32 == 0 && cfg->feat_channel_up > 0 && cfg->mlp_hidden_channels > 0,
@@ -513,6 +857,26 @@ int s3d_ae_create_variant(const s3d_decoder_cfg* cfg, int variant, s3d_ae** out)
     a->variant = variant; a->nnets = tex ? 2 : 1;
     a->geo = cfg->geo_feat_channels; a->tex = tfc; a->up = cfg->feat_channel_up; a->hid = cfg->mlp_hidden_channels;
     a->TC = tex ? cfg->tex_channels : 0; a->C = 1 + a->TC;
+    ae_specs(a.get());
+    *out = a.release();
+    return 0;
+}
+int s3d_ae_create_pbr(const s3d_decoder_cfg* cfg, s3d_ae** out) {
+    S3D_CHECK(cfg && out, S3D_ERR_INVALID, "ae_create_pbr: null argument");
+    S3D_CHECK(cfg->tex_channels == 8, S3D_ERR_UNSUPPORTED, "ae training: the PBR net has 8 material channels, got tex_channels=%d", cfg->tex_channels);
+    S3D_CHECK(cfg->mlp_hidden_layers == 4, S3D_ERR_UNSUPPORTED, "ae: mlp_hidden_layers=%d (only the default 4 is built)", cfg->mlp_hidden_layers);
+    S3D_CHECK(cfg->feat_channel_up % 32 == 0 && cfg->mlp_hidden_channels % 32 == 0 && cfg->feat_channel_up > 0 && cfg->mlp_hidden_channels > 0,
+              S3D_ERR_UNSUPPORTED, "ae training: feat_channel_up=%d and mlp_hidden_channels=%d must be multiples of 32",
+              cfg->feat_channel_up, cfg->mlp_hidden_channels);
+    S3D_CHECK(cfg->geo_feat_channels >= 1 && cfg->tex_feat_channels >= 1 && cfg->geo_feat_channels + cfg->tex_feat_channels <= 12 &&
+              cfg->geo_feat_channels % 4 == 0 && cfg->tex_feat_channels % 4 == 0,
+              S3D_ERR_UNSUPPORTED, "ae training: feature groups must be multiples of 4 channels, at most 12 together; got geo=%d tex=%d",
+              cfg->geo_feat_channels, cfg->tex_feat_channels);
+    std::unique_ptr<s3d_ae> a(new s3d_ae());
+    a->cfg = *cfg;
+    a->variant = 2; a->nnets = 2;
+    a->geo = cfg->geo_feat_channels; a->tex = cfg->tex_feat_channels; a->up = cfg->feat_channel_up; a->hid = cfg->mlp_hidden_channels;
+    a->TC = 8; a->C = 9;
     ae_specs(a.get());
     *out = a.release();
     return 0;
@@ -597,6 +961,7 @@ int s3d_ae_loss_grads(s3d_ae* a, const float* pts, const float* sdf, const float
     S3D_CHECK(a && pts && sdf && (tex || a->TC == 0) && aabb && cfg && losses && grads && N >= 1, S3D_ERR_INVALID, "ae_loss_grads: bad argument");
     S3D_CHECK(a->flat && a->has_volume, S3D_ERR_INVALID, "ae_loss_grads: attach parameters and set the volume first");
     S3D_CHECK(cfg->sdf_loss >= 0 && cfg->sdf_loss <= 1 && cfg->tex_loss >= 0 && cfg->tex_loss <= 2, S3D_ERR_INVALID, "ae_loss_grads: unknown loss type");
+    S3D_CHECK(a->variant != 2, S3D_ERR_INVALID, "ae_loss_grads: the PBR net has four losses; call s3d_ae_loss_grads_groups");
     return ae_run(a, pts, sdf, tex, N, aabb, *cfg, false, losses, pred, grads, static_cast<hipStream_t>(stream));
 }
 int s3d_ae_loss_grads_groups(s3d_ae* a, const float* pts, const float* sdf, const float* tex, int64_t N, const float aabb[6],

@@ -720,6 +720,150 @@ int launch_add_slice(const float* a, const float* b, int bstride, int coff, floa
     S3D_HIP(hipGetLastError());
     return 0;
 }
+// The PBR net's three heads read ONE gathered feature: its gradient is the sum over the heads (rgb, mr, normal, in that order) of
+// a_j[n][c] + b_j[n][coff + c], formed in one pass as ((a0 + b0) + (a1 + b1)) + (a2 + b2)
+struct AddSlice3Args { const float* a[3]; const float* b[3]; float* out; long long rows; int bstride, coff, C; };
+__global__ __launch_bounds__(256) void k_add_slices3(AddSlice3Args s) {
+    const int cq = s.C / 4;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= s.rows * cq) return;
+    const long long n = i / cq;
+    const int q = int(i % cq);
+    float4 t[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float4 a = reinterpret_cast<const float4*>(s.a[j])[i];
+        const float4 b = *reinterpret_cast<const float4*>(s.b[j] + n * s.bstride + s.coff + 4 * q);
+        t[j] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+    }
+    reinterpret_cast<float4*>(s.out)[i] = make_float4((t[0].x + t[1].x) + t[2].x, (t[0].y + t[1].y) + t[2].y, (t[0].z + t[1].z) + t[2].z,
+                                                      (t[0].w + t[1].w) + t[2].w);
+}
+int launch_add_slices3(const float* const a[3], const float* const b[3], int bstride, int coff, float* out, long long rows, int C,
+                       hipStream_t st) {
+    if (!rows) return 0;
+    S3D_CHECK(C % 4 == 0 && bstride % 4 == 0 && coff % 4 == 0, S3D_ERR_INVALID, "add_slices3: C=%d stride=%d off=%d", C, bstride, coff);
+    AddSlice3Args s; s.out = out; s.rows = rows; s.bstride = bstride; s.coff = coff; s.C = C;
+    for (int j = 0; j < 3; ++j) { s.a[j] = a[j]; s.b[j] = b[j]; }
+    hipLaunchKernelGGL(k_add_slices3, dim3(cdivll(rows * (C / 4), 256)), dim3(256), 0, st, s);
+    S3D_HIP(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------ backward of an INPUT norm (the PBR net's tex_convs.1)
+// Forward (blocks.py:238-239): xn = IN(x; gamma, beta), the block's convolutions read SiLU(xn) and its identity shortcut adds xn
+// itself.  So d_xn = dres + du * SiLU'(xn) (dres: the block's output gradient through the shortcut; du: the gradient of SiLU(xn)
+// from the first convolution's dgrad), and with xh = (x - mean) * rstd
+//   dx = rstd * gamma * (d_xn - mean(d_xn) - xh * mean(d_xn * xh)) ;  dgamma += sum d_xn * xh ;  dbeta += sum d_xn
+// `+=`: the same gamma / beta normalise the block's hidden maps too, and that use's gradient (launch_gn_act_bwd, which WRITES) is
+// enqueued first on the same stream.  Three launches over the three planes, as the forward: per-chunk sums in double (chunks of
+// the forward's partial pass), their ordered sum per channel (eight lanes, fixed xor tree), apply.  xn is recomputed.
+struct InBwd3Args {
+    const float* x[3]; const float* dres[3]; const float* du[3]; float* dx[3];
+    const float* gamma[3]; const float* beta[3]; float* dgamma[3]; float* dbeta[3];
+    const float* mr; double* part[3]; float* k12; double count[3]; int hw[3]; int C;     // mr [3][C][2]; part [chunks][C][2]; k12 [3][C][2]
+};
+__device__ __forceinline__ float in_bwd_dxn(float x, float m, float r, float g, float b, float dres, float du, float& xh) {
+    xh = (x - m) * r;
+    const float xn = fmaf(xh, g, b), sg = 1.f / (1.f + expf(-xn));
+    return fmaf(du, sg * (1.f + xn * (1.f - sg)), dres);
+}
+__global__ __launch_bounds__(256) void k_in_bwd_part(InBwd3Args a) {           // grid (kInNormChunks, 3); block: C/4 quads x pl pixel lanes
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    double* sm = reinterpret_cast<double*>(smem_raw);                          // [pl][C][2]
+    const int p = blockIdx.y, C = a.C, hw = a.hw[p];
+    const int cq = C / 4, pl = blockDim.x / cq;
+    const int q = threadIdx.x % cq, l = threadIdx.x / cq;
+    const int per = (hw + kInNormChunks - 1) / kInNormChunks;
+    const int p0 = blockIdx.x * per, p1 = min(hw, p0 + per);
+    float m[4], r[4], g[4], b[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = 4 * q + k;
+        m[k] = a.mr[(size_t(p) * C + c) * 2]; r[k] = a.mr[(size_t(p) * C + c) * 2 + 1]; g[k] = a.gamma[p][c]; b[k] = a.beta[p][c];
+    }
+    double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+    for (int pix = p0 + l; pix < p1; pix += pl) {
+        const size_t i = size_t(pix) * cq + q;
+        const float4 xv = reinterpret_cast<const float4*>(a.x[p])[i], rv = reinterpret_cast<const float4*>(a.dres[p])[i];
+        const float4 uv = reinterpret_cast<const float4*>(a.du[p])[i];
+        const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, rs[4] = {rv.x, rv.y, rv.z, rv.w}, us[4] = {uv.x, uv.y, uv.z, uv.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float xh;
+            const float d = in_bwd_dxn(xs[k], m[k], r[k], g[k], b[k], rs[k], us[k], xh);
+            s1[k] += d; s2[k] += double(d) * xh;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { sm[(size_t(l) * C + 4 * q + k) * 2] = s1[k]; sm[(size_t(l) * C + 4 * q + k) * 2 + 1] = s2[k]; }
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        double S1 = 0, S2 = 0;
+        for (int ll = 0; ll < pl; ++ll) { S1 += sm[(size_t(ll) * C + c) * 2]; S2 += sm[(size_t(ll) * C + c) * 2 + 1]; }
+        a.part[p][(size_t(blockIdx.x) * C + c) * 2] = S1; a.part[p][(size_t(blockIdx.x) * C + c) * 2 + 1] = S2;
+    }
+}
+__global__ __launch_bounds__(256) void k_in_bwd_fin(InBwd3Args a) {            // grid (ceil(8 C / 256), 3)
+    const int p = blockIdx.y, C = a.C;
+    const int gt = blockIdx.x * blockDim.x + threadIdx.x, c = gt >> 3, l = gt & 7;
+    const double* part = a.part[p];
+    double S1 = 0, S2 = 0;
+    if (c < C)
+#pragma unroll 4
+        for (int k = l; k < kInNormChunks; k += 8) { S1 += part[(size_t(k) * C + c) * 2]; S2 += part[(size_t(k) * C + c) * 2 + 1]; }
+#pragma unroll
+    for (int d = 1; d < 8; d <<= 1) { S1 += __shfl_xor(S1, d, 8); S2 += __shfl_xor(S2, d, 8); }
+    if (c >= C || l != 0) return;
+    a.k12[(size_t(p) * C + c) * 2] = float(S1 / a.count[p]); a.k12[(size_t(p) * C + c) * 2 + 1] = float(S2 / a.count[p]);
+    a.dgamma[p][c] += float(S2); a.dbeta[p][c] += float(S1);                   // the second use of these parameters, after the first
+}
+__global__ __launch_bounds__(256) void k_in_bwd_apply(InBwd3Args a) {          // grid (blocks, 3), grid-stride over the plane's channel quads
+    const int p = blockIdx.y, C = a.C, cq = C / 4;
+    const long long n = (long long)a.hw[p] * cq;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const int q = int(i % cq);
+        const float4 xv = reinterpret_cast<const float4*>(a.x[p])[i], rv = reinterpret_cast<const float4*>(a.dres[p])[i];
+        const float4 uv = reinterpret_cast<const float4*>(a.du[p])[i];
+        const float xs[4] = {xv.x, xv.y, xv.z, xv.w}, rs[4] = {rv.x, rv.y, rv.z, rv.w}, us[4] = {uv.x, uv.y, uv.z, uv.w};
+        float o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const size_t c = size_t(p) * C + 4 * q + k;
+            const float r = a.mr[c * 2 + 1], g = a.gamma[p][4 * q + k];
+            float xh;
+            const float d = in_bwd_dxn(xs[k], a.mr[c * 2], r, g, a.beta[p][4 * q + k], rs[k], us[k], xh);
+            o[k] = r * g * (d - a.k12[c * 2] - xh * a.k12[c * 2 + 1]);
+        }
+        reinterpret_cast<float4*>(a.dx[p])[i] = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+size_t in_norm_bwd_ws_bytes(int C) { return size_t(3) * kInNormChunks * C * 2 * sizeof(double) + size_t(3) * C * 2 * sizeof(float); }
+int launch_in_norm_bwd3(const float* const x[3], const float* mr, const float* const gamma[3], const float* const beta[3],
+                        const float* const dres[3], const float* const du[3], float* const dx[3], float* const dgamma[3],
+                        float* const dbeta[3], const size_t hw[3], int C, void* ws, hipStream_t st) {
+    S3D_CHECK(C % 4 == 0 && C >= 4 && C <= 1024, S3D_ERR_INVALID, "in_norm_bwd: C=%d", C);
+    InBwd3Args a; a.mr = mr; a.C = C;
+    double* part = static_cast<double*>(ws);
+    a.k12 = reinterpret_cast<float*>(part + size_t(3) * kInNormChunks * C * 2);
+    int mx = 0;
+    for (int p = 0; p < 3; ++p) {
+        a.x[p] = x[p]; a.dres[p] = dres[p]; a.du[p] = du[p]; a.dx[p] = dx[p]; a.gamma[p] = gamma[p]; a.beta[p] = beta[p];
+        a.dgamma[p] = dgamma[p]; a.dbeta[p] = dbeta[p]; a.part[p] = part + size_t(p) * kInNormChunks * C * 2;
+        a.hw[p] = int(hw[p]); a.count[p] = double(hw[p]);
+        mx = std::max(mx, a.hw[p]);
+    }
+    if (!mx) return 0;
+    const int cq = C / 4, pl = std::max(1, 256 / cq);
+    hipLaunchKernelGGL(k_in_bwd_part, dim3(kInNormChunks, 3), dim3(cq * pl), size_t(pl) * C * 2 * sizeof(double), st, a);
+    S3D_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_in_bwd_fin, dim3(cdiv(C * 8, 256), 3), dim3(256), 0, st, a);
+    S3D_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_in_bwd_apply, dim3(std::min(1024, (mx * cq + 255) / 256), 3), dim3(256), 0, st, a);
+    S3D_HIP(hipGetLastError());
+    return 0;
+}
+
 // column sums of a [rows][C] matrix (bias gradients): two-stage, fixed order
 size_t colsum_ws_floats(int C) { return size_t(kColChunks) * C; }
 int launch_colsum(const float* x, long long rows, int C, float* ws, float* out, hipStream_t st, float* out2) {

@@ -161,6 +161,37 @@ int launch_inorm_silu3(float* const x[3], double* const part[3], const float* co
     return 0;
 }
 
+// ... and k_inorm_keep's: the normalised maps stored beside their SiLU (the training tier's tex_convs.1 of the PBR net)
+struct InNormKeep3Args { InNorm3Args n; float* xn[3]; };
+__global__ __launch_bounds__(256) void k_inorm_keep3(InNormKeep3Args k) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    const InNorm3Args& a = k.n;
+    const int p = blockIdx.y, C = a.C;
+    float* A = reinterpret_cast<float*>(smem_raw); float* Bc = A + C;
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        const float m = a.mr[(size_t(p) * C + c) * 2], scale = a.mr[(size_t(p) * C + c) * 2 + 1] * a.gamma[p][c];
+        A[c] = scale; Bc[c] = a.beta[p][c] - scale * m;
+    }
+    __syncthreads();
+    inorm_apply<true>(a.x[p], A, Bc, k.xn[p], a.y[p], a.hw[p], C);
+}
+int launch_inorm_keep3(float* const x[3], double* const part[3], const float* const gamma[3], const float* const beta[3], float* const xn[3],
+                       float* const y[3], const size_t hw[3], int C, float eps, float* mr, hipStream_t st) {
+    InNormKeep3Args k; InNorm3Args& a = k.n; a.C = C; a.mr = mr;
+    int mx = 0;
+    for (int p = 0; p < 3; ++p) {
+        a.x[p] = x[p]; a.y[p] = y[p]; a.part[p] = part[p]; a.gamma[p] = gamma[p]; a.beta[p] = beta[p]; a.hw[p] = int(hw[p]); k.xn[p] = xn[p];
+        mx = std::max(mx, a.hw[p]);
+    }
+    const int cq = C / 4, pl = std::max(1, 256 / cq);
+    hipLaunchKernelGGL(k_chan_partials3, dim3(kInNormChunks, 3), dim3(cq * pl), size_t(pl) * C * 2 * sizeof(double), st, a);
+    S3D_HIP(hipGetLastError());
+    S3D_TRY(launch_mr_from_partials3(part, kInNormChunks, C, hw, eps, mr, st));
+    hipLaunchKernelGGL(k_inorm_keep3, dim3(std::min(1024, (mx * cq + 255) / 256), 3), dim3(256), size_t(2) * C * sizeof(float), st, k);
+    S3D_HIP(hipGetLastError());
+    return 0;
+}
+
 // ------------------------------------------------------------------ fused gather + MLP
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -263,11 +263,7 @@ class ShapeAutoEncoder:
     def _load_data(self, path, sdf_renorm=False):
         """The preprocessed .npz of one shape: grid + near-surface samples (reference :51-112).  data_type sdf has no tex_*
         arrays and a 1-channel volume; sdfpbr has 8 material channels."""
-        if self.net.variant == 2:
-            raise NotImplementedError("auto-encoder training is not built for the PBR network with texture (--enc_net_type pbr "
-                                      "--data_type sdfpbr): train it with --enc_net_type skip; it is sampled and decoded here "
-                                      "(DESIGN.md §18)")
-        self.net.build_training_tier()
+        self._build_tier()
         data = np.load(path)
         has_tex = self.data_type != "sdf"
         dev = self.device
@@ -302,6 +298,13 @@ class ShapeAutoEncoder:
         if sdf_renorm:
             self.sdf_grid = self.sdf_grid / thr
             self.sdf_near_surf = self.sdf_near_surf / thr
+
+    def _build_tier(self):
+        """the network's s3d_ae_* tier; the PBR network with texture (three material heads) is named explicitly"""
+        if self.net.variant == 2:
+            self.net.build_training_tier(material_heads=True)
+        else:
+            self.net.build_training_tier()
 
     def _sample_batch(self, batch_size):
         """vol_ratio of the batch from the regular grid, the rest near the surface (reference :114-127)."""
@@ -368,8 +371,7 @@ class ShapeAutoEncoder:
     @torch.no_grad()
     def encode(self, vol=None):
         """reference :309-317"""
-        if self.net.variant != 2:
-            self.net.build_training_tier()
+        self._build_tier()
         return self.net.encode(self.input_grid if vol is None else vol)
 
     def save_ckpt(self, name):

@@ -4,10 +4,10 @@
 The decode side covers the reference's three data types: sdftex (skip net, 1+3 columns), sdf (use_tex=False: the geo network
 alone, 1 column, feature maps of fdim_geo channels) and sdfpbr (skip net with 8 sigmoid channels, or the PBR net: sdf | rgb 3 |
 metallic-roughness 2 | normal 3, no sigmoid).  The training tier below is built for the skip net with 1..8 texture channels
-(sdftex, and sdfpbr with --enc_net_type skip) and for the geometry-only net of either class (sdf).  The sdftex net has it from
-construction; the other two keep their earlier decode-only contract (`encode`, `forward`, `loss_and_grads` raise
-NotImplementedError) until `build_training_tier()` is called, which ShapeAutoEncoder does for training; the PBR net with texture
-has none.
+(sdftex, and sdfpbr with --enc_net_type skip), for the geometry-only net of either class (sdf) and for the PBR net with its three
+material heads (sdfpbr with --enc_net_type pbr).  The sdftex net has it from construction; the others keep their earlier
+decode-only contract (`encode`, `forward`, `loss_and_grads` raise NotImplementedError) until `build_training_tier()` is called —
+for the PBR net with texture `build_training_tier(material_heads=True)` —, which ShapeAutoEncoder does for training.
 
 `decode(x, feat_maps, aabb)` keeps the reference semantics (sdf, sigmoid(rgb)); the per-plane conv blocks are
 evaluated once per distinct triplane and cached (the reference recomputes them on every call with identical
@@ -110,17 +110,21 @@ class AutoEncoderGroupSkip(nn.Module):
     def training_tier_built(self):
         """Whether encode, forward(vol, x), loss_and_grads and flat_parameters run: always for the skip net with up to 3 texture
         channels (sdftex); for the geometry-only net of either class (sdf) and the skip net with up to 8 channels (sdfpbr with
-        --enc_net_type skip) once build_training_tier() was called; never for the PBR net with texture."""
+        --enc_net_type skip) once build_training_tier() was called; for the PBR net with texture once
+        build_training_tier(material_heads=True) was."""
         return self._tier_built
 
-    def build_training_tier(self):
+    def build_training_tier(self, material_heads=False):
         """Switch the s3d_ae_* tier on for this network (ShapeAutoEncoder does before it loads training data).  A network as
         constructed keeps what it did before this tier covered it: the geometry-only and the 8-channel nets decode only and
-        say so.  The PBR net with texture has no training tier: NotImplementedError."""
-        if self.variant not in (0, 1):
+        say so.  The PBR net with texture trains through s3d_ae_create_pbr and is switched on by naming it:
+        build_training_tier(material_heads=True); without the argument it raises NotImplementedError, as it always did."""
+        if self.variant not in (0, 1) and not material_heads:
             raise NotImplementedError(
-                f"{type(self).__name__}(use_tex={self.use_tex}, tex_channels={self.cfg[5]}): the training tier is not built for the "
-                "PBR network with texture; it decodes only (DESIGN.md §18)")
+                f"{type(self).__name__}(use_tex={self.use_tex}, tex_channels={self.cfg[5]}): the training tier of the PBR network "
+                "with texture is not built by this call: build_training_tier(material_heads=True) switches it on")
+        if material_heads and self.variant != 2:
+            raise ValueError(f"{type(self).__name__}(use_tex={self.use_tex}): material_heads=True is the PBR network with texture's")
         self._tier_built = True
         return self
 
@@ -150,14 +154,17 @@ class AutoEncoderGroupSkip(nn.Module):
             raise NotImplementedError(
                 f"{type(self).__name__}(use_tex={self.use_tex}, tex_channels={self.cfg[5]}): the training tier (encode, "
                 "forward(vol, x), loss_and_grads, flat_parameters) of this network is not built yet: call build_training_tier() "
-                "first, as ShapeAutoEncoder does for training; the PBR network with texture has none and decodes only "
-                "(DESIGN.md §18)")
+                "first (build_training_tier(material_heads=True) for the PBR network with texture), as ShapeAutoEncoder does "
+                "for training")
         lib = _lib.load()
         params = dict(self.named_parameters())
         if self._ae is None:
             h = C.c_void_p()
             cfg = _lib.DecoderCfg(*self.cfg)
-            _lib.check(lib.s3d_ae_create_variant(C.byref(cfg), self.variant, C.byref(h)))
+            if self.variant == 2:
+                _lib.check(lib.s3d_ae_create_pbr(C.byref(cfg), C.byref(h)))
+            else:
+                _lib.check(lib.s3d_ae_create_variant(C.byref(cfg), self.variant, C.byref(h)))
             assert lib.s3d_ae_out_channels(h) == self.out_channels
             self._ae = h
         intact = self._ae_flat is not None and all(
@@ -400,9 +407,10 @@ class AutoEncoderGroupSkip(nn.Module):
 
 class AutoEncoderGroupPBR(AutoEncoderGroupSkip):
     """Reference :227-316: the geo side of the skip net; tex_convs = two 3x3 blocks (the second normalises its input and adds
-    that normalised input back); rgb / mr / normal heads on one gathered feature, no sigmoid.  With texture it decodes only; with
-    use_tex=False it is the base class's geometry-only net and trains like it.  The handle, the triplane cache, `decode`,
-    `decode_grid`, `prepare`, `reset_aabb` and the parameter groups are the base class's."""
+    that normalised input back); rgb / mr / normal heads on one gathered feature, no sigmoid.  With texture it trains through
+    s3d_ae_create_pbr once build_training_tier(material_heads=True) was called (the tex group is the encoder, both blocks and
+    the three heads, :260-262); with use_tex=False it is the base class's geometry-only net and trains like it.  The handle, the
+    triplane cache, `decode`, `decode_grid`, `prepare`, `reset_aabb` and the parameter groups are the base class's."""
     _TEX_VARIANT = 2
     _TEX_PREFIXES = ("tex_encoder", "tex_convs", "rgb_decoder", "mr_decoder", "normal_decoder")
 

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Step time of the auto-encoder training iteration for the network variants the training tier covers, interleaved in ONE
 process (round-robin, so that clock drift falls on all of them alike): sdftex (skip net, 3 colour channels), geo (geometry
-only, data_type sdf) and skip8 (skip net, 8 material channels, data_type sdfpbr).  128^3 feature maps, 65 536 points per step,
+only, data_type sdf), skip8 (skip net, 8 material channels, data_type sdfpbr) and pbr (the PBR net with its three material
+heads, data_type sdfpbr with --enc_net_type pbr).  128^3 feature maps, 65 536 points per step,
 AdamW included — the configuration of tools/bench_ae_train.py, whose default is the sdftex line.  Not the scored bench line.
 
     python tools/bench_ae_variants.py [--fm 128 128 128] [--points 65536] [--rounds 5] [--steps 10] [--only geo]
 
 Prints one JSON line: ms per iteration (median over the rounds) per variant, its ratio to sdftex, and the ratio its FLOP count
-predicts (forward flops as executed: both plane blocks with their input channels padded to 32, the MLPs per point)."""
+predicts (forward flops as executed: the plane blocks with their input channels padded to 32, the MLPs per point; for pbr
+one 5x5 and two 3x3 blocks and four MLPs), also relative to skip8 for pbr."""
 import argparse
 import json
 import os
@@ -21,7 +23,7 @@ import torch  # noqa: E402
 
 from sin3dm_amd import testing as T  # noqa: E402
 from sin3dm_amd.encoding.model import FlatGroupAdamW, ae_loss_cfg  # noqa: E402
-from sin3dm_amd.encoding.networks import AutoEncoderGroupSkip  # noqa: E402
+from sin3dm_amd.encoding.networks import AutoEncoderGroupPBR, AutoEncoderGroupSkip  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--fm", type=int, nargs=3, default=(128, 128, 128))
@@ -35,7 +37,8 @@ H, W, D = args.fm
 N = args.points
 dev = torch.device("cuda:0")
 UP, HID = 64, 256
-VARIANTS = {"sdftex": dict(use_tex=True, tc=3), "geo": dict(use_tex=False, tc=0), "skip8": dict(use_tex=True, tc=8)}
+VARIANTS = {"sdftex": dict(use_tex=True, tc=3), "geo": dict(use_tex=False, tc=0), "skip8": dict(use_tex=True, tc=8),
+            "pbr": dict(use_tex=True, tc=8, pbr=True)}
 
 
 def flops(v):
@@ -45,16 +48,25 @@ def flops(v):
     hw = H * W + H * D + W * D
     mlp = 2 * (UP * HID + 2 * HID * HID + (UP + HID) * HID + HID * HID)
     last = 2 * HID * (1 + v["tc"])
+    if v.get("pbr"):
+        # geometry side as above; texture side: tex_convs.0 at 3x3 with its 1x1 shortcut, tex_convs.1 (two 64 -> 64 3x3 convs), three heads
+        geo = mlp * N + 2 * 25 * (32 * UP + UP * UP) * hw + 2 * 32 * UP * hw
+        tex = 3 * mlp * N + 2 * 9 * (32 * UP + UP * UP) * hw + 2 * 32 * UP * hw + 2 * 9 * 2 * UP * UP * hw
+        return geo + tex + last * N
     return nets * (mlp * N + 2 * 25 * (32 * UP + UP * UP) * hw + 2 * 32 * UP * hw) + last * N
 
 
 def make(v):
-    shapes = (T.ae_param_shapes(4, 8, UP, HID, 4, v["tc"], with_encoder=True) if v["use_tex"]
-              else T.geo_only_param_shapes(4, UP, HID, 4, with_encoder=True))
-    net = AutoEncoderGroupSkip(4, 8, UP, HID, 4, use_tex=v["use_tex"], tex_channels=max(v["tc"], 1))
+    if v.get("pbr"):
+        shapes = T.pbr_param_shapes(4, 8, UP, HID, 4, 8, with_encoder=True)
+        net = AutoEncoderGroupPBR(4, 8, UP, HID, 4, tex_channels=8)
+    else:
+        shapes = (T.ae_param_shapes(4, 8, UP, HID, 4, v["tc"], with_encoder=True) if v["use_tex"]
+                  else T.geo_only_param_shapes(4, UP, HID, 4, with_encoder=True))
+        net = AutoEncoderGroupSkip(4, 8, UP, HID, 4, use_tex=v["use_tex"], tex_channels=max(v["tc"], 1))
     net.load_state_dict(T.synthetic_state_dict(shapes, 5), strict=False)
     net.to(dev)
-    net.build_training_tier()
+    net.build_training_tier(**({"material_heads": True} if v.get("pbr") else {}))
     g = torch.Generator(device=dev).manual_seed(0)
     vol = torch.rand((1, 1 + v["tc"], 2 * H, 2 * W, 2 * D), device=dev, generator=g)
     vol[:, :1] = vol[:, :1] * 0.2 - 0.1
@@ -100,4 +112,7 @@ for name, (net, step, times) in runs.items():
     ms = statistics.median(times)
     line[name] = {"ms_per_step": round(ms, 3), "min": round(min(times), 3), "max": round(max(times), 3),
                   "ratio_to_sdftex": round(ms / base, 3), "flop_ratio_predicted": round(flops(VARIANTS[name]) / flops(dict(use_tex=True, tc=3)), 3)}
+    if name == "pbr" and "skip8" in runs:
+        line[name]["ratio_to_skip8"] = round(ms / statistics.median(runs["skip8"][2]), 3)
+        line[name]["flop_ratio_to_skip8_predicted"] = round(flops(VARIANTS["pbr"]) / flops(VARIANTS["skip8"]), 3)
 print(json.dumps(line), flush=True)
