@@ -56,14 +56,10 @@ struct ScatterSortedArgs {
     const unsigned* order[3]; const unsigned* start[3];            // sorted point ids / first position of every cell
     long long begin[4];
 };
-struct ScatterPlan { ScatterSortedArgs args; bool ready = false; };     // the point order of one batch (launch_scatter_prepare)
 // backward of launch_gather: dfeat (every element written) from dX; ws: scatter_ws_bytes(...) bytes.  No float atomics.
 size_t scatter_ws_bytes(long long Np, const int ph[3], const int pw[3]);
 int launch_scatter(const PointSet& ps, float* const dfeat[2][3], const int ph[3], const int pw[3], int C, int nnets,
                    const float* const dX[2], void* ws, hipStream_t st);
-// the same in two halves: the point order depends on the points alone (21 small dependent launches) and may be enqueued early
-int launch_scatter_prepare(const PointSet& ps, const int ph[3], const int pw[3], int C, int nnets, void* ws, ScatterPlan& plan, hipStream_t st);
-int launch_scatter_apply(ScatterPlan& plan, float* const dfeat[2][3], const float* const dX[2], hipStream_t st);
 
 // dpre = dact[:, coff:coff+C] * (act > 0) and colsum[C] = its column sums (ws: colsum_ws_floats(C))
 int launch_relu_bwd(const float* dact, int dstride, int coff, const float* act, float* dpre, long long rows, int C, float* ws,
@@ -73,7 +69,6 @@ int launch_add_slice(const float* a, const float* b, int bstride, int coff, floa
 int launch_add_slices3(const float* const a[3], const float* const b[3], int bstride, int coff, float* out, long long rows, int C,
                        hipStream_t st);
 size_t colsum_ws_floats(int C);
-int launch_colsum(const float* x, long long rows, int C, float* ws, float* out, hipStream_t st, float* out2 = nullptr);   // out2: a second parameter with the same gradient
 int launch_last_fwd(const float* h, const float* W, const float* b, int I, int O, int sigm, float* pred, int pstride, int ooff,
                     long long N, hipStream_t st);
 size_t last_bwd_ws_floats(int I, int O);

@@ -19,11 +19,13 @@
 //            gradient as a 2-D correlation with the projections.
 // Parameters: one flat fp32 device vector in the order [geo_encoder, geo_convs, geo_decoder | tex_encoder, tex_convs,
 // tex_decoder] — the reference's two AdamW parameter groups (networks.py:146-150) are the two halves.
-// Variants (s3d_ae_create_variant, the numbers of s3d_decoder_create_variant): 0 is the net above with 1..8 texture channels (a
-// volume of 1 + tex_channels channels; 3 is sdftex, 8 sdfpbr on the skip net), 1 the geometry net alone (use_tex=False: one net,
-// a 1-channel volume, no tex group), 2 — the PBR net — is refused there and made by s3d_ae_create_pbr: its iteration is ae_step_pbr
-// (two 3x3 texture blocks, the second with an input norm that shares its parameters with the hidden norm, three heads on one gather).
-// Every loop over the nets in ae_step runs to a->nnets.
+// Variants (the numbers of s3d_decoder_create_variant): 0 is the net above with 1..8 texture channels (a volume of 1 + tex_channels
+// channels; 3 is sdftex, 8 sdfpbr on the skip net), 1 the geometry net alone (use_tex=False: one net, a 1-channel volume, no tex
+// group), 2 the PBR net (AutoEncoderGroupPBR, networks.py:227-333; made by s3d_ae_create_pbr, refused by s3d_ae_create_variant):
+// two 3x3 texture blocks, the second with an input norm that shares its parameters with the hidden norm, three heads on one gather.
+// All three run the ONE iteration ae_step, which reads the net as data from the handle: nnets plane blocks (AeNet, kernel size ks),
+// tex_convs.1 when has_tex1 (AeTex1) and nmlp MLPs (AeMlp: which side's gather each reads, which chain it runs on, where its
+// outputs go).  ae_specs names the parameters from that description and ae_plan looks them up.
 #include <memory>
 
 #include "s3d_ae.h"
@@ -33,22 +35,37 @@
 namespace s3d {
 
 static const char* kAePl[3] = {"xy", "xz", "yz"};
+static const char* kAeLn[6] = {".first_layers.0", ".first_layers.2", ".first_layers.4", ".second_layers.0", ".second_layers.2", ".second_layers.4"};
+constexpr size_t kNone = size_t(-1);                         // "no such parameter" where a flat offset is expected
 
 struct AeSpec { std::string name; std::vector<int64_t> shape; size_t numel() const { size_t n = 1; for (auto d : shape) n *= size_t(d); return n; } };
 
+// a plane block (geo_convs, tex_convs, the PBR net's tex_convs.0): conv ks x ks -> InstanceNorm(affine) -> SiLU -> conv ks x ks + 1x1 shortcut
 struct AeNet {
-    int cin = 0, nout = 0;                                   // real feature channels (4 / 8), outputs (1 / tex_channels)
-    size_t f_in_w, f_in_b, f_out_w, f_out_b, f_sc_w, f_sc_b, f_gamma[3], f_beta[3], f_mw[6], f_mb[6];   // flat offsets
-    size_t in_dense[3], out_dense[3], sc_dense[3], in_T[3], out_T[3], sc_T[3], mT[5];                   // packed offsets
-    int I[6], O[6];
-    int ks = 5;                                              // plane-block kernel size (3 for the PBR net's texture blocks)
+    int cin = 0, ks = 5;                                     // real feature channels (4 / 8); kernel size (3 for the PBR net's texture side)
+    size_t f_in_w, f_in_b, f_out_w, f_out_b, f_sc_w, f_sc_b, f_gamma[3], f_beta[3];   // flat offsets
+    size_t in_dense[3], out_dense[3], sc_dense[3], in_T[3], out_T[3], sc_T[3];        // packed offsets
 };
-// the PBR net's texture side beyond its first block (which is net[1] at 3x3): tex_convs.1 and the three heads
-struct AePbr {
-    size_t f_in_w, f_in_b, f_out_w, f_out_b, f_gamma[3], f_beta[3];      // tex_convs.1 (no shortcut parameters)
+// the PBR net's tex_convs.1, a different kind of block: an input norm, the SAME norm_p again on the hidden maps, the identity
+// shortcut on the normalised input, in_layers.1 (no shortcut parameters); 3x3
+struct AeTex1 {
+    static constexpr int taps = 9;
+    size_t f_in_w, f_in_b, f_out_w, f_out_b, f_gamma[3], f_beta[3];
     size_t in_dense[3], in_T[3], out_dense[3], out_T[3];
-    struct Head { size_t f_mw[6], f_mb[6], mT[5]; int nout, ooff; } head[3];   // rgb | mr | normal: pred columns ooff .. ooff + nout
 };
+// a DecoderMLPSkipConcat: six layers, the last one into pred columns ooff .. ooff + nout
+struct AeMlp {
+    const char* name;
+    int nout, ooff, sigm;                                    // sigm: sigmoid on its outputs
+    int src;                                                 // the gathered feature it reads: 0 geo, 1 tex
+    int chain;                                               // its backward chain: 0 the caller's stream, 1 chain2 (a side's MLPs share
+                                                             // that side's chain, in handle order: ae_step adds their point gradients per chain)
+    size_t f_mw[6], f_mb[6], mT[5];                          // flat offsets; packed transposes of the five hidden layers
+};
+// layer l of an MLP takes I[l] and gives O[l] channels (the skip concatenation enters layer 3)
+static void mlp_dims(int up, int hid, int nout, int I[6], int O[6]) {
+    for (int l = 0; l < 6; ++l) { I[l] = l == 0 ? up : (l == 3 ? up + hid : hid); O[l] = l == 5 ? nout : hid; }
+}
 
 }  // namespace s3d
 
@@ -56,14 +73,17 @@ using namespace s3d;
 
 struct s3d_ae {
     s3d_decoder_cfg cfg;
-    int variant = 0;                    // s3d_decoder_create_variant's numbers: 0 skip net with texture, 1 geometry only (tex = TC = 0, C = 1, one net)
+    int variant = 0;                    // s3d_decoder_create_variant's numbers: 0 skip net with texture, 1 geometry only (tex = TC = 0, C = 1, one net), 2 PBR net
     int geo, tex, up, hid, TC, C, nnets = 2;
     std::vector<AeSpec> specs;
     std::vector<size_t> flat_off;
     int64_t tex_begin = 0;
     float* flat = nullptr;
     AeNet net[2];
-    AePbr pbr;                          // variant 2 only
+    bool has_tex1 = false;              // variant 2: tex_convs.1 follows net[1]
+    AeTex1 tex1;
+    AeMlp mlp[4];                       // variant 1: geo | 0: geo, tex | 2: geo, rgb, mr, normal
+    int nmlp = 0;
     size_t f_enc_w[2], f_enc_b[2];
     // packed image
     DevBuf pbuf, descs_dev;
@@ -78,7 +98,7 @@ struct s3d_ae {
     // backward pass: weight-gradient launches (no consumer before the optimizer) on a handle-owned low-priority side stream, beside
     // the chain of input gradients — as in the denoiser's backward pass (s3d_train.hip: Bwd::edge / join)
     hipStream_t side = nullptr;
-    hipStream_t chain2 = nullptr;       // the texture MLP's backward chain beside the geometry MLP's (the two nets only meet at the scatter)
+    hipStream_t chain2 = nullptr;       // the texture side's chain beside the geometry side's (the two only meet at the gather, the scatter and the encoder)
     std::vector<hipEvent_t> events;
     ~s3d_ae() {
         for (auto e : events) (void)hipEventDestroy(e);
@@ -94,32 +114,47 @@ struct s3d_ae {
 
 namespace s3d {
 
+// the net as data: what ae_specs, ae_plan and ae_step loop over
+static void ae_describe(s3d_ae* a) {
+    auto mlp = [&](const char* name, int nout, int ooff, int sigm, int side) {
+        AeMlp& M = a->mlp[a->nmlp++];
+        M.name = name; M.nout = nout; M.ooff = ooff; M.sigm = sigm; M.src = M.chain = side;
+    };
+    a->net[0].cin = a->geo; a->net[0].ks = 5;
+    a->net[1].cin = a->tex; a->net[1].ks = a->variant == 2 ? 3 : 5;
+    a->has_tex1 = a->variant == 2;
+    a->nmlp = 0;
+    mlp("geo_decoder", 1, 0, 0, 0);
+    if (a->variant == 0) mlp("tex_decoder", a->TC, 1, 1, 1);
+    if (a->variant == 2) { mlp("rgb_decoder", 3, 1, 0, 1); mlp("mr_decoder", 2, 4, 0, 1); mlp("normal_decoder", 3, 6, 0, 1); }
+}
+
 static void ae_specs(s3d_ae* a) {
     const int up = a->up, hid = a->hid;
     auto add = [&](const std::string& n, std::vector<int64_t> s) { a->specs.push_back({n, std::move(s)}); };
     const char* pre[2] = {"geo", "tex"};
-    const int cin[2] = {a->geo, a->tex}, cout[2] = {1, a->TC}, encin[2] = {1, a->C};
-    const char* ln[6] = {".first_layers.0", ".first_layers.2", ".first_layers.4", ".second_layers.0", ".second_layers.2", ".second_layers.4"};
-    auto mlp = [&](const std::string& ml, int nout) {
-        const int I[6] = {up, hid, hid, up + hid, hid, hid}, O[6] = {hid, hid, hid, hid, hid, nout};
-        for (int l = 0; l < 6; ++l) { add(ml + ln[l] + ".weight", {O[l], I[l]}); add(ml + ln[l] + ".bias", {O[l]}); }
+    const int encin[2] = {1, a->C};
+    auto mlp = [&](const AeMlp& M) {
+        int I[6], O[6];
+        mlp_dims(up, hid, M.nout, I, O);
+        for (int l = 0; l < 6; ++l) { add(std::string(M.name) + kAeLn[l] + ".weight", {O[l], I[l]}); add(std::string(M.name) + kAeLn[l] + ".bias", {O[l]}); }
     };
     for (int k = 0; k < a->nnets; ++k) {
         if (k == 1) { int64_t n = 0; for (auto& s : a->specs) n += int64_t(s.numel()); a->tex_begin = n; }
-        const bool pbr = a->variant == 2 && k == 1;          // the PBR net's texture side: two 3x3 blocks, three heads
-        const int ks = pbr ? 3 : 5;
-        const std::string e = std::string(pre[k]) + "_encoder", cv = std::string(pre[k]) + (pbr ? "_convs.0" : "_convs"), ml = std::string(pre[k]) + "_decoder";
-        add(e + ".weight", {cin[k], encin[k], 4, 4, 4}); add(e + ".bias", {cin[k]});
-        add(cv + ".in_layers.0.weight", {3 * up, cin[k], ks, ks}); add(cv + ".in_layers.0.bias", {3 * up});
+        const int cin = a->net[k].cin, ks = a->net[k].ks;
+        const std::string e = std::string(pre[k]) + "_encoder", cv = std::string(pre[k]) + (k == 1 && a->has_tex1 ? "_convs.0" : "_convs");
+        add(e + ".weight", {cin, encin[k], 4, 4, 4}); add(e + ".bias", {cin});
+        add(cv + ".in_layers.0.weight", {3 * up, cin, ks, ks}); add(cv + ".in_layers.0.bias", {3 * up});
         for (int p = 0; p < 3; ++p) { add(cv + ".norm_" + kAePl[p] + ".weight", {up}); add(cv + ".norm_" + kAePl[p] + ".bias", {up}); }
         add(cv + ".out_layers.1.weight", {3 * up, up, ks, ks}); add(cv + ".out_layers.1.bias", {3 * up});
-        add(cv + ".shortcut.weight", {3 * up, cin[k], 1, 1}); add(cv + ".shortcut.bias", {3 * up});
-        if (!pbr) { mlp(ml, cout[k]); continue; }
-        const std::string c1 = "tex_convs.1";
-        add(c1 + ".in_layers.1.weight", {3 * up, up, 3, 3}); add(c1 + ".in_layers.1.bias", {3 * up});
-        for (int p = 0; p < 3; ++p) { add(c1 + ".norm_" + kAePl[p] + ".weight", {up}); add(c1 + ".norm_" + kAePl[p] + ".bias", {up}); }
-        add(c1 + ".out_layers.1.weight", {3 * up, up, 3, 3}); add(c1 + ".out_layers.1.bias", {3 * up});
-        mlp("rgb_decoder", 3); mlp("mr_decoder", 2); mlp("normal_decoder", 3);
+        add(cv + ".shortcut.weight", {3 * up, cin, 1, 1}); add(cv + ".shortcut.bias", {3 * up});
+        if (k == 1 && a->has_tex1) {
+            const std::string c1 = "tex_convs.1";
+            add(c1 + ".in_layers.1.weight", {3 * up, up, 3, 3}); add(c1 + ".in_layers.1.bias", {3 * up});
+            for (int p = 0; p < 3; ++p) { add(c1 + ".norm_" + kAePl[p] + ".weight", {up}); add(c1 + ".norm_" + kAePl[p] + ".bias", {up}); }
+            add(c1 + ".out_layers.1.weight", {3 * up, up, 3, 3}); add(c1 + ".out_layers.1.bias", {3 * up});
+        }
+        for (int m = 0; m < a->nmlp; ++m) if (a->mlp[m].src == k) mlp(a->mlp[m]);
     }
     a->flat_off.resize(a->specs.size());
     size_t off = 0;
@@ -136,65 +171,52 @@ static int ae_plan(s3d_ae* a) {
         d.kind = kind; d.cout = cout; d.ctot = ctot; d.cin = cin; d.slot = slot; d.taps = taps; d.src = (long long)src; d.dst = (long long)dst; d.n = n;
         a->descs.push_back(d);
     };
+    auto mlp = [&](AeMlp& M) {
+        int I[6], O[6];
+        mlp_dims(up, hid, M.nout, I, O);
+        for (int l = 0; l < 6; ++l) {
+            M.f_mw[l] = a->off_of(std::string(M.name) + kAeLn[l] + ".weight"); M.f_mb[l] = a->off_of(std::string(M.name) + kAeLn[l] + ".bias");
+            if (l < 5) { M.mT[l] = palloc(size_t(I[l]) * O[l]); add(PK_TRANS2D, M.f_mw[l], M.mT[l], (long long)I[l] * O[l], O[l], 0, I[l]); }
+        }
+    };
     a->descs.clear();
     const char* pre[2] = {"geo", "tex"};
-    const int cin[2] = {a->geo, a->tex}, cout[2] = {1, a->TC};
     a->encb_off = palloc(a->geo + a->tex);
     a->wp_off = palloc(size_t(3) * (a->geo + a->tex) * 16 * 4 * a->C);
-    const char* ln[6] = {".first_layers.0", ".first_layers.2", ".first_layers.4", ".second_layers.0", ".second_layers.2", ".second_layers.4"};
     for (int k = 0; k < a->nnets; ++k) {
         AeNet& N = a->net[k];
-        N.cin = cin[k]; N.nout = cout[k];
-        const bool pbr = a->variant == 2 && k == 1;
-        const int T = pbr ? 9 : 25;
-        N.ks = pbr ? 3 : 5;
-        const std::string e = std::string(pre[k]) + "_encoder", cv = std::string(pre[k]) + (pbr ? "_convs.0" : "_convs"), ml = std::string(pre[k]) + "_decoder";
+        const int cin = N.cin, T = N.ks * N.ks;
+        const std::string e = std::string(pre[k]) + "_encoder", cv = std::string(pre[k]) + (k == 1 && a->has_tex1 ? "_convs.0" : "_convs");
         a->f_enc_w[k] = a->off_of(e + ".weight"); a->f_enc_b[k] = a->off_of(e + ".bias");
-        add(PK_COPY, a->f_enc_b[k], a->encb_off + (k == 0 ? 0 : a->geo), cin[k]);
+        add(PK_COPY, a->f_enc_b[k], a->encb_off + (k == 0 ? 0 : a->geo), cin);
         N.f_in_w = a->off_of(cv + ".in_layers.0.weight"); N.f_in_b = a->off_of(cv + ".in_layers.0.bias");
         N.f_out_w = a->off_of(cv + ".out_layers.1.weight"); N.f_out_b = a->off_of(cv + ".out_layers.1.bias");
         N.f_sc_w = a->off_of(cv + ".shortcut.weight"); N.f_sc_b = a->off_of(cv + ".shortcut.bias");
         for (int p = 0; p < 3; ++p) {
             N.f_gamma[p] = a->off_of(cv + ".norm_" + kAePl[p] + ".weight"); N.f_beta[p] = a->off_of(cv + ".norm_" + kAePl[p] + ".bias");
-            const size_t win = N.f_in_w + size_t(p) * up * cin[k] * T, wout = N.f_out_w + size_t(p) * up * up * T, wsc = N.f_sc_w + size_t(p) * up * cin[k];
-            N.in_dense[p] = palloc(size_t(T) * up * 32); add(PK_DENSE_PAD, win, N.in_dense[p], (long long)T * up * cin[k], up, cin[k], cin[k], T, 32);
-            N.in_T[p] = palloc(size_t(T) * 32 * up);     add(PK_DENSE_T_PAD, win, N.in_T[p], (long long)T * up * cin[k], up, cin[k], cin[k], T, 32);
+            const size_t win = N.f_in_w + size_t(p) * up * cin * T, wout = N.f_out_w + size_t(p) * up * up * T, wsc = N.f_sc_w + size_t(p) * up * cin;
+            N.in_dense[p] = palloc(size_t(T) * up * 32); add(PK_DENSE_PAD, win, N.in_dense[p], (long long)T * up * cin, up, cin, cin, T, 32);
+            N.in_T[p] = palloc(size_t(T) * 32 * up);     add(PK_DENSE_T_PAD, win, N.in_T[p], (long long)T * up * cin, up, cin, cin, T, 32);
             N.out_dense[p] = palloc(size_t(T) * up * up); add(PK_DENSE, wout, N.out_dense[p], (long long)up * up, up, up, up, T);
             N.out_T[p] = palloc(size_t(T) * up * up);    add(PK_DENSE_T, wout, N.out_T[p], (long long)up * up, up, up, up, T);
-            N.sc_dense[p] = palloc(size_t(up) * 32);      add(PK_DENSE_PAD, wsc, N.sc_dense[p], (long long)up * cin[k], up, cin[k], cin[k], 1, 32);
-            N.sc_T[p] = palloc(size_t(32) * up);          add(PK_DENSE_T_PAD, wsc, N.sc_T[p], (long long)up * cin[k], up, cin[k], cin[k], 1, 32);
+            N.sc_dense[p] = palloc(size_t(up) * 32);      add(PK_DENSE_PAD, wsc, N.sc_dense[p], (long long)up * cin, up, cin, cin, 1, 32);
+            N.sc_T[p] = palloc(size_t(32) * up);          add(PK_DENSE_T_PAD, wsc, N.sc_T[p], (long long)up * cin, up, cin, cin, 1, 32);
         }
-        const int I[6] = {up, hid, hid, up + hid, hid, hid}, O[6] = {hid, hid, hid, hid, hid, cout[k]};
-        for (int l = 0; l < 6; ++l) { N.I[l] = I[l]; N.O[l] = O[l]; }
-        if (!pbr) {
-            for (int l = 0; l < 6; ++l) {
-                N.f_mw[l] = a->off_of(ml + ln[l] + ".weight"); N.f_mb[l] = a->off_of(ml + ln[l] + ".bias");
-                if (l < 5) { N.mT[l] = palloc(size_t(I[l]) * O[l]); add(PK_TRANS2D, N.f_mw[l], N.mT[l], (long long)I[l] * O[l], O[l], 0, I[l]); }
-            }
-            continue;
-        }
-        AePbr& Q = a->pbr;
-        const std::string c1 = "tex_convs.1";
-        Q.f_in_w = a->off_of(c1 + ".in_layers.1.weight"); Q.f_in_b = a->off_of(c1 + ".in_layers.1.bias");
-        Q.f_out_w = a->off_of(c1 + ".out_layers.1.weight"); Q.f_out_b = a->off_of(c1 + ".out_layers.1.bias");
-        for (int p = 0; p < 3; ++p) {
-            Q.f_gamma[p] = a->off_of(c1 + ".norm_" + kAePl[p] + ".weight"); Q.f_beta[p] = a->off_of(c1 + ".norm_" + kAePl[p] + ".bias");
-            const size_t win = Q.f_in_w + size_t(p) * up * up * 9, wout = Q.f_out_w + size_t(p) * up * up * 9;
-            Q.in_dense[p] = palloc(size_t(9) * up * up);  add(PK_DENSE, win, Q.in_dense[p], (long long)up * up, up, up, up, 9);
-            Q.in_T[p] = palloc(size_t(9) * up * up);      add(PK_DENSE_T, win, Q.in_T[p], (long long)up * up, up, up, up, 9);
-            Q.out_dense[p] = palloc(size_t(9) * up * up); add(PK_DENSE, wout, Q.out_dense[p], (long long)up * up, up, up, up, 9);
-            Q.out_T[p] = palloc(size_t(9) * up * up);     add(PK_DENSE_T, wout, Q.out_T[p], (long long)up * up, up, up, up, 9);
-        }
-        const char* hn[3] = {"rgb_decoder", "mr_decoder", "normal_decoder"};
-        const int hout[3] = {3, 2, 3}, hoff[3] = {1, 4, 6};
-        for (int j = 0; j < 3; ++j) {
-            AePbr::Head& Hd = Q.head[j];
-            Hd.nout = hout[j]; Hd.ooff = hoff[j];
-            for (int l = 0; l < 6; ++l) {
-                Hd.f_mw[l] = a->off_of(std::string(hn[j]) + ln[l] + ".weight"); Hd.f_mb[l] = a->off_of(std::string(hn[j]) + ln[l] + ".bias");
-                if (l < 5) { Hd.mT[l] = palloc(size_t(I[l]) * O[l]); add(PK_TRANS2D, Hd.f_mw[l], Hd.mT[l], (long long)I[l] * O[l], O[l], 0, I[l]); }
+        if (k == 1 && a->has_tex1) {
+            AeTex1& Q = a->tex1;
+            const std::string c1 = "tex_convs.1";
+            Q.f_in_w = a->off_of(c1 + ".in_layers.1.weight"); Q.f_in_b = a->off_of(c1 + ".in_layers.1.bias");
+            Q.f_out_w = a->off_of(c1 + ".out_layers.1.weight"); Q.f_out_b = a->off_of(c1 + ".out_layers.1.bias");
+            for (int p = 0; p < 3; ++p) {
+                Q.f_gamma[p] = a->off_of(c1 + ".norm_" + kAePl[p] + ".weight"); Q.f_beta[p] = a->off_of(c1 + ".norm_" + kAePl[p] + ".bias");
+                const size_t win = Q.f_in_w + size_t(p) * up * up * 9, wout = Q.f_out_w + size_t(p) * up * up * 9;
+                Q.in_dense[p] = palloc(size_t(9) * up * up);  add(PK_DENSE, win, Q.in_dense[p], (long long)up * up, up, up, up, 9);
+                Q.in_T[p] = palloc(size_t(9) * up * up);      add(PK_DENSE_T, win, Q.in_T[p], (long long)up * up, up, up, up, 9);
+                Q.out_dense[p] = palloc(size_t(9) * up * up); add(PK_DENSE, wout, Q.out_dense[p], (long long)up * up, up, up, up, 9);
+                Q.out_T[p] = palloc(size_t(9) * up * up);     add(PK_DENSE_T, wout, Q.out_T[p], (long long)up * up, up, up, up, 9);
             }
         }
+        for (int m = 0; m < a->nmlp; ++m) if (a->mlp[m].src == k) mlp(a->mlp[m]);
     }
     a->psize = ps;
     S3D_TRY(a->pbuf.reserve(ps * sizeof(float)));
@@ -203,11 +225,26 @@ static int ae_plan(s3d_ae* a) {
     return 0;
 }
 
+// what a plane block / tex_convs.1 keeps of its forward pass for the backward
+struct BlockAct { float *x[3], *a1[3], *y[3], *s[3], *f[3], *mr; double* part[3]; };
+struct Tex1Act { float *xn[3], *v[3], *a2[3], *y2[3], *f1[3], *mr_in, *mr_hid; double* part[3]; };   // mr_*: {mean, rstd} of f0 (the input norm) / of a2 (the hidden norm)
+
+// One pass over the net: the streams and their edges, and the pieces of ae_step that work on the three planes of a side.  Every
+// piece allocates from the arena in both passes and launches in the run pass only.
 struct AeRun {
     s3d_ae* a; hipStream_t st; float* grads;
     hipStream_t sw = nullptr;             // weight gradients; `side` says whether it is a stream of its own (the caller's stream may be the null stream)
     bool side = false;
     size_t ev_next = 0;
+    // set by ae_step before the first piece runs
+    Geo g{};
+    size_t hw[3] = {};
+    int up = 0, CO = 0;
+    float *feat[3] = {}, *dfeat[3] = {}, *cws2 = nullptr;   // encoder planes and their gradient; workspace of the bias sums (it belongs to their stream)
+    BlockAct A[2];
+    Tex1Act B;
+    DeferredTail tail;
+
     Arena& ar() { return a->arena; }
     bool meas() { return a->arena.measuring; }
     int edge(hipStream_t from, hipStream_t to) {           // `to` waits for what has been enqueued on `from` so far
@@ -224,20 +261,24 @@ struct AeRun {
     }
     const float* F(size_t off) const { return a->flat + off; }
     float* G(size_t off) const { return grads ? grads + off : reinterpret_cast<float*>(uintptr_t(256)); }
+    void planes(float* o[3], int C) { for (int p = 0; p < 3; ++p) o[p] = ar().alloc<float>(hw[p] * C); }
+    void dw3(size_t f, size_t per, float* o[3]) const { for (int p = 0; p < 3; ++p) o[p] = G(f + size_t(p) * per); }
 
-    int conv(ConvKind kind, int cin, int cout, const Geo& g, float* const in[3], const float* const wgt[3], const float* const bias[3],
-             float* const res[3], float* const out[3], int njobs = 3, bool relu = false, hipStream_t on = nullptr, bool use_on = false) {
+    // a side's three planes as the three jobs of one launch.  w: packed offsets; fb: flat offset of the [3 * cout] bias, kNone none
+    int conv3(ConvKind kind, int cin, int cout, float* const in[3], const size_t w[3], size_t fb, float* const res[3], float* const out[3],
+              hipStream_t on) {
         if (meas()) return 0;
         ConvArgs ca; memset(&ca, 0, sizeof ca);
-        ca.B = 1; ca.cin = cin; ca.cout = cout; ca.njobs = njobs; ca.relu = relu ? 1 : 0;
-        for (int p = 0; p < njobs; ++p) {
+        ca.B = 1; ca.cin = cin; ca.cout = cout; ca.njobs = 3;
+        for (int p = 0; p < 3; ++p) {
             ConvJob& J = ca.job[p];
-            J.in = in[p]; J.wgt = wgt[p]; J.bias = bias ? bias[p] : nullptr; J.res = res ? res[p] : nullptr; J.out = out[p];
+            J.in = in[p]; J.wgt = a->P(w[p]); J.bias = fb == kNone ? nullptr : F(fb + size_t(p) * cout); J.res = res ? res[p] : nullptr; J.out = out[p];
             J.h = g.h[p]; J.w = g.w[p];
         }
-        return launch_conv(kind, ca, use_on ? on : st);
+        return launch_conv(kind, ca, on);
     }
-    // the point list as up to kMaxConvJobs 1x1 jobs of one launch (the PBR net's four MLPs advance a layer per launch; Geo has three slots)
+    // the point list as up to kMaxConvJobs 1x1 jobs of one launch, each h = Np / 64 rows of w = 64 points: every MLP of the net
+    // advances a layer per launch in the forward pass, a chain's MLPs take a dgrad per launch in the backward pass
     int lin_jobs(int cin, int cout, long long Np, int njobs, float* const in[], const float* const wgt[], const float* const bias[],
                  float* const out[], bool relu, hipStream_t on) {
         if (meas()) return 0;
@@ -250,22 +291,116 @@ struct AeRun {
         }
         return launch_conv(CONV_1x1, ca, on);
     }
-    // from / use_from: the stream dy was produced on when it is not the caller's (the second MLP chain)
-    int wgrad(int taps, int cin, int cin_store, int cout, const Geo& g, float* const dy[3], int a_cstride, float* const act[3],
-              float* const dW[3], int nplanes = 3, hipStream_t from = nullptr, bool use_from = false) {
+    // from: the stream dy was produced on
+    int wgrad(int taps, int cin, int cin_store, int cout, const Geo& wg, float* const dy[3], int a_cstride, float* const act[3],
+              float* const dW[3], int nplanes, hipStream_t from) {
         WgradArgs w;
-        w.dy.C = cout; w.a.C = a_cstride; w.dy.g = w.a.g = g;
+        w.dy.C = cout; w.a.C = a_cstride; w.dy.g = w.a.g = wg;
         for (int p = 0; p < 3; ++p) { w.dy.p[p] = p < nplanes ? dy[p] : nullptr; w.a.p[p] = p < nplanes ? act[p] : nullptr; }
         w.B = 1; w.cin = cin; w.cout = cout; w.ctot = cin_store; w.taps = taps; w.cin_store = cin_store; w.nplanes = nplanes;
-        w.ksplit = wgrad_ksplit(g, 1, cin, cout, taps);
+        w.ksplit = wgrad_ksplit(wg, 1, cin, cout, taps);
         for (int p = 0; p < nplanes; ++p) { w.part[p] = ar().alloc<float>(wgrad_part_floats(w.ksplit, cin, cout, taps)); w.dW[p] = dW[p]; }
         if (meas()) return 0;
-        hipStream_t src = use_from ? from : st;
-        hipStream_t on = side ? sw : src;
-        S3D_TRY(edge(src, on));                            // dy and the activation are final in the order of the stream that produced them
+        hipStream_t on = side ? sw : from;
+        S3D_TRY(edge(from, on));                           // dy and the activation are final in the order of the stream that produced them
         return launch_wgrad(w, on, &tail);                 // (the split-K partials stay in the arena; every reduction of the pass in ONE launch at its end)
     }
-    DeferredTail tail;
+    // InstanceNorm(affine) + SiLU backward = GroupNorm backward with one channel per group; WRITES dgamma / dbeta
+    int gn_bwd(float* const x[3], float* const dy[3], float* const dx[3], const size_t fg[3], const size_t fbeta[3], float* mr, hipStream_t cs) {
+        GnActBwd s;
+        s.x.C = s.dy.C = s.dx.C = up; s.x.g = s.dy.g = s.dx.g = g;
+        for (int p = 0; p < 3; ++p) {
+            s.x.p[p] = x[p]; s.dy.p[p] = dy[p]; s.dx.p[p] = dx[p];
+            s.gamma[p] = F(fg[p]); s.beta[p] = F(fbeta[p]); s.dgamma[p] = G(fg[p]); s.dbeta[p] = G(fbeta[p]);
+        }
+        s.rowadd = nullptr; s.coladd = nullptr; s.add = nullptr; s.stats.mr = mr; s.film = nullptr; s.dfilm = nullptr; s.film_stride = 0;
+        s.B = 1; s.ngroups = up;
+        s.ws = ar().alloc<float>(gn_bwd_ws_floats(1, up));
+        return meas() ? 0 : launch_gn_act_bwd(s, cs);
+    }
+    // bias gradients are column sums nobody inside the pass reads: side stream.  fb2: a second bias with the same gradient, or kNone
+    int colsum_side(float* const x[3], size_t fb, size_t fb2, hipStream_t cs) {
+        if (meas()) return 0;
+        hipStream_t sb = side ? sw : st;
+        S3D_TRY(edge(cs, sb));
+        float *o[3], *o2[3];
+        dw3(fb, up, o);
+        if (fb2 != kNone) dw3(fb2, up, o2);
+        return launch_colsum3(x, hw, up, cws2, o, fb2 == kNone ? nullptr : o2, sb);
+    }
+
+    // plane block n on chain cs: its slice of the encoder's planes -> A[n].f
+    int block_fwd(int n, hipStream_t cs) {
+        const AeNet& N_ = a->net[n];
+        BlockAct& T = A[n];
+        const ConvKind kind = N_.ks == 3 ? CONV_3x3 : CONV_5x5;
+        planes(T.x, 32); planes(T.a1, up); planes(T.y, up); planes(T.s, up); planes(T.f, up);
+        for (int p = 0; p < 3; ++p) T.part[p] = ar().alloc<double>(size_t(kInNormChunks) * up * 2);
+        T.mr = ar().alloc<float>(size_t(3) * up * 2);
+        if (!meas()) S3D_TRY(launch_slice_pad_nhwc3(feat, T.x, hw, CO, n == 0 ? 0 : a->geo, N_.cin, cs));
+        S3D_TRY(conv3(kind, 32, up, T.x, N_.in_dense, N_.f_in_b, nullptr, T.a1, cs));
+        if (!meas()) {
+            const float *gam[3], *bet[3];
+            for (int p = 0; p < 3; ++p) { gam[p] = F(N_.f_gamma[p]); bet[p] = F(N_.f_beta[p]); }
+            S3D_TRY(launch_inorm_silu3(T.a1, T.part, gam, bet, T.y, hw, up, 1e-6f, T.mr, cs));
+        }
+        S3D_TRY(conv3(CONV_1x1, 32, up, T.x, N_.sc_dense, N_.f_sc_b, nullptr, T.s, cs));
+        return conv3(kind, up, up, T.y, N_.out_dense, N_.f_out_b, T.s, T.f, cs);
+    }
+    // its backward: the block's output gradient dFn -> its slice of dfeat
+    int block_bwd(int n, float* const dFn[3], hipStream_t cs) {
+        const AeNet& N_ = a->net[n];
+        BlockAct& T = A[n];
+        const int taps = N_.ks * N_.ks;
+        const ConvKind kind = N_.ks == 3 ? CONV_3x3 : CONV_5x5;
+        float *d_y[3], *d_xs[3], *d_a1[3], *d_x[3], *dw_out[3], *dw_sc[3], *dw_in[3];
+        planes(d_y, up); planes(d_xs, 32); planes(d_a1, up); planes(d_x, 32);
+        dw3(N_.f_out_w, size_t(up) * up * taps, dw_out); dw3(N_.f_sc_w, size_t(up) * N_.cin, dw_sc); dw3(N_.f_in_w, size_t(up) * N_.cin * taps, dw_in);
+        S3D_TRY(colsum_side(dFn, N_.f_out_b, N_.f_sc_b, cs));      // out conv and shortcut share dy: identical bias gradients, one pass, two outputs
+        S3D_TRY(conv3(kind, up, up, dFn, N_.out_T, kNone, nullptr, d_y, cs));
+        S3D_TRY(wgrad(taps, up, up, up, g, dFn, up, T.y, dw_out, 3, cs));
+        S3D_TRY(conv3(CONV_1x1, up, 32, dFn, N_.sc_T, kNone, nullptr, d_xs, cs));
+        S3D_TRY(wgrad(1, 32, N_.cin, up, g, dFn, 32, T.x, dw_sc, 3, cs));
+        S3D_TRY(gn_bwd(T.a1, d_y, d_a1, N_.f_gamma, N_.f_beta, T.mr, cs));
+        S3D_TRY(colsum_side(d_a1, N_.f_in_b, kNone, cs));
+        S3D_TRY(wgrad(taps, 32, N_.cin, up, g, d_a1, 32, T.x, dw_in, 3, cs));
+        S3D_TRY(conv3(kind, up, 32, d_a1, N_.in_T, kNone, d_xs, d_x, cs));
+        return meas() ? 0 : launch_unslice_nhwc3(d_x, dfeat, hw, CO, n == 0 ? 0 : a->geo, N_.cin, cs);
+    }
+    // tex_convs.1 on f0 = A[1].f -> B.f1
+    int tex1_fwd(hipStream_t cs) {
+        const AeTex1& Q = a->tex1;
+        planes(B.xn, up); planes(B.v, up); planes(B.a2, up); planes(B.y2, up); planes(B.f1, up);
+        for (int p = 0; p < 3; ++p) B.part[p] = ar().alloc<double>(size_t(kInNormChunks) * up * 2);
+        B.mr_in = ar().alloc<float>(size_t(3) * up * 2);
+        B.mr_hid = ar().alloc<float>(size_t(3) * up * 2);
+        const float *gam[3], *bet[3];
+        for (int p = 0; p < 3; ++p) { gam[p] = F(Q.f_gamma[p]); bet[p] = F(Q.f_beta[p]); }
+        if (!meas()) S3D_TRY(launch_inorm_keep3(A[1].f, B.part, gam, bet, B.xn, B.v, hw, up, 1e-6f, B.mr_in, cs));
+        S3D_TRY(conv3(CONV_3x3, up, up, B.v, Q.in_dense, Q.f_in_b, nullptr, B.a2, cs));
+        if (!meas()) S3D_TRY(launch_inorm_silu3(B.a2, B.part, gam, bet, B.y2, hw, up, 1e-6f, B.mr_hid, cs));
+        return conv3(CONV_3x3, up, up, B.y2, Q.out_dense, Q.f_out_b, B.xn, B.f1, cs);
+    }
+    // its backward: dF1 -> d_f0.  norm_p receives its hidden-map gradient first (written) and its input-norm gradient second (added)
+    int tex1_bwd(float* const dF1[3], float* d_f0[3], hipStream_t cs) {
+        const AeTex1& Q = a->tex1;
+        float *d_y2[3], *d_a2[3], *d_u[3], *dw_out[3], *dw_in[3];
+        planes(d_y2, up); planes(d_a2, up); planes(d_u, up); planes(d_f0, up);
+        dw3(Q.f_out_w, size_t(up) * up * Q.taps, dw_out); dw3(Q.f_in_w, size_t(up) * up * Q.taps, dw_in);
+        void* iws = ar().alloc<char>(in_norm_bwd_ws_bytes(up));
+        S3D_TRY(colsum_side(dF1, Q.f_out_b, kNone, cs));
+        S3D_TRY(conv3(CONV_3x3, up, up, dF1, Q.out_T, kNone, nullptr, d_y2, cs));
+        S3D_TRY(wgrad(Q.taps, up, up, up, g, dF1, up, B.y2, dw_out, 3, cs));
+        S3D_TRY(gn_bwd(B.a2, d_y2, d_a2, Q.f_gamma, Q.f_beta, B.mr_hid, cs));      // first use of norm_p: dgamma / dbeta written
+        S3D_TRY(colsum_side(d_a2, Q.f_in_b, kNone, cs));
+        S3D_TRY(wgrad(Q.taps, up, up, up, g, d_a2, up, B.v, dw_in, 3, cs));
+        S3D_TRY(conv3(CONV_3x3, up, up, d_a2, Q.in_T, kNone, nullptr, d_u, cs));
+        if (meas()) return 0;
+        const float *gam[3], *bet[3];
+        float *dg[3], *db[3];
+        for (int p = 0; p < 3; ++p) { gam[p] = F(Q.f_gamma[p]); bet[p] = F(Q.f_beta[p]); dg[p] = G(Q.f_gamma[p]); db[p] = G(Q.f_beta[p]); }
+        return launch_in_norm_bwd3(A[1].f, B.mr_in, gam, bet, dF1, d_u, d_f0, dg, db, hw, up, iws, cs);   // second use: added
+    }
 };
 
 // encode: projections -> pre-activation planes -> InstanceNorm + tanh.  pre/feat: NHWC [hw][CO] per plane
@@ -277,7 +412,11 @@ static int ae_encode(AeRun& R, float* pre[3], float* feat[3], float* mr) {
     return launch_enc_norm(false, pre, feat, mr, nullptr, nullptr, a->enc.g, a->enc.CO, nullptr, R.st);
 }
 
-// Forward + (when grads != null) backward of one batch of points.  pred: [N][1+TC] output.
+// Forward + (when grads != null) backward of one batch of points, for every variant.  pred: [N][1+TC] output.
+// Streams (training with the side streams on; in line everything is the caller's stream, with the same bits): the geometry side on
+// the caller's stream, the texture side — its plane blocks, its MLPs' backward — on chain2 beside it (the two sides share nothing
+// but the encoder's planes, the gather and the scatter), weight and bias gradients on the low-priority side stream.  With one net
+// c2 is the caller's stream and every edge to or from it is a no-op.
 static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* tex, long long N, const float aabb[6],
                    const s3d_ae_loss_cfg& lc, bool groups, float* losses, float* pred_out, float* grads, hipStream_t st) {
     AeRun R{a, st, grads};
@@ -294,94 +433,68 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
         R.sw = a->side;
         R.side = true;
     }
-    const int up = a->up, hid = a->hid, CO = a->geo + a->tex, S = 1 + a->TC, NN = a->nnets;
-    const bool two = NN == 2;                               // (the second chain exists with a second net only)
+    const int up = a->up, hid = a->hid, CO = a->geo + a->tex, S = 1 + a->TC, NN = a->nnets, M = a->nmlp;
+    const bool two = NN == 2;
     const Geo g = a->enc.g;
     const long long Np = (N + 63) / 64 * 64;
     const bool bwd = grads != nullptr || meas;              // the measuring pass sizes the workspace for both
-    size_t hw[3];
-    for (int p = 0; p < 3; ++p) hw[p] = size_t(g.h[p]) * g.w[p];
+    hipStream_t c2 = R.side && two ? a->chain2 : st;        // the texture side's chain
+    hipStream_t chain[2] = {st, c2};
+    R.g = g; R.up = up; R.CO = CO;
+    for (int p = 0; p < 3; ++p) R.hw[p] = size_t(g.h[p]) * g.w[p];
+    int I[6], O[6];
+    mlp_dims(up, hid, 0, I, O);                             // (the hidden layers': the last layer has launchers of its own)
+    int mb[3] = {0, 0, 0};                                  // chain c's MLPs are [mb[c], mb[c + 1])
+    for (int m = 0; m < M; ++m) for (int c = a->mlp[m].chain; c < 2; ++c) ++mb[c + 1];
 
     // ---- encode
-    float *pre[3], *feat[3];
-    for (int p = 0; p < 3; ++p) { pre[p] = ar.alloc<float>(hw[p] * CO); feat[p] = ar.alloc<float>(hw[p] * CO); }
+    float *pre[3];
+    R.planes(pre, CO); R.planes(R.feat, CO);
     float* enc_mr = ar.alloc<float>(size_t(3) * CO * 2);
-    S3D_TRY(ae_encode(R, pre, feat, enc_mr));
+    S3D_TRY(ae_encode(R, pre, R.feat, enc_mr));
 
     // ---- plane blocks
-    struct NetAct { float *x[3], *a1[3], *y[3], *s[3], *f[3], *mr; double* part[3]; } A[2];
-    // (training with the side streams on: the texture net's plane blocks run as a second chain beside the geometry net's — they
-    // share nothing but the encoder's feature planes — here, and again in the backward pass)
-    if (!meas && R.side && two) S3D_TRY(R.edge(st, a->chain2));
-    for (int n = 0; n < NN; ++n) {
-        const AeNet& N_ = a->net[n];
-        NetAct& T = A[n];
-        const bool second = n == 1 && R.side && !meas;
-        hipStream_t cs = second ? a->chain2 : st;
-        for (int p = 0; p < 3; ++p) {
-            T.x[p] = ar.alloc<float>(hw[p] * 32); T.a1[p] = ar.alloc<float>(hw[p] * up); T.y[p] = ar.alloc<float>(hw[p] * up);
-            T.s[p] = ar.alloc<float>(hw[p] * up); T.f[p] = ar.alloc<float>(hw[p] * up);
-            T.part[p] = ar.alloc<double>(size_t(kInNormChunks) * up * 2);
-        }
-        T.mr = ar.alloc<float>(size_t(3) * up * 2);
-        const float *w_in[3], *b_in[3], *w_out[3], *b_out[3], *w_sc[3], *b_sc[3];
-        for (int p = 0; p < 3; ++p) {
-            w_in[p] = a->P(N_.in_dense[p]); b_in[p] = R.F(N_.f_in_b + size_t(p) * up);
-            w_out[p] = a->P(N_.out_dense[p]); b_out[p] = R.F(N_.f_out_b + size_t(p) * up);
-            w_sc[p] = a->P(N_.sc_dense[p]); b_sc[p] = R.F(N_.f_sc_b + size_t(p) * up);
-        }
-        if (!meas) S3D_TRY(launch_slice_pad_nhwc3(feat, T.x, hw, CO, n == 0 ? 0 : a->geo, N_.cin, cs));
-        S3D_TRY(R.conv(CONV_5x5, 32, up, g, T.x, w_in, b_in, nullptr, T.a1, 3, false, cs, true));
-        if (!meas) {
-            const float *gam[3], *bet[3];
-            for (int p = 0; p < 3; ++p) { gam[p] = R.F(N_.f_gamma[p]); bet[p] = R.F(N_.f_beta[p]); }
-            S3D_TRY(launch_inorm_silu3(T.a1, T.part, gam, bet, T.y, hw, up, 1e-6f, T.mr, cs));
-        }
-        S3D_TRY(R.conv(CONV_1x1, 32, up, g, T.x, w_sc, b_sc, nullptr, T.s, 3, false, cs, true));
-        S3D_TRY(R.conv(CONV_5x5, up, up, g, T.y, w_out, b_out, T.s, T.f, 3, false, cs, true));
-    }
-    if (!meas && R.side && two) S3D_TRY(R.edge(a->chain2, st));   // the gather reads both nets' planes
+    S3D_TRY(R.edge(st, c2));
+    for (int n = 0; n < NN; ++n) S3D_TRY(R.block_fwd(n, chain[n]));
+    if (a->has_tex1) S3D_TRY(R.tex1_fwd(c2));
+    S3D_TRY(R.edge(c2, st));                                // the gather reads both sides' planes
     // (measured and not kept: the backward scatter's point sort — 21 small dependent launches that depend on the points alone —
     // enqueued here on the second chain's stream, beside the MLPs' forward pass: every one of them waits for a slot behind the
     // 8192-block launches of that pass, the chain arrives late at its backward half, 5.00 -> 5.30 ms/iteration)
     PointSet ps; ps.pts = pts; ps.N = N; ps.Np = Np;
     for (int k = 0; k < 6; ++k) ps.aabb[k] = aabb[k];
 
-    // ---- points: gather, MLPs
-    float *X0[2] = {nullptr, nullptr}, *H[2][5], *CAT[2];
-    for (int n = 0; n < NN; ++n) {
-        X0[n] = ar.alloc<float>(size_t(Np) * up);
-        for (int l = 0; l < 5; ++l) H[n][l] = ar.alloc<float>(size_t(Np) * hid);
-        CAT[n] = ar.alloc<float>(size_t(Np) * (up + hid));
+    // ---- points: ONE gather per side, then the MLPs a layer per launch
+    float *X0[2] = {nullptr, nullptr}, *Xm[4], *H[5][4], *CAT[4];      // H[l][m]: hidden activation l of MLP m
+    for (int n = 0; n < NN; ++n) X0[n] = ar.alloc<float>(size_t(Np) * up);
+    for (int m = 0; m < M; ++m) {
+        Xm[m] = X0[a->mlp[m].src];
+        for (int l = 0; l < 5; ++l) H[l][m] = ar.alloc<float>(size_t(Np) * hid);
+        CAT[m] = ar.alloc<float>(size_t(Np) * (up + hid));
     }
     float* pred = ar.alloc<float>(size_t(Np) * S);
-    Geo gp; for (int p = 0; p < 3; ++p) { gp.h[p] = p < NN ? int(Np / 64) : 0; gp.w[p] = p < NN ? 64 : 0; }   // the point list as two "planes" (geo, tex)
-    auto lin = [&](int l, float* const in[2], float* const out[2]) -> int {       // both groups in one launch
-        const float *w[3], *b[3];
-        float *i3[3], *o3[3];
-        for (int n = 0; n < NN; ++n) { w[n] = R.F(a->net[n].f_mw[l]); b[n] = R.F(a->net[n].f_mb[l]); i3[n] = in[n]; o3[n] = out[n]; }
-        return R.conv(CONV_1x1, a->net[0].I[l], a->net[0].O[l], gp, i3, w, b, nullptr, o3, NN, /*relu=*/true);
-    };
     if (!meas) {
         const float* fp[2][3] = {};
-        for (int n = 0; n < NN; ++n) for (int p = 0; p < 3; ++p) fp[n][p] = A[n].f[p];
+        for (int n = 0; n < NN; ++n) for (int p = 0; p < 3; ++p) fp[n][p] = n == 1 && a->has_tex1 ? R.B.f1[p] : R.A[n].f[p];
         S3D_TRY(launch_gather(ps, fp, g.h, g.w, up, NN, X0, st));
     }
-    {
-        float *h0[2], *h1[2], *h2[2], *h3[2], *h4[2];
-        for (int n = 0; n < 2; ++n) { const int m = n < NN ? n : 0; h0[n] = H[m][0]; h1[n] = H[m][1]; h2[n] = H[m][2]; h3[n] = H[m][3]; h4[n] = H[m][4]; }
-        S3D_TRY(lin(0, X0, h0)); S3D_TRY(lin(1, h0, h1)); S3D_TRY(lin(2, h1, h2));
-        if (!meas)
-            for (int n = 0; n < NN; ++n) {
-                S3D_TRY(launch_copy_slice(X0[n], 1, up, int(Np / 64), 64, CAT[n], up + hid, 0, st));
-                S3D_TRY(launch_copy_slice(H[n][2], 1, hid, int(Np / 64), 64, CAT[n], up + hid, up, st));
-            }
-        S3D_TRY(lin(3, CAT, h3)); S3D_TRY(lin(4, h3, h4));
-        if (!meas)
-            for (int n = 0; n < NN; ++n)
-                S3D_TRY(launch_last_fwd(H[n][4], R.F(a->net[n].f_mw[5]), R.F(a->net[n].f_mb[5]), hid, a->net[n].nout, n == 1, pred, S,
-                                        n == 0 ? 0 : 1, N, st));
-    }
+    auto lin = [&](int l, float* const in[]) -> int {
+        const float *w[4], *b[4];
+        for (int m = 0; m < M; ++m) { w[m] = R.F(a->mlp[m].f_mw[l]); b[m] = R.F(a->mlp[m].f_mb[l]); }
+        return R.lin_jobs(I[l], O[l], Np, M, in, w, b, H[l], true, st);
+    };
+    S3D_TRY(lin(0, Xm)); S3D_TRY(lin(1, H[0])); S3D_TRY(lin(2, H[1]));
+    if (!meas)
+        for (int m = 0; m < M; ++m) {
+            S3D_TRY(launch_copy_slice(Xm[m], 1, up, int(Np / 64), 64, CAT[m], up + hid, 0, st));
+            S3D_TRY(launch_copy_slice(H[2][m], 1, hid, int(Np / 64), 64, CAT[m], up + hid, up, st));
+        }
+    S3D_TRY(lin(3, CAT)); S3D_TRY(lin(4, H[3]));
+    if (!meas)
+        for (int m = 0; m < M; ++m) {
+            const AeMlp& Q = a->mlp[m];
+            S3D_TRY(launch_last_fwd(H[4][m], R.F(Q.f_mw[5]), R.F(Q.f_mb[5]), hid, Q.nout, Q.sigm, pred, S, Q.ooff, N, st));
+        }
     if (!meas && pred_out) S3D_HIP(hipMemcpyAsync(pred_out, pred, size_t(N) * S * sizeof(float), hipMemcpyDeviceToDevice, st));
 
     // ---- losses and d loss / d (pre-activation outputs)
@@ -389,10 +502,11 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
     float* loss3 = ar.alloc<float>(8);
     float* dout = bwd ? ar.alloc<float>(size_t(Np) * S) : nullptr;
     if (!meas && sdf && groups) {
-        // sdfpbr's eight material channels are three means (rgb | metallic-roughness | normal); any other width is one group, none is sdf
+        // eight material channels are three means (rgb | metallic-roughness | normal); any other width is one group, none is sdf.
+        // The skip net's texture columns are sigmoid outputs, the PBR net's heads are not
         const int gb8[4] = {0, 3, 5, 8}, gb1[4] = {0, a->TC, 0, 0};
         const int ng = a->TC == 8 ? 3 : (a->TC ? 1 : 0);
-        S3D_TRY(launch_ae_loss_groups(pred, sdf, tex, N, Np, a->TC, ng, a->TC == 8 ? gb8 : gb1, /*sigm=*/1, lc.sdf_loss, lc.tex_loss,
+        S3D_TRY(launch_ae_loss_groups(pred, sdf, tex, N, Np, a->TC, ng, a->TC == 8 ? gb8 : gb1, /*sigm=*/a->variant != 2, lc.sdf_loss, lc.tex_loss,
                                       lc.sdf_threshold * lc.tex_threshold_ratio, lc.tex_weight, loss_ws, loss3, grads ? dout : nullptr, st));
         if (losses) S3D_HIP(hipMemcpyAsync(losses, loss3, 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
     } else if (!meas && sdf) {
@@ -403,422 +517,90 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
     if (!bwd) return 0;
 
     // ================================================================= backward
-    // ---- MLPs
-    float* dX0[2];
-    float* cws = ar.alloc<float>(colsum_ws_floats(std::max(hid, up)));
-    float* cws2 = ar.alloc<float>(3 * colsum_ws_floats(up));       // the plane blocks' bias sums (side stream, three planes per launch) have a workspace of their own
-    // The two MLPs' backward chains are independent until the scatter: the texture net's runs on a second stream beside the
-    // geometry net's (side-stream builds only) — each alternates a bandwidth-bound ReLU backward with an MFMA-bound 1x1 dgrad, so
-    // the two chains want different things at most times.  Same kernels on the same operands: same bits.
-    float* cws_n[2] = {cws, ar.alloc<float>(colsum_ws_floats(std::max(hid, up)))};
-    if (!meas && R.side && two) S3D_TRY(R.edge(st, a->chain2));
-    // (issued layer by layer for BOTH nets, not net after net: the two chains then advance together however far the host is ahead)
+    // ---- MLPs.  The two sides' backward chains are independent until the scatter: the texture side's runs on a second stream
+    // beside the geometry side's — each alternates a bandwidth-bound ReLU backward with an MFMA-bound 1x1 dgrad, so the two chains
+    // want different things at most times.  Same kernels on the same operands: same bits.
+    R.cws2 = ar.alloc<float>(3 * colsum_ws_floats(up));
+    float* cws_c[2] = {ar.alloc<float>(colsum_ws_floats(std::max(hid, up))), ar.alloc<float>(colsum_ws_floats(std::max(hid, up)))};   // per chain
+    S3D_TRY(R.edge(st, c2));
+    // hidden layers 4..0: dP = dH * relu'(H_l) ; db_l = colsum(dP) ; dW_l = dP^T in_l ; d in_l = dP W_l
     struct Step { int l; float* act; float* in; int in_stride; float* din; const float* dact; int dstride, coff; };
-    Step steps[2][5];
-    float *dXa_n[2], *dCAT_n[2];
-    hipStream_t cs_n[2];
-    for (int n = 0; n < NN; ++n) {
-        const AeNet& N_ = a->net[n];
-        cs_n[n] = n == 1 && R.side && !meas ? a->chain2 : st;      // this net's chain
+    Step steps[4][5];
+    float *dXa[4], *dCAT[4];
+    for (int m = 0; m < M; ++m) {
+        const AeMlp& Q = a->mlp[m];
         float* dH = ar.alloc<float>(size_t(Np) * hid);            // gradient of a hidden activation (reused)
-        float* dCAT = ar.alloc<float>(size_t(Np) * (up + hid));
-        float* dXa = ar.alloc<float>(size_t(Np) * up);
-        dX0[n] = ar.alloc<float>(size_t(Np) * up);
-        dXa_n[n] = dXa; dCAT_n[n] = dCAT;
-        float* lws = ar.alloc<float>(last_bwd_ws_floats(hid, N_.nout));
-        if (!meas) S3D_TRY(launch_last_bwd(dout, S, n == 0 ? 0 : 1, R.F(N_.f_mw[5]), H[n][4], hid, N_.nout, Np, dH, lws, R.G(N_.f_mw[5]), R.G(N_.f_mb[5]), cs_n[n]));
-        // hidden layers 4..0: dP = dH * relu'(H_l) ; db_l = colsum(dP) ; dW_l = dP^T in_l ; d in_l = dP W_l
-        const Step st5[5] = {{4, H[n][4], H[n][3], hid, dH, dH, hid, 0},
-                             {3, H[n][3], CAT[n], up + hid, dCAT, dH, hid, 0},
-                             {2, H[n][2], H[n][1], hid, dH, dCAT, up + hid, up},
-                             {1, H[n][1], H[n][0], hid, dH, dH, hid, 0},
-                             {0, H[n][0], X0[n], up, dXa, dH, hid, 0}};
-        for (int k = 0; k < 5; ++k) steps[n][k] = st5[k];
-    }
-    for (int kk = 0; kk < 5 * NN; ++kk) {
-            const int k = kk / NN, n = kk % NN;
-            const AeNet& N_ = a->net[n];
-            const Step& s = steps[n][k];
-            hipStream_t cs = cs_n[n];
-            const int I = N_.I[s.l], O = N_.O[s.l];
-            // gradient of the layer's pre-activation: one buffer per layer — the weight gradient that reads it runs on the side
-            // stream while this chain has moved on
-            float* dP = ar.alloc<float>(size_t(Np) * hid);
-            if (!meas) S3D_TRY(launch_relu_bwd(s.dact, s.dstride, s.coff, s.act, dP, Np, O, cws_n[n], R.G(N_.f_mb[s.l]), cs));
-            Geo g1; for (int p = 0; p < 3; ++p) { g1.h[p] = p == 0 ? int(Np / 64) : 0; g1.w[p] = p == 0 ? 64 : 0; }
-            float* dy3[3] = {dP, nullptr, nullptr}; float* a3[3] = {s.in, nullptr, nullptr}; float* dw3[3] = {R.G(N_.f_mw[s.l]), nullptr, nullptr};
-            S3D_TRY(R.wgrad(1, I, I, O, g1, dy3, s.in_stride, a3, dw3, 1, cs, true));
-            const float* wT[3] = {a->P(N_.mT[s.l]), nullptr, nullptr};
-            float* o3[3] = {s.din, nullptr, nullptr};
-            S3D_TRY(R.conv(CONV_1x1, O, I, g1, dy3, wT, nullptr, nullptr, o3, 1, false, cs, true));
-        }
-    for (int n = 0; n < NN; ++n)
-        if (!meas) S3D_TRY(launch_add_slice(dXa_n[n], dCAT_n[n], up + hid, 0, dX0[n], Np, up, cs_n[n]));
-    if (!meas && R.side && two) S3D_TRY(R.edge(a->chain2, st));   // the scatter reads both nets' point gradients
-    // ---- scatter the point gradients onto the planes
-    float* dF[2][3] = {};
-    for (int n = 0; n < NN; ++n) for (int p = 0; p < 3; ++p) dF[n][p] = ar.alloc<float>(hw[p] * up);
-    char* sws = ar.alloc<char>(scatter_ws_bytes(Np, g.h, g.w));
-    if (!meas) {
-        const float* dx[2] = {dX0[0], two ? dX0[1] : nullptr};
-        S3D_TRY(launch_scatter(ps, dF, g.h, g.w, up, NN, dx, sws, st));
-    }
-    // ---- plane blocks
-    float* dfeat[3];
-    for (int p = 0; p < 3; ++p) dfeat[p] = ar.alloc<float>(hw[p] * CO);
-    if (!meas && R.side && two) S3D_TRY(R.edge(st, a->chain2));   // (the scatter's plane gradients are final)
-    for (int n = 0; n < NN; ++n) {
-        const AeNet& N_ = a->net[n];
-        NetAct& T = A[n];
-        const bool second = n == 1 && R.side && !meas;
-        hipStream_t cs = second ? a->chain2 : st;                  // this net's chain (see the forward pass)
-        float *d_y[3], *d_xs[3], *d_a1[3], *d_x[3];
-        for (int p = 0; p < 3; ++p) {
-            d_y[p] = ar.alloc<float>(hw[p] * up); d_xs[p] = ar.alloc<float>(hw[p] * 32);
-            d_a1[p] = ar.alloc<float>(hw[p] * up); d_x[p] = ar.alloc<float>(hw[p] * 32);
-        }
-        const float *w_outT[3], *w_scT[3], *w_inT[3];
-        float *dw_out[3], *dw_sc[3], *dw_in[3];
-        for (int p = 0; p < 3; ++p) {
-            w_outT[p] = a->P(N_.out_T[p]); w_scT[p] = a->P(N_.sc_T[p]); w_inT[p] = a->P(N_.in_T[p]);
-            dw_out[p] = R.G(N_.f_out_w + size_t(p) * up * up * 25); dw_sc[p] = R.G(N_.f_sc_w + size_t(p) * up * N_.cin);
-            dw_in[p] = R.G(N_.f_in_w + size_t(p) * up * N_.cin * 25);
-        }
-        // bias gradients are column sums nobody inside the pass reads: side stream (the workspace `cws2` belongs to it in this phase)
-        hipStream_t sb = R.side ? R.sw : st;
-        if (!meas) {
-            S3D_TRY(R.edge(cs, sb));
-            float *ob[3], *sb2[3];                     // out conv and shortcut share dy: identical bias gradients, one pass, two outputs
-            for (int p = 0; p < 3; ++p) { ob[p] = R.G(N_.f_out_b + size_t(p) * up); sb2[p] = R.G(N_.f_sc_b + size_t(p) * up); }
-            S3D_TRY(launch_colsum3(dF[n], hw, up, cws2, ob, sb2, sb));
-        }
-        S3D_TRY(R.conv(CONV_5x5, up, up, g, dF[n], w_outT, nullptr, nullptr, d_y, 3, false, cs, true));
-        S3D_TRY(R.wgrad(25, up, up, up, g, dF[n], up, T.y, dw_out, 3, cs, true));
-        S3D_TRY(R.conv(CONV_1x1, up, 32, g, dF[n], w_scT, nullptr, nullptr, d_xs, 3, false, cs, true));
-        S3D_TRY(R.wgrad(1, 32, N_.cin, up, g, dF[n], 32, T.x, dw_sc, 3, cs, true));
-        {   // InstanceNorm(affine) + SiLU backward = GroupNorm backward with one channel per group
-            GnActBwd s;
-            s.x.C = s.dy.C = s.dx.C = up; s.x.g = s.dy.g = s.dx.g = g;
-            for (int p = 0; p < 3; ++p) {
-                s.x.p[p] = T.a1[p]; s.dy.p[p] = d_y[p]; s.dx.p[p] = d_a1[p];
-                s.gamma[p] = R.F(N_.f_gamma[p]); s.beta[p] = R.F(N_.f_beta[p]); s.dgamma[p] = R.G(N_.f_gamma[p]); s.dbeta[p] = R.G(N_.f_beta[p]);
-            }
-            s.rowadd = nullptr; s.coladd = nullptr; s.add = nullptr; s.stats.mr = T.mr; s.film = nullptr; s.dfilm = nullptr; s.film_stride = 0;
-            s.B = 1; s.ngroups = up;
-            s.ws = ar.alloc<float>(gn_bwd_ws_floats(1, up));
-            if (!meas) S3D_TRY(launch_gn_act_bwd(s, cs));
-        }
-        if (!meas) {
-            S3D_TRY(R.edge(cs, sb));                    // d_a1 is final
-            float* ib[3];
-            for (int p = 0; p < 3; ++p) ib[p] = R.G(N_.f_in_b + size_t(p) * up);
-            S3D_TRY(launch_colsum3(d_a1, hw, up, cws2, ib, nullptr, sb));
-        }
-        S3D_TRY(R.wgrad(25, 32, N_.cin, up, g, d_a1, 32, T.x, dw_in, 3, cs, true));
-        S3D_TRY(R.conv(CONV_5x5, up, 32, g, d_a1, w_inT, nullptr, d_xs, d_x, 3, false, cs, true));
-        if (!meas)
-            S3D_TRY(launch_unslice_nhwc3(d_x, dfeat, hw, CO, n == 0 ? 0 : a->geo, N_.cin, cs));
-    }
-    if (!meas && R.side && two) S3D_TRY(R.edge(a->chain2, st));   // the encoder's backward reads both nets' slices of dfeat
-    // ---- encoder
-    float* dpre[3];
-    for (int p = 0; p < 3; ++p) dpre[p] = ar.alloc<float>(hw[p] * CO);
-    float* ews = ar.alloc<float>(std::max(enc_wgrad_ws_floats(a->C, CO), enc_norm_bwd_ws_bytes(CO) / sizeof(float)));
-    if (!meas) {
-        S3D_TRY(launch_enc_norm(true, pre, feat, enc_mr, dfeat, dpre, g, CO, ews, st));        // (its chunk sums are consumed before the weight gradient reuses ews)
-        S3D_TRY(launch_enc_wgrad(a->enc, dpre, a->geo, a->tex, ews, R.G(a->f_enc_w[0]), R.G(a->f_enc_b[0]), two ? R.G(a->f_enc_w[1]) : nullptr,
-                                 two ? R.G(a->f_enc_b[1]) : nullptr, st));
-        S3D_TRY(R.tail.flush(R.side ? R.sw : st));        // the 16 weight-gradient reductions (they were 16 launches on the stream the iteration waits for)
-        S3D_TRY(R.edge(R.sw, st));                        // every gradient of the pass is final in the order of the caller's stream (no-op in line)
-    }
-    return 0;
-}
-
-// The PBR net's iteration (variant 2; AutoEncoderGroupPBR, networks.py:227-333).  A function of its own: variants 0 and 1 keep
-// ae_step's launches.  Geometry side: ae_step's, on the caller's stream.  Texture side on chain2: tex_convs.0 (the plane block at
-// 3x3), tex_convs.1 (input norm kept, the same norm_p again on the hidden maps, identity shortcut on the NORMALISED input), ONE
-// gather, three heads.  The four MLPs advance a layer per launch in the forward pass (four jobs); in the backward pass the three
-// heads share chain2: per layer three ReLU backwards, three weight gradients (side stream) and ONE three-job 1x1 dgrad launch.
-// The gradient of the gathered feature is ((rgb) + (mr)) + (normal), each term dXa + dCAT[:, :up], in one launch.  norm_p of
-// tex_convs.1 receives its hidden-map gradient first (written) and its input-norm gradient second (added), both on chain2.
-static int ae_step_pbr(s3d_ae* a, const float* pts, const float* sdf, const float* tex, long long N, const float aabb[6],
-                       const s3d_ae_loss_cfg& lc, float* losses, float* pred_out, float* grads, hipStream_t st) {
-    AeRun R{a, st, grads};
-    Arena& ar = a->arena;
-    const bool meas = ar.measuring;
-    ar.reset();
-    if (!meas && grads && opt_on(OPT_BWD_SIDE)) {
-        if (!a->side) {
-            int least = 0, greatest = 0;
-            (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-            S3D_HIP(hipStreamCreateWithPriority(&a->side, hipStreamNonBlocking, least));
-        }
-        if (!a->chain2) S3D_HIP(hipStreamCreateWithFlags(&a->chain2, hipStreamNonBlocking));
-        R.sw = a->side;
-        R.side = true;
-    }
-    const int up = a->up, hid = a->hid, CO = a->geo + a->tex, S = 9;
-    const Geo g = a->enc.g;
-    const long long Np = (N + 63) / 64 * 64;
-    const bool bwd = grads != nullptr || meas;
-    const AePbr& Q = a->pbr;
-    hipStream_t c2 = R.side && !meas ? a->chain2 : st;      // the texture side's chain
-    hipStream_t sb = R.side ? R.sw : st;                    // bias column sums: nobody inside the pass reads them
-    size_t hw[3];
-    for (int p = 0; p < 3; ++p) hw[p] = size_t(g.h[p]) * g.w[p];
-    auto planes = [&](float* o[3], int C) { for (int p = 0; p < 3; ++p) o[p] = ar.alloc<float>(hw[p] * C); };
-    auto conv3 = [&](ConvKind kind, int cin, int cout, float* const in[3], const size_t w[3], size_t fb, float* const res[3], float* const out[3],
-                     hipStream_t on) -> int {                 // fb: flat offset of the [3 * cout] bias, size_t(-1) none
-        const float *wp[3], *bp[3];
-        for (int p = 0; p < 3; ++p) { wp[p] = a->P(w[p]); bp[p] = fb == size_t(-1) ? nullptr : R.F(fb + size_t(p) * cout); }
-        return R.conv(kind, cin, cout, g, in, wp, fb == size_t(-1) ? nullptr : bp, res, out, 3, false, on, true);
-    };
-
-    // ---- encode
-    float *pre[3], *feat[3];
-    for (int p = 0; p < 3; ++p) { pre[p] = ar.alloc<float>(hw[p] * CO); feat[p] = ar.alloc<float>(hw[p] * CO); }
-    float* enc_mr = ar.alloc<float>(size_t(3) * CO * 2);
-    S3D_TRY(ae_encode(R, pre, feat, enc_mr));
-
-    // ---- plane blocks: geo_convs (5x5) and tex_convs.0 (3x3) are the same block
-    struct BlockAct { float *x[3], *a1[3], *y[3], *s[3], *f[3], *mr; double* part[3]; } A[2];
-    auto block_fwd = [&](int n, hipStream_t cs) -> int {
-        const AeNet& N_ = a->net[n];
-        BlockAct& T = A[n];
-        const ConvKind kind = N_.ks == 3 ? CONV_3x3 : CONV_5x5;
-        planes(T.x, 32); planes(T.a1, up); planes(T.y, up); planes(T.s, up); planes(T.f, up);
-        for (int p = 0; p < 3; ++p) T.part[p] = ar.alloc<double>(size_t(kInNormChunks) * up * 2);
-        T.mr = ar.alloc<float>(size_t(3) * up * 2);
-        if (!meas) S3D_TRY(launch_slice_pad_nhwc3(feat, T.x, hw, CO, n == 0 ? 0 : a->geo, N_.cin, cs));
-        S3D_TRY(conv3(kind, 32, up, T.x, N_.in_dense, N_.f_in_b, nullptr, T.a1, cs));
-        if (!meas) {
-            const float *gam[3], *bet[3];
-            for (int p = 0; p < 3; ++p) { gam[p] = R.F(N_.f_gamma[p]); bet[p] = R.F(N_.f_beta[p]); }
-            S3D_TRY(launch_inorm_silu3(T.a1, T.part, gam, bet, T.y, hw, up, 1e-6f, T.mr, cs));
-        }
-        S3D_TRY(conv3(CONV_1x1, 32, up, T.x, N_.sc_dense, N_.f_sc_b, nullptr, T.s, cs));
-        return conv3(kind, up, up, T.y, N_.out_dense, N_.f_out_b, T.s, T.f, cs);
-    };
-    if (!meas && R.side) S3D_TRY(R.edge(st, c2));
-    S3D_TRY(block_fwd(0, st));
-    S3D_TRY(block_fwd(1, c2));
-    // tex_convs.1 on f0 = A[1].f
-    float *xn[3], *v[3], *a2[3], *y2[3], *f1[3];
-    double* part1[3];
-    planes(xn, up); planes(v, up); planes(a2, up); planes(y2, up); planes(f1, up);
-    for (int p = 0; p < 3; ++p) part1[p] = ar.alloc<double>(size_t(kInNormChunks) * up * 2);
-    float* mr_in = ar.alloc<float>(size_t(3) * up * 2);      // {mean, rstd} of f0 (the input norm) and of a2 (the hidden norm)
-    float* mr_hid = ar.alloc<float>(size_t(3) * up * 2);
-    const float *gam1[3], *bet1[3];
-    for (int p = 0; p < 3; ++p) { gam1[p] = R.F(Q.f_gamma[p]); bet1[p] = R.F(Q.f_beta[p]); }
-    if (!meas) S3D_TRY(launch_inorm_keep3(A[1].f, part1, gam1, bet1, xn, v, hw, up, 1e-6f, mr_in, c2));
-    S3D_TRY(conv3(CONV_3x3, up, up, v, Q.in_dense, Q.f_in_b, nullptr, a2, c2));
-    if (!meas) S3D_TRY(launch_inorm_silu3(a2, part1, gam1, bet1, y2, hw, up, 1e-6f, mr_hid, c2));
-    S3D_TRY(conv3(CONV_3x3, up, up, y2, Q.out_dense, Q.f_out_b, xn, f1, c2));
-    if (!meas && R.side) S3D_TRY(R.edge(c2, st));           // the gather reads both sides' planes
-    PointSet ps; ps.pts = pts; ps.N = N; ps.Np = Np;
-    for (int k = 0; k < 6; ++k) ps.aabb[k] = aabb[k];
-
-    // ---- points: ONE gather per side, four MLPs (0 geo, 1 rgb, 2 mr, 3 normal)
-    constexpr int M = 4;
-    const int I[6] = {up, hid, hid, up + hid, hid, hid};
-    const size_t* f_mw[M] = {a->net[0].f_mw, Q.head[0].f_mw, Q.head[1].f_mw, Q.head[2].f_mw};
-    const size_t* f_mb[M] = {a->net[0].f_mb, Q.head[0].f_mb, Q.head[1].f_mb, Q.head[2].f_mb};
-    const size_t* mT[M] = {a->net[0].mT, Q.head[0].mT, Q.head[1].mT, Q.head[2].mT};
-    const int nout[M] = {1, Q.head[0].nout, Q.head[1].nout, Q.head[2].nout}, ooff[M] = {0, Q.head[0].ooff, Q.head[1].ooff, Q.head[2].ooff};
-    float *X0[2], *Xm[M], *H[M][5], *CAT[M];
-    for (int n = 0; n < 2; ++n) X0[n] = ar.alloc<float>(size_t(Np) * up);
-    for (int m = 0; m < M; ++m) {
-        Xm[m] = X0[m ? 1 : 0];
-        for (int l = 0; l < 5; ++l) H[m][l] = ar.alloc<float>(size_t(Np) * hid);
-        CAT[m] = ar.alloc<float>(size_t(Np) * (up + hid));
-    }
-    float* pred = ar.alloc<float>(size_t(Np) * S);
-    if (!meas) {
-        const float* fp[2][3];
-        for (int p = 0; p < 3; ++p) { fp[0][p] = A[0].f[p]; fp[1][p] = f1[p]; }
-        S3D_TRY(launch_gather(ps, fp, g.h, g.w, up, 2, X0, st));
-    }
-    auto lin = [&](int l, float* const in[M], int lo) -> int {
-        const float *w[M], *b[M];
-        float* out[M];
-        for (int m = 0; m < M; ++m) { w[m] = R.F(f_mw[m][l]); b[m] = R.F(f_mb[m][l]); out[m] = H[m][lo]; }
-        return R.lin_jobs(I[l], hid, Np, M, in, w, b, out, true, st);
-    };
-    {
-        float *h0[M], *h1[M], *h3[M];
-        for (int m = 0; m < M; ++m) { h0[m] = H[m][0]; h1[m] = H[m][1]; h3[m] = H[m][3]; }
-        S3D_TRY(lin(0, Xm, 0)); S3D_TRY(lin(1, h0, 1)); S3D_TRY(lin(2, h1, 2));
-        if (!meas)
-            for (int m = 0; m < M; ++m) {
-                S3D_TRY(launch_copy_slice(Xm[m], 1, up, int(Np / 64), 64, CAT[m], up + hid, 0, st));
-                S3D_TRY(launch_copy_slice(H[m][2], 1, hid, int(Np / 64), 64, CAT[m], up + hid, up, st));
-            }
-        S3D_TRY(lin(3, CAT, 3)); S3D_TRY(lin(4, h3, 4));
-        if (!meas)
-            for (int m = 0; m < M; ++m)                       // pred = sdf | rgb | mr | normal, no sigmoid on the material columns
-                S3D_TRY(launch_last_fwd(H[m][4], R.F(f_mw[m][5]), R.F(f_mb[m][5]), hid, nout[m], /*sigm=*/0, pred, S, ooff[m], N, st));
-    }
-    if (!meas && pred_out) S3D_HIP(hipMemcpyAsync(pred_out, pred, size_t(N) * S * sizeof(float), hipMemcpyDeviceToDevice, st));
-
-    // ---- losses (sdfpbr's three masked means) and d loss / d pred
-    float* loss_ws = ar.alloc<float>(512);
-    float* loss3 = ar.alloc<float>(8);
-    float* dout = bwd ? ar.alloc<float>(size_t(Np) * S) : nullptr;
-    if (!meas && sdf) {
-        const int gb8[4] = {0, 3, 5, 8};
-        S3D_TRY(launch_ae_loss_groups(pred, sdf, tex, N, Np, 8, 3, gb8, /*sigm=*/0, lc.sdf_loss, lc.tex_loss,
-                                      lc.sdf_threshold * lc.tex_threshold_ratio, lc.tex_weight, loss_ws, loss3, grads ? dout : nullptr, st));
-        if (losses) S3D_HIP(hipMemcpyAsync(losses, loss3, 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
-    if (!bwd) return 0;
-
-    // ================================================================= backward
-    // ---- MLPs: the geometry net's chain on the caller's stream, the three heads' on chain2
-    float* cws2 = ar.alloc<float>(3 * colsum_ws_floats(up));
-    float* cws_c[2] = {ar.alloc<float>(colsum_ws_floats(std::max(hid, up))), ar.alloc<float>(colsum_ws_floats(std::max(hid, up)))};
-    if (!meas && R.side) S3D_TRY(R.edge(st, c2));
-    struct Step { int l; float* act; float* in; int in_stride; float* din; const float* dact; int dstride, coff; };
-    Step steps[M][5];
-    float *dXa[M], *dCAT[M];
-    for (int m = 0; m < M; ++m) {
-        hipStream_t cs = m ? c2 : st;
-        float* dH = ar.alloc<float>(size_t(Np) * hid);
         dCAT[m] = ar.alloc<float>(size_t(Np) * (up + hid));
         dXa[m] = ar.alloc<float>(size_t(Np) * up);
-        float* lws = ar.alloc<float>(last_bwd_ws_floats(hid, nout[m]));
-        if (!meas) S3D_TRY(launch_last_bwd(dout, S, ooff[m], R.F(f_mw[m][5]), H[m][4], hid, nout[m], Np, dH, lws, R.G(f_mw[m][5]), R.G(f_mb[m][5]), cs));
-        const Step st5[5] = {{4, H[m][4], H[m][3], hid, dH, dH, hid, 0},
-                             {3, H[m][3], CAT[m], up + hid, dCAT[m], dH, hid, 0},
-                             {2, H[m][2], H[m][1], hid, dH, dCAT[m], up + hid, up},
-                             {1, H[m][1], H[m][0], hid, dH, dH, hid, 0},
-                             {0, H[m][0], Xm[m], up, dXa[m], dH, hid, 0}};
+        float* lws = ar.alloc<float>(last_bwd_ws_floats(hid, Q.nout));
+        if (!meas) S3D_TRY(launch_last_bwd(dout, S, Q.ooff, R.F(Q.f_mw[5]), H[4][m], hid, Q.nout, Np, dH, lws, R.G(Q.f_mw[5]), R.G(Q.f_mb[5]), chain[Q.chain]));
+        const Step st5[5] = {{4, H[4][m], H[3][m], hid, dH, dH, hid, 0},
+                             {3, H[3][m], CAT[m], up + hid, dCAT[m], dH, hid, 0},
+                             {2, H[2][m], H[1][m], hid, dH, dCAT[m], up + hid, up},
+                             {1, H[1][m], H[0][m], hid, dH, dH, hid, 0},
+                             {0, H[0][m], Xm[m], up, dXa[m], dH, hid, 0}};
         for (int k = 0; k < 5; ++k) steps[m][k] = st5[k];
     }
+    // Issued layer by layer for both chains, not chain after chain: the two then advance together however far the host is ahead.
+    // Within a layer chain by chain: each MLP's ReLU backward and weight gradient, then the chain's dgrad with its MLPs as jobs.
     Geo g1; for (int p = 0; p < 3; ++p) { g1.h[p] = p == 0 ? int(Np / 64) : 0; g1.w[p] = p == 0 ? 64 : 0; }
-    for (int k = 0; k < 5; ++k) {
-        const int l = steps[0][k].l, Il = I[l];
-        float* dP[M];
-        for (int m = 0; m < M; ++m) {
-            const Step& s = steps[m][k];
-            hipStream_t cs = m ? c2 : st;
-            dP[m] = ar.alloc<float>(size_t(Np) * hid);
-            if (!meas) S3D_TRY(launch_relu_bwd(s.dact, s.dstride, s.coff, s.act, dP[m], Np, hid, cws_c[m ? 1 : 0], R.G(f_mb[m][l]), cs));
-            float* dy3[3] = {dP[m], nullptr, nullptr}; float* a3[3] = {s.in, nullptr, nullptr}; float* dw3[3] = {R.G(f_mw[m][l]), nullptr, nullptr};
-            S3D_TRY(R.wgrad(1, Il, Il, hid, g1, dy3, s.in_stride, a3, dw3, 1, cs, true));
+    for (int k = 0; k < 5; ++k)
+        for (int c = 0; c < NN; ++c) {
+            const int l = steps[0][k].l, m0 = mb[c], nj = mb[c + 1] - m0;
+            // gradient of the layer's pre-activation: one buffer per layer — the weight gradient that reads it runs on the side
+            // stream while this chain has moved on
+            float *dP[3], *din[3];
+            const float* wT[3];
+            for (int j = 0; j < nj; ++j) {
+                const AeMlp& Q = a->mlp[m0 + j];
+                const Step& s = steps[m0 + j][k];
+                dP[j] = ar.alloc<float>(size_t(Np) * hid);
+                if (!meas) S3D_TRY(launch_relu_bwd(s.dact, s.dstride, s.coff, s.act, dP[j], Np, O[l], cws_c[c], R.G(Q.f_mb[l]), chain[c]));
+                float* dy3[3] = {dP[j], nullptr, nullptr}; float* a3[3] = {s.in, nullptr, nullptr}; float* dw[3] = {R.G(Q.f_mw[l]), nullptr, nullptr};
+                S3D_TRY(R.wgrad(1, I[l], I[l], O[l], g1, dy3, s.in_stride, a3, dw, 1, chain[c]));
+                wT[j] = a->P(Q.mT[l]); din[j] = s.din;
+            }
+            S3D_TRY(R.lin_jobs(O[l], I[l], Np, nj, dP, wT, nullptr, din, false, chain[c]));
         }
-        {   // geometry net's dgrad, then the heads' as three jobs of one launch
-            const float* wT[1] = {a->P(mT[0][l])};
-            float* o[1] = {steps[0][k].din};
-            S3D_TRY(R.lin_jobs(hid, Il, Np, 1, dP, wT, nullptr, o, false, st));
-            const float* wT3[3] = {a->P(mT[1][l]), a->P(mT[2][l]), a->P(mT[3][l])};
-            float* o3[3] = {steps[1][k].din, steps[2][k].din, steps[3][k].din};
-            S3D_TRY(R.lin_jobs(hid, Il, Np, 3, dP + 1, wT3, nullptr, o3, false, c2));
-        }
+    // ---- a side's point gradient: dXa + dCAT[:, :up] of its MLP, or of its three heads as ((rgb) + (mr)) + (normal) in one launch
+    float* dX0[2] = {nullptr, nullptr};
+    for (int c = 0; c < NN; ++c) dX0[c] = ar.alloc<float>(size_t(Np) * up);
+    for (int c = 0; c < NN && !meas; ++c) {
+        if (mb[c + 1] - mb[c] == 3) S3D_TRY(launch_add_slices3(dXa + mb[c], dCAT + mb[c], up + hid, 0, dX0[c], Np, up, chain[c]));
+        else S3D_TRY(launch_add_slice(dXa[mb[c]], dCAT[mb[c]], up + hid, 0, dX0[c], Np, up, chain[c]));
     }
-    float* dX0[2] = {ar.alloc<float>(size_t(Np) * up), ar.alloc<float>(size_t(Np) * up)};
-    if (!meas) {
-        S3D_TRY(launch_add_slice(dXa[0], dCAT[0], up + hid, 0, dX0[0], Np, up, st));
-        S3D_TRY(launch_add_slices3(dXa + 1, dCAT + 1, up + hid, 0, dX0[1], Np, up, c2));
-    }
-    if (!meas && R.side) S3D_TRY(R.edge(c2, st));            // the scatter reads both sides' point gradients
-    // ---- scatter
+    S3D_TRY(R.edge(c2, st));                                // the scatter reads both sides' point gradients
+    // ---- scatter the point gradients onto the planes
     float* dF[2][3] = {};
-    for (int n = 0; n < 2; ++n) planes(dF[n], up);
+    for (int n = 0; n < NN; ++n) R.planes(dF[n], up);
     char* sws = ar.alloc<char>(scatter_ws_bytes(Np, g.h, g.w));
-    if (!meas) S3D_TRY(launch_scatter(ps, dF, g.h, g.w, up, 2, dX0, sws, st));
+    if (!meas) S3D_TRY(launch_scatter(ps, dF, g.h, g.w, up, NN, dX0, sws, st));
     // ---- plane blocks
-    float* dfeat[3];
-    planes(dfeat, CO);
-    if (!meas && R.side) S3D_TRY(R.edge(st, c2));
-    auto gn_bwd = [&](float* const x[3], float* const dy[3], float* const dx[3], const size_t fg[3], const size_t fbeta[3], float* mr,
-                      hipStream_t cs) -> int {              // InstanceNorm(affine) + SiLU backward; WRITES dgamma / dbeta
-        GnActBwd s;
-        s.x.C = s.dy.C = s.dx.C = up; s.x.g = s.dy.g = s.dx.g = g;
-        for (int p = 0; p < 3; ++p) {
-            s.x.p[p] = x[p]; s.dy.p[p] = dy[p]; s.dx.p[p] = dx[p];
-            s.gamma[p] = R.F(fg[p]); s.beta[p] = R.F(fbeta[p]); s.dgamma[p] = R.G(fg[p]); s.dbeta[p] = R.G(fbeta[p]);
-        }
-        s.rowadd = nullptr; s.coladd = nullptr; s.add = nullptr; s.stats.mr = mr; s.film = nullptr; s.dfilm = nullptr; s.film_stride = 0;
-        s.B = 1; s.ngroups = up;
-        s.ws = ar.alloc<float>(gn_bwd_ws_floats(1, up));
-        return meas ? 0 : launch_gn_act_bwd(s, cs);
-    };
-    auto colsum_side = [&](float* const x[3], size_t fb, size_t fb2, hipStream_t cs) -> int {
-        if (meas) return 0;
-        S3D_TRY(R.edge(cs, sb));
-        float *o[3], *o2[3];
-        for (int p = 0; p < 3; ++p) { o[p] = R.G(fb + size_t(p) * up); o2[p] = fb2 == size_t(-1) ? nullptr : R.G(fb2 + size_t(p) * up); }
-        return launch_colsum3(x, hw, up, cws2, o, fb2 == size_t(-1) ? nullptr : o2, sb);
-    };
-    auto dw3 = [&](size_t f, size_t per, float* o[3]) { for (int p = 0; p < 3; ++p) o[p] = R.G(f + size_t(p) * per); };
-    // the block of block_fwd: its output gradient dFn -> its slice of dfeat
-    auto block_bwd = [&](int n, float* const dFn[3], hipStream_t cs) -> int {
-        const AeNet& N_ = a->net[n];
-        BlockAct& T = A[n];
-        const int taps = N_.ks * N_.ks;
-        const ConvKind kind = N_.ks == 3 ? CONV_3x3 : CONV_5x5;
-        float *d_y[3], *d_xs[3], *d_a1[3], *d_x[3], *dw_out[3], *dw_sc[3], *dw_in[3];
-        planes(d_y, up); planes(d_xs, 32); planes(d_a1, up); planes(d_x, 32);
-        dw3(N_.f_out_w, size_t(up) * up * taps, dw_out); dw3(N_.f_sc_w, size_t(up) * N_.cin, dw_sc); dw3(N_.f_in_w, size_t(up) * N_.cin * taps, dw_in);
-        S3D_TRY(colsum_side(dFn, N_.f_out_b, N_.f_sc_b, cs));
-        S3D_TRY(conv3(kind, up, up, dFn, N_.out_T, size_t(-1), nullptr, d_y, cs));
-        S3D_TRY(R.wgrad(taps, up, up, up, g, dFn, up, T.y, dw_out, 3, cs, true));
-        S3D_TRY(conv3(CONV_1x1, up, 32, dFn, N_.sc_T, size_t(-1), nullptr, d_xs, cs));
-        S3D_TRY(R.wgrad(1, 32, N_.cin, up, g, dFn, 32, T.x, dw_sc, 3, cs, true));
-        S3D_TRY(gn_bwd(T.a1, d_y, d_a1, N_.f_gamma, N_.f_beta, T.mr, cs));
-        S3D_TRY(colsum_side(d_a1, N_.f_in_b, size_t(-1), cs));
-        S3D_TRY(R.wgrad(taps, 32, N_.cin, up, g, d_a1, 32, T.x, dw_in, 3, cs, true));
-        S3D_TRY(conv3(kind, up, 32, d_a1, N_.in_T, size_t(-1), d_xs, d_x, cs));
-        return meas ? 0 : launch_unslice_nhwc3(d_x, dfeat, hw, CO, n == 0 ? 0 : a->geo, N_.cin, cs);
-    };
-    S3D_TRY(block_bwd(0, dF[0], st));
-    {   // tex_convs.1: dF1 = dF[1]
-        float *d_y2[3], *d_a2[3], *d_u[3], *d_f0[3], *dw_out[3], *dw_in[3];
-        planes(d_y2, up); planes(d_a2, up); planes(d_u, up); planes(d_f0, up);
-        dw3(Q.f_out_w, size_t(up) * up * 9, dw_out); dw3(Q.f_in_w, size_t(up) * up * 9, dw_in);
-        void* iws = ar.alloc<char>(in_norm_bwd_ws_bytes(up));
-        S3D_TRY(colsum_side(dF[1], Q.f_out_b, size_t(-1), c2));
-        S3D_TRY(conv3(CONV_3x3, up, up, dF[1], Q.out_T, size_t(-1), nullptr, d_y2, c2));
-        S3D_TRY(R.wgrad(9, up, up, up, g, dF[1], up, y2, dw_out, 3, c2, true));
-        S3D_TRY(gn_bwd(a2, d_y2, d_a2, Q.f_gamma, Q.f_beta, mr_hid, c2));          // first use of norm_p: dgamma / dbeta written
-        S3D_TRY(colsum_side(d_a2, Q.f_in_b, size_t(-1), c2));
-        S3D_TRY(R.wgrad(9, up, up, up, g, d_a2, up, v, dw_in, 3, c2, true));
-        S3D_TRY(conv3(CONV_3x3, up, up, d_a2, Q.in_T, size_t(-1), nullptr, d_u, c2));
-        if (!meas) {
-            float *dg[3], *db[3];
-            for (int p = 0; p < 3; ++p) { dg[p] = R.G(Q.f_gamma[p]); db[p] = R.G(Q.f_beta[p]); }
-            S3D_TRY(launch_in_norm_bwd3(A[1].f, mr_in, gam1, bet1, dF[1], d_u, d_f0, dg, db, hw, up, iws, c2));   // second use: added
-        }
-        S3D_TRY(block_bwd(1, d_f0, c2));
+    R.planes(R.dfeat, CO);
+    S3D_TRY(R.edge(st, c2));                                // (the scatter's plane gradients are final)
+    S3D_TRY(R.block_bwd(0, dF[0], st));
+    if (two) {
+        float* d_f0[3];
+        if (a->has_tex1) S3D_TRY(R.tex1_bwd(dF[1], d_f0, c2));
+        S3D_TRY(R.block_bwd(1, a->has_tex1 ? d_f0 : dF[1], c2));
     }
-    if (!meas && R.side) S3D_TRY(R.edge(c2, st));            // the encoder's backward reads both slices of dfeat
+    S3D_TRY(R.edge(c2, st));                                // the encoder's backward reads both sides' slices of dfeat
     // ---- encoder
     float* dpre[3];
-    planes(dpre, CO);
+    R.planes(dpre, CO);
     float* ews = ar.alloc<float>(std::max(enc_wgrad_ws_floats(a->C, CO), enc_norm_bwd_ws_bytes(CO) / sizeof(float)));
     if (!meas) {
-        S3D_TRY(launch_enc_norm(true, pre, feat, enc_mr, dfeat, dpre, g, CO, ews, st));
-        S3D_TRY(launch_enc_wgrad(a->enc, dpre, a->geo, a->tex, ews, R.G(a->f_enc_w[0]), R.G(a->f_enc_b[0]), R.G(a->f_enc_w[1]), R.G(a->f_enc_b[1]), st));
-        S3D_TRY(R.tail.flush(R.side ? R.sw : st));
-        S3D_TRY(R.edge(R.sw, st));
+        S3D_TRY(launch_enc_norm(true, pre, R.feat, enc_mr, R.dfeat, dpre, g, CO, ews, st));    // (its chunk sums are consumed before the weight gradient reuses ews)
+        S3D_TRY(launch_enc_wgrad(a->enc, dpre, a->geo, a->tex, ews, R.G(a->f_enc_w[0]), R.G(a->f_enc_b[0]), two ? R.G(a->f_enc_w[1]) : nullptr,
+                                 two ? R.G(a->f_enc_b[1]) : nullptr, st));
+        S3D_TRY(R.tail.flush(R.side ? R.sw : st));        // the weight-gradient reductions of the pass (they were 16 launches on the stream the iteration waits for)
+        S3D_TRY(R.edge(R.sw, st));                        // every gradient of the pass is final in the order of the caller's stream (no-op in line)
     }
     return 0;
 }
 
 static int ae_run(s3d_ae* a, const float* pts, const float* sdf, const float* tex, long long N, const float aabb[6],
                   const s3d_ae_loss_cfg& lc, bool groups, float* losses, float* pred, float* grads, hipStream_t st) {
-    if (a->variant == 2) {                                  // the PBR net: its own iteration, always the grouped losses
-        a->arena.measuring = true; a->arena.high = 0;
-        int rc = ae_step_pbr(a, pts, sdf, tex, N, aabb, lc, losses, pred, grads, st);
-        a->arena.measuring = false;
-        if (rc) return rc;
-        if (a->arena.high > a->arena.buf.cap) {
-            S3D_HIP(hipStreamSynchronize(st));
-            S3D_TRY(a->arena.buf.reserve(a->arena.high + (a->arena.high >> 3)));
-        }
-        return ae_step_pbr(a, pts, sdf, tex, N, aabb, lc, losses, pred, grads, st);
-    }
     a->arena.measuring = true; a->arena.high = 0;
     int rc = ae_step(a, pts, sdf, tex, N, aabb, lc, groups, losses, pred, grads, st);
     a->arena.measuring = false;
@@ -830,6 +612,37 @@ static int ae_run(s3d_ae* a, const float* pts, const float* sdf, const float* te
     return ae_step(a, pts, sdf, tex, N, aabb, lc, groups, losses, pred, grads, st);
 }
 
+// what every constructor refuses; the geometry-only net (variant 1) ignores the tex_* fields
+static int ae_check_cfg(const s3d_decoder_cfg* cfg, int variant) {
+    const bool tex = variant != 1;
+    const int tfc = tex ? cfg->tex_feat_channels : 0;
+    S3D_CHECK(variant != 2 || cfg->tex_channels == 8, S3D_ERR_UNSUPPORTED, "ae training: the PBR net has 8 material channels, got tex_channels=%d",
+              cfg->tex_channels);
+    S3D_CHECK(cfg->mlp_hidden_layers == 4, S3D_ERR_UNSUPPORTED, "ae: mlp_hidden_layers=%d (only the default 4 is built)", cfg->mlp_hidden_layers);
+    S3D_CHECK(cfg->feat_channel_up % 32 == 0 && cfg->mlp_hidden_channels % 32 == 0 && cfg->feat_channel_up > 0 && cfg->mlp_hidden_channels > 0,
+              S3D_ERR_UNSUPPORTED, "ae training: feat_channel_up=%d and mlp_hidden_channels=%d must be multiples of 32",
+              cfg->feat_channel_up, cfg->mlp_hidden_channels);
+    S3D_CHECK(cfg->geo_feat_channels >= 1 && (!tex || tfc >= 1) && cfg->geo_feat_channels + tfc <= 12 &&
+              cfg->geo_feat_channels % 4 == 0 && tfc % 4 == 0,
+              S3D_ERR_UNSUPPORTED, "ae training: feature groups must be multiples of 4 channels, at most 12 together; got geo=%d tex=%d",
+              cfg->geo_feat_channels, tfc);
+    S3D_CHECK(!tex || (cfg->tex_channels >= 1 && cfg->tex_channels <= 8), S3D_ERR_UNSUPPORTED, "ae: tex_channels must be 1..8, got %d",
+              cfg->tex_channels);
+    return 0;
+}
+static int ae_new(const s3d_decoder_cfg* cfg, int variant, s3d_ae** out) {
+    const bool tex = variant != 1;
+    std::unique_ptr<s3d_ae> a(new s3d_ae());
+    a->cfg = *cfg;
+    a->variant = variant; a->nnets = tex ? 2 : 1;
+    a->geo = cfg->geo_feat_channels; a->tex = tex ? cfg->tex_feat_channels : 0; a->up = cfg->feat_channel_up; a->hid = cfg->mlp_hidden_channels;
+    a->TC = tex ? cfg->tex_channels : 0; a->C = 1 + a->TC;
+    ae_describe(a.get());
+    ae_specs(a.get());
+    *out = a.release();
+    return 0;
+}
+
 }  // namespace s3d
 
 extern "C" {
@@ -838,48 +651,14 @@ int s3d_ae_create(const s3d_decoder_cfg* cfg, s3d_ae** out) { return s3d_ae_crea
 int s3d_ae_create_variant(const s3d_decoder_cfg* cfg, int variant, s3d_ae** out) {
     S3D_CHECK(cfg && out, S3D_ERR_INVALID, "ae_create: null argument");
     S3D_CHECK(variant >= 0 && variant <= 2, S3D_ERR_INVALID, "ae_create: variant %d (0 skip net, 1 geometry only, 2 PBR net)", variant);
-    S3D_CHECK(variant != 2 || cfg->tex_channels == 8, S3D_ERR_UNSUPPORTED, "ae: the PBR net has 8 material channels, got tex_channels=%d",
-              cfg->tex_channels);
+    S3D_TRY(ae_check_cfg(cfg, variant));
     S3D_CHECK(variant != 2, S3D_ERR_UNSUPPORTED, "ae training: the PBR net (variant 2) is not built by this call; use s3d_ae_create_pbr");
-    const bool tex = variant != 1;
-    S3D_CHECK(cfg->mlp_hidden_layers == 4, S3D_ERR_UNSUPPORTED, "ae: mlp_hidden_layers=%d (only the default 4 is built)", cfg->mlp_hidden_layers);
-    S3D_CHECK(cfg->feat_channel_up % 32 == 0 && cfg->mlp_hidden_channels % 32 == 0 && cfg->feat_channel_up > 0 && cfg->mlp_hidden_channels > 0,
-              S3D_ERR_UNSUPPORTED, "ae training: feat_channel_up=%d and mlp_hidden_channels=%d must be multiples of 32",
-              cfg->feat_channel_up, cfg->mlp_hidden_channels);
-    const int tfc = tex ? cfg->tex_feat_channels : 0;           // (the geometry-only net ignores the tex_* fields)
-    S3D_CHECK(cfg->geo_feat_channels >= 1 && (!tex || tfc >= 1) && cfg->geo_feat_channels + tfc <= 12 &&
-              cfg->geo_feat_channels % 4 == 0 && tfc % 4 == 0,
-              S3D_ERR_UNSUPPORTED, "ae training: feature groups must be multiples of 4 channels, at most 12 together");
-    S3D_CHECK(!tex || (cfg->tex_channels >= 1 && cfg->tex_channels <= 8), S3D_ERR_UNSUPPORTED, "ae: tex_channels must be 1..8, got %d",
-              cfg->tex_channels);
-    std::unique_ptr<s3d_ae> a(new s3d_ae());
-    a->cfg = *cfg;
-    a->variant = variant; a->nnets = tex ? 2 : 1;
-    a->geo = cfg->geo_feat_channels; a->tex = tfc; a->up = cfg->feat_channel_up; a->hid = cfg->mlp_hidden_channels;
-    a->TC = tex ? cfg->tex_channels : 0; a->C = 1 + a->TC;
-    ae_specs(a.get());
-    *out = a.release();
-    return 0;
+    return ae_new(cfg, variant, out);
 }
 int s3d_ae_create_pbr(const s3d_decoder_cfg* cfg, s3d_ae** out) {
     S3D_CHECK(cfg && out, S3D_ERR_INVALID, "ae_create_pbr: null argument");
-    S3D_CHECK(cfg->tex_channels == 8, S3D_ERR_UNSUPPORTED, "ae training: the PBR net has 8 material channels, got tex_channels=%d", cfg->tex_channels);
-    S3D_CHECK(cfg->mlp_hidden_layers == 4, S3D_ERR_UNSUPPORTED, "ae: mlp_hidden_layers=%d (only the default 4 is built)", cfg->mlp_hidden_layers);
-    S3D_CHECK(cfg->feat_channel_up % 32 == 0 && cfg->mlp_hidden_channels % 32 == 0 && cfg->feat_channel_up > 0 && cfg->mlp_hidden_channels > 0,
-              S3D_ERR_UNSUPPORTED, "ae training: feat_channel_up=%d and mlp_hidden_channels=%d must be multiples of 32",
-              cfg->feat_channel_up, cfg->mlp_hidden_channels);
-    S3D_CHECK(cfg->geo_feat_channels >= 1 && cfg->tex_feat_channels >= 1 && cfg->geo_feat_channels + cfg->tex_feat_channels <= 12 &&
-              cfg->geo_feat_channels % 4 == 0 && cfg->tex_feat_channels % 4 == 0,
-              S3D_ERR_UNSUPPORTED, "ae training: feature groups must be multiples of 4 channels, at most 12 together; got geo=%d tex=%d",
-              cfg->geo_feat_channels, cfg->tex_feat_channels);
-    std::unique_ptr<s3d_ae> a(new s3d_ae());
-    a->cfg = *cfg;
-    a->variant = 2; a->nnets = 2;
-    a->geo = cfg->geo_feat_channels; a->tex = cfg->tex_feat_channels; a->up = cfg->feat_channel_up; a->hid = cfg->mlp_hidden_channels;
-    a->TC = 8; a->C = 9;
-    ae_specs(a.get());
-    *out = a.release();
-    return 0;
+    S3D_TRY(ae_check_cfg(cfg, 2));
+    return ae_new(cfg, 2, out);
 }
 void s3d_ae_destroy(s3d_ae* a) { delete a; }
 int s3d_ae_out_channels(const s3d_ae* a) { return a ? 1 + a->TC : S3D_ERR_INVALID; }

@@ -581,16 +581,17 @@ size_t scatter_ws_bytes(long long Np, const int ph[3], const int pw[3]) {
     for (int p = 0; p < 3; ++p) cells += size_t(ph[p]) * pw[p] + 2;
     return ((cub + 255) & ~size_t(255)) + (size_t(12) * Np + cells) * sizeof(unsigned) + 1024;
 }
-// Two halves: the point ORDER (cell keys, one radix sort over the three planes' keys, bin starts) depends on the points alone;
-// the scatter proper follows when dX is final.  (Enqueued early — on the second chain's stream beside the MLPs' forward pass, or
-// on the idle weight-gradient stream from the first moment of the iteration — the order costs more than it returns: DESIGN.md §9.)
-int launch_scatter_prepare(const PointSet& ps, const int ph[3], const int pw[3], int C, int nnets, void* ws, ScatterPlan& plan, hipStream_t st) {
-    ScatterSortedArgs& s = plan.args; memset(&s, 0, sizeof s);
+// First the point ORDER (cell keys, one radix sort over the three planes' keys, bin starts), which depends on the points alone,
+// then the scatter proper.  (The order enqueued early as a launcher of its own — on the second chain's stream beside the MLPs'
+// forward pass, or on the idle weight-gradient stream from the first moment of the iteration — costs more than it returns:
+// DESIGN.md §9.)
+int launch_scatter(const PointSet& ps, float* const dfeat[2][3], const int ph[3], const int pw[3], int C, int nnets,
+                   const float* const dX[2], void* ws, hipStream_t st) {
+    ScatterSortedArgs s; memset(&s, 0, sizeof s);
     GatherArgs& a = s.g;
     a.pts = ps.pts; a.N = ps.N; a.Np = ps.Np; a.C = C; a.nnets = nnets;
     for (int k = 0; k < 3; ++k) { a.amin[k] = ps.aabb[k]; a.ainv[k] = 1.f / (ps.aabb[3 + k] - ps.aabb[k]); a.ph[k] = ph[k]; a.pw[k] = pw[k]; }
     const long long Np = ps.Np;
-    plan.ready = false;
     if (!Np) return 0;
     size_t cub = 0;
     unsigned* d0 = nullptr;
@@ -618,29 +619,18 @@ int launch_scatter_prepare(const PointSet& ps, const int ph[3], const int pw[3],
         b0 += ncell + 1;
         s.begin[p + 1] = s.begin[p] + (long long)ncell * (C / 4);
     }
-    plan.ready = true;
-    return 0;
-}
-int launch_scatter_apply(ScatterPlan& plan, float* const dfeat[2][3], const float* const dX[2], hipStream_t st) {
-    if (!plan.ready) return 0;
-    ScatterSortedArgs& s = plan.args;
-    for (int n = 0; n < s.g.nnets; ++n) { s.g.dX[n] = dX[n]; for (int p = 0; p < 3; ++p) s.g.dfeat[n][p] = dfeat[n][p]; }
-    hipLaunchKernelGGL(k_scatter_sorted, dim3(cdivll(s.begin[3] * s.g.nnets, 256)), dim3(256), 0, st, s);
+    for (int n = 0; n < nnets; ++n) { a.dX[n] = dX[n]; for (int p = 0; p < 3; ++p) a.dfeat[n][p] = dfeat[n][p]; }
+    hipLaunchKernelGGL(k_scatter_sorted, dim3(cdivll(s.begin[3] * nnets, 256)), dim3(256), 0, st, s);
     S3D_HIP(hipGetLastError());
     return 0;
-}
-int launch_scatter(const PointSet& ps, float* const dfeat[2][3], const int ph[3], const int pw[3], int C, int nnets,
-                   const float* const dX[2], void* ws, hipStream_t st) {
-    ScatterPlan plan;
-    S3D_TRY(launch_scatter_prepare(ps, ph, pw, C, nnets, ws, plan, st));
-    return launch_scatter_apply(plan, dfeat, dX, st);
 }
 
 // ------------------------------------------------------------------ small element-wise pieces of the MLP
 // dpre[n][c] = dact[n][coff + c] * (act[n][c] > 0)   (dact row stride dstride), and the column sums of dpre (the bias
 // gradient) in the same pass: per-chunk partials here, added in chunk order by k_colsum_fin
 // (round 5: 1024 threads per chunk with four rows of loads in flight per thread — 16 waves per CU instead of 4 walking 64
-// dependent trips: the launch moved 200 MB in 115 us —; the column-sum pass below is the same kernel without the mask)
+// dependent trips: the launch moved 200 MB in 115 us.  MASK = false was the single-plane column-sum pass, which k_colsum3_part
+// replaced; only MASK = true is instantiated, under the kernel name the profiles know)
 constexpr int kColChunks = 256, kColThreads = 1024;
 template <bool MASK>
 __global__ __launch_bounds__(kColThreads) void k_relu_bwd(const float* __restrict__ dact, int dstride, int coff, const float* __restrict__ act,
@@ -864,20 +854,9 @@ int launch_in_norm_bwd3(const float* const x[3], const float* mr, const float* c
     return 0;
 }
 
-// column sums of a [rows][C] matrix (bias gradients): two-stage, fixed order
+// column sums of [rows][C] matrices (bias gradients): two-stage, fixed order
 size_t colsum_ws_floats(int C) { return size_t(kColChunks) * C; }
-int launch_colsum(const float* x, long long rows, int C, float* ws, float* out, hipStream_t st, float* out2) {
-    S3D_CHECK(C % 4 == 0 && C <= 1024, S3D_ERR_INVALID, "colsum: C=%d", C);
-    const int cq = C / 4, pl = std::max(1, kColThreads / cq);
-    hipLaunchKernelGGL(k_relu_bwd<false>, dim3(kColChunks), dim3(cq * pl), size_t(pl) * C * sizeof(float), st, x, C, 0, (const float*)nullptr,
-                       (float*)nullptr, rows, C, ws);
-    S3D_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_colsum_fin, dim3(cdiv(C, 64)), dim3(1024), 0, st, ws, out, C, out2);
-    S3D_HIP(hipGetLastError());
-    return 0;
-}
-
-// the same for three planes in one launch pair (blockIdx.y; ws: 3 * colsum_ws_floats(C)) — the plane blocks' bias gradients were
+// three planes in one launch pair (blockIdx.y; ws: 3 * colsum_ws_floats(C)) — the plane blocks' bias gradients were
 // twelve launch pairs per iteration on the weight-gradient stream, which is what the iteration waits for
 struct ColSum3Args { const float* x[3]; long long rows[3]; float* out[3]; float* out2[3]; float* part; int C; };
 __global__ __launch_bounds__(kColThreads) void k_colsum3_part(ColSum3Args a) {
