@@ -537,6 +537,20 @@ S3D_API int s3d_tex_quantize(const float* colors, const int64_t* texel_index, in
 /* out = image where face_id >= 0, elsewhere the per-channel maximum of image over the 3 x 3 neighbourhood inside the atlas
  * (cv2.dilate with a 3 x 3 kernel blended by the mask, model.py:426-428).  out must not alias image. */
 S3D_API int s3d_tex_dilate(const uint8_t* image, const int32_t* face_id, int texreso, int channels, uint8_t* out, void* stream);
+/* Tangent-space normal map of a field on the atlas (an own addition).  image [T*T][3] = (128, 128, 255) and
+ * status [T*T] = 0 first; then for every i < n, texel texel_index[i] (all different; one outside [0, T*T) or under no chart is
+ * skipped): the unit gradient grad[i] / |grad[i]| in the frame (T', B', N) of s3d_pbr_shade on the texel's face, byte =
+ * floor(clamp((t + 1) * 127.5, 0, 255) + 0.5).  Face and barycentrics as in s3d_tex_texel_positions.  N: the normalised mix of
+ * base_normals [n_verts][3] at the barycentrics, turned to the gradient's side of the face; the face normal on that side when
+ * base_normals is null, a corner's normal is zero, or the mix has no direction or points away from it.  tangents [n_faces][2][3]
+ * as s3d_pbr_face_tangents writes them.  status: 1 encoded, 4 encoded around the face normal, 2 flat texel because the gradient
+ * is not finite or |grad|^2 < 1e-20, 3 flat texel because the face has no area or no tangent.  Float64 after the barycentrics. */
+S3D_API int s3d_tex_normal_texels(const float* grad, const int64_t* texel_index, int64_t n, const float* verts, int64_t n_verts,
+                                  const int32_t* tris, const int32_t* corner0, int64_t n_faces, int texreso, int cells_per_row, int cell,
+                                  const float* base_normals, const float* tangents, uint8_t* image, uint8_t* status, void* stream);
+/* out = image where face_id >= 0; elsewhere the whole texel of the first covered neighbour inside the atlas in the order (dx, dy) =
+ * (0,-1) (-1,0) (+1,0) (0,+1) (-1,-1) (+1,-1) (-1,+1) (+1,+1); image itself where there is none.  out must not alias image. */
+S3D_API int s3d_tex_dilate_nearest(const uint8_t* image, const int32_t* face_id, int texreso, int channels, uint8_t* out, void* stream);
 
 /* Quadric-error decimation (Garland-Heckbert edge collapse in parallel rounds of independent collapses, DESIGN.md §15;
  * isosurface.simplify_mesh_quadric drives the rounds and does the sorting, unique and compaction in between).

@@ -460,6 +460,45 @@ def bake_texture(verts, tris, texreso, decode_fn):
     return image, mask.view(T, T), pos.view(T, T, 3), uvs, corner0
 
 
+def bake_normal_map(verts, tris, texreso, grad_fn, base_normals=None):
+    """Tangent-space normal map of a field on the triangle_atlas layout of bake_texture: `grad_fn(points [N,3]) ->
+    gradients [N,3]` is called ONCE on the covered texels' positions; every texel then holds the unit gradient in the frame
+    (T', B', N) that s3d_pbr_shade builds on its face from rasterizer.face_tangents of the atlas' own uvs and the base normal N
+    (the mix of base_normals [V,3], None: the face normal), as (t + 1) * 127.5 rounded.  Uncovered texels take the whole texel of
+    their nearest covered neighbour (s3d_tex_dilate_nearest), the flat (128, 128, 255) where there is none.
+    Returns (image uint8 [T,T,3] with row 0 = texel row y = 0, status uint8 [T,T], tangents float32 [F,2,3]); status 0 uncovered,
+    1 encoded, 4 encoded around the face normal, 2 / 3 flat for want of a gradient direction / of a frame."""
+    from ..rendering.rasterizer import face_tangents
+    T = int(texreso)
+    face_id, pos, corner0, atlas = atlas_texels(verts, tris, T)
+    dev, lib = pos.device, _lib.load()
+    v = verts.contiguous().float()
+    t = tris.contiguous().to(torch.int32)
+    F = t.shape[0]
+    base = None
+    if base_normals is not None:
+        base = base_normals.to(dev).contiguous().float().reshape(-1, 3)
+        if base.shape[0] != v.shape[0]:
+            raise ValueError(f"bake_normal_map: {base.shape[0]} base normals for {v.shape[0]} vertices")
+    with torch.cuda.device(dev):
+        idx = torch.nonzero(face_id >= 0).squeeze(1)
+        grad = grad_fn(pos[idx])
+        if grad.dim() != 2 or tuple(grad.shape) != (idx.shape[0], 3):
+            raise ValueError(f"grad_fn returned {tuple(grad.shape)} for {idx.shape[0]} points: expected [N, 3]")
+        grad = grad.contiguous().float()
+        uvs = torch.from_numpy(atlas.uvs(corner0.cpu().numpy())).to(dev)
+        tangents = face_tangents(v, t, uvs.reshape(F, 3, 2))
+        raw = torch.empty((T, T, 3), device=dev, dtype=torch.uint8)
+        image = torch.empty_like(raw)
+        status = torch.empty((T, T), device=dev, dtype=torch.uint8)
+        _lib.check(lib.s3d_tex_normal_texels(_lib.ptr(grad), _lib.ptr(idx), idx.shape[0], _lib.ptr(v), v.shape[0], _lib.ptr(t), _lib.ptr(corner0),
+                                             F, T, atlas.n, atlas.c, _lib.ptr(base), _lib.ptr(tangents), _lib.ptr(raw), _lib.ptr(status),
+                                             _lib.stream_ptr()))
+        _lib.check(lib.s3d_tex_dilate_nearest(_lib.ptr(raw), _lib.ptr(face_id), T, 3, _lib.ptr(image), _lib.stream_ptr()))
+        torch.cuda.current_stream().synchronize()          # `v`, `t`, `base`, `grad` may be temporaries
+    return image, status, tangents
+
+
 # ------------------------------------------------------------------ writers (host)
 def _np(x):
     return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
@@ -499,13 +538,16 @@ def read_material_params_from_mtl(path):
 _MATERIAL_DEFAULTS = {"Kd": [1, 1, 1], "Ka": [0, 0, 0], "Ks": [0.4, 0.4, 0.4], "Ns": 10}
 
 
-def export_textured_obj(path, verts, tris, uvs, image, material=None, mtl_str=None, normals=None):
+def export_textured_obj(path, verts, tris, uvs, image, material=None, mtl_str=None, normals=None, normal_map=None):
     """`path` (x.obj) plus x.mtl and x.png beside it.  image [T,T,C] uint8 with row 0 = texel row y = 0 (written as the BOTTOM row of
     the PNG, so that vt = texel / T); uvs [3F,2], three per face in the face's vertex order.  The material block is `mtl_str`
     (read_material_params_from_mtl) when given, else Kd/Ka/Ks/Ns of `material` (missing or None entries: Kd 1 1 1, Ka 0 0 0,
-    Ks 0.4 0.4 0.4, Ns 10) and illum 2.  normals [V,3]: `vn` lines and faces `f v/vt/vn` (None: the file as it always was)."""
+    Ks 0.4 0.4 0.4, Ns 10) and illum 2.  normals [V,3]: `vn` lines and faces `f v/vt/vn` (None: the file as it always was).
+    normal_map [T,T,3] uint8, rows as `image` (bake_normal_map): x_normal.png and a last MTL line `map_Bump -bm 1.000000 x_normal.png`."""
     if not path.endswith(".obj"):
         raise ValueError(f"export_textured_obj: {path!r} does not end in .obj")
+    if normal_map is not None and (_np(normal_map).dtype != np.uint8 or _np(normal_map).ndim != 3 or _np(normal_map).shape[2] != 3):
+        raise ValueError(f"export_textured_obj: normal_map must be uint8 [T,T,3], got {_np(normal_map).dtype} {_np(normal_map).shape}")
     v, f, vt = _np(verts), _np(tris).astype(np.int64), _np(uvs)
     if vt.shape[0] != 3 * f.shape[0]:
         raise ValueError(f"export_textured_obj: {vt.shape[0]} texture coordinates for {f.shape[0]} faces")
@@ -522,8 +564,13 @@ def export_textured_obj(path, verts, tris, uvs, image, material=None, mtl_str=No
                 fh.write(f"{k} {m[k][0]} {m[k][1]} {m[k][2]}\n")
             fh.write(f"Ns {m['Ns']}\nillum 2\n")
         fh.write(f"map_Kd {stem}.png\n")
+        if normal_map is not None:
+            fh.write(f"map_Bump -bm 1.000000 {stem}_normal.png\n")
     with open(path[:-4] + ".png", "wb") as fh:
         fh.write(png_bytes(_np(image)[::-1]))
+    if normal_map is not None:
+        with open(path[:-4] + "_normal.png", "wb") as fh:
+            fh.write(png_bytes(_np(normal_map)[::-1]))
     _write_uv_obj(path, stem, v, vt, f, _unit_normals(normals, v.shape[0], "export_textured_obj"))
 
 
@@ -593,20 +640,27 @@ def export_pbr_obj(path, verts, tris, uvs, albedo, metallic, roughness, normal, 
     _write_uv_obj(path, stem, v, vt, f, _unit_normals(normals, v.shape[0], "export_pbr_obj"))
 
 
-def export_glb(path, verts, tris, uvs, image, normals=None):
+def export_glb(path, verts, tris, uvs, image, normals=None, normal_map=None, tangents=None):
     """Binary glTF 2.0: one un-indexed triangle primitive of 3F vertices (POSITION, TEXCOORD_0 with v_gltf = 1 - v_obj), the PNG of
-    export_textured_obj embedded as a bufferView, base colour factor 1, metallic 0, roughness 1, double sided.  normals [V,3]: a NORMAL accessor (None: the file as it always was)."""
+    export_textured_obj embedded as a bufferView, base colour factor 1, metallic 0, roughness 1, double sided.  normals [V,3]: a NORMAL accessor (None: the file as it always was).
+    normal_map [T,T,3] uint8 (bake_normal_map): a second image, the material's normalTexture; tangents [F,2,3] (with normals): a
+    TANGENT accessor, see _write_glb."""
     material = {"pbrMetallicRoughness": {"baseColorFactor": [1.0, 1.0, 1.0, 1.0], "baseColorTexture": {"index": 0},
                                          "metallicFactor": 0.0, "roughnessFactor": 1.0}, "doubleSided": True}
-    _write_glb(path, verts, tris, uvs, [png_bytes(_np(image)[::-1])], material, "export_glb", normals)
+    pngs = [png_bytes(_np(image)[::-1])]
+    if normal_map is not None:
+        pngs.append(png_bytes(_np(normal_map)[::-1]))
+        material["normalTexture"] = {"index": 1}
+    _write_glb(path, verts, tris, uvs, pngs, material, "export_glb", normals, tangents)
 
 
-def export_pbr_glb(path, verts, tris, uvs, albedo, metallic, roughness, normal, normals=None):
+def export_pbr_glb(path, verts, tris, uvs, albedo, metallic, roughness, normal, normals=None, tangents=None):
     """Binary glTF 2.0 with one metallic-roughness material (an own design: the reference has no PBR GLB): baseColorTexture =
     albedo, metallicRoughnessTexture = ONE RGB image with G = roughness, B = metallic (glTF's channel assignment) and R = 0,
     normalTexture = normal; three embedded PNGs, the albedo's bytes equal to export_pbr_obj's.  metallicFactor and
     roughnessFactor are 1.0: glTF multiplies the texture by them, so export_glb's 0.0 / 1.0 would cancel the metallic map.
-    Double sided.  Arrays as in export_pbr_obj; normals [V,3]: per-vertex geometric normals as a NORMAL accessor."""
+    Double sided.  Arrays as in export_pbr_obj; normals [V,3]: per-vertex geometric normals as a NORMAL accessor; tangents [F,2,3]
+    (with normals): a TANGENT accessor, see _write_glb."""
     al, me, ro, no = _np(albedo), _np(metallic), _np(roughness), _np(normal)
     if me.shape != ro.shape or me.ndim != 2 or al.shape != me.shape + (3,) or no.shape != al.shape:
         raise ValueError(f"export_pbr_glb: albedo {al.shape}, metallic {me.shape}, roughness {ro.shape}, normal {no.shape}")
@@ -614,12 +668,37 @@ def export_pbr_glb(path, verts, tris, uvs, albedo, metallic, roughness, normal, 
     material = {"pbrMetallicRoughness": {"baseColorFactor": [1.0, 1.0, 1.0, 1.0], "baseColorTexture": {"index": 0},
                                          "metallicRoughnessTexture": {"index": 1}, "metallicFactor": 1.0, "roughnessFactor": 1.0},
                 "normalTexture": {"index": 2}, "doubleSided": True}
-    _write_glb(path, verts, tris, uvs, [png_bytes(m[::-1]) for m in (al, packed, no)], material, "export_pbr_glb", normals)
+    _write_glb(path, verts, tris, uvs, [png_bytes(m[::-1]) for m in (al, packed, no)], material, "export_pbr_glb", normals, tangents)
 
 
-def _write_glb(path, verts, tris, uvs, pngs, material, who, normals=None):
+def corner_tangents(corner_normals, tangents):
+    """float32 [3F,4], glTF's TANGENT of every corner: xyz = normalize(T - n (n.T)) against that corner's normal n [3F,3], w =
+    sign(cross(n, T').B) (+1 at 0) with (T, B) = tangents [F,2,3] of the corner's face (rasterizer.face_tangents).  Where that has no
+    direction (a face without tangent, T parallel to n to 1e-12 of its length): the coordinate axis on which n is smallest in magnitude (the first of
+    them), made orthogonal to n the same way, and w = 1."""
+    n = np.asarray(corner_normals, dtype=np.float64).reshape(-1, 3)
+    tb = np.repeat(np.asarray(_np(tangents), dtype=np.float64).reshape(-1, 2, 3), 3, axis=0)
+    if tb.shape[0] != n.shape[0]:
+        raise ValueError(f"corner_tangents: {tb.shape[0] // 3} face tangents for {n.shape[0]} corners")
+
+    def against(t):
+        size = (t * t).sum(1)
+        t = t - n * (n * t).sum(1, keepdims=True)
+        l2 = (t * t).sum(1)
+        ok = (l2 > 1e-24 * size) & np.isfinite(l2)
+        return np.where(ok[:, None], t / np.sqrt(np.where(ok, l2, 1.0))[:, None], 0.0), ok
+    tp, ok = against(tb[:, 0])
+    ok &= tb.reshape(-1, 6).any(1)
+    w = np.where((np.cross(n, tp) * tb[:, 1]).sum(1) < 0, -1.0, 1.0)
+    axis = against(np.eye(3)[np.argmin(np.abs(n), axis=1)])[0]            # (at least 2/3 of that axis is left: never degenerate)
+    out = np.concatenate([np.where(ok[:, None], tp, axis), np.where(ok, w, 1.0)[:, None]], 1)
+    return np.ascontiguousarray(out, dtype="<f4")
+
+
+def _write_glb(path, verts, tris, uvs, pngs, material, who, normals=None, tangents=None):
     """The GLB container of export_glb / export_pbr_glb: texture i = image i = pngs[i].  normals [V,3] (per vertex, expanded to the
-    3F corners like the positions): accessor 2 = NORMAL, its bufferView after the images so that every other index stays."""
+    3F corners like the positions): accessor 2 = NORMAL, its bufferView after the images so that every other index stays.
+    tangents [F,2,3] (needs normals): accessor 3 = TANGENT, VEC4 per corner (corner_tangents), appended after NORMAL."""
     v, f, vt = _np(verts).astype(np.float32), _np(tris).astype(np.int64), _np(uvs).astype(np.float32)
     if vt.shape[0] != 3 * f.shape[0]:
         raise ValueError(f"{who}: {vt.shape[0]} texture coordinates for {f.shape[0]} faces")
@@ -627,15 +706,19 @@ def _write_glb(path, verts, tris, uvs, pngs, material, who, normals=None):
     uv = np.ascontiguousarray(np.stack([vt[:, 0], 1.0 - vt[:, 1]], 1), dtype="<f4")
     parts = [pos.tobytes(), uv.tobytes(), *pngs]
     vn = _unit_normals(normals, v.shape[0], who)
+    if tangents is not None and vn is None:
+        raise ValueError(f"{who}: tangents without normals")
     if vn is not None:
         parts.append(np.ascontiguousarray(vn[f.reshape(-1)], dtype="<f4").reshape(-1, 3).tobytes())
+    if tangents is not None:
+        parts.append(corner_tangents(np.ascontiguousarray(vn[f.reshape(-1)], dtype="<f4"), tangents).tobytes())
     views, blob = [], b""
     for p in parts:
         views.append({"buffer": 0, "byteOffset": len(blob), "byteLength": len(p)})
         blob += p + b"\0" * (-len(p) % 4)
     views[0]["target"] = views[1]["target"] = 34962                                        # ARRAY_BUFFER
-    if vn is not None:
-        views[-1]["target"] = 34962
+    for k in range(2 + len(pngs), len(views)):
+        views[k]["target"] = 34962
     n = pos.shape[0]
     bounds = {"min": pos.min(0).tolist(), "max": pos.max(0).tolist()} if n else {"min": [0.0] * 3, "max": [0.0] * 3}
     gltf = {
@@ -652,7 +735,10 @@ def _write_glb(path, verts, tris, uvs, pngs, material, who, normals=None):
     }
     if vn is not None:
         gltf["meshes"][0]["primitives"][0]["attributes"]["NORMAL"] = 2
-        gltf["accessors"].append({"bufferView": len(views) - 1, "componentType": 5126, "count": n, "type": "VEC3"})
+        gltf["accessors"].append({"bufferView": 2 + len(pngs), "componentType": 5126, "count": n, "type": "VEC3"})
+    if tangents is not None:
+        gltf["meshes"][0]["primitives"][0]["attributes"]["TANGENT"] = 3
+        gltf["accessors"].append({"bufferView": 3 + len(pngs), "componentType": 5126, "count": n, "type": "VEC4"})
     js = json.dumps(gltf, separators=(",", ":")).encode()
     js += b" " * (-len(js) % 4)
     total = 12 + 8 + len(js) + 8 + len(blob)

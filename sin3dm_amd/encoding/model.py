@@ -198,7 +198,8 @@ class ShapeAutoEncoder:
 
     @torch.no_grad()
     def decode_texmesh(self, save_dir, triplane_feat, reso, n_faces=10000, texture_reso=2048, only_largest_cc=True, save_voxel=True,
-                       mtl_path=None, file_format="obj", decimation="cluster", refine=0, refine_max_move=0.5, normals=None):
+                       mtl_path=None, file_format="obj", decimation="cluster", refine=0, refine_max_move=0.5, normals=None,
+                       normal_map=None, normal_map_project=0, normal_map_max_move=1.0):
         """Reference :362-473 for data_type sdftex: decode_grid -> voxel.npz -> iso-surface -> largest component -> the re-normalisation
         of decode_mesh -> decimation to n_faces (isosurface.simplify_mesh) -> UV atlas at texture_reso and ONE decode_batch call over
         its covered texels, quantised and dilated on the device (isosurface.bake_texture) -> object.obj + object.mtl + object.png, or
@@ -211,7 +212,16 @@ class ShapeAutoEncoder:
         object.glb with one metallic-roughness material (export_pbr_glb).
         refine=K > 0 projects the DECIMATED vertices onto the decoded zero level set (_refine_and_normals) before the atlas, so the
         texel positions are taken on the refined mesh; normals="field" writes the field's unit normals (`vn`, or NORMAL in the GLB)
-        and returns them as "normals".  With the defaults every file is what it always was.
+        and returns them as "normals".
+        normal_map="field" (not for data_type sdf) bakes the decoded field's normals on the final mesh into a
+        tangent-space map on the same atlas (isosurface.bake_normal_map): the detail the decimation removed, kept for shading.  The
+        gradient is net.sdf_and_grad at the texel positions; normal_map_project=K > 0 first projects those positions onto the zero
+        level set in K Newton steps (step and total move at most normal_map_max_move cells of the decode grid per axis) and takes
+        the gradient there — the colour bake keeps its on-face positions.  Base normals: those of normals="field" when asked for,
+        else the area-weighted vertex normals; they are always written then (a tangent-space map means nothing without them).
+        sdftex: object_normal.png + a `map_Bump` line, or normalTexture and TANGENT in the GLB; sdfpbr: the baked map takes the
+        place of the normal head's image.  Returned as "normal_map" [T,T,3] and "normal_status" [T,T].
+        With the defaults every file is what it always was.
         Returns a dict of what was written (verts, tris, info, and with a texture uvs, image, mask, gb_pos, corner0), or None for
         an empty iso-surface (no mesh file is written then)."""
         import warnings
@@ -220,6 +230,15 @@ class ShapeAutoEncoder:
             raise NotImplementedError(f"file_format {file_format!r}: 'obj' or 'glb'")
         if decimation not in ("cluster", "quadric"):
             raise ValueError(f"decimation {decimation!r}: expected 'cluster' or 'quadric'")
+        if normal_map not in (None, "field"):
+            raise ValueError(f"normal_map {normal_map!r}: expected 'field' (or None)")
+        if normal_map is not None:
+            if self.data_type == "sdf":
+                raise ValueError("normal_map='field' needs a texture atlas: data_type sdf writes none")
+            normal_map_project = int(normal_map_project)
+            if normal_map_project < 0 or not normal_map_max_move > 0:
+                raise ValueError(f"normal_map_project={normal_map_project}, normal_map_max_move={normal_map_max_move}: expected a number "
+                                 f"of steps >= 0 and a positive move")
         H, W = triplane_feat[0].shape[-2:]
         D = triplane_feat[1].shape[-1]
         aabb = self._resize_aabb((H, W, D))
@@ -246,18 +265,45 @@ class ShapeAutoEncoder:
             return {"verts": verts, "tris": tris, "info": info, **nk}
         image, mask, gb_pos, uvs, corner0 = iso.bake_texture(
             verts, tris, texture_reso, lambda p: self.decode_batch(triplane_feat, p, aabb=aabb)[..., 1:])
+        nm, glb_nm, obj_nm = {}, {}, {}
+        if normal_map is not None:
+            nk, nmap, nstat, tang = self._bake_field_normal_map(triplane_feat, aabb, verts, tris, texture_reso, reso, box_size, vn,
+                                                                normal_map_project, normal_map_max_move)
+            nm = {"normal_map": nmap, "normal_status": nstat}
+            glb_nm, obj_nm = {"tangents": tang}, {"normal_map": nmap}
         if self.data_type == "sdfpbr":
             maps = iso.split_pbr_image(image)
+            if normal_map is not None:
+                maps = maps[:3] + (nmap,)
             if file_format == "obj":
                 iso.export_pbr_obj(os.path.join(save_dir, "object.obj"), verts, tris, uvs, *maps, **nk)
             else:
-                iso.export_pbr_glb(os.path.join(save_dir, "object.glb"), verts, tris, uvs, *maps, **nk)
+                iso.export_pbr_glb(os.path.join(save_dir, "object.glb"), verts, tris, uvs, *maps, **nk, **glb_nm)
         elif file_format == "obj":
             mtl_str = iso.read_material_params_from_mtl(mtl_path) if mtl_path is not None else None
-            iso.export_textured_obj(os.path.join(save_dir, "object.obj"), verts, tris, uvs, image, material=self.material, mtl_str=mtl_str, **nk)
+            iso.export_textured_obj(os.path.join(save_dir, "object.obj"), verts, tris, uvs, image, material=self.material, mtl_str=mtl_str,
+                                    **nk, **obj_nm)
         else:
-            iso.export_glb(os.path.join(save_dir, "object.glb"), verts, tris, uvs, image, **nk)
-        return {"verts": verts, "tris": tris, "uvs": uvs, "image": image, "mask": mask, "gb_pos": gb_pos, "corner0": corner0, "info": info, **nk}
+            iso.export_glb(os.path.join(save_dir, "object.glb"), verts, tris, uvs, image, **nk, **obj_nm, **glb_nm)
+        return {"verts": verts, "tris": tris, "uvs": uvs, "image": image, "mask": mask, "gb_pos": gb_pos, "corner0": corner0, "info": info,
+                **nk, **nm}
+
+    def _bake_field_normal_map(self, triplane_feat, aabb, verts, tris, texture_reso, reso, box_size, vn, project, max_move):
+        """decode_texmesh(normal_map="field"): ({"normals": base normals [V,3]}, map uint8 [T,T,3], status uint8 [T,T], face
+        tangents [F,2,3]).  The base normals are `vn` (normals="field") when given, else the area-weighted vertex normals."""
+        from . import isosurface as iso
+        from ..rendering.rasterizer import vertex_normals
+        self.net.eval()
+        base = vn if vn is not None else vertex_normals(verts, tris)
+        limit = float(max_move) * float(box_size) / float(reso)
+        if project > 0:
+            def grad_fn(p):
+                return self.net.project_to_surface(p, triplane_feat, aabb=aabb, iters=project, max_step=limit, max_move=limit)[2]
+        else:
+            def grad_fn(p):
+                return self.net.sdf_and_grad(p, triplane_feat, aabb=aabb)[1]
+        nmap, nstat, tang = iso.bake_normal_map(verts, tris, texture_reso, grad_fn, base_normals=base)
+        return {"normals": base}, nmap, nstat, tang
 
     # ------------------------------------------------------------------ training (reference :51-139, 178-258)
     def _load_data(self, path, sdf_renorm=False):

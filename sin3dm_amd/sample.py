@@ -23,10 +23,14 @@ metallic-roughness object.glb) there, one of --data_type sdf writes sdfgrid_r<re
 they write object.obj coloured by the albedo / without colours.  The data type comes from EXP/encoding/args.json.
 S3D_MESH_REFINE=K (default 0) projects the exported vertices onto the decoded zero level set in K Newton steps, and
 S3D_MESH_NORMALS=field writes the field's unit normals into the mesh files; edit.py reads both as well.
+S3D_MESH_NORMAL_MAP=field beside S3D_MESH=textured bakes the field's normals on the decimated mesh into a tangent-space normal map
+(object_normal.png, textures/normal.png for sdfpbr, normalTexture in a GLB), S3D_MESH_NORMAL_MAP_PROJECT=K takes them
+at the texel positions projected onto the zero level set in K Newton steps; edit.py reads both as well.
 S3D_RENDER=views beside any of these also writes renderings/000.png ... 007.png into every sample folder that gets a mesh: the
 reference's eight views, drawn on the device from the arrays the export holds (sin3dm_amd/rendering).
 S3D_RENDER_SHADING=smooth or pbr beside it draws them with smooth normals and the three-light GGX model of DESIGN.md §24 (pbr: the
-metallic, roughness and normal channels of an sdfpbr sample's bake included); unset: the flat shader, as before.
+metallic, roughness and normal channels of an sdfpbr sample's bake included, and the map of S3D_MESH_NORMAL_MAP=field for either
+data type); unset: the flat shader, as before.
 """
 from __future__ import annotations
 
@@ -111,6 +115,28 @@ def mesh_normals(mode=None):
     return name
 
 
+def mesh_normal_map(mode=None):
+    """"" (the default: no baked normal map) or "field": decode_texmesh(normal_map="field"), DESIGN.md §27.  mode=None reads the
+    environment variable S3D_MESH_NORMAL_MAP."""
+    name = mode if mode is not None else (os.environ.get("S3D_MESH_NORMAL_MAP") or "")
+    if name not in ("", "field"):
+        raise ValueError(f"mesh normal map {name!r}: expected 'field' (or unset)")
+    return name
+
+
+def mesh_normal_map_project(value=None):
+    """K >= 0 (default 0): Newton steps of the texel positions onto the zero level set before the gradient of the baked normal
+    map is taken (decode_texmesh normal_map_project=K).  value=None reads the environment variable S3D_MESH_NORMAL_MAP_PROJECT."""
+    raw = value if value is not None else (os.environ.get("S3D_MESH_NORMAL_MAP_PROJECT") or "0")
+    try:
+        k = int(raw)
+    except (TypeError, ValueError):
+        k = -1
+    if k < 0:
+        raise ValueError(f"mesh normal map project {raw!r}: expected a number of steps >= 0")
+    return k
+
+
 def render_shading(mode=None):
     """"" (the default: the flat shader the views always had), "flat", "smooth" or "pbr": the shading of the S3D_RENDER=views
     renders (rendering/rasterizer.render_views).  mode=None reads the environment variable S3D_RENDER_SHADING."""
@@ -123,7 +149,8 @@ def render_shading(mode=None):
 def render_sample(save_dir, mesh, shading=None):
     """renderings/ beside a decoded mesh.  mesh: what decode_mesh (verts, tris, colours) or decode_texmesh (a dict, or None for an
     empty iso-surface) returned.  shading: see render_shading; with "pbr" the 8-channel bake of an sdfpbr sample is used as it
-    lies on the device (albedo [..., :3], metallic [..., 3], roughness [..., 4], normal [..., 5:]).  Field normals in the mesh (a
+    lies on the device (albedo [..., :3], metallic [..., 3], roughness [..., 4], normal [..., 5:]); a baked "normal_map" in the dict
+    (decode_texmesh normal_map="field") is the material's normal_image under "pbr", for an sdftex sample too.  Field normals in the mesh (a
     dict's "normals", a fourth tuple entry) are passed on to render_views, which uses them under "smooth" and "pbr".  Returns the
     paths written."""
     from .rendering.rasterizer import render_views
@@ -141,6 +168,8 @@ def render_sample(save_dir, mesh, shading=None):
         elif mesh.get("image") is not None:
             # the baked image has texel row 0 first, which the PNG shows as its bottom row: the rasteriser reads top row first
             kw = dict(uvs=mesh["uvs"].reshape(-1, 3, 2), materials=[{"Kd": (1.0, 1.0, 1.0), "image": mesh["image"][..., :3].flip(0)}])
+        if kw and shading == "pbr" and mesh.get("normal_map") is not None:
+            kw["materials"][0]["normal_image"] = mesh["normal_map"].flip(0)
     else:
         verts, tris, cols = mesh[:3]
         vn = mesh[3] if len(mesh) > 3 else None
@@ -257,6 +286,13 @@ def decode(args, paths):
         field["refine"] = mesh_refine()
     if mesh_normals():
         field["normals"] = mesh_normals()
+    baked = {}
+    if mesh_normal_map():
+        if not textured:
+            raise ValueError("S3D_MESH_NORMAL_MAP=field needs S3D_MESH=textured: the vertex-coloured mesh has no atlas")
+        baked["normal_map"] = mesh_normal_map()
+        if mesh_normal_map_project():
+            baked["normal_map_project"] = mesh_normal_map_project()
     ae = ShapeAutoEncoder(encoding_log_dir(args.tag), args, device=dist_util.dev())
     ae.load_ckpt("final")
     views = render_mode() == "views"
@@ -268,7 +304,7 @@ def decode(args, paths):
             continue
         if textured:
             mesh = ae.decode_texmesh(os.path.dirname(path), fm, args.reso, n_faces=args.n_faces, texture_reso=args.texreso,
-                                     mtl_path=find_copy_mtl(args), file_format=args.file_format, **decimate, **field)
+                                     mtl_path=find_copy_mtl(args), file_format=args.file_format, **decimate, **field, **baked)
         else:
             # iso-surface on the device, vertex-coloured object.obj
             mesh = ae.decode_mesh(os.path.dirname(path), fm, args.reso, **field, **({"return_normals": True} if "normals" in field else {}))
