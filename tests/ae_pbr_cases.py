@@ -99,7 +99,6 @@ def batch(case, seed, n=N_POINTS):
 def tex_block1(sd, f0, fault=None):
     """tex_convs.1 (input_norm, input_act): xn = IN(f0; norm_p); a2 = conv3x3(SiLU(xn)); y2 = SiLU(IN(a2; the SAME norm_p));
     f1 = conv3x3(y2) + xn — the identity shortcut acts on the normalised input"""
-    import torch.nn.functional as F
     pre = "tex_convs.1"
     up = sd[pre + ".in_layers.1.weight"].shape[0] // 3
     out = []
@@ -112,39 +111,51 @@ def tex_block1(sd, f0, fault=None):
         elif fault == "norm1_out_only":
             gi, bi = g1.detach(), b1.detach()
         xn = V._inorm(x, gi, bi, eps=1e-6)
-        h = F.conv2d(xn * xn.sigmoid(), sd[pre + ".in_layers.1.weight"][r], sd[pre + ".in_layers.1.bias"][r], padding=1)
+        h = V.conv(xn * xn.sigmoid(), sd[pre + ".in_layers.1.weight"][r], sd[pre + ".in_layers.1.bias"][r], 3, fault)
         h = V._inorm(h, g1, b1, eps=1e-6)
-        h = F.conv2d(h * h.sigmoid(), sd[pre + ".out_layers.1.weight"][r], sd[pre + ".out_layers.1.bias"][r], padding=1)
+        h = V.conv(h * h.sigmoid(), sd[pre + ".out_layers.1.weight"][r], sd[pre + ".out_layers.1.bias"][r], 3, fault)
         out.append(h + (x if fault == "residual_f0" else xn))
     return out
+
+
+# further faults, which tests/test_ae_variants_f64_host.py holds the bounds of tests/ae_f64_cases.py against: they show at shapes
+# and loss modes that the fixture does not have
+NEW_FAULTS = ("conv3_short_row",   # the gradients of a 3x3 convolution whose zero padding begins one row early (V.conv)
+              "mean_cnt8",         # every group mean divided by rows * 8 (V.losses)
+              "normal_point_grad",  # the normal head's gradient never reaches the gathered feature
+              "aabb_centred",      # the aabb's centre ignored (V.normalise)
+              "band_le")           # the band taken with <= (V.losses)
 
 
 def decode(sd, pts, fm, aabb, geo_dim=4, fault=None, taps=None):
     """pred = sdf | rgb | mr | normal (no sigmoid); the three heads read ONE gathered feature"""
     import torch
-    x = 2 * (pts - aabb[:3]) / (aabb[3:] - aabb[:3]) - 1
+    x = V.normalise(pts, aabb, fault)
     out = [V.mlp(sd, "geo_decoder", V.gather(V.plane_block(sd, "geo_convs", [f[:, :geo_dim] for f in fm]), x), taps)]
-    f0 = V.plane_block(sd, "tex_convs.0", [f[:, geo_dim:] for f in fm], ks=3)
+    f0 = V.plane_block(sd, "tex_convs.0", [f[:, geo_dim:] for f in fm], ks=3, fault=fault)
     X = V.gather(tex_block1(sd, f0, fault), x)
     for head, _ in HEADS:
-        Xh = X.detach() if fault == "rgb_point_grad" and head != "rgb_decoder" else X
-        out.append(V.mlp(sd, head, Xh, taps))
+        cut = (fault == "rgb_point_grad" and head != "rgb_decoder") or (fault == "normal_point_grad" and head == "normal_decoder")
+        out.append(V.mlp(sd, head, X.detach() if cut else X, taps))
     pred = torch.cat(out, dim=1)
     if fault == "sigmoid":
         pred = torch.cat([pred[:, :1], pred[:, 1:].sigmoid()], dim=1)
     return pred
 
 
-def forward_backward(case, sd, vol, pts, sdf, tex, fault=None, taps=None):
-    """One iteration on a state dict of leaf tensors: (feature maps, pred, losses, {name: gradient of the summed losses})."""
+def forward_backward(case, sd, vol, pts, sdf, tex, fault=None, taps=None, aabb=AABB, thr=THR, ratio=RATIO, tex_weight=1.0,
+                     sdf_loss="weightedl1", sdf_renorm=False, geo_dim=None):
+    """One iteration on a state dict of leaf tensors: (feature maps, pred, losses, {name: gradient of the summed losses}).
+    `case` names an entry of CASES, or is such an entry (args)."""
     import torch
-    assert fault is None or fault in FAULTS, fault
-    aabb = torch.tensor(AABB, dtype=vol.dtype)
+    assert fault is None or fault in FAULTS + NEW_FAULTS, fault
+    c = CASES[case] if isinstance(case, str) else case
+    aabb = torch.tensor(aabb, dtype=vol.dtype)
     with torch.enable_grad():
         p = OrderedDict((k, v.detach().clone().requires_grad_(True)) for k, v in sd.items())
         fm = V.encode(p, vol, "pbr")
-        pred = decode(p, pts, fm, aabb, CASES[case]["args"][0], fault, taps)
-        ls = V.losses(pred, sdf, tex, "pbr", fault="one_mean" if fault == "one_mean" else None)
+        pred = decode(p, pts, fm, aabb, c["args"][0] if geo_dim is None else geo_dim, fault, taps)
+        ls = V.losses(pred, sdf, tex, "pbr", thr, ratio, tex_weight, fault if fault in V.LOSS_FAULTS else None, sdf_loss, sdf_renorm)
         grads = torch.autograd.grad(sum(ls.values()), list(p.values()), allow_unused=True)
     named = OrderedDict((k, torch.zeros_like(v) if g is None else g) for (k, v), g in zip(p.items(), grads))
     return [f.detach() for f in fm], pred.detach(), OrderedDict((k, v.detach()) for k, v in ls.items()), named

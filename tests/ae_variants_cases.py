@@ -12,7 +12,8 @@ targets uniform in [0, 1].  Weights are sin3dm_amd.testing.synthetic_state_dict(
 
 The restatement is written functionally over a state dict (as oracle/torch_port.py:ae_* is), runs in whatever dtype its inputs
 have, and takes `fault` to inject one deliberate mistake, which tests/test_ae_variants_host.py uses to show that the bounds of
-tests/test_ae_variants_gpu.py catch it."""
+tests/test_ae_variants_gpu.py catch it.  The aabb, the texture band, the loss mode and the network's widths are arguments whose
+defaults are the fixture's constants; tests/ae_f64_cases.py runs the same functions over its grid of shapes and loss modes."""
 from collections import OrderedDict
 
 import numpy as np
@@ -89,16 +90,31 @@ def encode(sd, vol, kind):
     return [torch.tanh(0.5 * _inorm(f.mean(dim=d))) for d in (4, 3, 2)]
 
 
-def plane_block(sd, prefix, fm, ks=5):
+def conv(x, w, b, ks, fault=None):
+    """conv ks x ks, zero padding ks // 2.  fault "conv3_short_row" (3x3 only): the values are right, but the gradients (of the
+    input, the weight and the bias) are those of a convolution whose zero padding begins one row early at the lower edge, so that
+    the halo row H-1 reads as zero from the output row above it"""
+    import torch.nn.functional as F
+    y = F.conv2d(x, w, b, padding=ks // 2)
+    if fault != "conv3_short_row" or ks != 3 or x.shape[2] < 2:
+        return y
+    xs = x.clone()
+    xs[:, :, -1] = 0
+    bad = y.clone()
+    bad[:, :, -2] = F.conv2d(xs, w, b, padding=1)[:, :, -2]
+    return y.detach() + (bad - bad.detach())
+
+
+def plane_block(sd, prefix, fm, ks=5, fault=None):
     """per plane: conv ks x ks -> InstanceNorm(affine, eps 1e-6) -> SiLU -> conv ks x ks, plus a 1x1 shortcut of the input"""
     import torch.nn.functional as F
     up = sd[prefix + ".in_layers.0.weight"].shape[0] // 3
     out = []
     for p, (name, x) in enumerate(zip(PLANES, fm)):
         r = slice(p * up, (p + 1) * up)
-        h = F.conv2d(x, sd[prefix + ".in_layers.0.weight"][r], sd[prefix + ".in_layers.0.bias"][r], padding=ks // 2)
+        h = conv(x, sd[prefix + ".in_layers.0.weight"][r], sd[prefix + ".in_layers.0.bias"][r], ks, fault)
         h = _inorm(h, sd[f"{prefix}.norm_{name}.weight"], sd[f"{prefix}.norm_{name}.bias"], eps=1e-6)
-        h = F.conv2d(h * h.sigmoid(), sd[prefix + ".out_layers.1.weight"][r], sd[prefix + ".out_layers.1.bias"][r], padding=ks // 2)
+        h = conv(h * h.sigmoid(), sd[prefix + ".out_layers.1.weight"][r], sd[prefix + ".out_layers.1.bias"][r], ks, fault)
         out.append(h + F.conv2d(x, sd[prefix + ".shortcut.weight"][r], sd[prefix + ".shortcut.bias"][r]))
     return out
 
@@ -131,48 +147,79 @@ def gather(planes, x):
     return tot
 
 
-def decode(sd, pts, fm, aabb, kind, geo_dim=4, taps=None):
+def normalise(pts, aabb, fault=None):
+    """aabb -> [-1, 1] per axis.  fault "aabb_centred": the box's extent about the origin, its centre ignored"""
+    if fault == "aabb_centred":
+        return 2 * pts / (aabb[3:] - aabb[:3])
+    return 2 * (pts - aabb[:3]) / (aabb[3:] - aabb[:3]) - 1
+
+
+def decode(sd, pts, fm, aabb, kind, geo_dim=4, taps=None, fault=None):
+    """fault "chain2_drop": the texture head's gradient never reaches its gathered feature (tex_convs and tex_encoder then get
+    no gradient)"""
     import torch
-    x = 2 * (pts - aabb[:3]) / (aabb[3:] - aabb[:3]) - 1
+    x = normalise(pts, aabb, fault)
     out = mlp(sd, "geo_decoder", gather(plane_block(sd, "geo_convs", [f[:, :geo_dim] for f in fm]), x), taps)
     if kind == "geo":
         return out
-    tex = mlp(sd, "tex_decoder", gather(plane_block(sd, "tex_convs", [f[:, geo_dim:] for f in fm]), x), taps)
+    X = gather(plane_block(sd, "tex_convs", [f[:, geo_dim:] for f in fm]), x)
+    tex = mlp(sd, "tex_decoder", X.detach() if fault == "chain2_drop" else X, taps)
     return torch.cat([out, tex.sigmoid()], dim=1)
 
 
-def losses(pred, sdf, tex, kind, thr=THR, ratio=RATIO, tex_weight=1.0, fault=None):
-    """weighted-l1 sdf loss; for the 8 material channels three l1 means (columns 0-2, 3-4, 5-7) over the points with
-    |sdf| < float32(thr * ratio), the test made on the float32 sdf samples.  fault "one_mean": ONE mean over the eight columns,
-    reported under rgb_loss (it scales the groups' gradients 3/8 : 2/8 : 3/8 instead of 1/3 : 1/2 : 1/3)."""
+GROUPS = (("rgb_loss", slice(0, 3)), ("mr_loss", slice(3, 5)), ("normal_loss", slice(5, 8)))
+LOSS_FAULTS = ("one_mean", "mean_cnt8", "band_le")
+
+
+def losses(pred, sdf, tex, kind, thr=THR, ratio=RATIO, tex_weight=1.0, fault=None, sdf_loss="weightedl1", sdf_renorm=False):
+    """sdf loss l1 | weightedl1 over all rows; over the rows with |sdf| < float32(band), band = thr * ratio (1.0 * ratio with
+    sdf_renorm, where the samples are already divided by thr) and the test made on the float32 sdf samples: for 8 material
+    channels three l1 means (columns 0-2, 3-4, 5-7), for any other width one l1 mean (tex_loss); each times tex_weight.
+    faults: "one_mean"  ONE mean over the eight columns, reported under rgb_loss (it scales the groups' gradients 3/8 : 2/8 : 3/8
+    instead of 1/3 : 1/2 : 1/3); "mean_cnt8"  every group's sum divided by rows * 8 instead of rows * its own columns;
+    "band_le"  the band taken with <=."""
     import torch
     ps = pred[:, :1]
-    w = 1 + 0.5 * torch.sign(sdf) * torch.sign(sdf - ps)
-    out = OrderedDict(sdf_loss=((ps - sdf).abs() * w).mean())
+    if sdf_loss == "l1":
+        out = OrderedDict(sdf_loss=(ps - sdf).abs().mean())
+    else:
+        assert sdf_loss == "weightedl1", sdf_loss
+        w = 1 + 0.5 * torch.sign(sdf) * torch.sign(sdf - ps)
+        out = OrderedDict(sdf_loss=((ps - sdf).abs() * w).mean())
     if kind == "geo":
         return out
-    mask = sdf[:, 0].float().abs() < thr * ratio
+    band = (1.0 if sdf_renorm else thr) * ratio
+    a = sdf[:, 0].float().abs()
+    mask = a <= band if fault == "band_le" else a < band
     d = (pred[:, 1:] - tex)[mask].abs()
+    if d.shape[1] != 8:
+        assert fault in (None, "band_le"), fault
+        out["tex_loss"] = d.mean() * tex_weight
+        return out
     if fault == "one_mean":
         out["rgb_loss"] = d.mean() * tex_weight
         out["mr_loss"] = out["normal_loss"] = d.sum() * 0
         return out
-    assert fault is None, fault
-    for name, cols in (("rgb_loss", slice(0, 3)), ("mr_loss", slice(3, 5)), ("normal_loss", slice(5, 8))):
-        out[name] = d[:, cols].mean() * tex_weight
+    assert fault is None or fault in LOSS_FAULTS, fault
+    for name, cols in GROUPS:
+        out[name] = (d[:, cols].sum() / (d.shape[0] * 8) if fault == "mean_cnt8" else d[:, cols].mean()) * tex_weight
     return out
 
 
-def forward_backward(case, sd, vol, pts, sdf, tex, fault=None, taps=None):
-    """One iteration on a state dict of leaf tensors: (feature maps, pred, losses, {name: gradient of the summed losses})."""
+def forward_backward(case, sd, vol, pts, sdf, tex, fault=None, taps=None, aabb=AABB, thr=THR, ratio=RATIO, tex_weight=1.0,
+                     sdf_loss="weightedl1", sdf_renorm=False, geo_dim=None):
+    """One iteration on a state dict of leaf tensors: (feature maps, pred, losses, {name: gradient of the summed losses}).
+    `case` names an entry of CASES, or is such an entry (kind and args)."""
     import torch
-    kind = CASES[case]["kind"]
-    aabb = torch.tensor(AABB, dtype=vol.dtype)
+    c = CASES[case] if isinstance(case, str) else case
+    kind = c["kind"]
+    aabb = torch.tensor(aabb, dtype=vol.dtype)
     with torch.enable_grad():
         p = OrderedDict((k, v.detach().clone().requires_grad_(True)) for k, v in sd.items())
         fm = encode(p, vol, kind)
-        pred = decode(p, pts, fm, aabb, kind, CASES[case]["args"][0], taps)
-        ls = losses(pred, sdf, tex, kind, fault=fault)
+        pred = decode(p, pts, fm, aabb, kind, c["args"][0] if geo_dim is None else geo_dim, taps,
+                      fault if fault in ("aabb_centred", "chain2_drop") else None)
+        ls = losses(pred, sdf, tex, kind, thr, ratio, tex_weight, fault if fault in LOSS_FAULTS else None, sdf_loss, sdf_renorm)
         grads = torch.autograd.grad(sum(ls.values()), list(p.values()), allow_unused=True)
     named = OrderedDict((k, torch.zeros_like(v) if g is None else g) for (k, v), g in zip(p.items(), grads))
     return [f.detach() for f in fm], pred.detach(), OrderedDict((k, v.detach()) for k, v in ls.items()), named
