@@ -372,35 +372,59 @@ int launch_upcat(const Tri& u, const Tri& sk, int B, Tri& out, hipStream_t st, c
 int launch_copy_slice(const float* in, int B, int C, int h, int w, float* out, int out_cstride, int out_coff,
                       hipStream_t st);
 
+// ---- one denoising step.  The seven step entry points of include/sin3dm_hip.h fill a StepReq, check_step() decides whether the
+// request is legal for the entry, plan_step() decides once how it runs; the forward and the output head only read the plan.
+struct StepReq {
+    const s3d_sampler_args* step = nullptr;      // the update's arguments (step->model_out counts only without a model in front)
+    const s3d_known_region* known = nullptr;     // + the known-region blend
+    const s3d_multistep* ms = nullptr;           // the update is the DPM-Solver++ multistep one
+    int carry_flags = 0;                         // S3D_CARRY_OUT | S3D_CARRY_IN (model entries)
+    float* model_out = nullptr;                  // where the model output is stored: the caller's buffer of a model entry (may be null)
+    bool model = false;                          // a UNet forward runs in front (s3d_unet_step_film*); else step->model_out is the input
+};
+// What an entry accepts beyond the rules its known region / multistep update bring along — the entries' differences, as data.
+struct StepEntry {
+    const char* who;         // leads the error text
+    bool lax;                // the plain and carry model entries: the mode's range, eta's need of noise and the pairing of y0 / mask go unchecked
+    bool sizes;              // T > 0, batch >= 0, per_sample >= 0 (the stand-alone entries and both multistep ones)
+};
+int check_step(const StepEntry& e, const StepReq& r);
+struct StepPlan {
+    enum Update { NONE, PLAIN, KNOWN, MULTI };
+    const StepReq* req = nullptr;
+    Update update = NONE;
+    bool px = false;         // the pixel-chunk head serves this width (else: k_out_head)
+    bool px_parts = false;   // ... and adds its input's GroupNorm partials itself when it can (inference)
+    bool in_head = false;    // the update runs in the head's launch, the model output is stored only into req->model_out (else: head,
+                             // then the stand-alone kernel on the stored model output)
+    bool ws_out = false;     // ... whose buffer comes from the workspace: the caller gave none
+    bool give = false;       // the head may leave the next step's in_conv behind (S3D_CARRY_OUT asked, and this step can)
+};
+// r == null: a plain forward.  C: the head's input width, Cout / Cin: the model's output / input channels.
+StepPlan plan_step(const StepReq* r, int C, int Cout, int Cin, bool training);
+
 // out head: GN + SiLU + 1x1 conv (C -> Cout small) + compose into NCHW [B,Cout,H+D,W+D] with zero corner
-// fuse != null: + the sampler update of the step on the model output (in the same launch when out_head_fuses_sampler(); then
-// `out` may be null and the model output is never stored)
-// carry (fused steps only): the head also evaluates the NEXT step's in_conv — TriplaneConv(in, ch, 1, is_rollout =
+// plan.update: + the sampler update of the step on the model output, where the plan says (in_head: `out` may be null and the model
+// output is then never stored)
+// carry (plan.give only): the head also evaluates the NEXT step's in_conv — TriplaneConv(in, ch, 1, is_rollout =
 // False), a pointwise map of x_{t-1}, unet_triplane.py:378, 482 — on the x_{t-1} values it has just formed, with k_in_conv_lds's
 // arithmetic, thread mapping and GroupNorm-partial order (same bits), into the workspace tensors the next forward will read
 struct InConvCarry { const float* wT; const float* bias; float* out[3]; double* part; int maxparts, Cin; };
+// part (with stats.mr == null; plan.px_parts and gn_act_can_add_parts): the head adds its input's GroupNorm partials itself — no
+// k_gn_finalize launch before it
 int launch_out_head(const Tri& x, int B, GnStats stats, const ActArgs& a, const float* w /*[3][Cout][C]*/,
                     const float* bias /*[3][Cout]*/, int Cout, int H, int W, int D, float* out, hipStream_t st,
-                    const s3d_sampler_args* fuse = nullptr, const GnPartials* part = nullptr, const InConvCarry* carry = nullptr,
-                    const s3d_known_region* known = nullptr,           // known: the step's known-region blend (fuse != null)
-                    const s3d_multistep* ms = nullptr);                // ms: the step's update is the multistep one (fuse != null, no known region)
-bool out_head_can_carry(int C, int Cin, int Cout_head);  // the pixel-chunk head of this width can run the in_conv tail
-bool out_head_fuses_sampler(int C, int Cout, int B);     // the update happens inside the head's launch (else: head, then k_sampler)
-bool out_head_px_takes(int C, int Cout);                 // the pixel-chunk head serves this width (it can add GroupNorm partials itself)
-// part (with stats.mr == null): the head adds its input's GroupNorm partials itself — no k_gn_finalize launch before it
-bool out_head_adds_parts(const GnPartials& part, int C, int Cout);
-long long out_head_px_blocks(const Geo& g, int B);         // grid of the pixel-chunk head
+                    const StepPlan& plan, const GnPartials* part = nullptr, const InConvCarry* carry = nullptr);
+bool out_head_px_form(int C, int Cout);                    // the pixel-chunk head serves this width
+long long out_head_px_blocks(const Geo& g, int B);         // its grid
 
 // small dense layers for the timestep path: y[b][o] = act_out( sum_i f(in[b][i]) * W[o][i] + bias[o] )
 // in_mode 0: plain, 1: SiLU(in), 2: in is t[b] -> sinusoidal embedding of width I (cos | sin)
 int launch_linear(const float* in, int B, int I, const float* W, const float* bias, int O, float* out,
                   int in_mode, int out_silu, hipStream_t st);
 
-int launch_sampler(const s3d_sampler_args& a, hipStream_t st);
-int launch_sampler_known(const s3d_sampler_args& a, const s3d_known_region& kr, hipStream_t st);
-// the argument rules of s3d_sampler_step_multistep / s3d_unet_step_film_multistep (need_model_out: the stand-alone entry)
-int check_multistep_args(const char* who, const s3d_sampler_args* a, const s3d_multistep* ms, bool need_model_out);
-int launch_sampler_multistep(const s3d_sampler_args& a, const s3d_multistep& ms, const s3d_known_region* known, hipStream_t st);
+// the stand-alone update on a stored model output (a.model_out): ms != null the multistep one, known != null + the known-region blend
+int launch_sampler(const s3d_sampler_args& a, const s3d_multistep* ms, const s3d_known_region* known, hipStream_t st);
 int launch_renoise(const float* xprev, const float* er, const float* ktab, const int64_t* t, int T, long long batch, long long per_sample,
                    float* xt, hipStream_t st);
 

@@ -1145,26 +1145,53 @@ __global__ __launch_bounds__(256, 3) void k_out_head_px_ms(OutHeadArgs a, int se
     const KnownArg<KNOWN> kn{};
 #include "s3d_out_head_px_body.h"
 }
-static bool out_head_px_form(int C, int Cout) { return (C == 64 || C == 128 || C == 256) && Cout <= 16; }      // (other widths: k_out_head)
-// The in-head sampler update: head + sampler kernel + their launch gap 23 -> 20 us at 128^3, batch 1.  Until the head's weight
-// rows stopped being fetched inside the contraction (round 4) it lost from batch 2 on (batch 8: 172 us fused against 82 + 35);
-// now it wins there too (config 3: 5.173 -> 5.160 ms/step) and is taken at every batch.
-bool out_head_fuses_sampler(int C, int Cout, int B) { (void)B; return out_head_px_form(C, Cout); }
-bool out_head_px_takes(int C, int Cout) { return out_head_px_form(C, Cout); }
-// fuse != null: the sampler update of one denoising step is applied to the model output (fuse->model_out is ignored).  When
-// the pixel-chunk form takes the launch it happens in the same kernel and `out` may be null (the model output is then never
-// stored); otherwise `out` is required and the stand-alone k_sampler follows.
-// part != null (stats.mr == null; only when out_head_adds_parts() says so): the kernel adds the producer's GroupNorm partials itself.
+bool out_head_px_form(int C, int Cout) { return (C == 64 || C == 128 || C == 256) && Cout <= 16; }      // (other widths: k_out_head)
 long long out_head_px_blocks(const Geo& g, int B) {
     long long n = 0;
     for (int p = 0; p < 3; ++p) { const int len = p == 2 ? g.h[p] : g.w[p], lines = p == 2 ? g.w[p] : g.h[p]; n += (long long)lines * cdiv(len, kOhPx); }
     return n * B;
 }
-bool out_head_adds_parts(const GnPartials& part, int C, int Cout) { return out_head_px_form(C, Cout) && gn_act_can_add_parts(part, C); }
-bool out_head_can_carry(int C, int Cin, int Cout_head) { return out_head_px_form(C, Cout_head) && Cin <= 16 && Cin == Cout_head; }
+// How a step runs, decided once (s3d_common.h).  The in-head sampler update: head + sampler kernel + their launch gap 23 -> 20 us
+// at 128^3, batch 1.  Until the head's weight rows stopped being fetched inside the contraction (round 4) it lost from batch 2 on
+// (batch 8: 172 us fused against 82 + 35); now it wins there too (config 3: 5.173 -> 5.160 ms/step) and is taken at every batch.
+// The KNOWN and MULTI head kernels store no model output: a step of theirs that asks for it runs head, then the stand-alone kernel.
+StepPlan plan_step(const StepReq* r, int C, int Cout, int Cin, bool training) {
+    StepPlan p;
+    p.px = out_head_px_form(C, Cout);
+    p.px_parts = p.px && !training;
+    if (!r) return p;
+    p.req = r;
+    p.update = r->ms ? StepPlan::MULTI : r->known ? StepPlan::KNOWN : StepPlan::PLAIN;
+    p.in_head = r->model && p.px && !((r->known || r->ms) && r->model_out);
+    p.ws_out = r->model && !p.in_head && !r->model_out;
+    // the in_conv tail of the pixel-chunk head: a pointwise map of the sample it has just formed, Cin == Cout <= 16
+    p.give = (r->carry_flags & S3D_CARRY_OUT) && p.in_head && !training && r->step->sample && r->step->mode != S3D_STEP_MEAN_ONLY &&
+             Cin <= 16 && Cin == Cout;
+    return p;
+}
+// the pixel-chunk head of one width: the kernel the plan selects
+template <int CQ>
+static void launch_out_head_px(const StepPlan& plan, const OutHeadArgs& a, const int segs[3], int B, const InConvCarry* carry, hipStream_t st) {
+    s3d_sampler_args sa;
+    memset(&sa, 0, sizeof sa);
+    if (plan.in_head) sa = *plan.req->step;
+    const InConvCarry cy = carry ? *carry : InConvCarry();
+    auto go = [&](auto kernel, auto extra) {
+        hipLaunchKernelGGL(kernel, dim3(segs[0] + segs[1] + segs[2], B), dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, extra);
+    };
+    if (!plan.in_head) go(k_out_head_px<CQ, false>, KnownArg<false>());
+    else if (plan.update == StepPlan::MULTI) {
+        const MultiArg<true> mu{*plan.req->ms};
+        if (carry) go(k_out_head_px_ms<CQ, true>, mu); else go(k_out_head_px_ms<CQ, false>, mu);
+    } else if (plan.update == StepPlan::KNOWN) {
+        const KnownArg<true> kn{*plan.req->known};
+        if (carry) go(k_out_head_px<CQ, true, true, true>, kn); else go(k_out_head_px<CQ, true, false, true>, kn);
+    } else if (carry) go(k_out_head_px<CQ, true, true>, KnownArg<false>());
+    else go(k_out_head_px<CQ, true>, KnownArg<false>());
+}
 int launch_out_head(const Tri& x, int B, GnStats stats, const ActArgs& aa, const float* w, const float* bias,
-                    int Cout, int H, int W, int D, float* out, hipStream_t st, const s3d_sampler_args* fuse, const GnPartials* part,
-                    const InConvCarry* carry, const s3d_known_region* known, const s3d_multistep* ms) {
+                    int Cout, int H, int W, int D, float* out, hipStream_t st, const StepPlan& plan, const GnPartials* part,
+                    const InConvCarry* carry) {
     OutHeadArgs a;
     int maxpix = D * D ? 1 : 0;
     for (int p = 0; p < 3; ++p) {
@@ -1175,82 +1202,28 @@ int launch_out_head(const Tri& x, int B, GnStats stats, const ActArgs& aa, const
     a.mr = stats.mr; a.w = w; a.bias = bias; a.out = out; a.C = x.C; a.Cout = Cout; a.H = H; a.W = W; a.D = D;
     memset(&a.ps, 0, sizeof a.ps);
     if (part) {
-        S3D_CHECK(!stats.mr && out_head_adds_parts(*part, x.C, Cout), S3D_ERR_INVALID, "out head: partial-sum statistics layout");
+        S3D_CHECK(!stats.mr && plan.px_parts && gn_act_can_add_parts(*part, x.C), S3D_ERR_INVALID, "out head: partial-sum statistics layout");
         a.ps = gn_part_src(*part, x.g, x.C);
     } else S3D_CHECK(stats.mr, S3D_ERR_INVALID, "out head: no GroupNorm statistics");
     thread_shape(x.C, a.cq, a.ppb);
-    S3D_CHECK(x.C % 32 == 0 && a.cq <= 1024, S3D_ERR_INVALID, "out head: C=%d unsupported", x.C);
+    S3D_CHECK(x.C % 32 == 0 && a.cq <= 1024 && plan.px == out_head_px_form(x.C, Cout), S3D_ERR_INVALID, "out head: C=%d unsupported", x.C);
+    S3D_CHECK(out || plan.in_head, S3D_ERR_INVALID, "out head: no model-output buffer");
     if (!maxpix || !B) return 0;
-    if (fuse) S3D_CHECK(fuse->batch == B && fuse->per_sample == (long long)Cout * (H + D) * (W + D), S3D_ERR_INVALID, "out head: the sampler step does not match the model output's shape");
-    if (known) S3D_CHECK(!fuse || !fuse->mean || !out_head_fuses_sampler(x.C, Cout, B) || out, S3D_ERR_INVALID, "out head: a known-region step that wants the posterior mean needs a model-output buffer");
-    if (ms) S3D_CHECK(fuse && !known && fuse->sample && fuse->mode == S3D_STEP_DDIM && !fuse->y0 && !fuse->mask && !fuse->mean, S3D_ERR_INVALID, "out head: the multistep update takes a DDIM-mode step without x0 replacement, posterior mean or known region");
-    const bool fuse_here = fuse && out_head_fuses_sampler(x.C, Cout, B) && !(known && out) && !(ms && out);
-    if (fuse && !fuse_here) S3D_CHECK(out, S3D_ERR_INVALID, "out head: this step needs a model-output buffer");
-    if (known) S3D_CHECK(fuse && fuse->sample && fuse->mode != S3D_STEP_MEAN_ONLY && !fuse->y0 && !fuse->mask, S3D_ERR_INVALID, "out head: a known region needs a DDPM / DDIM step without the x0 replacement");
-    if (out_head_px_form(x.C, Cout)) {
+    if (plan.px) {
         int segs[3];
         for (int p = 0; p < 3; ++p) { const int len = p == 2 ? a.h[p] : a.wd[p], lines = p == 2 ? a.wd[p] : a.h[p]; segs[p] = lines * cdiv(len, kOhPx); }
-        const dim3 grid(segs[0] + segs[1] + segs[2], B);
-        s3d_sampler_args sa;
-        memset(&sa, 0, sizeof sa);
-        if (carry) S3D_CHECK(fuse_here && out_head_can_carry(x.C, carry->Cin, Cout) && fuse->mode != S3D_STEP_MEAN_ONLY, S3D_ERR_INVALID, "out head: this step cannot carry the next in_conv");
-        if (fuse_here && ms) {
-            sa = *fuse;
-            MultiArg<true> mu; mu.ms = *ms;
-            const InConvCarry cy = carry ? *carry : InConvCarry();
-            if (carry) {
-                if (x.C == 64) hipLaunchKernelGGL((k_out_head_px_ms<16, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, mu);
-                else if (x.C == 128) hipLaunchKernelGGL((k_out_head_px_ms<32, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, mu);
-                else hipLaunchKernelGGL((k_out_head_px_ms<64, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, mu);
-            } else {
-                if (x.C == 64) hipLaunchKernelGGL((k_out_head_px_ms<16, false>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, mu);
-                else if (x.C == 128) hipLaunchKernelGGL((k_out_head_px_ms<32, false>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, mu);
-                else hipLaunchKernelGGL((k_out_head_px_ms<64, false>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, mu);
-            }
-        } else if (fuse_here && known) {
-            sa = *fuse;
-            KnownArg<true> kn; kn.kr = *known;
-            const InConvCarry cy = carry ? *carry : InConvCarry();
-            if (carry) {
-                if (x.C == 64) hipLaunchKernelGGL((k_out_head_px<16, true, true, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, kn);
-                else if (x.C == 128) hipLaunchKernelGGL((k_out_head_px<32, true, true, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, kn);
-                else hipLaunchKernelGGL((k_out_head_px<64, true, true, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, kn);
-            } else {
-                if (x.C == 64) hipLaunchKernelGGL((k_out_head_px<16, true, false, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, kn);
-                else if (x.C == 128) hipLaunchKernelGGL((k_out_head_px<32, true, false, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, kn);
-                else hipLaunchKernelGGL((k_out_head_px<64, true, false, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, cy, kn);
-            }
-        } else if (fuse_here && carry) {
-            sa = *fuse;
-            if (x.C == 64) hipLaunchKernelGGL((k_out_head_px<16, true, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, *carry);
-            else if (x.C == 128) hipLaunchKernelGGL((k_out_head_px<32, true, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, *carry);
-            else hipLaunchKernelGGL((k_out_head_px<64, true, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa, *carry);
-        } else if (fuse_here) {
-            sa = *fuse;
-            if (x.C == 64) hipLaunchKernelGGL((k_out_head_px<16, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa);
-            else if (x.C == 128) hipLaunchKernelGGL((k_out_head_px<32, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa);
-            else hipLaunchKernelGGL((k_out_head_px<64, true>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa);
-        } else {
-            if (x.C == 64) hipLaunchKernelGGL((k_out_head_px<16, false>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa);
-            else if (x.C == 128) hipLaunchKernelGGL((k_out_head_px<32, false>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa);
-            else hipLaunchKernelGGL((k_out_head_px<64, false>), grid, dim3(256), 0, st, a, segs[0], segs[1], segs[2], sa);
-        }
-        S3D_HIP(hipGetLastError());
-        if (fuse && !fuse_here) {
-            s3d_sampler_args sb = *fuse; sb.model_out = out;
-            if (ms) return launch_sampler_multistep(sb, *ms, nullptr, st);
-            return known ? launch_sampler_known(sb, *known, st) : launch_sampler(sb, st);
-        }
-        return 0;
+        if (x.C == 64) launch_out_head_px<16>(plan, a, segs, B, carry, st);
+        else if (x.C == 128) launch_out_head_px<32>(plan, a, segs, B, carry, st);
+        else launch_out_head_px<64>(plan, a, segs, B, carry, st);
+    } else {
+        const size_t shm = std::max(size_t(64), size_t(a.ppb) * kOutCo * (a.cq + 1)) * sizeof(float);
+        hipLaunchKernelGGL(k_out_head, dim3(cdiv(maxpix, a.ppb), 4, B), dim3(a.cq * a.ppb), shm, st, a);
     }
-    S3D_CHECK(out, S3D_ERR_INVALID, "out head: this width needs a model-output buffer");
-    size_t shm = std::max(size_t(64), size_t(a.ppb) * kOutCo * (a.cq + 1)) * sizeof(float);
-    hipLaunchKernelGGL(k_out_head, dim3(cdiv(maxpix, a.ppb), 4, B), dim3(a.cq * a.ppb), shm, st, a);
     S3D_HIP(hipGetLastError());
-    if (fuse) {
-        s3d_sampler_args sa = *fuse; sa.model_out = out;
-        if (ms) return launch_sampler_multistep(sa, *ms, nullptr, st);
-        return known ? launch_sampler_known(sa, *known, st) : launch_sampler(sa, st);
+    if (plan.update && !plan.in_head) {                      // head, then the stand-alone kernel on the model output it stored
+        s3d_sampler_args sb = *plan.req->step;
+        sb.model_out = out;
+        return launch_sampler(sb, plan.req->ms, plan.req->known, st);
     }
     return 0;
 }
@@ -1312,14 +1285,6 @@ __global__ void k_sampler(s3d_sampler_args a) {
         sampler_element(a, c, i, a.model_out[i]);
     }
 }
-int launch_sampler(const s3d_sampler_args& a, hipStream_t st) {
-    const long long n = a.batch * a.per_sample;
-    if (n <= 0) return 0;
-    unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_sampler, dim3(blocks), dim3(256), 0, st, a);
-    S3D_HIP(hipGetLastError());
-    return 0;
-}
 // ... with the known-region blend (s3d_sampler_step_known; widths the pixel-chunk head does not take)
 __global__ void k_sampler_known(s3d_sampler_args a, s3d_known_region kr) {
     const long long n = a.batch * a.per_sample;
@@ -1329,14 +1294,6 @@ __global__ void k_sampler_known(s3d_sampler_args a, s3d_known_region kr) {
         const KnownCoef kc = known_coef(kr, a.T, t);
         sampler_element_known(a, c, kr, kc, i, a.model_out[i]);
     }
-}
-int launch_sampler_known(const s3d_sampler_args& a, const s3d_known_region& kr, hipStream_t st) {
-    const long long n = a.batch * a.per_sample;
-    if (n <= 0) return 0;
-    unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(k_sampler_known, dim3(blocks), dim3(256), 0, st, a, kr);
-    S3D_HIP(hipGetLastError());
-    return 0;
 }
 // the DPM-Solver++ multistep update (s3d_sampler_step_multistep; the 32-channel model, steps that ask for the model output, every
 // step with a known region — the blend then follows the update and `sample` is stored once)
@@ -1354,14 +1311,14 @@ __global__ void k_sampler_multistep(s3d_sampler_args a, s3d_multistep ms, KnownA
         } else multistep_element(a, ms, c, i, a.model_out[i]);
     }
 }
-int launch_sampler_multistep(const s3d_sampler_args& a, const s3d_multistep& ms, const s3d_known_region* known, hipStream_t st) {
+int launch_sampler(const s3d_sampler_args& a, const s3d_multistep* ms, const s3d_known_region* known, hipStream_t st) {
     const long long n = a.batch * a.per_sample;
     if (n <= 0) return 0;
-    unsigned blocks = (unsigned)std::min<long long>((n + 255) / 256, 4096);
-    if (known) {
-        KnownArg<true> kn; kn.kr = *known;
-        hipLaunchKernelGGL(k_sampler_multistep<true>, dim3(blocks), dim3(256), 0, st, a, ms, kn);
-    } else hipLaunchKernelGGL(k_sampler_multistep<false>, dim3(blocks), dim3(256), 0, st, a, ms, KnownArg<false>());
+    const dim3 blocks((unsigned)std::min<long long>((n + 255) / 256, 4096));
+    if (ms && known) hipLaunchKernelGGL(k_sampler_multistep<true>, blocks, dim3(256), 0, st, a, *ms, KnownArg<true>{*known});
+    else if (ms) hipLaunchKernelGGL(k_sampler_multistep<false>, blocks, dim3(256), 0, st, a, *ms, KnownArg<false>());
+    else if (known) hipLaunchKernelGGL(k_sampler_known, blocks, dim3(256), 0, st, a, *known);
+    else hipLaunchKernelGGL(k_sampler, blocks, dim3(256), 0, st, a);
     S3D_HIP(hipGetLastError());
     return 0;
 }

@@ -98,7 +98,7 @@ struct s3d_unet {
     // Workspace lanes (s3d_unet_select_lane): independent sample chains on different HIP streams through ONE handle — the weights
     // are shared, everything a forward writes (the activation arena, the timestep MLP's scratch, the measured-shape key) exists
     // once per lane.  The fields above ARE the selected lane; the others are parked here.
-    // The next step's in_conv, left in this lane's workspace by the previous fused step's output head (s3d_unet_step_film_carry):
+    // The next step's in_conv, left in this lane's workspace by the output head of the previous step when its plan said so (StepPlan::give):
     // valid for exactly one following step on the tensor `sample` of that shape; any other forward, a workspace reallocation or
     // a parameter change drops it; so does an s3d_set_option call (key[4], the option generation: whether and where the tensor and
     // its partials exist depends on the forms selected).
@@ -206,11 +206,10 @@ int pack_all(s3d_unet* m);
 int finalize_pack_plan(std::vector<PackDesc>& descs, DevBuf& dev, int& blocks_out);   // block prefix + per-block job table, uploaded
 int launch_repack_generic(const PackDesc* descs_dev, int ndesc, int blocks, const float* flat, float* wbuf, float* tbuf, hipStream_t st);
 // ext_film != null: the FiLM table [B or 1][film_total] is given (s3d_unet_film), t is not read
-// fuse != null: one denoising step — the sampler update is applied to the model output by the output head; `out` may then be
-// null (the model output is not stored)
+// step != null: how this forward runs, decided by the caller (plan_step: one denoising step — the sampler update is applied to the
+// model output where the plan says; `out` may be null when that is the output head's launch); null: a plain forward
 int run_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, hipStream_t st,
-                Tape* tape, const float* ext_film = nullptr, int ext_film_stride = 0, const s3d_sampler_args* fuse = nullptr,
-                int carry_flags = 0, const s3d_known_region* known = nullptr, const s3d_multistep* ms = nullptr);
+                Tape* tape, const float* ext_film = nullptr, int ext_film_stride = 0, const StepPlan* step = nullptr);
 
 struct Fwd {
     s3d_unet* m;

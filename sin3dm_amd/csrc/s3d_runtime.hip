@@ -97,18 +97,39 @@ int device_cus() {
     return n;
 }
 
-// the argument rules of the two multistep entry points
-int check_multistep_args(const char* who, const s3d_sampler_args* a, const s3d_multistep* ms, bool need_model_out) {
-    S3D_CHECK(a->x && a->t && a->tables && a->sample && a->pred_xstart && (!need_model_out || a->model_out), S3D_ERR_INVALID,
-              "%s: %sx, t, tables, sample and pred_xstart are required", who, need_model_out ? "model_out, " : "");
-    S3D_CHECK(a->mode == S3D_STEP_DDIM, S3D_ERR_INVALID, "%s: the step's mode must be S3D_STEP_DDIM, not %d", who, a->mode);
-    S3D_CHECK(!a->y0 && !a->mask && !a->mean, S3D_ERR_INVALID, "%s: y0, mask and mean must be NULL (no x0 replacement, no posterior mean)", who);
-    S3D_CHECK(ms->tables, S3D_ERR_INVALID, "%s: the coefficient tables are required", who);
-    S3D_CHECK(ms->order == 1 || ms->order == 2, S3D_ERR_INVALID, "%s: order must be 1 or 2, not %d", who, ms->order);
-    S3D_CHECK(ms->order == 1 || ms->x0_prev, S3D_ERR_INVALID, "%s: order 2 needs x0_prev", who);
-    S3D_CHECK(ms->order == 1 || ms->x0_prev != a->pred_xstart, S3D_ERR_INVALID, "%s: x0_prev may not alias pred_xstart", who);
-    S3D_CHECK(a->T > 0 && a->batch >= 0 && a->per_sample >= 0, S3D_ERR_INVALID, "%s: bad sizes", who);
+// The argument rules of the seven step entry points.  What a known region and the multistep update bring along holds for every
+// entry that takes one; what differs between entries beyond that is in StepEntry.  Everything here comes before any launch.
+int check_step(const StepEntry& e, const StepReq& r) {
+    const s3d_sampler_args* a = r.step;
+    const char* who = e.who;
+    S3D_CHECK((r.carry_flags & ~(S3D_CARRY_OUT | S3D_CARRY_IN)) == 0, S3D_ERR_INVALID, "%s: unknown flag bits %d", who, r.carry_flags);
+    S3D_CHECK((r.model || a->model_out) && a->x && a->t && a->tables && a->pred_xstart, S3D_ERR_INVALID,
+              "%s: %sx, t, tables and pred_xstart are required", who, r.model ? "" : "model_out, ");
+    if (r.ms) S3D_CHECK(a->mode == S3D_STEP_DDIM, S3D_ERR_INVALID, "%s: the step's mode must be S3D_STEP_DDIM, not %d", who, a->mode);
+    else if (r.known) S3D_CHECK(a->mode == S3D_STEP_DDPM || a->mode == S3D_STEP_DDIM, S3D_ERR_INVALID, "%s: a DDPM or DDIM step, not mode %d", who, a->mode);
+    else if (!e.lax) S3D_CHECK(a->mode == S3D_STEP_DDPM || a->mode == S3D_STEP_DDIM || a->mode == S3D_STEP_MEAN_ONLY, S3D_ERR_INVALID, "%s: bad mode %d", who, a->mode);
+    S3D_CHECK(a->mode == S3D_STEP_MEAN_ONLY || a->sample, S3D_ERR_INVALID, "%s: sample output required", who);
+    S3D_CHECK(a->mode != S3D_STEP_DDPM || a->noise, S3D_ERR_INVALID, "%s: DDPM step needs noise", who);
+    if (!r.ms && !e.lax) S3D_CHECK(a->mode != S3D_STEP_DDIM || a->eta == 0.f || a->noise, S3D_ERR_INVALID, "%s: eta>0 needs noise", who);
+    if (r.known || r.ms) S3D_CHECK(!a->y0 && !a->mask, S3D_ERR_INVALID, "%s: the step's own y0 / mask (x0 replacement) cannot be combined with a known region or the multistep update", who);
+    else if (!e.lax) S3D_CHECK((a->y0 == nullptr) == (a->mask == nullptr), S3D_ERR_INVALID, "%s: y0 and mask go together", who);
+    if (r.ms) S3D_CHECK(!a->mean, S3D_ERR_INVALID, "%s: mean must be NULL (the multistep update has no posterior mean)", who);
+    else if (r.known) S3D_CHECK(!a->mean || !r.model || r.model_out, S3D_ERR_INVALID, "%s: the posterior mean is only written by a step that also stores the model output (model_out != NULL)", who);
+    if (r.known) S3D_CHECK(r.known->y0 && r.known->mask && r.known->noise && r.known->tables, S3D_ERR_INVALID, "%s: y0, mask, noise and tables of the known region are required", who);
+    if (r.ms) {
+        S3D_CHECK(r.ms->tables, S3D_ERR_INVALID, "%s: the coefficient tables are required", who);
+        S3D_CHECK(r.ms->order == 1 || r.ms->order == 2, S3D_ERR_INVALID, "%s: order must be 1 or 2, not %d", who, r.ms->order);
+        S3D_CHECK(r.ms->order == 1 || r.ms->x0_prev, S3D_ERR_INVALID, "%s: order 2 needs x0_prev", who);
+        S3D_CHECK(r.ms->order == 1 || r.ms->x0_prev != a->pred_xstart, S3D_ERR_INVALID, "%s: x0_prev may not alias pred_xstart", who);
+    }
+    if (e.sizes) S3D_CHECK(a->T > 0 && a->batch >= 0 && a->per_sample >= 0, S3D_ERR_INVALID, "%s: bad sizes", who);
     return 0;
+}
+
+// the stand-alone entries: the update on a stored model output
+static int sampler_entry(const char* who, const s3d_sampler_args* a, const s3d_multistep* ms, const s3d_known_region* known, void* stream) {
+    S3D_TRY(check_step(StepEntry{who, false, true}, StepReq{a, known, ms}));
+    return launch_sampler(*a, ms, known, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace s3d
@@ -155,40 +176,18 @@ int s3d_device_count(void) {
 }
 
 int s3d_sampler_step(const s3d_sampler_args* a, void* stream) {
-    using namespace s3d;
     S3D_CHECK(a != nullptr, S3D_ERR_INVALID, "sampler_step: null args");
-    S3D_CHECK(a->model_out && a->x && a->t && a->tables && a->pred_xstart, S3D_ERR_INVALID,
-              "sampler_step: model_out, x, t, tables and pred_xstart are required");
-    S3D_CHECK(a->mode == S3D_STEP_DDPM || a->mode == S3D_STEP_DDIM || a->mode == S3D_STEP_MEAN_ONLY, S3D_ERR_INVALID,
-              "sampler_step: bad mode %d", a->mode);
-    S3D_CHECK(a->mode == S3D_STEP_MEAN_ONLY || a->sample, S3D_ERR_INVALID, "sampler_step: sample output required");
-    S3D_CHECK(a->mode != S3D_STEP_DDPM || a->noise, S3D_ERR_INVALID, "sampler_step: DDPM step needs noise");
-    S3D_CHECK(a->mode != S3D_STEP_DDIM || a->eta == 0.f || a->noise, S3D_ERR_INVALID, "sampler_step: eta>0 needs noise");
-    S3D_CHECK((a->y0 == nullptr) == (a->mask == nullptr), S3D_ERR_INVALID, "sampler_step: y0 and mask go together");
-    S3D_CHECK(a->T > 0 && a->batch >= 0 && a->per_sample >= 0, S3D_ERR_INVALID, "sampler_step: bad sizes");
-    return launch_sampler(*a, static_cast<hipStream_t>(stream));
+    return s3d::sampler_entry("sampler_step", a, nullptr, nullptr, stream);
 }
 
 int s3d_sampler_step_known(const s3d_sampler_args* a, const s3d_known_region* known, void* stream) {
-    using namespace s3d;
     S3D_CHECK(a != nullptr && known != nullptr, S3D_ERR_INVALID, "sampler_step_known: null args");
-    S3D_CHECK(a->model_out && a->x && a->t && a->tables && a->pred_xstart && a->sample, S3D_ERR_INVALID,
-              "sampler_step_known: model_out, x, t, tables, sample and pred_xstart are required");
-    S3D_CHECK(a->mode == S3D_STEP_DDPM || a->mode == S3D_STEP_DDIM, S3D_ERR_INVALID, "sampler_step_known: a DDPM or DDIM step, not mode %d", a->mode);
-    S3D_CHECK(a->mode != S3D_STEP_DDPM || a->noise, S3D_ERR_INVALID, "sampler_step_known: DDPM step needs noise");
-    S3D_CHECK(a->mode != S3D_STEP_DDIM || a->eta == 0.f || a->noise, S3D_ERR_INVALID, "sampler_step_known: eta>0 needs noise");
-    S3D_CHECK(!a->y0 && !a->mask, S3D_ERR_INVALID, "sampler_step_known: the step's own y0 / mask (x0 replacement) cannot be combined with a known region");
-    S3D_CHECK(known->y0 && known->mask && known->noise && known->tables, S3D_ERR_INVALID, "sampler_step_known: y0, mask, noise and tables are required");
-    S3D_CHECK(a->T > 0 && a->batch >= 0 && a->per_sample >= 0, S3D_ERR_INVALID, "sampler_step_known: bad sizes");
-    return launch_sampler_known(*a, *known, static_cast<hipStream_t>(stream));
+    return s3d::sampler_entry("sampler_step_known", a, nullptr, known, stream);
 }
 
 int s3d_sampler_step_multistep(const s3d_sampler_args* a, const s3d_multistep* ms, const s3d_known_region* known, void* stream) {
-    using namespace s3d;
     S3D_CHECK(a != nullptr && ms != nullptr, S3D_ERR_INVALID, "sampler_step_multistep: null args");
-    S3D_TRY(check_multistep_args("sampler_step_multistep", a, ms, true));
-    if (known) S3D_CHECK(known->y0 && known->mask && known->noise && known->tables, S3D_ERR_INVALID, "sampler_step_multistep: y0, mask, noise and tables of the known region are required");
-    return launch_sampler_multistep(*a, *ms, known, static_cast<hipStream_t>(stream));
+    return s3d::sampler_entry("sampler_step_multistep", a, ms, known, stream);
 }
 
 int s3d_sampler_renoise(const float* x_prev, const float* noise, const float* known_tables, const int64_t* t, int32_t T, int64_t batch,

@@ -235,10 +235,11 @@ int pack_all(s3d_unet* m) {
 // ------------------------------------------------------------------ forward
 
 int run_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, hipStream_t st,
-                Tape* tape, const float* ext_film, int ext_film_stride, const s3d_sampler_args* fuse, int carry_flags,
-                const s3d_known_region* known, const s3d_multistep* ms) {
+                Tape* tape, const float* ext_film, int ext_film_stride, const StepPlan* step) {
     const s3d_unet_cfg& c = m->cfg;
     const int mc = c.model_channels, ted = 4 * mc;
+    const StepPlan plan = step ? *step : plan_step(nullptr, c.channel_mult[0] * mc, c.out_channels, c.in_channels, tape != nullptr);
+    const int carry_flags = plan.req ? plan.req->carry_flags : 0;
     Fwd f{m, B, st, nullptr};
     f.tape = tape;
     Arena& ar = m->arena;
@@ -325,7 +326,7 @@ int run_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W
                     gn_subgroup(Cc) == gn_subgroup(sk.C) && sk.part.nsub == sk.C / gn_subgroup(Cc) && h.C % gn_subgroup(Cc) == 0) {
                     Tri o;
                     // the last block feeds the output head, which adds the partial sums itself when it can (else: k_gn_finalize)
-                    S3D_TRY(f.resblock_cat(rb, h, sk, o, oi == c.n_levels - 1 ? (out_head_px_takes(rb.Cout, c.out_channels) ? 2 : 1) : 0));
+                    S3D_TRY(f.resblock_cat(rb, h, sk, o, oi == c.n_levels - 1 ? (plan.px_parts ? 2 : 1) : 0));
                     h = o;
                     continue;
                 }
@@ -358,7 +359,7 @@ int run_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W
         Tri o;
         // ... and so does the last one (out head) — which adds the partials itself when it can (inference): partials only
         const bool last = oi == c.n_levels - 1;
-        const int head_parts = last && !tape && out_head_px_takes(m->out_blocks[oi].Cout, c.out_channels) ? 2 : -1;
+        const int head_parts = last && plan.px_parts ? 2 : -1;
         S3D_TRY(f.resblock(m->out_blocks[oi], inp, o, last, head_parts));
         if (tape) { f.last_rb.index = oi; f.last_rb.is_out = true; tape->out_rb.push_back(f.last_rb); tape->cat_in.push_back(inp); }
         h = o;
@@ -366,31 +367,30 @@ int run_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W
     }
     // the decoder's Upsample of the LAST level-0 block does not exist (level > 0 only), so h is at full size
     GnStats stats{nullptr};
-    const bool head_few = !tape && !h.gn && h.part.p && out_head_adds_parts(h.part, h.C, c.out_channels);
+    const bool head_few = plan.px_parts && !h.gn && h.part.p && gn_act_can_add_parts(h.part, h.C);
     const bool head_adds = head_few && gn_parts_in_consumer(out_head_px_blocks(h.g, B));
     if (head_few && !head_adds) {                           // (bit-identical to the in-head addition: the head's 256-thread blocks)
         stats.mr = ar.alloc<float>(size_t(B) * 3 * 64);
         if (!meas) S3D_TRY(launch_gn_finalize_as(h.part, h.g, h.C, B, 256, stats, st));
     } else if (!head_adds) S3D_TRY(f.stats_of(h, stats));
     if (tape) { tape->head_in = h; tape->head_stats = stats; tape->arena_off = ar.off; tape->valid = !meas; }
-    // a fused step on a width the pixel-chunk head does not take: the model output goes through a workspace buffer
-    if (fuse && !out && !out_head_fuses_sampler(h.C, c.out_channels, B)) out = ar.alloc<float>(size_t(B) * c.out_channels * (H + D) * (W + D));
+    // a step whose update follows the head in a launch of its own, without a caller's buffer: the model output goes through the workspace
+    if (plan.ws_out) out = ar.alloc<float>(size_t(B) * c.out_channels * (H + D) * (W + D));
     if (!meas) {
         ActArgs aa;
         for (int p = 0; p < 3; ++p) { aa.gamma[p] = m->dev(m->out_norm.gamma[p]); aa.beta[p] = m->dev(m->out_norm.beta[p]); }
         aa.film = nullptr; aa.film_stride = 0;
         // S3D_CARRY_OUT: the head also runs the NEXT step's in_conv on the x_{t-1} it forms (unet_triplane.py:378, 482: a pointwise
-        // TriplaneConv) into h0 / part0 — dead since this step's first block consumed them
+        // TriplaneConv) into h0 / part0 — dead since this step's first block consumed them — when this forward left partials there
         InConvCarry cy;
-        const bool give = (carry_flags & S3D_CARRY_OUT) && fuse && !(known && out) && !(ms && out) && fuse->sample && fuse->mode != S3D_STEP_MEAN_ONLY && !tape && part0.p &&
-                          h.C == h0.C && out_head_fuses_sampler(h.C, c.out_channels, B) && out_head_can_carry(h.C, c.in_channels, c.out_channels);
+        const bool give = plan.give && part0.p && h.C == h0.C;
         if (give) {
             cy.wT = m->dev(m->in_wT); cy.bias = m->dev(m->in_b); cy.part = part0.p; cy.maxparts = part0.maxparts; cy.Cin = c.in_channels;
             for (int p = 0; p < 3; ++p) cy.out[p] = h0.p[p];
         }
-        S3D_TRY(launch_out_head(h, B, stats, aa, m->dev(m->out_w), m->dev(m->out_b), c.out_channels, H, W, D, out, st, fuse, head_adds ? &h.part : nullptr,
-                                give ? &cy : nullptr, known, ms));
-        if (give) { m->carry.valid = true; m->carry.sample = fuse->sample; memcpy(m->carry.key, ckey, sizeof ckey); }
+        S3D_TRY(launch_out_head(h, B, stats, aa, m->dev(m->out_w), m->dev(m->out_b), c.out_channels, H, W, D, out, st, plan, head_adds ? &h.part : nullptr,
+                                give ? &cy : nullptr));
+        if (give) { m->carry.valid = true; m->carry.sample = plan.req->step->sample; memcpy(m->carry.key, ckey, sizeof ckey); }
     }
     return 0;
 }
@@ -444,8 +444,7 @@ int s3d_unet_set_param(s3d_unet* m, const char* name, const float* data, const i
 }
 
 static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, void* stream,
-                        const float* ext_film, int ext_film_stride, const s3d_sampler_args* fuse = nullptr, int carry_flags = 0,
-                        const s3d_known_region* known = nullptr, const s3d_multistep* ms = nullptr);
+                        const float* ext_film, int ext_film_stride, const StepReq* step = nullptr);
 
 int s3d_unet_forward(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, void* stream) {
     S3D_CHECK(m && x && t && out, S3D_ERR_INVALID, "unet_forward: null argument");
@@ -490,63 +489,42 @@ int s3d_unet_forward_film(s3d_unet* m, const float* x, const float* film, int fi
     return forward_impl(m, x, nullptr, B, H, W, D, out, stream, film, film_stride);
 }
 
+// the four model entries: one denoising step in one call.  StepEntry{name, lax, sizes}; StepReq{step, known, ms, carry flags, model_out, model}
+static int step_entry(const StepEntry& e, s3d_unet* m, const float* film, int film_stride, int B, int H, int W, int D, const StepReq& r, void* stream) {
+    S3D_CHECK(film_stride == 0 || film_stride == m->film_total, S3D_ERR_INVALID, "%s: film_stride must be 0 or %d", e.who, m->film_total);
+    S3D_TRY(s3d::check_step(e, r));
+    S3D_CHECK(r.step->batch == B && r.step->per_sample == (long long)m->cfg.out_channels * (H + D) * (W + D) && m->cfg.in_channels == m->cfg.out_channels,
+              S3D_ERR_INVALID, "%s: the step's shape is not the model's", e.who);
+    return forward_impl(m, r.step->x, nullptr, B, H, W, D, r.model_out, stream, film, film_stride, &r);
+}
 int s3d_unet_step_film(s3d_unet* m, const float* film, int film_stride, int B, int H, int W, int D, const s3d_sampler_args* step,
                        float* model_out, void* stream) {
     S3D_CHECK(m && film && step, S3D_ERR_INVALID, "unet_step_film: null argument");
-    S3D_CHECK(film_stride == 0 || film_stride == m->film_total, S3D_ERR_INVALID, "unet_step_film: film_stride must be 0 or %d", m->film_total);
-    S3D_CHECK(step->x && step->t && step->tables && step->pred_xstart && (step->mode == S3D_STEP_MEAN_ONLY || step->sample) &&
-                  (step->mode != S3D_STEP_DDPM || step->noise),
-              S3D_ERR_INVALID, "unet_step_film: incomplete sampler arguments");
-    S3D_CHECK(step->batch == B && step->per_sample == (long long)m->cfg.out_channels * (H + D) * (W + D) && m->cfg.in_channels == m->cfg.out_channels,
-              S3D_ERR_INVALID, "unet_step_film: the step's shape is not the model's");
-    return forward_impl(m, step->x, nullptr, B, H, W, D, model_out, stream, film, film_stride, step, 0);
+    return step_entry({"unet_step_film", true, false}, m, film, film_stride, B, H, W, D, StepReq{step, nullptr, nullptr, 0, model_out, true}, stream);
 }
 
 int s3d_unet_step_film_carry(s3d_unet* m, const float* film, int film_stride, int B, int H, int W, int D, const s3d_sampler_args* step,
                              float* model_out, void* stream, int carry_flags) {
     S3D_CHECK(m && film && step, S3D_ERR_INVALID, "unet_step_film_carry: null argument");
-    S3D_CHECK((carry_flags & ~(S3D_CARRY_OUT | S3D_CARRY_IN)) == 0, S3D_ERR_INVALID, "unet_step_film_carry: unknown flag bits %d", carry_flags);
-    S3D_CHECK(film_stride == 0 || film_stride == m->film_total, S3D_ERR_INVALID, "unet_step_film_carry: film_stride must be 0 or %d", m->film_total);
-    S3D_CHECK(step->x && step->t && step->tables && step->pred_xstart && (step->mode == S3D_STEP_MEAN_ONLY || step->sample) &&
-                  (step->mode != S3D_STEP_DDPM || step->noise),
-              S3D_ERR_INVALID, "unet_step_film_carry: incomplete sampler arguments");
-    S3D_CHECK(step->batch == B && step->per_sample == (long long)m->cfg.out_channels * (H + D) * (W + D) && m->cfg.in_channels == m->cfg.out_channels,
-              S3D_ERR_INVALID, "unet_step_film_carry: the step's shape is not the model's");
-    return forward_impl(m, step->x, nullptr, B, H, W, D, model_out, stream, film, film_stride, step, carry_flags);
+    return step_entry({"unet_step_film_carry", true, false}, m, film, film_stride, B, H, W, D, StepReq{step, nullptr, nullptr, carry_flags, model_out, true}, stream);
 }
 
 int s3d_unet_step_film_known(s3d_unet* m, const float* film, int film_stride, int B, int H, int W, int D, const s3d_sampler_args* step,
                              const s3d_known_region* known, float* model_out, void* stream, int carry_flags) {
     S3D_CHECK(m && film && step && known, S3D_ERR_INVALID, "unet_step_film_known: null argument");
-    S3D_CHECK((carry_flags & ~(S3D_CARRY_OUT | S3D_CARRY_IN)) == 0, S3D_ERR_INVALID, "unet_step_film_known: unknown flag bits %d", carry_flags);
-    S3D_CHECK(film_stride == 0 || film_stride == m->film_total, S3D_ERR_INVALID, "unet_step_film_known: film_stride must be 0 or %d", m->film_total);
-    S3D_CHECK(step->x && step->t && step->tables && step->pred_xstart && step->sample && (step->mode == S3D_STEP_DDPM || step->mode == S3D_STEP_DDIM) &&
-                  (step->mode != S3D_STEP_DDPM || step->noise) && (step->mode != S3D_STEP_DDIM || step->eta == 0.f || step->noise),
-              S3D_ERR_INVALID, "unet_step_film_known: incomplete sampler arguments (a DDPM or DDIM step)");
-    S3D_CHECK(!step->mean || model_out, S3D_ERR_INVALID, "unet_step_film_known: the posterior mean is only written by a step that also stores the model output (model_out != NULL)");
-    S3D_CHECK(!step->y0 && !step->mask, S3D_ERR_INVALID, "unet_step_film_known: the step's own y0 / mask (x0 replacement) cannot be combined with a known region");
-    S3D_CHECK(known->y0 && known->mask && known->noise && known->tables, S3D_ERR_INVALID, "unet_step_film_known: y0, mask, noise and tables are required");
-    S3D_CHECK(step->batch == B && step->per_sample == (long long)m->cfg.out_channels * (H + D) * (W + D) && m->cfg.in_channels == m->cfg.out_channels,
-              S3D_ERR_INVALID, "unet_step_film_known: the step's shape is not the model's");
-    return forward_impl(m, step->x, nullptr, B, H, W, D, model_out, stream, film, film_stride, step, carry_flags, known);
+    return step_entry({"unet_step_film_known", false, false}, m, film, film_stride, B, H, W, D, StepReq{step, known, nullptr, carry_flags, model_out, true}, stream);
 }
 
 int s3d_unet_step_film_multistep(s3d_unet* m, const float* film, int film_stride, int B, int H, int W, int D, const s3d_sampler_args* step,
                                  const s3d_multistep* ms, float* model_out, void* stream, int carry_flags) {
     S3D_CHECK(m && film && step && ms, S3D_ERR_INVALID, "unet_step_film_multistep: null argument");
-    S3D_CHECK((carry_flags & ~(S3D_CARRY_OUT | S3D_CARRY_IN)) == 0, S3D_ERR_INVALID, "unet_step_film_multistep: unknown flag bits %d", carry_flags);
-    S3D_CHECK(film_stride == 0 || film_stride == m->film_total, S3D_ERR_INVALID, "unet_step_film_multistep: film_stride must be 0 or %d", m->film_total);
-    S3D_TRY(check_multistep_args("unet_step_film_multistep", step, ms, false));
-    S3D_CHECK(step->batch == B && step->per_sample == (long long)m->cfg.out_channels * (H + D) * (W + D) && m->cfg.in_channels == m->cfg.out_channels,
-              S3D_ERR_INVALID, "unet_step_film_multistep: the step's shape is not the model's");
-    return forward_impl(m, step->x, nullptr, B, H, W, D, model_out, stream, film, film_stride, step, carry_flags, nullptr, ms);
+    return step_entry({"unet_step_film_multistep", false, true}, m, film, film_stride, B, H, W, D, StepReq{step, nullptr, ms, carry_flags, model_out, true}, stream);
 }
 
 }  // extern "C"
 
 static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, void* stream,
-                        const float* ext_film, int ext_film_stride, const s3d_sampler_args* fuse, int carry_flags,
-                        const s3d_known_region* known, const s3d_multistep* ms) {
+                        const float* ext_film, int ext_film_stride, const StepReq* step) {
     S3D_CHECK(B >= 1 && H >= 1 && W >= 1 && D >= 1, S3D_ERR_INVALID, "unet_forward: B,H,W,D must be >= 1");
     if (!m->packed) S3D_TRY(pack_all(m));                             // (drops a carried in_conv: it was formed with the old weights)
     m->tape.valid = false;                    // the workspace is shared with the training tape
@@ -554,13 +532,15 @@ static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int 
     // pass 1: measure the workspace; grow it if needed (synchronising only when it really grows).  The walk is pure host
     // work and depends on the shapes and on the options (VCAT, GN_FUSED, RANK1_SLICES, ... decide what is allocated): skipped
     // when both repeat (every step of a sampling loop).
-    const long long key[5] = {B, H, W, D | (fuse && !out ? 1LL << 40 : 0), opt_generation()};      // (a fused step without a caller buffer may need one from the workspace)
+    const s3d_unet_cfg& c = m->cfg;
+    const StepPlan plan = plan_step(step, c.channel_mult[0] * c.model_channels, c.out_channels, c.in_channels, false);
+    const long long key[5] = {B, H, W, D | (plan.ws_out ? 1LL << 40 : 0), opt_generation()};      // (the model output's buffer comes from the workspace)
     const bool same = memcmp(m->inf_key, key, sizeof key) == 0;
     int rc = 0;
     if (!same || m->inf_high > m->arena.buf.cap) {
         m->arena.measuring = true;
         m->arena.high = 0;
-        rc = run_forward(m, x, t, B, H, W, D, out, st, nullptr, ext_film, ext_film_stride, fuse, 0, known, ms);
+        rc = run_forward(m, x, t, B, H, W, D, out, st, nullptr, ext_film, ext_film_stride, &plan);
         m->arena.measuring = false;
         if (rc) return rc;
         m->inf_high = m->arena.high;
@@ -575,7 +555,7 @@ static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int 
     ++m->fwd_count;
     if (m->prof_now) ++m->prof_forwards;
     m->arena.peak = 0;
-    rc = run_forward(m, x, t, B, H, W, D, out, st, nullptr, ext_film, ext_film_stride, fuse, carry_flags, known, ms);
+    rc = run_forward(m, x, t, B, H, W, D, out, st, nullptr, ext_film, ext_film_stride, &plan);
     m->prof_now = false;
     if (rc) return rc;
     return workspace_overrun("unet_forward", m->arena.peak, m->inf_high);

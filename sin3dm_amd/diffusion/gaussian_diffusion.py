@@ -273,7 +273,55 @@ class GaussianDiffusion:
         return (_extract_into_tensor(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
                 + _extract_into_tensor(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * noise)
 
-    # ------------------------------------------------------------------ one fused update
+    # ------------------------------------------------------------------ one update
+    def _evaluate(self, model, x, ts, model_kwargs, fuse, denoised_fn=None):
+        """-> (the denoiser's `denoise_step`, None) when the step can be ONE library call (asked for, offered, host-known timesteps,
+        nothing done to the model output), else (None, the model's output on x)."""
+        step_fn = getattr(model, "denoise_step", None) if fuse else None
+        if step_fn is not None and denoised_fn is None and host_values_of(ts) is not None and set(model_kwargs) == {"H", "W", "D"}:
+            return step_fn, None
+        out = model(x, ts, **model_kwargs)
+        assert out.shape == x.shape, "learned-variance outputs are not supported on this path"
+        if denoised_fn is not None:
+            if self.model_mean_type != ModelMeanType.START_X:
+                raise NotImplementedError("denoised_fn with epsilon prediction")
+            out = denoised_fn(out)
+        return None, out.contiguous()
+
+    def _known_args(self, known, x):
+        """known: (y0, mask, eps_known), each of x's shape, fp32, contiguous, on x's device -> _lib.KnownRegionArgs (None -> None)."""
+        if known is None:
+            return None
+        for k in known:
+            assert k.shape == x.shape and k.dtype == th.float32 and k.is_contiguous() and k.device == x.device
+        return _lib.KnownRegionArgs(y0=known[0].data_ptr(), mask=known[1].data_ptr(), noise=known[2].data_ptr(),
+                                    tables=self._known_tables(x.device).data_ptr())
+
+    def _sampler_args(self, mode, x, t64, clip_denoised, model_output, noise, sample, pred, eta=0.0, y0=None, mask=None,
+                      is_mask_t0=False, mean=None):
+        """_lib.SamplerArgs of one update on x (tensors or None; the caller keeps them alive until the call is made)."""
+        ptr = _lib.ptr
+        return _lib.SamplerArgs(mode=mode, mean_type=self._mean_type_code(), clip_denoised=int(bool(clip_denoised)),
+                                is_mask_t0=int(bool(is_mask_t0)), eta=float(eta), T=self.num_timesteps, batch=x.shape[0],
+                                per_sample=x[0].numel(), model_out=ptr(model_output), x=x.data_ptr(), noise=ptr(noise),
+                                t=t64.data_ptr(), tables=self._tables(x.device).data_ptr(), y0=ptr(y0), mask=ptr(mask),
+                                sample=ptr(sample), pred_xstart=pred.data_ptr(), mean=ptr(mean))
+
+    @staticmethod
+    def _run_update(step_fn, model, x, ts, a, carry, model_kwargs, kr=None, ms=None):
+        """The update `a`: in the denoiser's one call (step_fn, of _evaluate) or, on the model output a.model_out, by the
+        stand-alone entry.  denoise_step gets only the keywords this step needs (subclasses and wrappers may not know the others)."""
+        if step_fn is None:
+            entry, args = (("s3d_sampler_step_multistep", (a, ms, kr)) if ms is not None else
+                           ("s3d_sampler_step_known", (a, kr)) if kr is not None else ("s3d_sampler_step", (a,)))
+            with th.cuda.device(x.device):
+                return _lib.check(getattr(_lib.load(), entry)(*args, _lib.stream_ptr()))
+        extra = {k: v for k, v in (("known", kr), ("multistep", ms)) if v is not None}
+        carry = carry if getattr(model, "carries_in_conv", False) else 0
+        if carry or extra:
+            extra["carry"] = carry
+        step_fn(x, ts, a, **extra, **model_kwargs)
+
     def _step(self, mode, model, x, t, clip_denoised, denoised_fn, model_kwargs, eta=0.0, y0=None, mask=None,
               is_mask_t0=False, want_mean=False, fuse=False, noise=None, carry=0, known=None):
         """fuse (the sampling loops): when the denoiser offers `denoise_step` and the timestep values are known on the host,
@@ -285,28 +333,17 @@ class GaussianDiffusion:
         _lib.require_gpu(x)
         if model_kwargs is None:
             model_kwargs = {}
-        B, Cc = x.shape[:2]
-        assert t.shape == (B,)
+        assert t.shape == (x.shape[0],)
         x = x.contiguous().float()
-        step_fn = getattr(model, "denoise_step", None) if fuse else None
         ts = self._scale_timesteps(t)
-        fused = (step_fn is not None and denoised_fn is None and host_values_of(ts) is not None
-                 and mode in (_lib.STEP_DDPM, _lib.STEP_DDIM) and not want_mean and set(model_kwargs) == {"H", "W", "D"})
-        model_output = None
-        if not fused:
-            model_output = model(x, ts, **model_kwargs)
-            assert model_output.shape == x.shape, "learned-variance outputs are not supported on this path"
-            if denoised_fn is not None:
-                if self.model_mean_type != ModelMeanType.START_X:
-                    raise NotImplementedError("denoised_fn with epsilon prediction")
-                model_output = denoised_fn(model_output)
-            model_output = model_output.contiguous()
+        step_fn, model_output = self._evaluate(model, x, ts, model_kwargs, fuse and mode in (_lib.STEP_DDPM, _lib.STEP_DDIM) and not want_mean,
+                                               denoised_fn)
         sample = th.empty_like(x) if mode != _lib.STEP_MEAN_ONLY else None
         pred = th.empty_like(x)
         mean = th.empty_like(x) if want_mean else None
         if noise is not None:
             assert noise.shape == x.shape and noise.is_contiguous()
-        elif mode == _lib.STEP_DDPM or (mode == _lib.STEP_DDIM):
+        elif mode in (_lib.STEP_DDPM, _lib.STEP_DDIM):
             # the reference draws randn_like on every step, t == 0 and eta == 0 included (:431, :591); the single-step API does
             # the same (one randn_like per call).  The loops hand in `noise` from their own chunked draws (see _loop)
             noise = self._noise(x).contiguous()
@@ -315,40 +352,15 @@ class GaussianDiffusion:
             y0, mask = y0.contiguous().float(), mask.contiguous().float()
         else:
             y0 = mask = None
-        kr = None
         if known is not None:
             if y0 is not None:
                 raise ValueError("known= cannot be combined with the DDIM x0 replacement (y0= / mask=)")
             assert mode in (_lib.STEP_DDPM, _lib.STEP_DDIM) and not want_mean
-            for k in known:
-                assert k.shape == x.shape and k.dtype == th.float32 and k.is_contiguous() and k.device == x.device
-            kr = _lib.KnownRegionArgs(y0=known[0].data_ptr(), mask=known[1].data_ptr(), noise=known[2].data_ptr(),
-                                      tables=self._known_tables(x.device).data_ptr())
-        tab = self._tables(x.device)
+        kr = self._known_args(known, x)
         t64 = t.to(device=x.device, dtype=th.int64).contiguous()
-        a = _lib.SamplerArgs(mode=mode, mean_type=self._mean_type_code(), clip_denoised=int(bool(clip_denoised)),
-                             is_mask_t0=int(bool(is_mask_t0)), eta=float(eta), T=self.num_timesteps, batch=B,
-                             per_sample=x[0].numel(), model_out=model_output.data_ptr() if model_output is not None else None,
-                             x=x.data_ptr(),
-                             noise=noise.data_ptr() if noise is not None else None, t=t64.data_ptr(),
-                             tables=tab.data_ptr(), y0=y0.data_ptr() if y0 is not None else None,
-                             mask=mask.data_ptr() if mask is not None else None,
-                             sample=sample.data_ptr() if sample is not None else None, pred_xstart=pred.data_ptr(),
-                             mean=mean.data_ptr() if mean is not None else None)
-        if fused and kr is not None:
-            step_fn(x, ts, a, carry=carry if getattr(model, "carries_in_conv", False) else 0, known=kr, **model_kwargs)
-            return sample, pred, mean
-        if fused:
-            if carry and getattr(model, "carries_in_conv", False):
-                step_fn(x, ts, a, carry=carry, **model_kwargs)
-            else:
-                step_fn(x, ts, a, **model_kwargs)
-            return sample, pred, mean
-        with th.cuda.device(x.device):
-            if kr is not None:
-                _lib.check(_lib.load().s3d_sampler_step_known(a, kr, _lib.stream_ptr()))
-            else:
-                _lib.check(_lib.load().s3d_sampler_step(a, _lib.stream_ptr()))
+        a = self._sampler_args(mode, x, t64, clip_denoised, model_output, noise, sample, pred, eta=eta, y0=y0, mask=mask,
+                               is_mask_t0=is_mask_t0, mean=mean)
+        self._run_update(step_fn, model, x, ts, a, carry, model_kwargs, kr=kr)
         return sample, pred, mean
 
     def _multistep_step(self, model, x, t, clip_denoised, model_kwargs, order=1, x0_prev=None, sde=False, noise=None, carry=0,
@@ -363,8 +375,7 @@ class GaussianDiffusion:
         _lib.require_gpu(x)
         if model_kwargs is None:
             model_kwargs = {}
-        B = x.shape[0]
-        assert t.shape == (B,) and order in (1, 2)
+        assert t.shape == (x.shape[0],) and order in (1, 2)
         x = x.contiguous().float()
         if tables is None:
             tables = self._multistep_tables(x.device, 2, sde)[0]
@@ -373,34 +384,13 @@ class GaussianDiffusion:
             assert x0_prev is not None and x0_prev.shape == x.shape and x0_prev.dtype == th.float32 and x0_prev.is_contiguous() and x0_prev.device == x.device
         if noise is not None:
             assert noise.shape == x.shape and noise.is_contiguous() and noise.dtype == th.float32
-        step_fn = getattr(model, "denoise_step", None) if fuse else None
         ts = self._scale_timesteps(t)
-        fused = step_fn is not None and known is None and host_values_of(ts) is not None and set(model_kwargs) == {"H", "W", "D"}
-        model_output = None
-        if not fused:
-            model_output = model(x, ts, **model_kwargs)
-            assert model_output.shape == x.shape, "learned-variance outputs are not supported on this path"
-            model_output = model_output.contiguous()
+        step_fn, model_output = self._evaluate(model, x, ts, model_kwargs, fuse and known is None)
         sample, pred = th.empty_like(x), th.empty_like(x)
-        kr = None
-        if known is not None:
-            for k in known:
-                assert k.shape == x.shape and k.dtype == th.float32 and k.is_contiguous() and k.device == x.device
-            kr = _lib.KnownRegionArgs(y0=known[0].data_ptr(), mask=known[1].data_ptr(), noise=known[2].data_ptr(),
-                                      tables=self._known_tables(x.device).data_ptr())
         t64 = t.to(device=x.device, dtype=th.int64).contiguous()
-        a = _lib.SamplerArgs(mode=_lib.STEP_DDIM, mean_type=self._mean_type_code(), clip_denoised=int(bool(clip_denoised)), is_mask_t0=0,
-                             eta=0.0, T=self.num_timesteps, batch=B, per_sample=x[0].numel(),
-                             model_out=model_output.data_ptr() if model_output is not None else None, x=x.data_ptr(),
-                             noise=noise.data_ptr() if noise is not None else None, t=t64.data_ptr(),
-                             tables=self._tables(x.device).data_ptr(), y0=None, mask=None, sample=sample.data_ptr(),
-                             pred_xstart=pred.data_ptr(), mean=None)
+        a = self._sampler_args(_lib.STEP_DDIM, x, t64, clip_denoised, model_output, noise, sample, pred)
         ms = _lib.MultistepArgs(x0_prev=x0_prev.data_ptr() if order == 2 else None, tables=tables.data_ptr(), order=int(order))
-        if fused:
-            step_fn(x, ts, a, carry=carry if getattr(model, "carries_in_conv", False) else 0, multistep=ms, **model_kwargs)
-            return sample, pred
-        with th.cuda.device(x.device):
-            _lib.check(_lib.load().s3d_sampler_step_multistep(a, ms, kr, _lib.stream_ptr()))
+        self._run_update(step_fn, model, x, ts, a, carry, model_kwargs, kr=self._known_args(known, x), ms=ms)
         return sample, pred
 
     def renoise(self, x_prev, t, noise):

@@ -341,6 +341,11 @@ class _TriplaneUNetBase(nn.Module):
     # denoise_step takes `carry` (GaussianDiffusion._loop asks); S3D_CARRY_IN_CONV=0: every step launches its own in_conv (A/B)
     carries_in_conv = os.environ.get("S3D_CARRY_IN_CONV", "1") != "0"
 
+    # denoise_step's library call: the first entry whose argument the step brings; it follows `step` in the call (the structs), and
+    # every entry but the plain one takes the carry flags last
+    _STEP_ENTRIES = (("multistep", "s3d_unet_step_film_multistep"), ("known", "s3d_unet_step_film_known"),
+                     ("carry", "s3d_unet_step_film_carry"), (None, "s3d_unet_step_film"))
+
     def denoise_step(self, x, timesteps, step, H=None, W=None, D=None, carry=0, known=None, multistep=None):
         """One step of a sampling loop in one library call: this forward (host-known `timesteps`) with the sampler update
         `step` (_lib.SamplerArgs with x / noise / tables / outputs set; its model_out is ignored) applied by the output
@@ -363,19 +368,13 @@ class _TriplaneUNetBase(nn.Module):
         t = timesteps.to(device=x.device, dtype=th.float32).contiguous()
         with th.cuda.device(x.device):
             film, stride = self._film_for(lib, hv, t)
-            if multistep is not None:
-                assert known is None, "the known-region blend is not fused with the multistep update (forward + s3d_sampler_step_multistep)"
-                _lib.check(lib.s3d_unet_step_film_multistep(self._handle, _lib.ptr(film), stride, B, int(H), int(W), int(D), C.byref(step),
-                                                            C.byref(multistep), None, _lib.stream_ptr(), int(carry)))
-            elif known is not None:
-                _lib.check(lib.s3d_unet_step_film_known(self._handle, _lib.ptr(film), stride, B, int(H), int(W), int(D), C.byref(step),
-                                                        C.byref(known), None, _lib.stream_ptr(), int(carry)))
-            elif carry:
-                _lib.check(lib.s3d_unet_step_film_carry(self._handle, _lib.ptr(film), stride, B, int(H), int(W), int(D), C.byref(step),
-                                                        None, _lib.stream_ptr(), int(carry)))
-            else:
-                _lib.check(lib.s3d_unet_step_film(self._handle, _lib.ptr(film), stride, B, int(H), int(W), int(D), C.byref(step),
-                                                  None, _lib.stream_ptr()))
+            assert multistep is None or known is None, "the known-region blend is not fused with the multistep update (forward + s3d_sampler_step_multistep)"
+            given = {"multistep": multistep, "known": known, "carry": carry or None}
+            key, entry = next((k, e) for k, e in self._STEP_ENTRIES if k is None or given[k] is not None)
+            extra = [C.byref(given[key])] if key in ("multistep", "known") else []
+            flags = [int(carry)] if key is not None else []
+            _lib.check(getattr(lib, entry)(self._handle, _lib.ptr(film), stride, B, int(H), int(W), int(D), C.byref(step), *extra, None,
+                                           _lib.stream_ptr(), *flags))
 
     def prepare_timesteps(self, values, t_dev):
         """The FiLM tables of a whole schedule (host values + the same values on the device) in one batched launch (three

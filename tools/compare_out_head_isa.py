@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Is the output head of the default path still the kernel it was?  Compiles sin3dm_amd/csrc/s3d_kernels.hip of the working tree and
 of a git revision to gfx950 assembly (device side only, the Makefile's flags) and compares the instructions of every
-k_out_head_px<CQ, FUSED, CARRY, KNOWN> instantiation line by line, comments stripped (tools/compare_kdecode_isa.py does the same for
-k_decode).  The kernel's body (s3d_out_head_px_body.h) is shared with k_out_head_px_ms<CQ, CARRY> (the DPM-Solver++ multistep update,
-DESIGN.md section 26); the fifteen instantiations the sampling loops have used so far must keep their code.  Exit status 1 on a
+k_out_head_px<CQ, FUSED, CARRY, KNOWN> and k_out_head_px_ms<CQ, CARRY> instantiation (the DPM-Solver++ multistep update, DESIGN.md
+section 26: the same body, s3d_out_head_px_body.h) line by line, comments stripped (tools/compare_kdecode_isa.py does the same for
+k_decode): all twenty-one must keep their code, and none may appear or go.  Exit status 1 on a
 difference (the differing line counts and the first differing line are printed).  Also prints registers, LDS, scratch and spills of
 the k_out_head_px_ms instantiations next to their default counterparts.  Run it after touching the body or changing the compiler.
 
@@ -21,16 +21,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 KEYS = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count", "sgpr_spill_count")
 
 
-def assembly(source_text, tmp, tag):
-    src = os.path.join(CSRC, f".isa_{tag}.hip")          # beside the headers it includes
+def assembly(csrc, tmp, tag):
     out = os.path.join(tmp, tag + ".s")
-    with open(src, "w") as fh:
-        fh.write(source_text)
-    try:
-        subprocess.check_call([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fvisibility=hidden", "-S", "--cuda-device-only",
-                               src, "-o", out], stderr=subprocess.DEVNULL)
-    finally:
-        os.remove(src)
+    subprocess.check_call([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fvisibility=hidden", "-S", "--cuda-device-only",
+                           os.path.join(csrc, "s3d_kernels.hip"), "-o", out], stderr=subprocess.DEVNULL)
     return open(out).read().split("\n")
 
 
@@ -57,12 +51,12 @@ def metadata(lines, name_re):
 
 def main():
     rev = sys.argv[1] if len(sys.argv) > 1 else "HEAD~1"
-    old = subprocess.check_output(["git", "-C", REPO, "show", f"{rev}:sin3dm_amd/csrc/s3d_kernels.hip"], text=True)
-    new = open(os.path.join(CSRC, "s3d_kernels.hip")).read()
     with tempfile.TemporaryDirectory() as tmp:
-        a, b = assembly(old, tmp, "old"), assembly(new, tmp, "new")
-    prefix = "_ZN3s3d13k_out_head_pxI"
-    ka, kb = kernels(a, prefix), kernels(b, prefix)
+        # the revision's source beside the revision's own headers (the body is one of them)
+        tar = subprocess.check_output(["git", "-C", REPO, "archive", rev, "sin3dm_amd/csrc", "include"])
+        subprocess.run(["tar", "-x", "-C", tmp], input=tar, check=True)
+        a, b = assembly(os.path.join(tmp, "sin3dm_amd", "csrc"), tmp, "old"), assembly(CSRC, tmp, "new")
+    ka, kb = ({**kernels(x, "_ZN3s3d13k_out_head_pxI"), **kernels(x, "_ZN3s3d16k_out_head_px_msI")} for x in (a, b))
     same = sorted(ka) == sorted(kb)
     for k in sorted(ka):
         eq = kb.get(k) == ka[k]
@@ -72,7 +66,7 @@ def main():
             d = next((i for i, (x, y) in enumerate(zip(ka[k], kb[k])) if x != y), min(len(ka[k]), len(kb[k])))
             note = f" ({len(kb[k])} lines now; first difference at line {d}: {ka[k][d:d + 1]} -> {kb[k][d:d + 1]})"
         print(f"{k}: {len(ka[k])} lines, {'identical' if eq else 'DIFFERENT' + note}")
-    ma, mb = metadata(a, r"_ZN3s3d13k_out_head_pxI"), metadata(b, r"_ZN3s3d1[36]k_out_head_px(_ms)?I")
+    ma, mb = (metadata(x, r"_ZN3s3d1[36]k_out_head_px(_ms)?I") for x in (a, b))
     for k in sorted(ma):
         if ma[k] != mb.get(k):
             print(f"{k}: metadata {[ma[k].get(x) for x in KEYS]} -> {[mb.get(k, {}).get(x) for x in KEYS]}")
