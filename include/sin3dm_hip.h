@@ -503,6 +503,46 @@ S3D_API int s3d_mc_extract(s3d_mc* m, float* verts, float* attrs, int n_attr, in
 S3D_API int s3d_mesh_components(const int32_t* tris, int64_t n_tris, int64_t n_verts, int32_t* labels, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Narrow-band iso-surface extraction: the mesh of s3d_mc_* from the bricks the surface crosses only.
+ * Padded vertex space as above with pad = 1: P = dims + 2 vertices per axis, vertex p holds sample p - 1 or pad_value.
+ * Brick b holds the padded vertices [b B, b B + B) per axis (B = 4, 8 or 16; nb = ceil(P / B), the last brick may be partial).
+ * The caller owns the sample pool [slot][B^3][stride] (value in channel 0, attributes after it; local order lx, ly, lz): a
+ * brick gets a slot when it becomes active, slots are append-only, s3d_mcs_pending names the samples of the newest slots.
+ * A cell is extracted iff the bricks of all eight of its corners are active; the result is the dense mesh without the
+ * triangles of the other cells and without the vertices nothing references any more, in the dense order (vertices by
+ * edge axis, then padded linear vertex index; triangles by padded linear cell index), linear indices in 64 bits.
+ * Order of calls: plan, seed, then {pending, the caller fills the pool, grow} until grow reports no boundary cut edge,
+ * count, extract, occupancy.  Every call but pending / extract / occupancy synchronises `stream`.
+ * ------------------------------------------------------------------------------------------------ */
+#define S3D_MCS_MAX_BRICKS (1 << 27)           /* nb^3: the brick table and its scans, 512 MiB each */
+#define S3D_MCS_MAX_SAMPLES (1 << 30)          /* slots * B^3: pool entries (a 32-bit item count in the scans and sorts) */
+typedef struct s3d_mcs s3d_mcs;
+S3D_API int s3d_mcs_create(s3d_mcs** out);
+S3D_API void s3d_mcs_destroy(s3d_mcs* m);
+/* Forgets every slot.  nb[3]: bricks per axis.  pad must be 1.  More than S3D_MCS_MAX_BRICKS bricks: S3D_ERR_UNSUPPORTED, before
+ * anything is allocated. */
+S3D_API int s3d_mcs_plan(s3d_mcs* m, int X, int Y, int Z, int block, int pad, float pad_value, float iso, int nb[3]);
+/* lattice: the field on the brick corners, [(nb0+1)][(nb1+1)][(nb2+1)][lattice_stride] with the value in channel 0, point
+ * (i,j,k) at unpadded index coordinates i B - 1.5; the points outside [-0.5, dims - 0.5] are replaced by pad_value here.
+ * A brick is a seed iff `value < iso` differs among its eight corners; dilate adds the 26-neighbourhood that many times.
+ * all_active != 0: every brick is activated and lattice is not read (may be null).  n_new bricks got slots [0, n_new). */
+S3D_API int s3d_mcs_seed(s3d_mcs* m, const float* lattice, int lattice_stride, int dilate, int all_active, int64_t* n_seed,
+                         int64_t* n_new, void* stream);
+/* coords [n_new * B^3][3]: the unpadded index coordinates of the pool entries of the newest slots, in pool order.  An entry
+ * that is a pad vertex or lies beyond P is never read from the pool; its coordinates are clamped into the grid. */
+S3D_API int s3d_mcs_pending(s3d_mcs* m, float* coords, void* stream);
+/* The boundary pass over every slot (pool holds all of them): n_boundary cut edges have an extracted and a non-extracted cell
+ * around them; with activate != 0 the bricks of all corners of those non-extracted cells are activated, n_new of them new (slots
+ * appended), with activate = 0 the edges are only counted.  More than S3D_MCS_MAX_SAMPLES pool entries: S3D_ERR_UNSUPPORTED. */
+S3D_API int s3d_mcs_grow(s3d_mcs* m, const float* pool, int stride, int activate, int64_t* n_boundary, int64_t* n_new, void* stream);
+S3D_API int s3d_mcs_count(s3d_mcs* m, const float* pool, int stride, int64_t* n_verts, int64_t* n_tris, void* stream);
+/* verts [n_verts][3], attrs [n_verts][n_attr] or null (channels 1..n_attr of the pool), tris [n_tris][3]: the expressions of
+ * s3d_mc_extract, so with every brick active the bits of s3d_mc_count / s3d_mc_extract on the dense grid */
+S3D_API int s3d_mcs_extract(s3d_mcs* m, float* verts, float* attrs, int n_attr, int32_t* tris, void* stream);
+/* occ [X][Y][Z] uint8: `value < iso` from the pool in active bricks, the first lattice corner's in the others */
+S3D_API int s3d_mcs_occupancy(s3d_mcs* m, const float* pool, int stride, uint8_t* occ, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Textured mesh export: the device half of what follows the iso-surface in decode_texmesh
  * (src/encoding/model.py:389-430) — decimation, texel positions of a UV atlas, texture finishing.  An own design
  * (vertex clustering, an analytic per-face atlas): parity with open3d / xatlas / nvdiffrast is not claimed.

@@ -24,7 +24,8 @@ MEAN_START_X, MEAN_EPSILON = 0, 1
 ERR_INVALID, ERR_MISSING, ERR_HIP, ERR_UNSUPPORTED, ERR_INTERNAL = -1, -2, -3, -4, -5
 MAX_LANES = 16
 MESHSDF_MAX_PAIRS = 1 << 27           # S3D_MESHSDF_MAX_PAIRS (include/sin3dm_hip.h): 1.5 GiB of (cell, triangle) pairs
-RENDER_MAX_PAIRS = 1 << 27            # S3D_RENDER_MAX_PAIRS: 1 GiB of (tile, triangle) pairs
+MCS_MAX_BRICKS, MCS_MAX_SAMPLES = 1 << 27, 1 << 30      # S3D_MCS_MAX_BRICKS / S3D_MCS_MAX_SAMPLES
+RENDER_MAX_PAIRS = 1 << 27           # S3D_RENDER_MAX_PAIRS: 1 GiB of (tile, triangle) pairs
 RENDER_TILE, RENDER_SUBPIXEL, RENDER_MAX_COORD, RENDER_MAX_GRID = 16, 256, 1 << 20, 4096
 IMGFEAT_INCEPTION, IMGFEAT_ALEXNET = 0, 1          # S3D_IMGFEAT_*
 RENDER_AMBIENT, RENDER_DIFFUSE = 0.35, 0.65                    # S3D_RENDER_AMBIENT / S3D_RENDER_DIFFUSE
@@ -149,6 +150,16 @@ SIGNATURES = {
                                c_i64p, c_i64p, C.c_void_p]),
     "s3d_mc_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "s3d_mesh_components": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    # narrow-band iso-surface extraction
+    "s3d_mcs_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "s3d_mcs_destroy": (None, [C.c_void_p]),
+    "s3d_mcs_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(C.c_int)]),
+    "s3d_mcs_seed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_i64p, c_i64p, C.c_void_p]),
+    "s3d_mcs_pending": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3d_mcs_grow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_i64p, c_i64p, C.c_void_p]),
+    "s3d_mcs_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_i64p, c_i64p, C.c_void_p]),
+    "s3d_mcs_extract": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "s3d_mcs_occupancy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     # textured mesh export: decimation, atlas texel positions, texture finishing
     "s3d_mesh_cluster_keys": (C.c_int, [C.c_void_p, C.c_int64, c_fp, C.c_float, C.POINTER(C.c_int), C.c_void_p, C.c_void_p]),
     "s3d_mesh_cluster_means": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),

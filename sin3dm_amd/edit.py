@@ -14,7 +14,7 @@
 --resample R                 every step but the last runs R times with a re-noising in between (RePaint's resampling)
 
 --resize sets the canvas for --keep / --paste (as for sample.py); --outpaint sets its own.  Everything else — flags, lanes and
-chains at batch 1 and 2, S3D_NOISE / S3D_MESH / S3D_DECIMATE / S3D_MESH_NORMAL_MAP, S3D_SAMPLER (the few-step samplers of DESIGN.md section 26; not with
+chains at batch 1 and 2, S3D_NOISE / S3D_MESH / S3D_DECIMATE / S3D_MESH_NORMAL_MAP / S3D_MESH_SPARSE, S3D_SAMPLER (the few-step samplers of DESIGN.md section 26; not with
 --resample > 1), the per-sample feat.npz and mesh files, the aabb scaled with the canvas — is sin3dm_amd.sample's.  A box marks its projection on each plane, and a plane pixel stands for a whole column of the
 volume (sin3dm_amd/utils/region_util.py).
 """

@@ -62,6 +62,146 @@ def marching_cubes(grid, iso=0.0, pad_value=1.0, n_attr=0):
     return verts, tris, attrs
 
 
+_sparse_handles = {}       # device index -> s3d_mcs handle (brick table, key lists)
+
+
+def _sparse_handle(device):
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    if key not in _sparse_handles:
+        h = C.c_void_p()
+        _lib.check(_lib.load().s3d_mcs_create(C.byref(h)))
+        _sparse_handles[key] = h
+    return _sparse_handles[key]
+
+
+def release_sparse_workspace():
+    """Free the cached brick tables and key lists of marching_cubes_sparse."""
+    for h in _sparse_handles.values():
+        _lib.load().s3d_mcs_destroy(h)
+    _sparse_handles.clear()
+
+
+def sparse_lattice_coords(dims, block, device=None):
+    """([(nb0+1)(nb1+1)(nb2+1), 3] float32 index coordinates of the brick-corner lattice, clamped into [-0.5, dims - 0.5], nb):
+    point (i,j,k) sits at i * block - 1.5.  The points the clamp moved are replaced by pad_value in the seed pass,
+    whatever the field answers there."""
+    nb = [(d + 2 + block - 1) // block for d in dims]
+    axes = [torch.clamp(torch.arange(n + 1, dtype=torch.float32, device=device) * block - 1.5, -0.5, d - 0.5) for n, d in zip(nb, dims)]
+    return torch.stack(torch.meshgrid(*axes, indexing="ij"), -1).reshape(-1, 3), nb
+
+
+def marching_cubes_sparse(sample_fn, dims, iso=0.0, pad_value=1.0, n_attr=0, block=8, dilate=0, max_rounds=64, all_active=False,
+                          return_info=False, occupancy=False, device=None, stages=None):
+    """The mesh of marching_cubes(grid, iso, pad_value, n_attr) from the bricks the surface crosses, without the grid.
+    sample_fn(idx) takes float32 index coordinates [M,3] on the device — integers for the grid's samples, x.5 for the brick-corner
+    lattice — and returns [M,1+A] (value in column 0, A >= n_attr attributes after it).  dims: the grid's (X, Y, Z).
+    Bricks of block^3 padded vertices (4, 8 or 16) whose eight lattice corners do not all compare the same way against iso are
+    seeds (+ dilate rounds of their 26-neighbourhood); a cell is extracted iff the bricks of all eight of its corners are active;
+    while a cut edge has an extracted and a non-extracted cell around it the bricks of those cells are activated and evaluated,
+    at most max_rounds times.  The result is the dense mesh without the triangles of the cells that were not extracted, in the
+    dense order, with the dense path's bits; all_active=True activates every brick and gives the dense mesh itself.  When
+    info["closed"], the result is a union of whole connected components of the dense mesh: every component that has a triangle in
+    a cell of the seed bricks, and those a grown brick happens to hold.  A component no lattice point sees and no grown brick meets
+    is left out.
+    Returns (verts, tris, attrs) and, with return_info, info: rounds, closed, n_bricks, n_active, n_seed, n_samples (evaluations
+    of sample_fn, the lattice included), nb, and with occupancy=True "occupancy", uint8 [X,Y,Z]: value < iso, from the samples in
+    active bricks and the (unanimous) lattice corners of the others.
+    stages: a list that receives (name, milliseconds) of the stages from device events (lattice, seed, decode r, grow r, count,
+    extract, occupancy); measuring synchronises after every stage."""
+    _lib.require_gpu()
+    X, Y, Z = (int(d) for d in dims)
+    block, dilate, max_rounds, n_attr = int(block), int(dilate), int(max_rounds), int(n_attr)
+    if pad_value is None:
+        raise ValueError("marching_cubes_sparse works on the padded grid: pad_value=None is the dense path's")
+    if max_rounds < 0 or dilate < 0:
+        raise ValueError(f"max_rounds={max_rounds}, dilate={dilate}: expected both >= 0")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    lib = _lib.load()
+    h = _sparse_handle(dev)
+    per = block ** 3
+
+    def field(coords):
+        out = sample_fn(coords)
+        if out.dim() != 2 or out.shape[0] != coords.shape[0] or out.shape[1] < 1 + n_attr or not out.is_cuda:
+            raise ValueError(f"sample_fn returned {tuple(out.shape)} on {out.device} for {coords.shape[0]} points: expected [M, >= {1 + n_attr}] "
+                             f"on the device")
+        return out.contiguous().float()
+
+    def timed(name, fn):
+        if stages is None:
+            return fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        stages.append((name, e0.elapsed_time(e1)))
+        return out
+
+    with torch.cuda.device(dev):
+        st = _lib.stream_ptr()
+        nb = (C.c_int * 3)()
+        _lib.check(lib.s3d_mcs_plan(h, X, Y, Z, block, 1, float(pad_value), float(iso), nb))
+        n_seed, n_new, n_bound = C.c_int64(), C.c_int64(), C.c_int64()
+        n_samples = 0
+        if all_active:
+            _lib.check(lib.s3d_mcs_seed(h, None, 1, 0, 1, C.byref(n_seed), C.byref(n_new), st))
+        else:
+            lcoords, _ = sparse_lattice_coords((X, Y, Z), block, dev)
+            lattice = timed("lattice", lambda: field(lcoords))
+            n_samples += lcoords.shape[0]
+            timed("seed", lambda: _lib.check(lib.s3d_mcs_seed(h, _lib.ptr(lattice), lattice.shape[1], dilate, 0, C.byref(n_seed),
+                                                              C.byref(n_new), st)))
+            del lattice, lcoords
+        pool, stride, rounds, closed = None, 1 + n_attr, 0, True
+        while n_new.value:
+            def decode_new():
+                coords = torch.empty((n_new.value * per, 3), device=dev, dtype=torch.float32)
+                _lib.check(lib.s3d_mcs_pending(h, _lib.ptr(coords), st))
+                return field(coords)
+            part = timed(f"decode r{rounds}", decode_new)
+            n_samples += part.shape[0]
+            if pool is None:
+                pool, stride = part, part.shape[1]
+            else:
+                if part.shape[1] != stride:
+                    raise ValueError(f"sample_fn returned {part.shape[1]} columns after {stride}")
+                pool = torch.cat([pool, part])
+            del part
+            if all_active:
+                break
+            # one host sync per round: the boundary cut edges of the current set; their bricks get slots while rounds are left
+            grow = rounds < max_rounds
+            timed(f"grow r{rounds}", lambda: _lib.check(lib.s3d_mcs_grow(h, _lib.ptr(pool), stride, int(grow), C.byref(n_bound),
+                                                                      C.byref(n_new), st)))
+            closed = n_bound.value == 0
+            rounds += int(grow and not closed)
+        n_active = 0 if pool is None else pool.shape[0] // per
+        nv, nt = C.c_int64(), C.c_int64()
+        timed("count", lambda: _lib.check(lib.s3d_mcs_count(h, _lib.ptr(pool), stride, C.byref(nv), C.byref(nt), st)))
+        verts = torch.empty((nv.value, 3), device=dev, dtype=torch.float32)
+        tris = torch.empty((nt.value, 3), device=dev, dtype=torch.int32)
+        attrs = torch.empty((nv.value, n_attr), device=dev, dtype=torch.float32) if n_attr else None
+        timed("extract", lambda: _lib.check(lib.s3d_mcs_extract(h, _lib.ptr(verts), _lib.ptr(attrs), n_attr, _lib.ptr(tris), st)))
+        occ = None
+        if occupancy:
+            occ = torch.empty((X, Y, Z), device=dev, dtype=torch.uint8)
+            timed("occupancy", lambda: _lib.check(lib.s3d_mcs_occupancy(h, _lib.ptr(pool), stride, _lib.ptr(occ), st)))
+        torch.cuda.current_stream().synchronize()          # the pool is a temporary: the kernels must be done with it
+    if not return_info:
+        return verts, tris, attrs
+    info = {"rounds": rounds, "closed": bool(closed), "n_bricks": nb[0] * nb[1] * nb[2], "n_active": n_active, "n_seed": int(n_seed.value),
+            "n_samples": n_samples, "nb": (nb[0], nb[1], nb[2]), "block": block}
+    if occupancy:
+        info["occupancy"] = occ
+    return verts, tris, attrs, info
+
+
+def sparse_occupancy(sample_fn, dims, iso=0.0, pad_value=1.0, block=8, dilate=0, max_rounds=64):
+    """uint8 [X,Y,Z]: value < iso, from the narrow band of marching_cubes_sparse alone (its info["occupancy"])."""
+    return marching_cubes_sparse(sample_fn, dims, iso, pad_value, 0, block, dilate, max_rounds, return_info=True, occupancy=True)[3]["occupancy"]
+
+
 def mesh_components(tris, n_verts):
     """labels [n_verts] int32: the smallest vertex index of each vertex's connected component (device)."""
     _lib.require_gpu(tris)

@@ -15,6 +15,20 @@ import torch.nn.functional as F
 from .. import _lib
 from .networks import get_networks
 
+
+def _fma_f32(q, b, c):
+    """float32 [n]: q * b + c with a single rounding to nearest even (q float32 [n], b and c float32 values), exact through rationals
+    — a host fused multiply-add for the few thousand axis coordinates of index_sampler."""
+    from fractions import Fraction
+    out = np.empty(len(q), np.float32)
+    fb, fc = Fraction(float(np.float32(b))), Fraction(float(np.float32(c)))
+    for n, x in enumerate(np.asarray(q, np.float32)):
+        exact = Fraction(float(x)) * fb + fc
+        mid = np.float32(float(exact))
+        near = (np.nextafter(mid, np.float32(-np.inf)), mid, np.nextafter(mid, np.float32(np.inf)))
+        out[n] = min(near, key=lambda v: (abs(Fraction(float(v)) - exact), int(np.float32(v).view(np.uint32)) & 1))
+    return out
+
 _SDF_LOSS = {"l1": 0, "weightedl1": 1}
 _TEX_LOSS = {"l1": 0, "l2": 1, "huber": 2}
 
@@ -140,6 +154,46 @@ class ShapeAutoEncoder:
         np.savez_compressed(os.path.join(save_dir, f"r{reso}_voxel.npz"), voxel=vox)
         return vox
 
+    def index_sampler(self, triplane_feat, aabb, reso):
+        """(sample_fn, dims) for isosurface.marching_cubes_sparse: sample_fn maps float32 index coordinates [M,3] of the decode grid
+        (integers: its samples; x.5: the brick-corner lattice) to net.decode(points, ..., clamp_color=True).  The points are
+        k_decode's own grid expression AS COMPILED: q = (0.5 + i) / gdim rounded to float32 (IEEE division), then q * gsize + amin
+        with ONE rounding — hipcc contracts that product and sum into a fused multiply-add, the __fmul_rn / __fadd_rn spelling
+        notwithstanding (tools/compare_kdecode_isa.py holds the kernel's instructions in place).  They are taken per axis on the
+        host, exactly, and gathered on the device, so a band sample carries the bits of decode_grid's; the device test of
+        decode_mesh(sparse=...) against the dense files is what notices if either side changes."""
+        self.net.eval()
+        a = aabb.detach().to("cpu", torch.float32).reshape(6)
+        dims = (C.c_int * 3)()
+        _lib.check(_lib.load().s3d_decoder_grid_dims((C.c_float * 6)(*[float(v) for v in a]), int(reso), dims))
+        dims = (dims[0], dims[1], dims[2])
+        dev = triplane_feat[0].device
+        tabs = []
+        for k in range(3):                          # entry j: the coordinate i = j / 2 - 0.5, j = 0 .. 2 dims (every sample and half step)
+            i = torch.arange(2 * dims[k] + 1, dtype=torch.float32) / 2.0 - 0.5
+            q = ((0.5 + i) / float(dims[k])).numpy()
+            tabs.append(torch.from_numpy(_fma_f32(q, (a[3 + k] - a[k]).item(), a[k].item())).to(dev))
+
+        def sample_fn(idx):
+            j = (idx * 2.0 + 1.0).round().long()
+            pts = torch.stack([tabs[k][j[:, k].clamp(0, 2 * dims[k])] for k in range(3)], 1)
+            return self.net.decode(pts, triplane_feat, aabb=aabb, clamp_color=True)
+        return sample_fn, dims
+
+    def _sparse_isosurface(self, triplane_feat, aabb, reso, block, dilate, n_attr, occupancy):
+        """the iso-surface at level 0 of the padded decode grid from its narrow band -> (verts, tris, attrs, occupancy or None)"""
+        from .isosurface import marching_cubes_sparse
+        if block not in (4, 8, 16):
+            raise ValueError(f"sparse={block!r}: expected None or a brick size of 4, 8 or 16")
+        sample_fn, dims = self.index_sampler(triplane_feat, aabb, reso)
+        verts, tris, attrs, info = marching_cubes_sparse(sample_fn, dims, 0.0, 1.0, n_attr=n_attr, block=block, dilate=dilate,
+                                                         return_info=True, occupancy=occupancy, device=triplane_feat[0].device)
+        if not info["closed"]:
+            import warnings
+            warnings.warn(f"sparse iso-surface: the growth did not close in {info['rounds']} rounds; the mesh may have open borders")
+        self.last_sparse_info = {k: v for k, v in info.items() if k != "occupancy"}
+        return verts, tris, attrs, info.get("occupancy")
+
     def _refine_and_normals(self, triplane_feat, aabb, verts, tris, reso, box_size, refine, refine_max_move, normals):
         """The field's part of the mesh exports: `refine` Newton steps of the vertices onto the decoded zero level
         set, each step and the total move clamped to refine_max_move cells of the decode grid (box_size / reso, world units) per
@@ -167,7 +221,7 @@ class ShapeAutoEncoder:
 
     @torch.no_grad()
     def decode_mesh(self, save_dir, triplane_feat, reso, name="object.obj", only_largest_cc=True, save_voxel=True, refine=0,
-                    refine_max_move=0.5, normals=None, return_normals=False):
+                    refine_max_move=0.5, normals=None, return_normals=False, sparse=None, sparse_dilate=0):
         """The geometry half of decode_texmesh (reference :362-390): decode_grid -> voxel.npz -> iso-surface of the
         padded SDF grid at level 0 -> largest connected component -> `v / reso * box_size + box_min`, all on the device
         (sdfgrid_to_mesh, utils3d.py:196-208, used PyMCubes + point_cloud_utils on the CPU).  The decoded colour is
@@ -176,17 +230,25 @@ class ShapeAutoEncoder:
         refine=K > 0 projects the vertices onto the decoded zero level set after the re-normalisation (K Newton steps, at most
         refine_max_move cells per axis; the colours stay the interpolated ones); normals="field" writes the unit gradient there as
         `vn` lines (_refine_and_normals).  return_normals: a fourth entry, the normals [V,3] (None without them).  With the
-        defaults the file and the returned tuple are what they always were."""
+        defaults the file and the returned tuple are what they always were.
+        sparse=4 | 8 | 16 (+ sparse_dilate): the narrow-band front end (_sparse_isosurface) in place of the dense grid
+        — decode_grid is never called, voxel.npz comes from the band; everything after the iso-surface is the same code."""
         from .isosurface import export_obj, largest_component, marching_cubes
         H, W = triplane_feat[0].shape[-2:]
         D = triplane_feat[1].shape[-1]
         aabb = self._resize_aabb((H, W, D))
-        grid = self.decode_grid(triplane_feat, reso, aabb=aabb)                  # [Nx, Ny, Nz, 1+3], colours clamped
         os.makedirs(save_dir, exist_ok=True)
-        if save_voxel:
-            np.savez_compressed(os.path.join(save_dir, "voxel.npz"), vox_grid=(grid[..., 0] < 0).cpu().numpy())
         # vertex colour: the decoded rgb (sdftex), the albedo = columns 1..3 (sdfpbr), none (sdf)
-        verts, tris, cols = marching_cubes(grid, 0.0, 1.0, n_attr=min(grid.shape[-1] - 1, 3))
+        if sparse is not None:
+            verts, tris, cols, occ = self._sparse_isosurface(triplane_feat, aabb, reso, sparse, sparse_dilate,
+                                                             min(self.net.out_channels - 1, 3), save_voxel)
+            if save_voxel:
+                np.savez_compressed(os.path.join(save_dir, "voxel.npz"), vox_grid=occ.bool().cpu().numpy())
+        else:
+            grid = self.decode_grid(triplane_feat, reso, aabb=aabb)              # [Nx, Ny, Nz, 1+3], colours clamped
+            if save_voxel:
+                np.savez_compressed(os.path.join(save_dir, "voxel.npz"), vox_grid=(grid[..., 0] < 0).cpu().numpy())
+            verts, tris, cols = marching_cubes(grid, 0.0, 1.0, n_attr=min(grid.shape[-1] - 1, 3))
         if only_largest_cc:
             verts, tris, cols = largest_component(verts, tris, cols)
         box_min = aabb[:3]
@@ -199,7 +261,7 @@ class ShapeAutoEncoder:
     @torch.no_grad()
     def decode_texmesh(self, save_dir, triplane_feat, reso, n_faces=10000, texture_reso=2048, only_largest_cc=True, save_voxel=True,
                        mtl_path=None, file_format="obj", decimation="cluster", refine=0, refine_max_move=0.5, normals=None,
-                       normal_map=None, normal_map_project=0, normal_map_max_move=1.0):
+                       normal_map=None, normal_map_project=0, normal_map_max_move=1.0, sparse=None, sparse_dilate=0):
         """Reference :362-473 for data_type sdftex: decode_grid -> voxel.npz -> iso-surface -> largest component -> the re-normalisation
         of decode_mesh -> decimation to n_faces (isosurface.simplify_mesh) -> UV atlas at texture_reso and ONE decode_batch call over
         its covered texels, quantised and dilated on the device (isosurface.bake_texture) -> object.obj + object.mtl + object.png, or
@@ -221,6 +283,8 @@ class ShapeAutoEncoder:
         else the area-weighted vertex normals; they are always written then (a tangent-space map means nothing without them).
         sdftex: object_normal.png + a `map_Bump` line, or normalTexture and TANGENT in the GLB; sdfpbr: the baked map takes the
         place of the normal head's image.  Returned as "normal_map" [T,T,3] and "normal_status" [T,T].
+        sparse=4 | 8 | 16 (+ sparse_dilate): the narrow-band front end of decode_mesh; not for data_type sdf, whose
+        sdfgrid_r{reso}.npz is the dense grid itself.
         With the defaults every file is what it always was.
         Returns a dict of what was written (verts, tris, info, and with a texture uvs, image, mask, gb_pos, corner0), or None for
         an empty iso-surface (no mesh file is written then)."""
@@ -242,13 +306,20 @@ class ShapeAutoEncoder:
         H, W = triplane_feat[0].shape[-2:]
         D = triplane_feat[1].shape[-1]
         aabb = self._resize_aabb((H, W, D))
-        grid = self.decode_grid(triplane_feat, reso, aabb=aabb)
         os.makedirs(save_dir, exist_ok=True)
-        if save_voxel:
-            np.savez_compressed(os.path.join(save_dir, "voxel.npz"), vox_grid=(grid[..., 0] < 0).cpu().numpy())
-        if self.data_type == "sdf":
-            np.savez_compressed(os.path.join(save_dir, f"sdfgrid_r{reso}.npz"), sdf_grid=grid[..., 0].cpu().numpy())
-        verts, tris, _ = iso.marching_cubes(grid, 0.0, 1.0)
+        if sparse is not None:
+            if self.data_type == "sdf":
+                raise NotImplementedError("decode_texmesh(sparse=...): data_type sdf writes the dense sdfgrid_r{reso}.npz; use decode_mesh")
+            verts, tris, _, occ = self._sparse_isosurface(triplane_feat, aabb, reso, sparse, sparse_dilate, 0, save_voxel)
+            if save_voxel:
+                np.savez_compressed(os.path.join(save_dir, "voxel.npz"), vox_grid=occ.bool().cpu().numpy())
+        else:
+            grid = self.decode_grid(triplane_feat, reso, aabb=aabb)
+            if save_voxel:
+                np.savez_compressed(os.path.join(save_dir, "voxel.npz"), vox_grid=(grid[..., 0] < 0).cpu().numpy())
+            if self.data_type == "sdf":
+                np.savez_compressed(os.path.join(save_dir, f"sdfgrid_r{reso}.npz"), sdf_grid=grid[..., 0].cpu().numpy())
+            verts, tris, _ = iso.marching_cubes(grid, 0.0, 1.0)
         if only_largest_cc:
             verts, tris, _ = iso.largest_component(verts, tris)
         if tris.shape[0] == 0:

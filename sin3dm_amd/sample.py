@@ -26,6 +26,9 @@ S3D_MESH_NORMALS=field writes the field's unit normals into the mesh files (DESI
 S3D_MESH_NORMAL_MAP=field beside S3D_MESH=textured bakes the field's normals on the decimated mesh into a tangent-space normal map
 (object_normal.png, textures/normal.png for sdfpbr, normalTexture in a GLB), S3D_MESH_NORMAL_MAP_PROJECT=K takes them
 at the texel positions projected onto the zero level set in K Newton steps; edit.py reads both as well.
+S3D_MESH_SPARSE=B (4, 8 or 16) extracts the iso-surface from the bricks of B^3 grid vertices the surface crosses instead of the dense
+decode grid: the same mesh files wherever the largest component is seen by the brick lattice, a fraction of the decoder
+evaluations, and no 893^3 ceiling (--reso 1024 works); edit.py reads it as well.
 S3D_RENDER=views beside any of these also writes renderings/000.png ... 007.png into every sample folder that gets a mesh: the
 reference's eight views, drawn on the device from the arrays the export holds (sin3dm_amd/rendering).
 S3D_RENDER_SHADING=smooth or pbr beside it draws them with smooth normals and the three-light GGX model of DESIGN.md §24 (pbr: the
@@ -135,6 +138,20 @@ def mesh_normal_map_project(value=None):
     if k < 0:
         raise ValueError(f"mesh normal map project {raw!r}: expected a number of steps >= 0")
     return k
+
+
+def mesh_sparse(value=None):
+    """0 (the default: the dense decode grid) or a brick size of 4, 8 or 16: the narrow-band iso-surface of decode_mesh /
+    decode_texmesh sparse=B, which decodes only the bricks the surface crosses and has no 893^3 ceiling.
+    value=None reads the environment variable S3D_MESH_SPARSE."""
+    raw = value if value is not None else (os.environ.get("S3D_MESH_SPARSE") or "0")
+    try:
+        b = int(raw)
+    except (TypeError, ValueError):
+        b = -1
+    if b not in (0, 4, 8, 16):
+        raise ValueError(f"mesh sparse {raw!r}: expected a brick size of 4, 8 or 16 (or unset)")
+    return b
 
 
 def render_shading(mode=None):
@@ -286,6 +303,8 @@ def decode(args, paths):
         field["refine"] = mesh_refine()
     if mesh_normals():
         field["normals"] = mesh_normals()
+    if mesh_sparse():
+        field["sparse"] = mesh_sparse()
     baked = {}
     if mesh_normal_map():
         if not textured:
