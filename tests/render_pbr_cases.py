@@ -12,7 +12,13 @@ Ill-conditioned samples.  Two places of the formula are not continuous in a usab
 normal (dot(mix, flat) <= 0: a jump) and N.V near its floor 1e-4 (the relative error of a float32 dot product of unit vectors,
 about 1e-7 absolute, is 1e-3 there, under a specular term that divides by it).  A sample within EPS_FLIP of the first boundary or
 within EPS_NV of the second is flagged, and pixels holding one are left out; the share of flagged samples is capped at
-render_cases.MAX_LEFT_OUT per case, and the cases are chosen so that the restatement meets the cap."""
+render_cases.MAX_LEFT_OUT per case, and the cases are chosen so that the restatement meets the cap.
+
+The gain ladder (at the end of this file) reads the light model's float value out of the uint8 images: the same view under light
+intensities scaled by 2^0 ... 2^24, each pixel-channel compared at the largest gain that does not clip, within LADDER_BOUND levels
+of a level in [128, 255).  There a third flag joins the two: a sample with |N.L| < EPS_NL for a light, where the dot product's
+1e-7 absolute error is a large relative error of a value proportional to it, which a high gain magnifies.  FAULTS names wrong
+light models; test_render_pbr_host.py shows that the ladder sees each of them and which of them the images at gain 1 do not."""
 import functools
 import math
 
@@ -25,6 +31,7 @@ MIN_ROUGHNESS, GEO_GREY, NV_FLOOR = 0.089, 134.0 / 255.0, 1e-4
 AMBIENT = 0.1
 EPS_FLIP = 1e-5                                              # ten times the error of a float32 dot product of unit vectors
 EPS_NV = 1e-3                                                # ten times NV_FLOOR: beyond it a 1e-7 error is under 1e-4 relative
+EPS_NL = 3e-4                                                # the gain ladder only: 1e-7 / EPS_NL is under a tenth of half a level at 64 (>= 1.3e-4)
 # measured by measure() (profiles/render_pbr.txt); the device bounds derive from them
 NORMAL_GAP = 9.9e-08                                         # measured 9.885e-08
 TANGENT_GAP = 1.03e-07                                       # measured 1.024e-07
@@ -141,8 +148,17 @@ def gather_samples(case, xy, iw, face_id):
             "vid": np.array([r[4] for r in rec], dtype=np.int64).reshape(-1, 3), "swapped": np.array([r[5] for r in rec], dtype=bool)}
 
 
-def shade_pbr(case, matrix, smp, Ws, Hs, ss, dt=np.float64):
-    """({pass: rgba uint8 [H, W, 4]}, flagged bool [Hs, Ws]) of one view of a case on gathered samples, in the number type dt."""
+FAULTS = ("fresnel_pow4", "fresnel_pow6", "vh_unclamped", "geo_grey_133", "nv_floor_1e-2", "min_roughness_008", "drop_fourth_light",
+          "f0_045", "f0_041", "spec_x095", "spec_x099", "spec_guard_1e-5", "k_direct")
+INERT_FAULTS = ("vh_unclamped",)                             # H lies between V and L, so 0 <= V.H <= 1 already: the clamp never acts
+
+
+def shade_pbr(case, matrix, smp, Ws, Hs, ss, dt=np.float64, fault=None, raw=False):
+    """({pass: rgba uint8 [H, W, 4]}, flagged bool [Hs, Ws]) of one view of a case on gathered samples, in the number type dt.
+    fault: one of FAULTS, a deliberately wrong light model (the unfaulted path does not read it).  raw=True: instead, a dict of
+    the per-sample values before the clamp, "shaded" and "geo" [S, 3] in dt, with "flagged" [S] (the two rules above) and
+    "grazing" [S] (|N.L| < EPS_NL for a light, under either normal): what the gain ladder scales."""
+    assert fault is None or fault in FAULTS, fault
     S = len(smp["s"])
     verts, faces = _f32(case["verts"], dt).reshape(-1, 3), np.asarray(case["faces"]).reshape(-1, 3)
     shading = case["shading"]
@@ -229,62 +245,90 @@ def shade_pbr(case, matrix, smp, Ws, Hs, ss, dt=np.float64):
     P = b0 * verts[vid[:, 0]] + b1 * verts[vid[:, 1]] + b2 * verts[vid[:, 2]]
     pi = dt(3.14159265358979323846)
 
+    if fault == "drop_fourth_light":
+        lights = lights[:3]
+    nv_floor = dt(1e-2) if fault == "nv_floor_1e-2" else dt(NV_FLOOR)
+    min_rough = dt(0.08) if fault == "min_roughness_008" else dt(MIN_ROUGHNESS)
+    f0_base = dt({"f0_045": 0.045, "f0_041": 0.041}.get(fault, 0.04))
+    spec_guard = dt(1e-5) if fault == "spec_guard_1e-5" else dt(1e-6)
+    grazing = np.zeros(S, dtype=bool)
+
     def lit(Nn, alb, met, rgh):
-        nonlocal flagged
+        nonlocal flagged, grazing
         Vv, ok = _normalize(eye - P)
         Vv = np.where(ok[:, None], Vv, Nn)
         nv_raw = _dot(Nn, Vv)
         flagged = flagged | (np.abs(nv_raw.astype(np.float64) - NV_FLOOR) < EPS_NV)
-        NV = np.maximum(nv_raw, dt(NV_FLOOR))
-        r = np.minimum(np.maximum(rgh, dt(MIN_ROUGHNESS)), dt(1.0))
+        NV = np.maximum(nv_raw, nv_floor)
+        r = np.minimum(np.maximum(rgh, min_rough), dt(1.0))
         alpha = r * r
         a2, kk = alpha * alpha, dt(0.5) * alpha
+        if fault == "k_direct":
+            kk = (r + dt(1.0)) * (r + dt(1.0)) / dt(8.0)
         gv = NV / (NV * (dt(1.0) - kk) + kk)
-        F0 = dt(0.04) * (dt(1.0) - met)[:, None] + alb * met[:, None]
+        F0 = f0_base * (dt(1.0) - met)[:, None] + alb * met[:, None]
         out = ambient * alb
         for L in lights:
-            NL = np.maximum(_dot(Nn, L[:3]), dt(0.0))
+            nl_raw = _dot(Nn, L[:3])
+            grazing = grazing | (np.abs(nl_raw.astype(np.float64)) < EPS_NL)
+            NL = np.maximum(nl_raw, dt(0.0))
             Hh, ok = _normalize(L[:3] + Vv)
             Hh = np.where(ok[:, None], Hh, Nn)
             NH, VH = _dot(Nn, Hh), np.minimum(np.maximum(_dot(Vv, Hh), dt(0.0)), dt(1.0))
+            if fault == "vh_unclamped":
+                VH = _dot(Vv, Hh)
             x = dt(1.0) - VH
             x2 = x * x
             x5 = x2 * x2 * x
+            if fault in ("fresnel_pow4", "fresnel_pow6"):
+                x5 = x2 * x2 if fault == "fresnel_pow4" else x2 * x2 * x2
             dd = NH * NH * (a2 - dt(1.0)) + dt(1.0)
             D = a2 / (pi * dd * dd)
             G = NL / (NL * (dt(1.0) - kk) + kk) * gv
-            spec = pi * D * G / (dt(4.0) * NL * NV + dt(1e-6))
+            spec = pi * D * G / (dt(4.0) * NL * NV + spec_guard)
+            if fault in ("spec_x095", "spec_x099"):
+                spec = spec * dt(0.95 if fault == "spec_x095" else 0.99)
             w = L[3] * NL
             Fk = F0 + (dt(1.0) - F0) * x5[:, None]
             out = out + w[:, None] * ((dt(1.0) - Fk) * (dt(1.0) - met)[:, None] * alb + spec[:, None] * Fk)
         return out
 
     grey = lambda x: np.repeat(x[:, None], 3, 1)              # noqa: E731
+    geo_grey = 133.0 / 255.0 if fault == "geo_grey_133" else GEO_GREY
     values = {"shaded": lit(N_map, albedo, metal, rough), "albedo": albedo, "metallic": grey(metal), "roughness": grey(rough),
               "normal": dt(0.5) * N_map + dt(0.5),
-              "geo": lit(N, np.full((S, 3), GEO_GREY, dtype=np.float32).astype(dt), np.zeros(S, dtype=dt), np.full(S, 0.5, dtype=dt))}
+              "geo": lit(N, np.full((S, 3), geo_grey, dtype=np.float32).astype(dt), np.zeros(S, dtype=dt), np.full(S, 0.5, dtype=dt))}
+    if raw:
+        assert values["shaded"].dtype == dt and values["geo"].dtype == dt
+        return {"shaded": values["shaded"], "geo": values["geo"], "flagged": flagged, "grazing": grazing}
+    images = {}
+    for name, val in values.items():
+        assert val.dtype == dt, (name, val.dtype)
+        images[name] = resolve(val, smp, Ws, Hs, ss, dt)
+    flag = np.zeros(Hs * Ws, dtype=bool)
+    flag[smp["s"][flagged]] = True
+    return images, flag.reshape(Hs, Ws)
+
+
+def resolve(val, smp, Ws, Hs, ss, dt):
+    """rgba uint8 [H, W, 4] of per-sample values [S, 3]: clamped to [0, 1], the mean over a pixel's covered samples in row order,
+    uint8(255 x + 0.5); alpha the covered share.  The last step of shade_pbr, in the number type dt."""
     H, W = Hs // ss, Ws // ss
     cov = np.zeros(Hs * Ws, dtype=bool)
     cov[smp["s"]] = True
     n_cov = cov.reshape(H, ss, W, ss).sum((1, 3))
-    images = {}
-    for name, val in values.items():
-        assert val.dtype == dt, (name, val.dtype)
-        full = np.zeros((Hs * Ws, 3), dtype=dt)
-        full[smp["s"]] = np.minimum(np.maximum(val, dt(0.0)), dt(1.0))
-        full = full.reshape(H, ss, W, ss, 3)
-        acc = np.zeros((H, W, 3), dtype=dt)
-        for j in range(ss):                                      # row order; an uncovered sample adds an exact zero
-            for i in range(ss):
-                acc = acc + full[:, j, :, i]
-        mean = np.where(n_cov[..., None] > 0, acc / np.maximum(n_cov, 1)[..., None].astype(dt), dt(0.0))
-        rgba = np.zeros((H, W, 4), dtype=np.uint8)
-        rgba[..., :3] = np.floor(mean * dt(255.0) + dt(0.5)).astype(np.uint8)
-        rgba[..., 3] = np.floor(n_cov.astype(dt) / dt(ss * ss) * dt(255.0) + dt(0.5)).astype(np.uint8)
-        images[name] = rgba
-    flag = np.zeros(Hs * Ws, dtype=bool)
-    flag[smp["s"][flagged]] = True
-    return images, flag.reshape(Hs, Ws)
+    full = np.zeros((Hs * Ws, 3), dtype=dt)
+    full[smp["s"]] = np.minimum(np.maximum(val, dt(0.0)), dt(1.0))
+    full = full.reshape(H, ss, W, ss, 3)
+    acc = np.zeros((H, W, 3), dtype=dt)
+    for j in range(ss):                                          # row order; an uncovered sample adds an exact zero
+        for i in range(ss):
+            acc = acc + full[:, j, :, i]
+    mean = np.where(n_cov[..., None] > 0, acc / np.maximum(n_cov, 1)[..., None].astype(dt), dt(0.0))
+    rgba = np.zeros((H, W, 4), dtype=np.uint8)
+    rgba[..., :3] = np.floor(mean * dt(255.0) + dt(0.5)).astype(np.uint8)
+    rgba[..., 3] = np.floor(n_cov.astype(dt) / dt(ss * ss) * dt(255.0) + dt(0.5)).astype(np.uint8)
+    return rgba
 
 
 # ------------------------------------------------------------------ procedural cases
@@ -318,13 +362,13 @@ def _mapped_material():
     return {"Kd": (0.5, 0.5, 0.5), "image": albedo, "metallic_image": metallic, "roughness_image": roughness, "normal_image": normal}
 
 
-def _sphere(g, levels, shading, lights, inside_out=False, views=8, mapped=False):
+def _sphere(g, levels, shading, lights, inside_out=False, views=8, mapped=False, angles=None):
     Ws, Hs, ss = g
     v, f = R.icosphere(levels)
     verts = (v * np.array([0.5, 0.4, 0.3]) + np.array([0.2, -0.1, 0.4])).astype(np.float32)
     if inside_out:
         f = np.ascontiguousarray(f[:, ::-1])
-    angles = [(45.0 * k, 45.0) for k in range(8)][:views]
+    angles = [(45.0 * k, 45.0) for k in range(8)][:views] if angles is None else angles
     case = dict(verts=verts, faces=f, near=R.RIG_NEAR, shading=shading, lights=lights,
                 matrices=[R.rig_matrix(verts.astype(np.float64), az, el, Ws // ss, Hs // ss) for az, el in angles])
     if mapped:
@@ -382,10 +426,19 @@ def restated(name, grid, view=0, dt=np.float64):
     """The restatement of one view on its own float64 projection: ({pass: rgba}, flagged [Hs, Ws], raster dict).  Shared, unchanged."""
     c = case(name, grid)
     Ws, Hs, ss = GRIDS[grid]
+    smp, r = gathered(name, grid, view)
+    images, flagged = shade_pbr(c, c["matrices"][view], smp, Ws, Hs, ss, dt)
+    return images, flagged, r
+
+
+@functools.lru_cache(maxsize=None)
+def gathered(name, grid, view=0):
+    """(samples, raster dict) of one view on its own float64 projection.  Shared, unchanged."""
+    c = case(name, grid)
+    Ws, Hs, _ = GRIDS[grid]
     xy, iw = R.project(c["verts"], c["matrices"][view], Ws, Hs, c["near"])
     r = R.raster(xy, iw, c["faces"], Ws, Hs)
-    images, flagged = shade_pbr(c, c["matrices"][view], gather_samples(c, xy, iw, r["face_id"]), Ws, Hs, ss, dt)
-    return images, flagged, r
+    return gather_samples(c, xy, iw, r["face_id"]), r
 
 
 def all_views():
@@ -410,3 +463,142 @@ def measure():
         for p in PASSES:
             ig[p] = max(ig[p], int(np.abs(a[p].astype(np.int64) - b[p])[keep].max(initial=0)))
     return ng, tg, ig, share
+
+
+# ------------------------------------------------------------------ the gain ladder: the light model's float value read out of uint8
+# With ambient = 0 the model is linear in the light intensities, and scaling them by 2^k is exact in float32: before the clamp the
+# value at gain 2^k is 2^k times the value at gain 1.  A pixel-channel is read at the largest gain at which the float64 restatement
+# does not clip, where its level is in [128, 255) whatever its magnitude (down to 2^-24 of full scale): its leading 7 to 8 bits, so
+# the comparison is relative, 0.2 to 0.8 %, where the images at gain 1 are absolute, 0.4 % of full scale.
+LADDER_GAINS = tuple(2.0 ** k for k in range(25))
+LADDER_PASSES = ("shaded", "geo")
+LADDER_FLOOR = 64                                            # a readout below this level is not compared (the value is under 2^-23, or clipped early)
+LADDER_VIEWS = ((0.0, 45.0), (135.0, 45.0), (225.0, 45.0))
+LADDER_MATERIALS = {"m0_black_dielectric": {"Kd": (0.0, 0.0, 0.0), "Pm": 0.0, "Pr": 0.5},
+                    "m1_near_mirror": {"Kd": (0.0, 0.0, 0.0), "Pm": 0.0, "Pr": 0.05},
+                    "m2_polished_metal": {"Kd": (0.9, 0.6, 0.2), "Pm": 1.0, "Pr": 0.0},
+                    "m3_metal": {"Kd": (0.9, 0.6, 0.2), "Pm": 1.0, "Pr": 0.3},
+                    "m4_half_metal": {"Kd": (0.3, 0.5, 0.7), "Pm": 0.5, "Pr": 0.25},
+                    "m5_rough_white": {"Kd": (1.0, 1.0, 1.0), "Pm": 0.0, "Pr": 1.0}}
+# measured by measure_ladder() (profiles/render_pbr.txt): float32 against float64 at the readout, in levels
+LADDER_GAP = {"shaded": 1, "geo": 0}
+LADDER_BOUND = {p: max(1, 2 * int(math.ceil(g))) for p, g in LADDER_GAP.items()}
+
+
+def _ladder(grid, material=None, angles=LADDER_VIEWS, lights=None):
+    """The ellipsoid of _sphere at 320 faces, smooth normals, four rig lights, no ambient; material None: the four maps."""
+    c = _sphere(GRIDS[grid], 2, "pbr", rig_lights(4) if lights is None else lights, angles=list(angles), mapped=material is None)
+    if material is not None:
+        del c["vertex_colors"]
+        c["materials"] = [dict(material)]
+    c.update(ambient=0.0, grid=grid)
+    return c
+
+
+LADDER_CASES = {name: (lambda m=m: _ladder("g50", m)) for name, m in LADDER_MATERIALS.items()}
+# the tilted normals of the map turn up to a quarter of what some views see away from every light (exact zeros, which no gain
+# reads): the mapped case takes three views on which the restatement meets the caps of test_render_pbr_host.py with room to spare
+LADDER_CASES.update({"n_mapped": lambda: _ladder("g50", angles=((135.0, 30.0), (180.0, 45.0), (180.0, 30.0))),
+                     "s_supersampled": lambda: _ladder("g64", LADDER_MATERIALS["m4_half_metal"]),
+                     # one light, seen from near its own direction so that it reaches most of what the camera sees
+                     "o_one_light": lambda: _ladder("g50", LADDER_MATERIALS["m4_half_metal"], angles=((90.0, 20.0),), lights=rig_lights(4)[1:2])})
+
+
+@functools.lru_cache(maxsize=None)
+def ladder_case(name):
+    return LADDER_CASES[name]()
+
+
+def ladder_views():
+    return [(n, k) for n in LADDER_CASES for k in range(len(ladder_case(n)["matrices"]))]
+
+
+_LADDER_SAMPLES = {}
+
+
+def ladder_samples(c, view, xy=None, iw=None):
+    """(samples, raster dict) of one view of a ladder case on the given projection (None: its own float64 one); kept by content,
+    since the ladder cases share one mesh and their views."""
+    Ws, Hs, _ = GRIDS[c["grid"]]
+    if xy is None:
+        xy, iw = R.project(c["verts"], c["matrices"][view], Ws, Hs, c["near"])
+    key = (Ws, Hs, np.asarray(xy).tobytes(), np.asarray(iw).tobytes(), np.asarray(c["faces"]).tobytes())
+    if key not in _LADDER_SAMPLES:
+        r = R.raster(xy, iw, c["faces"], Ws, Hs)
+        _LADDER_SAMPLES[key] = (gather_samples(c, xy, iw, r["face_id"]), r)
+    return _LADDER_SAMPLES[key]
+
+
+def ladder_levels(val, smp, Ws, Hs, ss, dt):
+    """(levels uint8 [G, H, W, 3], unclipped bool [G, H, W, 3]) of per-sample values [S, 3] at gain 1: the value times each gain
+    (exact) through resolve(); unclipped: no sample of the pixel exceeds 1 in that channel at that gain."""
+    assert val.dtype == dt
+    H, W = Hs // ss, Ws // ss
+    full = np.zeros((Hs * Ws, 3), dtype=dt)
+    full[smp["s"]] = val
+    top = full.reshape(H, ss, W, ss, 3).max((1, 3))
+    levels = np.stack([resolve(val * dt(g), smp, Ws, Hs, ss, dt)[..., :3] for g in LADDER_GAINS])
+    unclipped = np.stack([top * dt(g) <= dt(1.0) for g in LADDER_GAINS])
+    return levels, unclipped
+
+
+def ladder_readout(levels_by_gain, reference_by_gain, unclipped=None):
+    """(got, want, read, gain index), each [...]: every pixel-channel at the largest gain at which the reference [G, ...] is below
+    255 (and, with unclipped [G, ...], none of the pixel's samples clips); read where there is such a gain and the reference's
+    level at it is at least LADDER_FLOOR.  levels_by_gain [G, ...] is read at the reference's choice of gain."""
+    ref, lev = np.asarray(reference_by_gain).astype(np.int64), np.asarray(levels_by_gain).astype(np.int64)
+    assert ref.shape == lev.shape and ref.shape[0] == len(LADDER_GAINS)
+    ok = ref < 255
+    if unclipped is not None:
+        ok = ok & np.asarray(unclipped)
+    k = len(ref) - 1 - np.argmax(ok[::-1], 0)                    # the largest gain index with ok (meaningless where none is)
+    want, got = np.take_along_axis(ref, k[None], 0)[0], np.take_along_axis(lev, k[None], 0)[0]
+    return got, want, ok.any(0) & (want >= LADDER_FLOOR), k
+
+
+def ladder_reference(name, view, dt=np.float64, fault=None, xy=None, iw=None):
+    """One view of a ladder case in the number type dt: dict of levels / unclipped {pass: [G, H, W, 3]}, left_out bool [H, W] (a
+    sample of the pixel is flagged by EPS_FLIP, EPS_NV or EPS_NL), covered bool [H, W], n_flagged / n_covered (samples), raster."""
+    c = ladder_case(name)
+    Ws, Hs, ss = GRIDS[c["grid"]]
+    smp, r = ladder_samples(c, view, xy, iw)
+    raw = shade_pbr(c, c["matrices"][view], smp, Ws, Hs, ss, dt, fault=fault, raw=True)
+    out = {"levels": {}, "unclipped": {}, "raster": r}
+    for p in LADDER_PASSES:
+        out["levels"][p], out["unclipped"][p] = ladder_levels(raw[p], smp, Ws, Hs, ss, dt)
+    per_pixel = lambda a: a.reshape(Hs // ss, ss, Ws // ss, ss).any((1, 3))          # noqa: E731
+    flag = np.zeros(Hs * Ws, dtype=bool)
+    flag[smp["s"][raw["flagged"] | raw["grazing"]]] = True
+    out.update(left_out=per_pixel(flag), covered=per_pixel(r["face_id"] >= 0), n_flagged=int(flag.sum()), n_covered=int((r["face_id"] >= 0).sum()))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def ladder_restated(name, view, dt=np.float64, fault=None):
+    """ladder_reference on the view's own float64 projection.  Shared, unchanged."""
+    return ladder_reference(name, view, dt, fault)
+
+
+def ladder_compare(got_levels, ref, agree=None):
+    """{pass: (largest |got - reference| in levels over the read pixel-channels that are not left out, read share of the covered
+    pixel-channels, gain indices read)} of levels {pass: [G, H, W, 3]} against a ladder_reference(); agree bool [H, W]: the
+    pixels to compare at all (those whose samples agree in face_id)."""
+    res = {}
+    for p in LADDER_PASSES:
+        got, want, read, k = ladder_readout(got_levels[p], ref["levels"][p], ref["unclipped"][p])
+        keep = read & ~ref["left_out"][..., None] & (True if agree is None else agree[..., None])
+        res[p] = (int(np.abs(got - want)[keep].max(initial=0)), float(read[ref["covered"]].mean()), np.unique(k[keep]))
+    return res
+
+
+def measure_ladder(fault=None, dt=np.float32):
+    """({pass: largest difference in levels}, {(case, view): {pass: difference}}): the float64 restatement against the evaluation
+    in dt with a fault, at the readout, over every ladder case.  fault None and float32: LADDER_GAP."""
+    worst, each = {p: 0 for p in LADDER_PASSES}, {}
+    for n, k in ladder_views():
+        ref, other = ladder_restated(n, k), ladder_restated(n, k, dt, fault)
+        res = ladder_compare(other["levels"], ref)
+        each[(n, k)] = {p: res[p][0] for p in LADDER_PASSES}
+        for p in LADDER_PASSES:
+            worst[p] = max(worst[p], res[p][0])
+    return worst, each

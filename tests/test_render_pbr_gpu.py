@@ -1,7 +1,9 @@
 """GPU: the PBR renders (s3d_render_pbr.hip, sin3dm_amd/rendering) against the restatement of tests/render_pbr_cases.py.
 Vertex normals and face tangents against float64 within ten times the measured float32 gap.  Images of every case, view and pass
 within max(1, 2 * the measured float32 gap) levels on the pixels whose samples all agree in face_id and hold no sample the
-restatement flags as ill-conditioned (at most render_cases.MAX_LEFT_OUT of a case's covered samples).  Same input, same bits; the
+restatement flags as ill-conditioned (at most render_cases.MAX_LEFT_OUT of a case's covered samples).  The light model's float
+value through the gain ladder of render_pbr_cases.py: the same views under light intensities times 2^0 ... 2^24, every
+pixel-channel read at the largest gain that does not clip, within LADDER_BOUND levels of a level in [128, 255).  Same input, same bits; the
 default call is the flat shader's call, byte for byte; the command line and the sampler hook end to end."""
 import functools
 import os
@@ -92,6 +94,73 @@ def test_images_of_every_view_and_pass(name, grid, record_property):
     for p in P.PASSES:
         record_property("levels_" + p, worst[p])
     assert all(worst[p] <= P.IMAGE_BOUND[p] for p in P.PASSES), worst
+
+
+# ------------------------------------------------------------------ the light model through the gain ladder
+def _ladder_render(name):
+    """One render_views call per gain, each with every view of the case and the passes shaded and geo:
+    ({pass: uint8 [G, n_views, H, W, 4]}, per view the buffers of the first call; the projection does not depend on the lights)."""
+    c = P.ladder_case(name)
+    Ws, Hs, ss = P.GRIDS[c["grid"]]
+    views, lights = _views(c), np.asarray(c["lights"], dtype=np.float64)
+    out, bufs = {p: [] for p in P.LADDER_PASSES}, None
+    for g in P.LADDER_GAINS:
+        scaled = dict(c, lights=lights * np.array([1.0, 1.0, 1.0, g]))           # a power of two: exact, in float64 and in float32
+        res = _render(scaled, views, Ws // ss, Hs // ss, ss, passes=P.LADDER_PASSES, return_buffers=bufs is None)
+        if bufs is None:
+            res, first = res
+            bufs = [{k: v.cpu().numpy() for k, v in b.items() if torch.is_tensor(v)} for b in first]
+        for p in P.LADDER_PASSES:
+            out[p].append(res[p].cpu().numpy())
+    return {p: np.stack(v) for p, v in out.items()}, bufs
+
+
+ladder_run = functools.lru_cache(maxsize=None)(_ladder_render)
+
+
+@pytest.mark.parametrize("name", list(P.LADDER_CASES))
+def test_light_model_through_the_gain_ladder(name, record_property):
+    """Every pixel-channel of shaded and geo at the largest gain at which the float64 restatement does not clip (a level in
+    [128, 255), so the difference is relative) within LADDER_BOUND levels, on the device's own projection."""
+    c = P.ladder_case(name)
+    Ws, Hs, ss = P.GRIDS[c["grid"]]
+    levels, bufs = ladder_run(name)
+    worst, share, own_share = {p: 0 for p in P.LADDER_PASSES}, {p: 1.0 for p in P.LADDER_PASSES}, {p: 1.0 for p in P.LADDER_PASSES}
+    for k, b in enumerate(bufs):
+        ref = P.ladder_reference(name, k, xy=b["xy_fixed"].astype(np.int64), iw=b["inv_w"].astype(np.float64))
+        assert ref["n_flagged"] <= R.MAX_LEFT_OUT * ref["n_covered"], (name, k, ref["n_flagged"])
+        agree = (b["face_id"] == ref["raster"]["face_id"]).reshape(Hs // ss, ss, Ws // ss, ss).all((1, 3))
+        assert (agree & ~ref["left_out"]).mean() >= 1 - 4 * R.MAX_LEFT_OUT
+        got = {p: levels[p][:, k, :, :, :3] for p in P.LADDER_PASSES}
+        assert all(got[p].shape == ref["levels"][p].shape and got[p].dtype == np.uint8 for p in got)
+        res = P.ladder_compare(got, ref, agree)
+        for p in P.LADDER_PASSES:
+            assert np.array_equal(levels[p][0, k, :, :, 3] > 0, ref["covered"])
+            own = float(P.ladder_readout(got[p], got[p])[2][ref["covered"]].mean())          # what the device's own images let one read
+            worst[p], share[p], own_share[p] = max(worst[p], res[p][0]), min(share[p], res[p][1]), min(own_share[p], own)
+            print(name, "view", k, p, "largest difference", res[p][0], "levels; bound", P.LADDER_BOUND[p], "; read share", round(res[p][1], 4),
+                  "the device's own", round(own, 4), "; gains 2^%d to 2^%d" % (res[p][2].min(), res[p][2].max()))
+    for p in P.LADDER_PASSES:
+        record_property("ladder_levels_" + p, worst[p])
+        record_property("ladder_read_share_" + p, share[p])
+    assert all(share[p] >= 0.95 and own_share[p] >= 0.95 for p in P.LADDER_PASSES), (share, own_share)
+    assert all(worst[p] <= P.LADDER_BOUND[p] for p in P.LADDER_PASSES), worst
+
+
+def test_ladder_gain_changes_nothing_but_the_intensity():
+    """level = floor(255 g x + 0.5): doubling g doubles the level to within 1 wherever the higher gain does not clip; and the
+    same ladder twice gives the same bits."""
+    levels, _ = ladder_run("m1_near_mirror")
+    pairs = 0
+    for p in P.LADDER_PASSES:
+        lev = levels[p][..., :3].astype(np.int64)
+        both = lev[1:] < 255
+        pairs += int((both & (lev[:-1] > 0)).sum())
+        assert np.abs(lev[1:] - 2 * lev[:-1])[both].max() <= 1, p
+        assert np.array_equal(levels[p][1:, ..., 3], levels[p][:-1, ..., 3])
+    assert pairs > 20000
+    again, _ = _ladder_render("m1_near_mirror")
+    assert all(np.array_equal(again[p], levels[p]) for p in P.LADDER_PASSES)
 
 
 def test_same_input_same_bits_and_views_and_passes_separately():

@@ -1,6 +1,6 @@
 """CPU-only: the host half of the PBR renders (sin3dm_amd/rendering/{pbr,render_pbr}.py, s3d_render_pbr.hip).  The
 restatement of tests/render_pbr_cases.py against closed forms, its measured float32 gaps and its leave-out cap on every case; the
-MTL parser, the command line's argument errors, the light rig, the header, the binding and the argument checks of the entry
+gain ladder's gap and conditions, and the wrong light models it sees where the images at gain 1 do not; the MTL parser, the command line's argument errors, the light rig, the header, the binding and the argument checks of the entry
 points (which launch nothing, so they run without a GPU)."""
 import ctypes as C
 import math
@@ -152,6 +152,134 @@ def test_cases_cover_what_they_are_for():
     assert im["roughness"][..., 0][im["roughness"][..., 3] == 255].min() < 255 * P.MIN_ROUGHNESS
     t = P.map_images()[3].astype(np.float64) / 255 * 2 - 1
     assert (t[..., 2] / np.linalg.norm(t, axis=2)).min() < 0.6                     # tilted by more than 50 degrees somewhere
+
+
+# ------------------------------------------------------------------ the gain ladder: its gap, its conditions, the faults it sees
+def test_ladder_gap_is_the_recorded_one():
+    gap, each = P.measure_ladder()
+    print("float32 against float64 at the readout, levels:", gap, {k: v for k, v in each.items() if any(v.values())})
+    assert gap == P.LADDER_GAP
+    assert P.LADDER_BOUND == {p: max(1, 2 * g) for p, g in P.LADDER_GAP.items()} == {"shaded": 2, "geo": 1}
+    text = open(os.path.join(REPO, "profiles", "render_pbr.txt")).read()
+    assert f"ladder gap in uint8 levels {P.LADDER_GAP}" in text
+    # the flag keeps a float32 dot product's 1e-7 under a tenth of half a level at the floor of the readout
+    assert 1e-7 / P.EPS_NL <= 0.1 * 0.5 / P.LADDER_FLOOR and P.LADDER_GAINS == tuple(2.0 ** k for k in range(25))
+
+
+@pytest.mark.parametrize("name,view", P.ladder_views())
+def test_ladder_conditions_hold_for_the_restatement(name, view):
+    """Conditions on the cases, not measurements: what the three flags leave out, what depth leaves unclear and what the ladder
+    cannot read (exact zeros, and channels that clip at gain 1) stay under their caps for the float64 restatement alone."""
+    c, ref = P.ladder_case(name), P.ladder_restated(name, view)
+    res = P.ladder_compare(ref["levels"], ref)
+    print(name, view, "covered", ref["n_covered"], "flagged", ref["n_flagged"], "unclear", int(ref["raster"]["unclear"].sum()),
+          "read share", {p: round(res[p][1], 4) for p in res})
+    assert ref["n_covered"] > 700 and c["ambient"] == 0.0 and c["shading"] == "pbr" and len(R.icosphere(2)[1]) == len(c["faces"]) == 320
+    assert ref["n_flagged"] <= R.MAX_LEFT_OUT * ref["n_covered"]
+    assert ref["raster"]["unclear"].sum() <= R.MAX_LEFT_OUT * ref["n_covered"]
+    for p in P.LADDER_PASSES:
+        assert res[p][0] == 0 and res[p][1] >= 0.95, (p, res[p][:2])
+
+
+def test_ladder_cases_cover_what_they_are_for():
+    names = list(P.LADDER_CASES)
+    assert names[:6] == list(P.LADDER_MATERIALS) and len(P.ladder_views()) == 6 * 3 + 3 + 3 + 1
+    assert [len(P.ladder_case(n)["lights"]) for n in names] == [4] * 8 + [1]
+    assert [P.ladder_case(n)["grid"] for n in names] == ["g50"] * 7 + ["g64", "g50"] and P.GRIDS["g64"][2] == 2
+    mapped = P.ladder_case("n_mapped")
+    assert mapped["uvs"].shape == (320, 3, 2) and mapped["materials"][0]["normal_image"] is not None
+    assert all(P.ladder_case(n).get("uvs") is None for n in names if n != "n_mapped")
+    # the ladder reaches small values: the readouts use at least 12 distinct gains, the longest of them past 2^20
+    gains = set()
+    for n, k in P.ladder_views():
+        ref = P.ladder_restated(n, k)
+        for p, (_, _, used) in P.ladder_compare(ref["levels"], ref).items():
+            gains |= set(int(g) for g in used)
+    print("gain indices read", sorted(gains))
+    assert len(gains) >= 12 and max(gains) > 20
+    # a pixel of the supersampled case is read only where none of its samples clips: some gains below 255 are refused for that
+    ref = P.ladder_restated("s_supersampled", 0)
+    assert ((ref["levels"]["shaded"] < 255) & ~ref["unclipped"]["shaded"]).any()
+    # the readout rule on a hand-made ladder: 100 -> 200 -> clipped; 40 at the last unclipped gain is under the floor; never unclipped
+    lev = np.zeros((25, 3), dtype=np.uint8)
+    lev[:, 0], lev[:, 1], lev[:, 2] = [100, 200] + [255] * 23, [0] * 24 + [40], 255
+    got, want, read, k = P.ladder_readout(lev + (lev < 255), lev)
+    assert want.tolist()[:2] == [200, 40] and got.tolist()[:2] == [201, 41] and read.tolist() == [True, False, False] and k.tolist()[:2] == [1, 24]
+
+
+# per fault: the largest difference in levels (shaded, geo) under the comparison of the images at gain 1 (every case, grid and view of
+# P.CASES, flagged pixels left out, as test_render_pbr_gpu.py compares them) and under the ladder, on the float64 restatement
+FAULT_LEVELS = {"fresnel_pow4": ((1, 1), (70, 30)), "fresnel_pow6": ((1, 1), (43, 18)), "vh_unclamped": ((0, 0), (0, 0)),
+                "geo_grey_133": ((0, 1), (0, 2)), "nv_floor_1e-2": ((2, 1), (147, 1)), "min_roughness_008": ((9, 0), (88, 0)),
+                "drop_fourth_light": ((3, 3), (254, 252)), "f0_045": ((4, 4), (29, 8)), "f0_041": ((1, 1), (7, 2)),
+                "spec_x095": ((11, 2), (13, 6)), "spec_x099": ((2, 1), (3, 2)), "spec_guard_1e-5": ((2, 1), (129, 1)),
+                "k_direct": ((21, 2), (243, 22))}
+UNSEEN_AT_GAIN_ONE = ("fresnel_pow4", "fresnel_pow6", "geo_grey_133", "f0_041")     # the gap the ladder closes; update deliberately if the cases change
+
+
+@pytest.mark.parametrize("fault", P.FAULTS)
+def test_ladder_sees_the_fault(fault):
+    assert set(FAULT_LEVELS) == set(P.FAULTS)
+    old = {p: 0 for p in P.LADDER_PASSES}
+    for n, g, k in P.all_views():
+        c = P.case(n, g)
+        Ws, Hs, ss = P.GRIDS[g]
+        want, flagged, _ = P.restated(n, g, k)
+        got, _ = P.shade_pbr(c, c["matrices"][k], P.gathered(n, g, k)[0], Ws, Hs, ss, fault=fault)
+        keep = ~flagged.reshape(Hs // ss, ss, Ws // ss, ss).any((1, 3))
+        for p in old:
+            old[p] = max(old[p], int(np.abs(got[p].astype(np.int64) - want[p])[keep].max(initial=0)))
+        assert all(np.array_equal(got[p], want[p]) for p in P.PASSES if p not in old)          # a fault of the light model only
+    new, each = P.measure_ladder(fault, np.float64)
+    seen = [k for k, v in each.items() if any(v[p] > P.LADDER_BOUND[p] for p in v)]
+    print(fault, "images at gain 1:", old, "bound", {p: P.IMAGE_BOUND[p] for p in old}, "ladder:", new, "bound", P.LADDER_BOUND, "seen on", len(seen), "views")
+    assert ((old["shaded"], old["geo"]), (new["shaded"], new["geo"])) == FAULT_LEVELS[fault]
+    if fault in P.INERT_FAULTS:
+        # H = normalize(L + V) lies between V and L, so 0 <= V.H <= 1 whenever H exists: the clamp never acts, an equivalent mutant
+        assert not any(old.values()) and not any(new.values())
+    else:
+        assert seen and (fault != "fresnel_pow4" or all(("m0_black_dielectric", k) in seen for k in range(3)))
+    assert all(old[p] <= P.IMAGE_BOUND[p] for p in old) == (fault in UNSEEN_AT_GAIN_ONE + P.INERT_FAULTS)
+
+
+def test_fresnel_at_grazing_incidence():
+    """One sample of a black dielectric (F0 = 0.04) on a face seen at 66 degrees from its normal, under a light near the mirror
+    direction: (1 - F0)(1 - V.H)^5 is more than half of F, so the value is I NL pi D G F / (4 NL NV + 1e-6) with a Fresnel term
+    that the exponent decides.  The restatement rounds 1 / w to float32 as the device does, 6e-8 relative, which moves the point by
+    as much; D's denominator amplifies a change of N.H by 1 / dd < 20: a bound of 1e-5 relative leaves a factor of ten."""
+    verts = R.screen_verts([(10.0, 10.0, 1.0), (30.0, 10.0, 16.0), (10.0, 30.0, 1.0)], 64, 48)      # receding steeply to the right
+    a, b, c = verts.astype(np.float64)
+    n = np.cross(b - a, c - a)
+    n /= np.linalg.norm(n)
+    d = np.array([2 * 16.5 / 64 - 1, 1 - 2 * 16.5 / 48, 1.0])                # the ray of sample (16, 16) from the eye at the origin
+    n = -n if n @ d > 0 else n
+    p = d * (n @ a) / (n @ d)
+    v = -p / np.linalg.norm(p)
+    mirror = (2 * (n @ v) * n - v) + np.array([0.02, -0.01, 0.015])          # a little off the mirror direction, so N.H < 1
+    light = (mirror / np.linalg.norm(mirror)).astype(np.float32).astype(np.float64)
+    case = dict(verts=verts, faces=np.array([[0, 1, 2]], dtype=np.int32), shading="pbr_flat", lights=np.array([[*light, 0.9]]), ambient=0.0,
+                uvs=None, materials=[{"Kd": (0.0, 0.0, 0.0), "Pm": 0.0, "Pr": 0.5}])
+    xy, iw = R.project(verts, R.SCREEN, 64, 48, R.SCREEN_NEAR)
+    r = R.raster(xy, iw, case["faces"], 64, 48)
+    smp = P.gather_samples(case, xy, iw, r["face_id"])
+    at = np.flatnonzero(smp["s"] == 16 * 64 + 16)[0]
+    one = {k: x[at:at + 1] for k, x in smp.items()}
+    got = P.shade_pbr(case, R.SCREEN, one, 64, 48, 1, raw=True)["shaded"][0]
+    h = light + v
+    h /= np.linalg.norm(h)
+    nl, nv, nh, vh = n @ light, n @ v, n @ h, v @ h
+    schlick = 0.96 * (1 - vh) ** 5
+    F = 0.04 + schlick
+    a2, k = 0.5 ** 4, 0.5 ** 2 / 2
+    D = a2 / (math.pi * (nh * nh * (a2 - 1) + 1) ** 2)
+    G = nl / (nl * (1 - k) + k) * nv / (nv * (1 - k) + k)
+    want = np.float32(0.9).astype(np.float64) * nl * math.pi * D * G * F / (4 * nl * nv + 1e-6)
+    print("N.V", nv, "N.L", nl, "N.H", nh, "V.H", vh, "Schlick term / F", schlick / F, "value", want, "restated", got)
+    assert schlick >= 0.5 * F and 0.3 < nv < 0.5 and 0.3 < nl < 0.5 and 0.2 < want < 1.0
+    assert np.abs(got - want).max() <= 1e-5 * want
+    for fault in ("fresnel_pow4", "fresnel_pow6"):
+        wrong = P.shade_pbr(case, R.SCREEN, one, 64, 48, 1, raw=True, fault=fault)["shaded"][0]
+        assert np.abs(wrong - want).min() > 0.2 * want, fault
 
 
 # ------------------------------------------------------------------ the MTL parser, the rig, the command line
