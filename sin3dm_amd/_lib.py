@@ -6,6 +6,7 @@ entry point raises.  torch is used by the callers only for device memory and str
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -374,3 +375,15 @@ def ptr(t):
 
 def ptr3(ts):
     return (C.c_void_p * 3)(*[C.c_void_p(t.data_ptr()) for t in ts])
+
+
+def read_layout(n, info):
+    """[(name, offset, numel, shape)] of a handle's n flat parameters; info(i, name, shape, ndim, offset) fills ctypes references for entry i
+    (the handle's param_info, and its param_offset where that is a call of its own)."""
+    layout = []
+    for i in range(n):
+        name, shape, nd, off = C.c_char_p(), (C.c_int64 * 5)(), C.c_int(), C.c_int64()
+        info(i, C.byref(name), shape, C.byref(nd), C.byref(off))
+        shp = tuple(shape[k] for k in range(nd.value))
+        layout.append((name.value.decode(), off.value, math.prod(shp), shp))
+    return layout

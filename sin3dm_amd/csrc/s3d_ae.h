@@ -28,7 +28,8 @@ int launch_mr_from_partials3(double* const part[3], int nchunks, int C, const si
 // InstanceNorm2d(affine) + SiLU of a net's three planes + their {mean, rstd} (mr [3][C][2]): partials, statistics, apply — three launches
 int launch_inorm_silu3(float* const x[3], double* const part[3], const float* const gamma[3], const float* const beta[3], float* const y[3],
                        const size_t hw[3], int C, float eps, float* mr, hipStream_t st);
-// the same with both results kept — xn = IN(x) and y = SiLU(xn) — for a block that normalises its INPUT (the PBR net's tex_convs.1)
+// the same with both results kept — xn = IN(x) and y = SiLU(xn) — for a block that normalises its INPUT (the PBR net's tex_convs.1);
+// xn null: not kept (launch_inorm_silu3 is that call)
 int launch_inorm_keep3(float* const x[3], double* const part[3], const float* const gamma[3], const float* const beta[3], float* const xn[3],
                        float* const y[3], const size_t hw[3], int C, float eps, float* mr, hipStream_t st);
 // backward of that input norm: dx from (dres, du) — see s3d_ae_kernels.hip — and dgamma / dbeta ADDED to what is there

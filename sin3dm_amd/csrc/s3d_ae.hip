@@ -23,49 +23,33 @@
 // channels; 3 is sdftex, 8 sdfpbr on the skip net), 1 the geometry net alone (use_tex=False: one net, a 1-channel volume, no tex
 // group), 2 the PBR net (AutoEncoderGroupPBR, networks.py:227-333; made by s3d_ae_create_pbr, refused by s3d_ae_create_variant):
 // two 3x3 texture blocks, the second with an input norm that shares its parameters with the hidden norm, three heads on one gather.
-// All three run the ONE iteration ae_step, which reads the net as data from the handle: nnets plane blocks (AeNet, kernel size ks),
-// tex_convs.1 when has_tex1 (AeTex1) and nmlp MLPs (AeMlp: which side's gather each reads, which chain it runs on, where its
-// outputs go).  ae_specs names the parameters from that description and ae_plan looks them up.
+// All three run the ONE iteration ae_step, which reads the net as data: the description of s3d_aenet.h (the one the inference
+// handle reads too: blocks, heads, parameter names) and what this handle computes for it — nnets plane blocks (AeNet), tex_convs.1
+// when has_tex1 (tex1) and nmlp MLPs (AeMlp: flat and packed offsets, the chain each runs on).  ae_plan looks the parameters up.
 #include <memory>
 
 #include "s3d_ae.h"
+#include "s3d_aenet.h"
 #include "s3d_bwd.h"
 #include "s3d_model.h"
 
 namespace s3d {
 
-static const char* kAePl[3] = {"xy", "xz", "yz"};
-static const char* kAeLn[6] = {".first_layers.0", ".first_layers.2", ".first_layers.4", ".second_layers.0", ".second_layers.2", ".second_layers.4"};
 constexpr size_t kNone = size_t(-1);                         // "no such parameter" where a flat offset is expected
 
-struct AeSpec { std::string name; std::vector<int64_t> shape; size_t numel() const { size_t n = 1; for (auto d : shape) n *= size_t(d); return n; } };
-
-// a plane block (geo_convs, tex_convs, the PBR net's tex_convs.0): conv ks x ks -> InstanceNorm(affine) -> SiLU -> conv ks x ks + 1x1 shortcut
+// a plane block of the description: conv ks x ks -> InstanceNorm(affine) -> SiLU -> conv ks x ks + 1x1 shortcut (geo_convs, tex_convs,
+// the PBR net's tex_convs.0).  The PBR net's tex_convs.1 is a different kind of block — an input norm, the SAME norm_p again on the
+// hidden maps, the identity shortcut on the normalised input — and leaves the sc fields unset
 struct AeNet {
-    int cin = 0, ks = 5;                                     // real feature channels (4 / 8); kernel size (3 for the PBR net's texture side)
     size_t f_in_w, f_in_b, f_out_w, f_out_b, f_sc_w, f_sc_b, f_gamma[3], f_beta[3];   // flat offsets
     size_t in_dense[3], out_dense[3], sc_dense[3], in_T[3], out_T[3], sc_T[3];        // packed offsets
 };
-// the PBR net's tex_convs.1, a different kind of block: an input norm, the SAME norm_p again on the hidden maps, the identity
-// shortcut on the normalised input, in_layers.1 (no shortcut parameters); 3x3
-struct AeTex1 {
-    static constexpr int taps = 9;
-    size_t f_in_w, f_in_b, f_out_w, f_out_b, f_gamma[3], f_beta[3];
-    size_t in_dense[3], in_T[3], out_dense[3], out_T[3];
-};
-// a DecoderMLPSkipConcat: six layers, the last one into pred columns ooff .. ooff + nout
+// a DecoderMLPSkipConcat (head m of the description, which says whose gather it reads and where its outputs go)
 struct AeMlp {
-    const char* name;
-    int nout, ooff, sigm;                                    // sigm: sigmoid on its outputs
-    int src;                                                 // the gathered feature it reads: 0 geo, 1 tex
     int chain;                                               // its backward chain: 0 the caller's stream, 1 chain2 (a side's MLPs share
                                                              // that side's chain, in handle order: ae_step adds their point gradients per chain)
     size_t f_mw[6], f_mb[6], mT[5];                          // flat offsets; packed transposes of the five hidden layers
 };
-// layer l of an MLP takes I[l] and gives O[l] channels (the skip concatenation enters layer 3)
-static void mlp_dims(int up, int hid, int nout, int I[6], int O[6]) {
-    for (int l = 0; l < 6; ++l) { I[l] = l == 0 ? up : (l == 3 ? up + hid : hid); O[l] = l == 5 ? nout : hid; }
-}
 
 }  // namespace s3d
 
@@ -75,13 +59,14 @@ struct s3d_ae {
     s3d_decoder_cfg cfg;
     int variant = 0;                    // s3d_decoder_create_variant's numbers: 0 skip net with texture, 1 geometry only (tex = TC = 0, C = 1, one net), 2 PBR net
     int geo, tex, up, hid, TC, C, nnets = 2;
-    std::vector<AeSpec> specs;
+    AeNetDesc desc;                     // blocks [0, nnets) are net[], block 2 is tex1; head m is mlp[m]
+    std::vector<ParamSpec> specs;
     std::vector<size_t> flat_off;
     int64_t tex_begin = 0;
     float* flat = nullptr;
     AeNet net[2];
     bool has_tex1 = false;              // variant 2: tex_convs.1 follows net[1]
-    AeTex1 tex1;
+    AeNet tex1;
     AeMlp mlp[4];                       // variant 1: geo | 0: geo, tex | 2: geo, rgb, mr, normal
     int nmlp = 0;
     size_t f_enc_w[2], f_enc_b[2];
@@ -114,54 +99,6 @@ struct s3d_ae {
 
 namespace s3d {
 
-// the net as data: what ae_specs, ae_plan and ae_step loop over
-static void ae_describe(s3d_ae* a) {
-    auto mlp = [&](const char* name, int nout, int ooff, int sigm, int side) {
-        AeMlp& M = a->mlp[a->nmlp++];
-        M.name = name; M.nout = nout; M.ooff = ooff; M.sigm = sigm; M.src = M.chain = side;
-    };
-    a->net[0].cin = a->geo; a->net[0].ks = 5;
-    a->net[1].cin = a->tex; a->net[1].ks = a->variant == 2 ? 3 : 5;
-    a->has_tex1 = a->variant == 2;
-    a->nmlp = 0;
-    mlp("geo_decoder", 1, 0, 0, 0);
-    if (a->variant == 0) mlp("tex_decoder", a->TC, 1, 1, 1);
-    if (a->variant == 2) { mlp("rgb_decoder", 3, 1, 0, 1); mlp("mr_decoder", 2, 4, 0, 1); mlp("normal_decoder", 3, 6, 0, 1); }
-}
-
-static void ae_specs(s3d_ae* a) {
-    const int up = a->up, hid = a->hid;
-    auto add = [&](const std::string& n, std::vector<int64_t> s) { a->specs.push_back({n, std::move(s)}); };
-    const char* pre[2] = {"geo", "tex"};
-    const int encin[2] = {1, a->C};
-    auto mlp = [&](const AeMlp& M) {
-        int I[6], O[6];
-        mlp_dims(up, hid, M.nout, I, O);
-        for (int l = 0; l < 6; ++l) { add(std::string(M.name) + kAeLn[l] + ".weight", {O[l], I[l]}); add(std::string(M.name) + kAeLn[l] + ".bias", {O[l]}); }
-    };
-    for (int k = 0; k < a->nnets; ++k) {
-        if (k == 1) { int64_t n = 0; for (auto& s : a->specs) n += int64_t(s.numel()); a->tex_begin = n; }
-        const int cin = a->net[k].cin, ks = a->net[k].ks;
-        const std::string e = std::string(pre[k]) + "_encoder", cv = std::string(pre[k]) + (k == 1 && a->has_tex1 ? "_convs.0" : "_convs");
-        add(e + ".weight", {cin, encin[k], 4, 4, 4}); add(e + ".bias", {cin});
-        add(cv + ".in_layers.0.weight", {3 * up, cin, ks, ks}); add(cv + ".in_layers.0.bias", {3 * up});
-        for (int p = 0; p < 3; ++p) { add(cv + ".norm_" + kAePl[p] + ".weight", {up}); add(cv + ".norm_" + kAePl[p] + ".bias", {up}); }
-        add(cv + ".out_layers.1.weight", {3 * up, up, ks, ks}); add(cv + ".out_layers.1.bias", {3 * up});
-        add(cv + ".shortcut.weight", {3 * up, cin, 1, 1}); add(cv + ".shortcut.bias", {3 * up});
-        if (k == 1 && a->has_tex1) {
-            const std::string c1 = "tex_convs.1";
-            add(c1 + ".in_layers.1.weight", {3 * up, up, 3, 3}); add(c1 + ".in_layers.1.bias", {3 * up});
-            for (int p = 0; p < 3; ++p) { add(c1 + ".norm_" + kAePl[p] + ".weight", {up}); add(c1 + ".norm_" + kAePl[p] + ".bias", {up}); }
-            add(c1 + ".out_layers.1.weight", {3 * up, up, 3, 3}); add(c1 + ".out_layers.1.bias", {3 * up});
-        }
-        for (int m = 0; m < a->nmlp; ++m) if (a->mlp[m].src == k) mlp(a->mlp[m]);
-    }
-    a->flat_off.resize(a->specs.size());
-    size_t off = 0;
-    for (size_t i = 0; i < a->specs.size(); ++i) { a->flat_off[i] = off; off += a->specs[i].numel(); }
-    if (a->nnets == 1) a->tex_begin = int64_t(off);          // no tex group: it begins where the vector ends
-}
-
 static int ae_plan(s3d_ae* a) {
     const int up = a->up, hid = a->hid;
     size_t ps = 0;
@@ -171,52 +108,50 @@ static int ae_plan(s3d_ae* a) {
         d.kind = kind; d.cout = cout; d.ctot = ctot; d.cin = cin; d.slot = slot; d.taps = taps; d.src = (long long)src; d.dst = (long long)dst; d.n = n;
         a->descs.push_back(d);
     };
-    auto mlp = [&](AeMlp& M) {
+    auto mlp = [&](int m) {
+        AeMlp& M = a->mlp[m];
+        const AeHead& H = a->desc.heads[m];
         int I[6], O[6];
-        mlp_dims(up, hid, M.nout, I, O);
+        mlp_dims(up, hid, H.nout, I, O);
         for (int l = 0; l < 6; ++l) {
-            M.f_mw[l] = a->off_of(std::string(M.name) + kAeLn[l] + ".weight"); M.f_mb[l] = a->off_of(std::string(M.name) + kAeLn[l] + ".bias");
+            M.f_mw[l] = a->off_of(std::string(H.name) + kMlpLayer[l] + ".weight"); M.f_mb[l] = a->off_of(std::string(H.name) + kMlpLayer[l] + ".bias");
             if (l < 5) { M.mT[l] = palloc(size_t(I[l]) * O[l]); add(PK_TRANS2D, M.f_mw[l], M.mT[l], (long long)I[l] * O[l], O[l], 0, I[l]); }
         }
     };
+    // the dense and the transposed image of plane p's [up][cin][T] slice of a conv weight; pad: cin real channels in a 32-channel tensor
+    auto conv = [&](size_t w, int p, int cin, int T, bool pad, size_t& dense, size_t& trans) {
+        const size_t src = w + size_t(p) * up * cin * T;
+        const int ci = pad ? 32 : cin, slot = pad ? 32 : 0;
+        const long long n = (long long)(pad ? T : 1) * up * cin;
+        dense = palloc(size_t(T) * up * ci); add(pad ? PK_DENSE_PAD : PK_DENSE, src, dense, n, up, cin, cin, T, slot);
+        trans = palloc(size_t(T) * ci * up); add(pad ? PK_DENSE_T_PAD : PK_DENSE_T, src, trans, n, up, cin, cin, T, slot);
+    };
     a->descs.clear();
-    const char* pre[2] = {"geo", "tex"};
     a->encb_off = palloc(a->geo + a->tex);
     a->wp_off = palloc(size_t(3) * (a->geo + a->tex) * 16 * 4 * a->C);
     for (int k = 0; k < a->nnets; ++k) {
-        AeNet& N = a->net[k];
-        const int cin = N.cin, T = N.ks * N.ks;
-        const std::string e = std::string(pre[k]) + "_encoder", cv = std::string(pre[k]) + (k == 1 && a->has_tex1 ? "_convs.0" : "_convs");
+        const std::string e = k == 0 ? "geo_encoder" : "tex_encoder";
         a->f_enc_w[k] = a->off_of(e + ".weight"); a->f_enc_b[k] = a->off_of(e + ".bias");
-        add(PK_COPY, a->f_enc_b[k], a->encb_off + (k == 0 ? 0 : a->geo), cin);
-        N.f_in_w = a->off_of(cv + ".in_layers.0.weight"); N.f_in_b = a->off_of(cv + ".in_layers.0.bias");
-        N.f_out_w = a->off_of(cv + ".out_layers.1.weight"); N.f_out_b = a->off_of(cv + ".out_layers.1.bias");
-        N.f_sc_w = a->off_of(cv + ".shortcut.weight"); N.f_sc_b = a->off_of(cv + ".shortcut.bias");
-        for (int p = 0; p < 3; ++p) {
-            N.f_gamma[p] = a->off_of(cv + ".norm_" + kAePl[p] + ".weight"); N.f_beta[p] = a->off_of(cv + ".norm_" + kAePl[p] + ".bias");
-            const size_t win = N.f_in_w + size_t(p) * up * cin * T, wout = N.f_out_w + size_t(p) * up * up * T, wsc = N.f_sc_w + size_t(p) * up * cin;
-            N.in_dense[p] = palloc(size_t(T) * up * 32); add(PK_DENSE_PAD, win, N.in_dense[p], (long long)T * up * cin, up, cin, cin, T, 32);
-            N.in_T[p] = palloc(size_t(T) * 32 * up);     add(PK_DENSE_T_PAD, win, N.in_T[p], (long long)T * up * cin, up, cin, cin, T, 32);
-            N.out_dense[p] = palloc(size_t(T) * up * up); add(PK_DENSE, wout, N.out_dense[p], (long long)up * up, up, up, up, T);
-            N.out_T[p] = palloc(size_t(T) * up * up);    add(PK_DENSE_T, wout, N.out_T[p], (long long)up * up, up, up, up, T);
-            N.sc_dense[p] = palloc(size_t(up) * 32);      add(PK_DENSE_PAD, wsc, N.sc_dense[p], (long long)up * cin, up, cin, cin, 1, 32);
-            N.sc_T[p] = palloc(size_t(32) * up);          add(PK_DENSE_T_PAD, wsc, N.sc_T[p], (long long)up * cin, up, cin, cin, 1, 32);
-        }
-        if (k == 1 && a->has_tex1) {
-            AeTex1& Q = a->tex1;
-            const std::string c1 = "tex_convs.1";
-            Q.f_in_w = a->off_of(c1 + ".in_layers.1.weight"); Q.f_in_b = a->off_of(c1 + ".in_layers.1.bias");
-            Q.f_out_w = a->off_of(c1 + ".out_layers.1.weight"); Q.f_out_b = a->off_of(c1 + ".out_layers.1.bias");
+        add(PK_COPY, a->f_enc_b[k], a->encb_off + (k == 0 ? 0 : a->geo), a->desc.side_channels(k));
+        for (const AeBlock& B : a->desc.blocks) {
+            if (B.side != k) continue;
+            const int T = B.ks * B.ks;
+            // the first block of its side is net[k] and reads its slice of the encoder's planes: cin real channels in a 32-channel tensor;
+            // the one behind it (AeNetDesc::runnable: at most one, the input-norm block) is tex1 and takes the `up` channels before it
+            const bool first = &B == &a->desc.blocks[k];
+            AeNet& N = first ? a->net[k] : a->tex1;
+            auto off = [&](const std::string& n) { return a->off_of(B.prefix + n); };
+            N.f_in_w = a->off_of(B.in_conv() + ".weight"); N.f_in_b = a->off_of(B.in_conv() + ".bias");
+            N.f_out_w = off(".out_layers.1.weight"); N.f_out_b = off(".out_layers.1.bias");
+            if (B.shortcut) { N.f_sc_w = off(".shortcut.weight"); N.f_sc_b = off(".shortcut.bias"); }
             for (int p = 0; p < 3; ++p) {
-                Q.f_gamma[p] = a->off_of(c1 + ".norm_" + kAePl[p] + ".weight"); Q.f_beta[p] = a->off_of(c1 + ".norm_" + kAePl[p] + ".bias");
-                const size_t win = Q.f_in_w + size_t(p) * up * up * 9, wout = Q.f_out_w + size_t(p) * up * up * 9;
-                Q.in_dense[p] = palloc(size_t(9) * up * up);  add(PK_DENSE, win, Q.in_dense[p], (long long)up * up, up, up, up, 9);
-                Q.in_T[p] = palloc(size_t(9) * up * up);      add(PK_DENSE_T, win, Q.in_T[p], (long long)up * up, up, up, up, 9);
-                Q.out_dense[p] = palloc(size_t(9) * up * up); add(PK_DENSE, wout, Q.out_dense[p], (long long)up * up, up, up, up, 9);
-                Q.out_T[p] = palloc(size_t(9) * up * up);     add(PK_DENSE_T, wout, Q.out_T[p], (long long)up * up, up, up, up, 9);
+                N.f_gamma[p] = off(std::string(".norm_") + kPlane[p] + ".weight"); N.f_beta[p] = off(std::string(".norm_") + kPlane[p] + ".bias");
+                conv(N.f_in_w, p, B.cin, T, first, N.in_dense[p], N.in_T[p]);
+                conv(N.f_out_w, p, up, T, false, N.out_dense[p], N.out_T[p]);
+                if (B.shortcut) conv(N.f_sc_w, p, B.cin, 1, true, N.sc_dense[p], N.sc_T[p]);
             }
         }
-        for (int m = 0; m < a->nmlp; ++m) if (a->mlp[m].src == k) mlp(a->mlp[m]);
+        for (int m = 0; m < a->nmlp; ++m) if (a->desc.heads[m].side == k) mlp(m);
     }
     a->psize = ps;
     S3D_TRY(a->pbuf.reserve(ps * sizeof(float)));
@@ -332,12 +267,13 @@ struct AeRun {
     // plane block n on chain cs: its slice of the encoder's planes -> A[n].f
     int block_fwd(int n, hipStream_t cs) {
         const AeNet& N_ = a->net[n];
+        const AeBlock& D = a->desc.blocks[n];
         BlockAct& T = A[n];
-        const ConvKind kind = N_.ks == 3 ? CONV_3x3 : CONV_5x5;
+        const ConvKind kind = D.ks == 3 ? CONV_3x3 : CONV_5x5;
         planes(T.x, 32); planes(T.a1, up); planes(T.y, up); planes(T.s, up); planes(T.f, up);
         for (int p = 0; p < 3; ++p) T.part[p] = ar().alloc<double>(size_t(kInNormChunks) * up * 2);
         T.mr = ar().alloc<float>(size_t(3) * up * 2);
-        if (!meas()) S3D_TRY(launch_slice_pad_nhwc3(feat, T.x, hw, CO, n == 0 ? 0 : a->geo, N_.cin, cs));
+        if (!meas()) S3D_TRY(launch_slice_pad_nhwc3(feat, T.x, hw, CO, n == 0 ? 0 : a->geo, D.cin, cs));
         S3D_TRY(conv3(kind, 32, up, T.x, N_.in_dense, N_.f_in_b, nullptr, T.a1, cs));
         if (!meas()) {
             const float *gam[3], *bet[3];
@@ -350,26 +286,27 @@ struct AeRun {
     // its backward: the block's output gradient dFn -> its slice of dfeat
     int block_bwd(int n, float* const dFn[3], hipStream_t cs) {
         const AeNet& N_ = a->net[n];
+        const AeBlock& D = a->desc.blocks[n];
         BlockAct& T = A[n];
-        const int taps = N_.ks * N_.ks;
-        const ConvKind kind = N_.ks == 3 ? CONV_3x3 : CONV_5x5;
+        const int taps = D.ks * D.ks;
+        const ConvKind kind = D.ks == 3 ? CONV_3x3 : CONV_5x5;
         float *d_y[3], *d_xs[3], *d_a1[3], *d_x[3], *dw_out[3], *dw_sc[3], *dw_in[3];
         planes(d_y, up); planes(d_xs, 32); planes(d_a1, up); planes(d_x, 32);
-        dw3(N_.f_out_w, size_t(up) * up * taps, dw_out); dw3(N_.f_sc_w, size_t(up) * N_.cin, dw_sc); dw3(N_.f_in_w, size_t(up) * N_.cin * taps, dw_in);
+        dw3(N_.f_out_w, size_t(up) * up * taps, dw_out); dw3(N_.f_sc_w, size_t(up) * D.cin, dw_sc); dw3(N_.f_in_w, size_t(up) * D.cin * taps, dw_in);
         S3D_TRY(colsum_side(dFn, N_.f_out_b, N_.f_sc_b, cs));      // out conv and shortcut share dy: identical bias gradients, one pass, two outputs
         S3D_TRY(conv3(kind, up, up, dFn, N_.out_T, kNone, nullptr, d_y, cs));
         S3D_TRY(wgrad(taps, up, up, up, g, dFn, up, T.y, dw_out, 3, cs));
         S3D_TRY(conv3(CONV_1x1, up, 32, dFn, N_.sc_T, kNone, nullptr, d_xs, cs));
-        S3D_TRY(wgrad(1, 32, N_.cin, up, g, dFn, 32, T.x, dw_sc, 3, cs));
+        S3D_TRY(wgrad(1, 32, D.cin, up, g, dFn, 32, T.x, dw_sc, 3, cs));
         S3D_TRY(gn_bwd(T.a1, d_y, d_a1, N_.f_gamma, N_.f_beta, T.mr, cs));
         S3D_TRY(colsum_side(d_a1, N_.f_in_b, kNone, cs));
-        S3D_TRY(wgrad(taps, 32, N_.cin, up, g, d_a1, 32, T.x, dw_in, 3, cs));
+        S3D_TRY(wgrad(taps, 32, D.cin, up, g, d_a1, 32, T.x, dw_in, 3, cs));
         S3D_TRY(conv3(kind, up, 32, d_a1, N_.in_T, kNone, d_xs, d_x, cs));
-        return meas() ? 0 : launch_unslice_nhwc3(d_x, dfeat, hw, CO, n == 0 ? 0 : a->geo, N_.cin, cs);
+        return meas() ? 0 : launch_unslice_nhwc3(d_x, dfeat, hw, CO, n == 0 ? 0 : a->geo, D.cin, cs);
     }
     // tex_convs.1 on f0 = A[1].f -> B.f1
     int tex1_fwd(hipStream_t cs) {
-        const AeTex1& Q = a->tex1;
+        const AeNet& Q = a->tex1;
         planes(B.xn, up); planes(B.v, up); planes(B.a2, up); planes(B.y2, up); planes(B.f1, up);
         for (int p = 0; p < 3; ++p) B.part[p] = ar().alloc<double>(size_t(kInNormChunks) * up * 2);
         B.mr_in = ar().alloc<float>(size_t(3) * up * 2);
@@ -383,17 +320,17 @@ struct AeRun {
     }
     // its backward: dF1 -> d_f0.  norm_p receives its hidden-map gradient first (written) and its input-norm gradient second (added)
     int tex1_bwd(float* const dF1[3], float* d_f0[3], hipStream_t cs) {
-        const AeTex1& Q = a->tex1;
+        const AeNet& Q = a->tex1;
         float *d_y2[3], *d_a2[3], *d_u[3], *dw_out[3], *dw_in[3];
         planes(d_y2, up); planes(d_a2, up); planes(d_u, up); planes(d_f0, up);
-        dw3(Q.f_out_w, size_t(up) * up * Q.taps, dw_out); dw3(Q.f_in_w, size_t(up) * up * Q.taps, dw_in);
+        dw3(Q.f_out_w, size_t(up) * up * 9, dw_out); dw3(Q.f_in_w, size_t(up) * up * 9, dw_in);
         void* iws = ar().alloc<char>(in_norm_bwd_ws_bytes(up));
         S3D_TRY(colsum_side(dF1, Q.f_out_b, kNone, cs));
         S3D_TRY(conv3(CONV_3x3, up, up, dF1, Q.out_T, kNone, nullptr, d_y2, cs));
-        S3D_TRY(wgrad(Q.taps, up, up, up, g, dF1, up, B.y2, dw_out, 3, cs));
+        S3D_TRY(wgrad(9, up, up, up, g, dF1, up, B.y2, dw_out, 3, cs));
         S3D_TRY(gn_bwd(B.a2, d_y2, d_a2, Q.f_gamma, Q.f_beta, B.mr_hid, cs));      // first use of norm_p: dgamma / dbeta written
         S3D_TRY(colsum_side(d_a2, Q.f_in_b, kNone, cs));
-        S3D_TRY(wgrad(Q.taps, up, up, up, g, d_a2, up, B.v, dw_in, 3, cs));
+        S3D_TRY(wgrad(9, up, up, up, g, d_a2, up, B.v, dw_in, 3, cs));
         S3D_TRY(conv3(CONV_3x3, up, up, d_a2, Q.in_T, kNone, nullptr, d_u, cs));
         if (meas()) return 0;
         const float *gam[3], *bet[3];
@@ -468,7 +405,7 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
     float *X0[2] = {nullptr, nullptr}, *Xm[4], *H[5][4], *CAT[4];      // H[l][m]: hidden activation l of MLP m
     for (int n = 0; n < NN; ++n) X0[n] = ar.alloc<float>(size_t(Np) * up);
     for (int m = 0; m < M; ++m) {
-        Xm[m] = X0[a->mlp[m].src];
+        Xm[m] = X0[a->desc.heads[m].side];
         for (int l = 0; l < 5; ++l) H[l][m] = ar.alloc<float>(size_t(Np) * hid);
         CAT[m] = ar.alloc<float>(size_t(Np) * (up + hid));
     }
@@ -493,7 +430,8 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
     if (!meas)
         for (int m = 0; m < M; ++m) {
             const AeMlp& Q = a->mlp[m];
-            S3D_TRY(launch_last_fwd(H[4][m], R.F(Q.f_mw[5]), R.F(Q.f_mb[5]), hid, Q.nout, Q.sigm, pred, S, Q.ooff, N, st));
+            const AeHead& D = a->desc.heads[m];
+            S3D_TRY(launch_last_fwd(H[4][m], R.F(Q.f_mw[5]), R.F(Q.f_mb[5]), hid, D.nout, D.sigmoid, pred, S, D.col0, N, st));
         }
     if (!meas && pred_out) S3D_HIP(hipMemcpyAsync(pred_out, pred, size_t(N) * S * sizeof(float), hipMemcpyDeviceToDevice, st));
 
@@ -529,11 +467,12 @@ static int ae_step(s3d_ae* a, const float* pts, const float* sdf, const float* t
     float *dXa[4], *dCAT[4];
     for (int m = 0; m < M; ++m) {
         const AeMlp& Q = a->mlp[m];
+        const AeHead& D = a->desc.heads[m];
         float* dH = ar.alloc<float>(size_t(Np) * hid);            // gradient of a hidden activation (reused)
         dCAT[m] = ar.alloc<float>(size_t(Np) * (up + hid));
         dXa[m] = ar.alloc<float>(size_t(Np) * up);
-        float* lws = ar.alloc<float>(last_bwd_ws_floats(hid, Q.nout));
-        if (!meas) S3D_TRY(launch_last_bwd(dout, S, Q.ooff, R.F(Q.f_mw[5]), H[4][m], hid, Q.nout, Np, dH, lws, R.G(Q.f_mw[5]), R.G(Q.f_mb[5]), chain[Q.chain]));
+        float* lws = ar.alloc<float>(last_bwd_ws_floats(hid, D.nout));
+        if (!meas) S3D_TRY(launch_last_bwd(dout, S, D.col0, R.F(Q.f_mw[5]), H[4][m], hid, D.nout, Np, dH, lws, R.G(Q.f_mw[5]), R.G(Q.f_mb[5]), chain[Q.chain]));
         const Step st5[5] = {{4, H[4][m], H[3][m], hid, dH, dH, hid, 0},
                              {3, H[3][m], CAT[m], up + hid, dCAT[m], dH, hid, 0},
                              {2, H[2][m], H[1][m], hid, dH, dCAT[m], up + hid, up},
@@ -637,8 +576,16 @@ static int ae_new(const s3d_decoder_cfg* cfg, int variant, s3d_ae** out) {
     a->variant = variant; a->nnets = tex ? 2 : 1;
     a->geo = cfg->geo_feat_channels; a->tex = tex ? cfg->tex_feat_channels : 0; a->up = cfg->feat_channel_up; a->hid = cfg->mlp_hidden_channels;
     a->TC = tex ? cfg->tex_channels : 0; a->C = 1 + a->TC;
-    ae_describe(a.get());
-    ae_specs(a.get());
+    a->desc = aenet_describe(*cfg, variant);
+    S3D_CHECK(a->desc.runnable(), S3D_ERR_UNSUPPORTED, "ae: ae_step is not written for this description of the net (s3d_aenet.h)");
+    a->has_tex1 = a->desc.blocks.size() > size_t(a->nnets);
+    a->nmlp = int(a->desc.heads.size());
+    for (int m = 0; m < a->nmlp; ++m) a->mlp[m].chain = a->desc.heads[m].side;
+    a->specs = aenet_params(a->desc, /*with_encoders=*/true);
+    a->flat_off.resize(a->specs.size());
+    size_t off = 0;
+    for (size_t i = 0; i < a->specs.size(); ++i) { a->flat_off[i] = off; off += a->specs[i].numel(); }
+    a->tex_begin = int64_t(a->nnets == 2 ? a->off_of("tex_encoder.weight") : off);      // no tex group: it begins where the vector ends
     *out = a.release();
     return 0;
 }
@@ -664,10 +611,7 @@ void s3d_ae_destroy(s3d_ae* a) { delete a; }
 int s3d_ae_out_channels(const s3d_ae* a) { return a ? 1 + a->TC : S3D_ERR_INVALID; }
 int s3d_ae_num_params(const s3d_ae* a) { return a ? int(a->specs.size()) : S3D_ERR_INVALID; }
 int s3d_ae_param_info(const s3d_ae* a, int i, const char** name, int64_t shape[5], int* ndim, int64_t* offset) {
-    S3D_CHECK(a && i >= 0 && i < int(a->specs.size()), S3D_ERR_INVALID, "ae param_info: index %d out of range", i);
-    if (name) *name = a->specs[i].name.c_str();
-    if (ndim) *ndim = int(a->specs[i].shape.size());
-    if (shape) for (size_t k = 0; k < a->specs[i].shape.size(); ++k) shape[k] = a->specs[i].shape[k];
+    S3D_TRY(registry_param_info(a ? &a->specs : nullptr, "ae ", i, name, shape, ndim));
     if (offset) *offset = int64_t(a->flat_off[i]);
     return 0;
 }

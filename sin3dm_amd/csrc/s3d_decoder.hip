@@ -24,10 +24,10 @@
 #include <memory>
 
 #include "s3d_ae.h"
+#include "s3d_aenet.h"
 
 namespace s3d {
 
-static const char* kPl[3] = {"xy", "xz", "yz"};
 static inline int rup32(int v) { return (v + 31) / 32 * 32; }
 
 // ------------------------------------------------------------------ small kernels of the plane block
@@ -144,24 +144,8 @@ __global__ void k_inorm_silu3(InNorm3Args a) {
     __syncthreads();
     inorm_apply<false>(a.x[p], A, Bc, nullptr, a.y[p], a.hw[p], C);
 }
-int launch_inorm_silu3(float* const x[3], double* const part[3], const float* const gamma[3], const float* const beta[3], float* const y[3],
-                       const size_t hw[3], int C, float eps, float* mr, hipStream_t st) {
-    InNorm3Args a; a.C = C; a.mr = mr;
-    int mx = 0;
-    for (int p = 0; p < 3; ++p) {
-        a.x[p] = x[p]; a.y[p] = y[p]; a.part[p] = part[p]; a.gamma[p] = gamma[p]; a.beta[p] = beta[p]; a.hw[p] = int(hw[p]);
-        mx = std::max(mx, a.hw[p]);
-    }
-    const int cq = C / 4, pl = std::max(1, 256 / cq);
-    hipLaunchKernelGGL(k_chan_partials3, dim3(kInNormChunks, 3), dim3(cq * pl), size_t(pl) * C * 2 * sizeof(double), st, a);
-    S3D_HIP(hipGetLastError());
-    S3D_TRY(launch_mr_from_partials3(part, kInNormChunks, C, hw, eps, mr, st));
-    hipLaunchKernelGGL(k_inorm_silu3, dim3(std::min(1024, (mx * cq + 255) / 256), 3), dim3(256), size_t(2) * C * sizeof(float), st, a);
-    S3D_HIP(hipGetLastError());
-    return 0;
-}
-
-// ... and k_inorm_keep's: the normalised maps stored beside their SiLU (the training tier's tex_convs.1 of the PBR net)
+// ... and k_inorm_keep's: the normalised maps stored beside their SiLU (the training tier's tex_convs.1 of the PBR net).  (The
+// scale / shift loop is written out in both kernels: as a shared __device__ helper it compiled to other instructions in both.)
 struct InNormKeep3Args { InNorm3Args n; float* xn[3]; };
 __global__ __launch_bounds__(256) void k_inorm_keep3(InNormKeep3Args k) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -175,21 +159,29 @@ __global__ __launch_bounds__(256) void k_inorm_keep3(InNormKeep3Args k) {
     __syncthreads();
     inorm_apply<true>(a.x[p], A, Bc, k.xn[p], a.y[p], a.hw[p], C);
 }
+// xn null: the normalised maps are not kept (k_inorm_silu3)
 int launch_inorm_keep3(float* const x[3], double* const part[3], const float* const gamma[3], const float* const beta[3], float* const xn[3],
                        float* const y[3], const size_t hw[3], int C, float eps, float* mr, hipStream_t st) {
     InNormKeep3Args k; InNorm3Args& a = k.n; a.C = C; a.mr = mr;
     int mx = 0;
     for (int p = 0; p < 3; ++p) {
-        a.x[p] = x[p]; a.y[p] = y[p]; a.part[p] = part[p]; a.gamma[p] = gamma[p]; a.beta[p] = beta[p]; a.hw[p] = int(hw[p]); k.xn[p] = xn[p];
+        a.x[p] = x[p]; a.y[p] = y[p]; a.part[p] = part[p]; a.gamma[p] = gamma[p]; a.beta[p] = beta[p]; a.hw[p] = int(hw[p]);
+        k.xn[p] = xn ? xn[p] : nullptr;
         mx = std::max(mx, a.hw[p]);
     }
     const int cq = C / 4, pl = std::max(1, 256 / cq);
     hipLaunchKernelGGL(k_chan_partials3, dim3(kInNormChunks, 3), dim3(cq * pl), size_t(pl) * C * 2 * sizeof(double), st, a);
     S3D_HIP(hipGetLastError());
     S3D_TRY(launch_mr_from_partials3(part, kInNormChunks, C, hw, eps, mr, st));
-    hipLaunchKernelGGL(k_inorm_keep3, dim3(std::min(1024, (mx * cq + 255) / 256), 3), dim3(256), size_t(2) * C * sizeof(float), st, k);
+    const dim3 grid(std::min(1024, (mx * cq + 255) / 256), 3);
+    if (xn) hipLaunchKernelGGL(k_inorm_keep3, grid, dim3(256), size_t(2) * C * sizeof(float), st, k);
+    else hipLaunchKernelGGL(k_inorm_silu3, grid, dim3(256), size_t(2) * C * sizeof(float), st, a);
     S3D_HIP(hipGetLastError());
     return 0;
+}
+int launch_inorm_silu3(float* const x[3], double* const part[3], const float* const gamma[3], const float* const beta[3], float* const y[3],
+                       const size_t hw[3], int C, float eps, float* mr, hipStream_t st) {
+    return launch_inorm_keep3(x, part, gamma, beta, nullptr, y, hw, C, eps, mr, st);
 }
 
 // ------------------------------------------------------------------ fused gather + MLP
@@ -550,18 +542,16 @@ using namespace s3d;
 struct s3d_decoder {
     s3d_decoder_cfg cfg;
     int variant = 0;          // 0 skip net with texture, 1 geometry only, 2 AutoEncoderGroupPBR (include/sin3dm_hip.h)
-    struct Spec { std::string name; std::vector<int64_t> shape; };
-    std::vector<Spec> specs;
+    AeNetDesc desc;           // the blocks and heads (s3d_aenet.h); real widths, the padding below is this handle's business
+    std::vector<ParamSpec> specs;
     std::map<std::string, std::vector<float>> host;
     bool packed = false;
     int up_p = 0, hid_p = 0;
     DevBuf wbuf;
-    // plane blocks: [0] geo_convs (5x5), [1] tex_convs (5x5) or tex_convs.0 (3x3, PBR), [2] tex_convs.1 (3x3, PBR, no shortcut)
-    struct Net { ConvW cin, cout_, sc; size_t gamma[3], beta[3]; int cin_ch; } net[3];
-    // MLP heads in output-column order, group by group
-    struct Head { std::string name; int group, nout, sigmoid; size_t mw[6], mb[6]; };
+    // packed offsets of desc.blocks[i] and desc.heads[i]
+    struct Net { ConvW cin, cout_, sc; size_t gamma[3], beta[3]; } net[3];
+    struct Head { size_t mw[6], mb[6]; };
     std::vector<Head> heads;
-    int ngroups = 2;
     // prepared features
     DevBuf feat;
     float* featp[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
@@ -574,53 +564,9 @@ struct s3d_decoder {
     bool gpacked = false;
     size_t gwt[6] = {0, 0, 0, 0, 0, 0};                  // wt4, wt3x, wt3h, wt2, wt1, wt0
     const float* dev(size_t off) const { return static_cast<const float*>(wbuf.p) + off; }
-    int out_channels() const { int c = 0; for (const auto& h : heads) c += h.nout; return c; }
 };
 
 namespace s3d {
-
-static void dec_specs(s3d_decoder* d) {
-    const s3d_decoder_cfg& c = d->cfg;
-    const int up = c.feat_channel_up, hid = c.mlp_hidden_channels, n = c.mlp_hidden_layers / 2;
-    auto add = [&](const std::string& nme, std::vector<int64_t> sh) { d->specs.push_back({nme, sh}); };
-    // TriplaneGroupResnetBlock (blocks.py:190-235): the conv of in_layers sits behind a SiLU when the block activates its input
-    auto block = [&](const std::string& cv, int cin, int ks, int conv_idx, bool shortcut) {
-        const std::string il = cv + ".in_layers." + std::to_string(conv_idx);
-        add(il + ".weight", {3 * up, cin, ks, ks}); add(il + ".bias", {3 * up});
-        for (int p = 0; p < 3; ++p) { add(cv + ".norm_" + kPl[p] + ".weight", {up}); add(cv + ".norm_" + kPl[p] + ".bias", {up}); }
-        add(cv + ".out_layers.1.weight", {3 * up, up, ks, ks}); add(cv + ".out_layers.1.bias", {3 * up});
-        if (shortcut) { add(cv + ".shortcut.weight", {3 * up, cin, 1, 1}); add(cv + ".shortcut.bias", {3 * up}); }
-    };
-    auto mlp = [&](const std::string& ml, int cout, int group, int sigmoid) {
-        add(ml + ".first_layers.0.weight", {hid, up}); add(ml + ".first_layers.0.bias", {hid});
-        for (int i = 0; i < n; ++i) {
-            add(ml + ".first_layers." + std::to_string(2 * (i + 1)) + ".weight", {hid, hid});
-            add(ml + ".first_layers." + std::to_string(2 * (i + 1)) + ".bias", {hid});
-        }
-        add(ml + ".second_layers.0.weight", {hid, up + hid}); add(ml + ".second_layers.0.bias", {hid});
-        for (int i = 0; i < n - 1; ++i) {
-            add(ml + ".second_layers." + std::to_string(2 * (i + 1)) + ".weight", {hid, hid});
-            add(ml + ".second_layers." + std::to_string(2 * (i + 1)) + ".bias", {hid});
-        }
-        add(ml + ".second_layers." + std::to_string(2 * n) + ".weight", {cout, hid});
-        add(ml + ".second_layers." + std::to_string(2 * n) + ".bias", {cout});
-        s3d_decoder::Head h; h.name = ml; h.group = group; h.nout = cout; h.sigmoid = sigmoid;
-        d->heads.push_back(h);
-    };
-    block("geo_convs", c.geo_feat_channels, 5, 0, true);
-    mlp("geo_decoder", 1, 0, 0);
-    d->ngroups = d->variant == 1 ? 1 : 2;
-    if (d->variant == 0) {
-        block("tex_convs", c.tex_feat_channels, 5, 0, true);
-        mlp("tex_decoder", c.tex_channels, 1, 1);
-    } else if (d->variant == 2) {                        // networks.py:246-253
-        block("tex_convs.0", c.tex_feat_channels, 3, 0, true);
-        block("tex_convs.1", up, 3, 1, false);
-        mlp("rgb_decoder", 3, 1, 0);
-        mlp("mr_decoder", 2, 1, 0);
-        mlp("normal_decoder", 3, 1, 0);
-    }
-}
 
 // dense [out][in] -> zero-padded [outp][inp] with column segments (in = seg0 | seg1 -> seg0p | seg1p)
 static size_t pack_linear(std::vector<float>& st, const std::vector<float>& W, int out, int seg0, int seg1, int outp,
@@ -645,11 +591,11 @@ static size_t pack_vec(std::vector<float>& st, const float* v, int n, int np) {
 static int dec_pack(s3d_decoder* d) {
     for (const auto& sp : d->specs)
         S3D_CHECK(d->host.count(sp.name), S3D_ERR_MISSING, "decoder parameter '%s' was never set", sp.name.c_str());
-    const s3d_decoder_cfg& c = d->cfg;
-    const int up = c.feat_channel_up, hid = c.mlp_hidden_channels, upp = d->up_p, hidp = d->hid_p;
+    const int up = d->desc.up, hid = d->desc.hid, upp = d->up_p, hidp = d->hid_p;
     std::vector<float> st;
     // pad every conv to (cin cip, cout upp): [tap][coutp][cinp]
-    auto pack_conv = [&](const std::vector<float>& W, const std::vector<float>& b, int ci, int cip, int kk, ConvW& cw) {
+    auto pack_conv = [&](const std::string& cv, int ci, int cip, int kk, ConvW& cw) {
+        const std::vector<float>&W = d->host.at(cv + ".weight"), &b = d->host.at(cv + ".bias");
         cw.cin = cip; cw.cout = upp; cw.k = kk; cw.rollout = false;
         const int taps = kk * kk;
         for (int p = 0; p < 3; ++p) {
@@ -663,38 +609,47 @@ static int dec_pack(s3d_decoder* d) {
                         dd[(size_t(t) * upp + co) * cip + ch] = W[((size_t(p) * up + co) * ci + ch) * taps + t];
         }
     };
-    auto pack_block = [&](s3d_decoder::Net& N, const std::string& cv, int ci, int cip, int kk, int conv_idx, bool shortcut) {
-        N.cin_ch = ci;
-        const std::string il = cv + ".in_layers." + std::to_string(conv_idx);
-        pack_conv(d->host.at(il + ".weight"), d->host.at(il + ".bias"), ci, cip, kk, N.cin);
-        pack_conv(d->host.at(cv + ".out_layers.1.weight"), d->host.at(cv + ".out_layers.1.bias"), up, upp, kk, N.cout_);
-        if (shortcut) pack_conv(d->host.at(cv + ".shortcut.weight"), d->host.at(cv + ".shortcut.bias"), ci, cip, 1, N.sc);
+    for (size_t i = 0; i < d->desc.blocks.size(); ++i) {
+        const AeBlock& B = d->desc.blocks[i];
+        s3d_decoder::Net& N = d->net[i];
+        const int cip = rup32(B.cin);
+        pack_conv(B.in_conv(), B.cin, cip, B.ks, N.cin);
+        pack_conv(B.prefix + ".out_layers.1", up, upp, B.ks, N.cout_);
+        if (B.shortcut) pack_conv(B.prefix + ".shortcut", B.cin, cip, 1, N.sc);
         for (int p = 0; p < 3; ++p) {
-            N.gamma[p] = pack_vec(st, d->host.at(cv + ".norm_" + kPl[p] + ".weight").data(), up, upp);
-            N.beta[p] = pack_vec(st, d->host.at(cv + ".norm_" + kPl[p] + ".bias").data(), up, upp);
+            N.gamma[p] = pack_vec(st, d->host.at(B.prefix + ".norm_" + kPlane[p] + ".weight").data(), up, upp);
+            N.beta[p] = pack_vec(st, d->host.at(B.prefix + ".norm_" + kPlane[p] + ".bias").data(), up, upp);
         }
-    };
-    pack_block(d->net[0], "geo_convs", c.geo_feat_channels, 32, 5, 0, true);
-    if (d->variant == 0) pack_block(d->net[1], "tex_convs", c.tex_feat_channels, 32, 5, 0, true);
-    if (d->variant == 2) {
-        pack_block(d->net[1], "tex_convs.0", c.tex_feat_channels, 32, 3, 0, true);
-        pack_block(d->net[2], "tex_convs.1", up, upp, 3, 1, false);
     }
-    for (auto& H : d->heads) {
-        const std::string& ml = H.name;
-        const char* ln[6] = {".first_layers.0", ".first_layers.2", ".first_layers.4", ".second_layers.0", ".second_layers.2", ".second_layers.4"};
-        const int outs[6] = {hid, hid, hid, hid, hid, H.nout};
-        const int outp[6] = {hidp, hidp, hidp, hidp, hidp, 32};
-        const int s0[6] = {up, hid, hid, up, hid, hid}, s1[6] = {0, 0, 0, hid, 0, 0};
-        const int s0p[6] = {upp, hidp, hidp, upp, hidp, hidp}, s1p[6] = {0, 0, 0, hidp, 0, 0};
-        for (int l = 0; l < 6; ++l) {
-            H.mw[l] = pack_linear(st, d->host.at(ml + ln[l] + ".weight"), outs[l], s0[l], s1[l], outp[l], s0p[l], s1p[l]);
-            H.mb[l] = pack_vec(st, d->host.at(ml + ln[l] + ".bias").data(), outs[l], outp[l]);
+    d->heads.resize(d->desc.heads.size());
+    for (size_t i = 0; i < d->heads.size(); ++i) {
+        const std::string ml = d->desc.heads[i].name;
+        int I[6], O[6];
+        mlp_dims(up, hid, d->desc.heads[i].nout, I, O);
+        for (int l = 0; l < 6; ++l) {                    // layers 0 and 3 start with the features, layer 3 goes on with the hidden units
+            const int s0 = l == 3 ? up : I[l], s0p = l == 0 || l == 3 ? upp : hidp, outp = l == 5 ? 32 : hidp;
+            d->heads[i].mw[l] = pack_linear(st, d->host.at(ml + kMlpLayer[l] + ".weight"), O[l], s0, I[l] - s0, outp, s0p, l == 3 ? hidp : 0);
+            d->heads[i].mb[l] = pack_vec(st, d->host.at(ml + kMlpLayer[l] + ".bias").data(), O[l], outp);
         }
     }
     S3D_TRY(upload(d->wbuf, st.data(), st.size() * sizeof(float)));
     d->packed = true;
     return 0;
+}
+// The compiled (UPT, HIDT) = (up_p / 32, hid_p / 32) pairs of k_decode and k_decode_grad: f(Tiles<UPT, HIDT>()) for the handle's pair
+template <int U, int H> struct Tiles { static constexpr int upt = U, hidt = H; };
+template <class F>
+static int with_tiles(const s3d_decoder* d, F&& f) {
+    const int upt = d->up_p / 32, hidt = d->hid_p / 32;
+    if (upt == 2 && hidt == 8) return f(Tiles<2, 8>());
+    if (upt == 1 && hidt == 1) return f(Tiles<1, 1>());
+    if (upt == 1 && hidt == 8) return f(Tiles<1, 8>());
+    if (upt == 1 && hidt == 2) return f(Tiles<1, 2>());
+    if (upt == 3 && hidt == 4) return f(Tiles<3, 4>());
+    set_error("decoder: feat_channel_up=%d / mlp_hidden_channels=%d has no compiled kernel (supported after padding to 32: "
+              "up<=64 with hidden 256, up<=32 with hidden 32 or 64, up 96 with hidden 128)", d->cfg.feat_channel_up,
+              d->cfg.mlp_hidden_channels);
+    return S3D_ERR_UNSUPPORTED;
 }
 template <int UPT, int HIDT>
 static int launch_decode(const DecodeArgs& a, hipStream_t st) {
@@ -709,36 +664,26 @@ static int run_decode(s3d_decoder* d, const float* pts, long long N, const float
                       float* out, hipStream_t st) {
     S3D_CHECK(d->prepared, S3D_ERR_INVALID, "decoder: call s3d_decoder_prepare_triplane first");
     DecodeArgs a; memset(&a, 0, sizeof a);
-    a.pts = pts; a.N = N; a.clamp_color = clamp; a.out = out; a.out_stride = d->out_channels();
+    a.pts = pts; a.N = N; a.clamp_color = clamp; a.out = out; a.out_stride = d->desc.out_channels();
     for (int k = 0; k < 3; ++k) {
         a.amin[k] = aabb[k]; a.gsize[k] = aabb[3 + k] - aabb[k];
         a.gdim[k] = gdim ? gdim[k] : 1; a.ph[k] = d->ph[k]; a.pw[k] = d->pw[k];
     }
-    a.ngroups = d->ngroups;
-    for (int g = 0; g < d->ngroups; ++g)
+    a.ngroups = d->desc.nsides;
+    for (int g = 0; g < a.ngroups; ++g)
         for (int p = 0; p < 3; ++p) a.feat[g][p] = d->featp[g][p];
     S3D_CHECK(int(d->heads.size()) <= kMaxHeads, S3D_ERR_INVALID, "decoder: %d heads", int(d->heads.size()));
-    int col = 0, h = 0;
+    int h = 0;
     for (int g = 0; g < 2; ++g) {                        // heads are stored group by group
         a.hbeg[g] = h;
-        while (h < int(d->heads.size()) && d->heads[h].group == g) {
-            const auto& H = d->heads[h];
-            for (int l = 0; l < 6; ++l) { a.mlp[h].w[l] = d->dev(H.mw[l]); a.mlp[h].b[l] = d->dev(H.mb[l]); }
-            a.col0[h] = col; a.ncol[h] = H.nout; a.sigm[h] = H.sigmoid;
-            col += H.nout; ++h;
+        for (; h < int(d->heads.size()) && d->desc.heads[h].side == g; ++h) {
+            const AeHead& H = d->desc.heads[h];
+            for (int l = 0; l < 6; ++l) { a.mlp[h].w[l] = d->dev(d->heads[h].mw[l]); a.mlp[h].b[l] = d->dev(d->heads[h].mb[l]); }
+            a.col0[h] = H.col0; a.ncol[h] = H.nout; a.sigm[h] = H.sigmoid;
         }
     }
     a.hbeg[2] = h;
-    const int upt = d->up_p / 32, hidt = d->hid_p / 32;
-    if (upt == 2 && hidt == 8) return launch_decode<2, 8>(a, st);
-    if (upt == 1 && hidt == 1) return launch_decode<1, 1>(a, st);
-    if (upt == 1 && hidt == 8) return launch_decode<1, 8>(a, st);
-    if (upt == 1 && hidt == 2) return launch_decode<1, 2>(a, st);
-    if (upt == 3 && hidt == 4) return launch_decode<3, 4>(a, st);
-    set_error("decoder: feat_channel_up=%d / mlp_hidden_channels=%d has no compiled kernel (supported after padding to 32: "
-              "up<=64 with hidden 256, up<=32 with hidden 32 or 64, up 96 with hidden 128)", d->cfg.feat_channel_up,
-              d->cfg.mlp_hidden_channels);
-    return S3D_ERR_UNSUPPORTED;
+    return with_tiles(d, [&](auto t) { return launch_decode<decltype(t)::upt, decltype(t)::hidt>(a, st); });
 }
 
 // columns [c0, c0+n) of dense W [out][in], transposed and zero-padded: [np][outp]
@@ -749,8 +694,8 @@ static size_t pack_transposed(std::vector<float>& st, const std::vector<float>& 
     return pack_linear(st, t, n, out, 0, np, outp, 0);
 }
 static int dec_pack_grad(s3d_decoder* d) {
-    const int up = d->cfg.feat_channel_up, hid = d->cfg.mlp_hidden_channels, upp = d->up_p, hidp = d->hid_p;
-    const std::string ml = d->heads[0].name;             // geo_decoder
+    const int up = d->desc.up, hid = d->desc.hid, upp = d->up_p, hidp = d->hid_p;
+    const std::string ml = d->desc.heads[0].name;        // geo_decoder
     auto W = [&](const char* layer) -> const std::vector<float>& { return d->host.at(ml + layer + ".weight"); };
     std::vector<float> st;
     d->gwt[0] = pack_transposed(st, W(".second_layers.2"), hid, hid, 0, hid, hidp, hidp);
@@ -787,7 +732,9 @@ int s3d_decoder_create_variant(const s3d_decoder_cfg* cfg, int32_t variant, s3d_
     d->variant = variant;
     d->up_p = rup32(cfg->feat_channel_up);
     d->hid_p = rup32(cfg->mlp_hidden_channels);
-    dec_specs(d.get());
+    d->desc = aenet_describe(*cfg, variant);
+    S3D_CHECK(d->desc.runnable(), S3D_ERR_UNSUPPORTED, "decoder: prepare_triplane is not written for this description of the net (s3d_aenet.h)");
+    d->specs = aenet_params(d->desc, /*with_encoders=*/false);
     *out = d.release();
     return 0;
 }
@@ -796,31 +743,17 @@ int s3d_decoder_create(const s3d_decoder_cfg* cfg, s3d_decoder** out) {
     S3D_CHECK(cfg->tex_channels >= 1 && cfg->tex_channels <= 3, S3D_ERR_UNSUPPORTED, "decoder: tex_channels must be 1..3");
     return s3d_decoder_create_variant(cfg, 0, out);
 }
-int s3d_decoder_out_channels(const s3d_decoder* d) { return d ? d->out_channels() : S3D_ERR_INVALID; }
+int s3d_decoder_out_channels(const s3d_decoder* d) { return d ? d->desc.out_channels() : S3D_ERR_INVALID; }
 void s3d_decoder_destroy(s3d_decoder* d) { delete d; }
 int s3d_decoder_num_params(const s3d_decoder* d) { return d ? int(d->specs.size()) : S3D_ERR_INVALID; }
 int s3d_decoder_param_info(const s3d_decoder* d, int i, const char** name, int64_t shape[4], int* ndim) {
-    S3D_CHECK(d && i >= 0 && i < int(d->specs.size()), S3D_ERR_INVALID, "decoder param_info: index %d out of range", i);
-    if (name) *name = d->specs[i].name.c_str();
-    if (ndim) *ndim = int(d->specs[i].shape.size());
-    if (shape) for (size_t k = 0; k < d->specs[i].shape.size(); ++k) shape[k] = d->specs[i].shape[k];
-    return 0;
+    return registry_param_info(d ? &d->specs : nullptr, "decoder ", i, name, shape, ndim);
 }
 int s3d_decoder_set_param(s3d_decoder* d, const char* name, const float* data, const int64_t* shape, int ndim) {
-    S3D_CHECK(d && name && data && shape, S3D_ERR_INVALID, "decoder set_param: null argument");
-    for (const auto& sp : d->specs) {
-        if (sp.name != name) continue;
-        bool ok = int(sp.shape.size()) == ndim;
-        size_t n = 1;
-        for (int k = 0; ok && k < ndim; ++k) { ok = sp.shape[k] == shape[k]; n *= size_t(shape[k]); }
-        S3D_CHECK(ok, S3D_ERR_INVALID, "size mismatch for %s", name);
-        d->host[sp.name].assign(data, data + n);
-        d->packed = false;
-        d->gpacked = false;
-        return 0;
-    }
-    set_error("unexpected key '%s' in decoder state_dict", name);
-    return S3D_ERR_INVALID;
+    S3D_TRY(registry_set_param(d ? &d->specs : nullptr, d ? &d->host : nullptr, "decoder ", name, data, shape, ndim));
+    d->packed = false;
+    d->gpacked = false;
+    return 0;
 }
 
 int s3d_decoder_prepare_triplane(s3d_decoder* d, const float* xy, const float* xz, const float* yz, int H, int W, int D,
@@ -832,14 +765,15 @@ int s3d_decoder_prepare_triplane(s3d_decoder* d, const float* xy, const float* x
     const float* in[3] = {xy, xz, yz};
     const int upp = d->up_p;
     const bool pbr = d->variant == 2;
+    const int ngroups = d->desc.nsides;
     // persistent outputs: groups x 3 planes x [h][w][upp]  (+ the PBR texture planes after block 0)
     size_t tot = 0;
     for (int p = 0; p < 3; ++p) tot += size_t(g.h[p]) * g.w[p] * upp;
     S3D_HIP(hipStreamSynchronize(st));               // the feature buffer may still be read by an earlier decode
-    S3D_TRY(d->feat.reserve((d->ngroups + (pbr ? 1 : 0)) * tot * sizeof(float)));
+    S3D_TRY(d->feat.reserve((ngroups + (pbr ? 1 : 0)) * tot * sizeof(float)));
     {
         float* base = static_cast<float*>(d->feat.p);
-        for (int n = 0; n < d->ngroups; ++n)
+        for (int n = 0; n < ngroups; ++n)
             for (int p = 0; p < 3; ++p) { d->featp[n][p] = base; base += size_t(g.h[p]) * g.w[p] * upp; }
         for (int p = 0; p < 3; ++p) { d->feat0p[p] = pbr ? base : nullptr; if (pbr) base += size_t(g.h[p]) * g.w[p] * upp; }
     }
@@ -851,7 +785,7 @@ int s3d_decoder_prepare_triplane(s3d_decoder* d, const float* xy, const float* x
         if (pass == 0) ar.high = 0;
         else if (ar.high > ar.buf.cap) S3D_TRY(ar.buf.reserve(ar.high));
         ar.reset();
-        for (int n = 0; n < d->ngroups; ++n) {
+        for (int n = 0; n < ngroups; ++n) {
             auto& N = d->net[n];
             const int c0 = n == 0 ? 0 : d->cfg.geo_feat_channels;
             const bool two = pbr && n == 1;              // the PBR texture branch: two 3x3 blocks
@@ -867,7 +801,7 @@ int s3d_decoder_prepare_triplane(s3d_decoder* d, const float* xy, const float* x
             if (pass == 0) continue;
             for (int p = 0; p < 3; ++p) {
                 const int hw = g.h[p] * g.w[p];
-                hipLaunchKernelGGL(k_slice_pad, dim3((unsigned)((size_t(hw) * 32 + 255) / 256)), dim3(256), 0, st, in[p], x.p[p], hw, c0, N.cin_ch);
+                hipLaunchKernelGGL(k_slice_pad, dim3((unsigned)((size_t(hw) * 32 + 255) / 256)), dim3(256), 0, st, in[p], x.p[p], hw, c0, d->desc.blocks[n].cin);
             }
             S3D_HIP(hipGetLastError());
             auto conv = [&](ConvKind kd, const ConvW& cw, const Tri& src, const Tri* res, float* const dst[3]) {
@@ -921,7 +855,7 @@ int s3d_decoder_plane_features(s3d_decoder* d, int group, int plane, float* out,
     S3D_CHECK(d && out && plane >= 0 && plane < 3, S3D_ERR_INVALID, "plane_features: bad argument");
     S3D_CHECK(d->prepared, S3D_ERR_INVALID, "decoder: call s3d_decoder_prepare_triplane first");
     const float* src = nullptr;
-    if (group >= 0 && group < d->ngroups) src = d->featp[group][plane];
+    if (group >= 0 && group < d->desc.nsides) src = d->featp[group][plane];
     else if (group == 2 && d->variant == 2) src = d->feat0p[plane];
     S3D_CHECK(src, S3D_ERR_INVALID, "plane_features: this decoder has no feature group %d", group);
     const long long hw = (long long)d->ph[plane] * d->pw[plane];
@@ -945,14 +879,7 @@ int s3d_decoder_sdf_grad(s3d_decoder* d, const float* pts, int64_t N, const floa
     S3D_CHECK(iters >= 0, S3D_ERR_INVALID, "sdf_grad: iters=%d", iters);
     S3D_CHECK(iters == 0 || N == 0 || pts_out, S3D_ERR_INVALID, "sdf_grad: iters=%d needs pts_out", iters);
     S3D_CHECK(iters == 0 || (max_step > 0.f && max_move > 0.f), S3D_ERR_INVALID, "sdf_grad: max_step=%g, max_move=%g must be positive", double(max_step), double(max_move));
-    const int upt = d->up_p / 32, hidt = d->hid_p / 32;
-    const bool built = (upt == 2 && hidt == 8) || (upt == 1 && (hidt == 1 || hidt == 2 || hidt == 8)) || (upt == 3 && hidt == 4);
-    if (!built) {
-        set_error("decoder: feat_channel_up=%d / mlp_hidden_channels=%d has no compiled kernel (supported after padding to 32: "
-                  "up<=64 with hidden 256, up<=32 with hidden 32 or 64, up 96 with hidden 128)", d->cfg.feat_channel_up,
-                  d->cfg.mlp_hidden_channels);
-        return S3D_ERR_UNSUPPORTED;
-    }
+    S3D_TRY(with_tiles(d, [](auto) { return 0; }));        // an uncompiled pair is refused whatever N is
     if (N == 0) return 0;
     S3D_CHECK(d->prepared, S3D_ERR_INVALID, "decoder: call s3d_decoder_prepare_triplane first");
     S3D_CHECK(d->packed, S3D_ERR_INVALID, "decoder: parameters changed since s3d_decoder_prepare_triplane; prepare again");
@@ -980,11 +907,10 @@ int s3d_decoder_sdf_grad(s3d_decoder* d, const float* pts, int64_t N, const floa
         da.pts = a.pts = it == 0 ? pts : pts_out;
         a.step = it < iters;
         a.pts_out = (a.step || iters == 0) ? pts_out : nullptr;
-        if (upt == 2 && hidt == 8) { S3D_TRY((launch_decode<2, 8>(da, st))); S3D_TRY((launch_decode_grad<2, 8>(a, st))); }
-        else if (upt == 1 && hidt == 1) { S3D_TRY((launch_decode<1, 1>(da, st))); S3D_TRY((launch_decode_grad<1, 1>(a, st))); }
-        else if (upt == 1 && hidt == 8) { S3D_TRY((launch_decode<1, 8>(da, st))); S3D_TRY((launch_decode_grad<1, 8>(a, st))); }
-        else if (upt == 1 && hidt == 2) { S3D_TRY((launch_decode<1, 2>(da, st))); S3D_TRY((launch_decode_grad<1, 2>(a, st))); }
-        else { S3D_TRY((launch_decode<3, 4>(da, st))); S3D_TRY((launch_decode_grad<3, 4>(a, st))); }
+        S3D_TRY(with_tiles(d, [&](auto t) {
+            S3D_TRY((launch_decode<decltype(t)::upt, decltype(t)::hidt>(da, st)));
+            return launch_decode_grad<decltype(t)::upt, decltype(t)::hidt>(a, st);
+        }));
     }
     return 0;
 }

@@ -5,17 +5,9 @@
 #include <cmath>
 #include <memory>
 
-#include "s3d_common.h"
+#include "s3d_params.h"
 
 namespace s3d {
-
-static const char* kPlane[3] = {"xy", "xz", "yz"};
-
-struct ParamSpec {
-    std::string name;
-    std::vector<int64_t> shape;
-    size_t numel() const { size_t n = 1; for (auto d : shape) n *= size_t(d); return n; }
-};
 
 struct NormW { size_t gamma[3], beta[3]; };
 struct ResBlockW {

@@ -7,7 +7,8 @@
 // (A body and not a function template called by the kernels, as s3d_wino24_block.h: as a __device__ __forceinline__ function template
 // behind two __global__ wrappers, every one of the fifteen k_out_head_px instantiations came out with other code than it had — up to 7
 // more scalar registers, two spilled scalars in five that had none, the known-region ones without CARRY among them, which
-// tests/test_edit_resources.py holds to none.  As text they keep their instructions: tools/compare_out_head_isa.py)
+// tests/test_edit_resources.py holds to none.  As text they keep their instructions: tools/compare_isa.py s3d_kernels.hip --kernels
+// 'k_out_head_px(_ms)?I')
     static_assert(FUSED || !KNOWN, "the blend belongs to the sampler update");
     static_assert(!MULTI || (FUSED && !KNOWN), "the multistep update is a fused step without a known region");
     constexpr int C = 4 * CQ, CPW = C / 4, LANES = 256 / CQ, LD = C + 4;

@@ -11,8 +11,6 @@ namespace s3d {
 int build_pack_plan(s3d_unet* m);
 int launch_repack(s3d_unet* m, hipStream_t st);
 
-static const char* kPl[3] = {"xy", "xz", "yz"};
-
 struct Bwd {
     s3d_unet* m;
     int B;
@@ -125,8 +123,8 @@ struct Bwd {
         }
         float* dbias[3]; float* dW[3];
         for (int p = 0; p < 3; ++p) {
-            dbias[p] = G(prefix + ".conv_" + kPl[p] + ".bias");
-            dW[p] = G(prefix + ".conv_" + kPl[p] + ".weight");
+            dbias[p] = G(prefix + ".conv_" + kPlane[p] + ".bias");
+            dW[p] = G(prefix + ".conv_" + kPlane[p] + ".weight");
             S3D_CHECK(dbias[p] && dW[p], S3D_ERR_INVALID, "backward: unknown parameter %s", prefix.c_str());
         }
         if (!meas()) {
@@ -223,7 +221,7 @@ struct Bwd {
         s.rowadd = ra; s.coladd = ca;
         for (int p = 0; p < 3; ++p) {
             s.gamma[p] = m->dev(nw.gamma[p]); s.beta[p] = m->dev(nw.beta[p]);
-            s.dgamma[p] = G(prefix + ".norm_" + kPl[p] + ".weight"); s.dbeta[p] = G(prefix + ".norm_" + kPl[p] + ".bias");
+            s.dgamma[p] = G(prefix + ".norm_" + kPlane[p] + ".weight"); s.dbeta[p] = G(prefix + ".norm_" + kPlane[p] + ".bias");
             S3D_CHECK(s.dgamma[p] && s.dbeta[p], S3D_ERR_INVALID, "backward: unknown parameter %s", prefix.c_str());
         }
         s.film = film_ptr; s.dfilm = dfilm_ptr; s.film_stride = m->film_total;
@@ -292,8 +290,8 @@ static int run_backward(s3d_unet* m, const float* d_out, float* grads, hipStream
             so.s = d_out; so.S = c.out_channels; so.v = act; so.Wt = m->dev(m->out_w); so.dv = &d_act; so.outer_transposed = 0;
             float* ssum[3];
             for (int p = 0; p < 3; ++p) {
-                so.outer[p] = b.G(std::string("out.2.conv_") + kPl[p] + ".weight");
-                ssum[p] = b.G(std::string("out.2.conv_") + kPl[p] + ".bias");
+                so.outer[p] = b.G(std::string("out.2.conv_") + kPlane[p] + ".weight");
+                ssum[p] = b.G(std::string("out.2.conv_") + kPlane[p] + ".bias");
             }
             so.ssum = ssum; so.vsum = nullptr; so.ws = ws;
             so.H = T.H; so.W = T.W; so.D = T.D; so.C = T.head_in.C; so.B = B;
@@ -365,8 +363,8 @@ static int run_backward(s3d_unet* m, const float* d_out, float* grads, hipStream
             so.s = T.x; so.S = c.in_channels; so.v = d_x; so.Wt = nullptr; so.dv = nullptr; so.outer_transposed = 1;
             float* vsum[3];
             for (int p = 0; p < 3; ++p) {
-                so.outer[p] = b.G(std::string("in_conv.0.conv_") + kPl[p] + ".weight");
-                vsum[p] = b.G(std::string("in_conv.0.conv_") + kPl[p] + ".bias");
+                so.outer[p] = b.G(std::string("in_conv.0.conv_") + kPlane[p] + ".weight");
+                vsum[p] = b.G(std::string("in_conv.0.conv_") + kPlane[p] + ".bias");
             }
             so.ssum = nullptr; so.vsum = vsum; so.ws = ws;
             so.H = T.H; so.W = T.W; so.D = T.D; so.C = d_x.C; so.B = B;

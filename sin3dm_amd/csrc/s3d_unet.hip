@@ -420,27 +420,13 @@ void s3d_unet_destroy(s3d_unet* m) { delete m; }
 int s3d_unet_num_params(const s3d_unet* m) { return m ? int(m->specs.size()) : S3D_ERR_INVALID; }
 
 int s3d_unet_param_info(const s3d_unet* m, int i, const char** name, int64_t shape[4], int* ndim) {
-    S3D_CHECK(m && i >= 0 && i < int(m->specs.size()), S3D_ERR_INVALID, "param_info: index %d out of range", i);
-    const ParamSpec& sp = m->specs[i];
-    if (name) *name = sp.name.c_str();
-    if (ndim) *ndim = int(sp.shape.size());
-    if (shape) for (size_t k = 0; k < sp.shape.size(); ++k) shape[k] = sp.shape[k];
-    return 0;
+    return registry_param_info(m ? &m->specs : nullptr, "", i, name, shape, ndim);
 }
 
 int s3d_unet_set_param(s3d_unet* m, const char* name, const float* data, const int64_t* shape, int ndim) {
-    S3D_CHECK(m && name && data && shape, S3D_ERR_INVALID, "set_param: null argument");
-    for (const auto& sp : m->specs) {
-        if (sp.name != name) continue;
-        bool ok = int(sp.shape.size()) == ndim;
-        for (int k = 0; ok && k < ndim; ++k) ok = sp.shape[k] == shape[k];
-        S3D_CHECK(ok, S3D_ERR_INVALID, "size mismatch for %s", name);
-        m->host[sp.name].assign(data, data + sp.numel());
-        m->packed = false;
-        return 0;
-    }
-    set_error("unexpected key '%s' in state_dict", name);
-    return S3D_ERR_INVALID;
+    S3D_TRY(registry_set_param(m ? &m->specs : nullptr, m ? &m->host : nullptr, "", name, data, shape, ndim));
+    m->packed = false;
+    return 0;
 }
 
 static int forward_impl(s3d_unet* m, const float* x, const float* t, int B, int H, int W, int D, float* out, void* stream,

@@ -192,17 +192,12 @@ class _TriplaneUNetBase(nn.Module):
         params = dict(self.named_parameters())
         dev = next(iter(params.values())).device
         _lib.require_gpu(next(iter(params.values())))
-        n = lib.s3d_unet_num_params(self._handle)
-        layout = []
-        for i in range(n):
-            name, shape, nd, off = C.c_char_p(), (C.c_int64 * 4)(), C.c_int(), C.c_int64()
-            _lib.check(lib.s3d_unet_param_info(self._handle, i, C.byref(name), shape, C.byref(nd)))
-            _lib.check(lib.s3d_unet_param_offset(self._handle, i, C.byref(off)))
-            shp = tuple(shape[k] for k in range(nd.value))
-            numel = 1
-            for d in shp:
-                numel *= d
-            layout.append((name.value.decode(), off.value, numel, shp))
+
+        def info(i, name, shape, nd, off):
+            _lib.check(lib.s3d_unet_param_info(self._handle, i, name, shape, nd))
+            _lib.check(lib.s3d_unet_param_offset(self._handle, i, off))
+
+        layout = _lib.read_layout(lib.s3d_unet_num_params(self._handle), info)
         total = lib.s3d_unet_param_numel(self._handle)
         flat = th.empty(total, device=dev, dtype=th.float32)
         with th.no_grad():

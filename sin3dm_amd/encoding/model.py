@@ -159,8 +159,8 @@ class ShapeAutoEncoder:
         (integers: its samples; x.5: the brick-corner lattice) to net.decode(points, ..., clamp_color=True).  The points are
         k_decode's own grid expression AS COMPILED: q = (0.5 + i) / gdim rounded to float32 (IEEE division), then q * gsize + amin
         with ONE rounding — hipcc contracts that product and sum into a fused multiply-add, the __fmul_rn / __fadd_rn spelling
-        notwithstanding (tools/compare_kdecode_isa.py holds the kernel's instructions in place).  They are taken per axis on the
-        host, exactly, and gathered on the device, so a band sample carries the bits of decode_grid's; the device test of
+        notwithstanding (tools/compare_isa.py s3d_decoder.hip --kernels k_decodeI holds the kernel's instructions in place).  They
+        are taken per axis on the host, exactly, and gathered on the device, so a band sample carries the bits of decode_grid's; the device test of
         decode_mesh(sparse=...) against the dense files is what notices if either side changes."""
         self.net.eval()
         a = aabb.detach().to("cpu", torch.float32).reshape(6)

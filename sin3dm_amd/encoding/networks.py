@@ -173,15 +173,8 @@ class AutoEncoderGroupSkip(nn.Module):
         if not intact:
             dev = next(iter(params.values())).device
             _lib.require_gpu(next(iter(params.values())))
-            layout = []
-            for i in range(lib.s3d_ae_num_params(self._ae)):
-                name, shape, nd, off = C.c_char_p(), (C.c_int64 * 5)(), C.c_int(), C.c_int64()
-                _lib.check(lib.s3d_ae_param_info(self._ae, i, C.byref(name), shape, C.byref(nd), C.byref(off)))
-                shp = tuple(shape[k] for k in range(nd.value))
-                numel = 1
-                for d in shp:
-                    numel *= d
-                layout.append((name.value.decode(), off.value, numel, shp))
+            layout = _lib.read_layout(lib.s3d_ae_num_params(self._ae),
+                                      lambda i, *refs: _lib.check(lib.s3d_ae_param_info(self._ae, i, *refs)))
             tb = C.c_int64()
             total = lib.s3d_ae_param_numel(self._ae, C.byref(tb))
             flat = torch.empty(total, device=dev, dtype=torch.float32)
