@@ -844,8 +844,8 @@ S3D_API int s3d_render_shade(const float* verts, const int32_t* xy_fixed, const 
 
 /* ------------------------------------------------------------------------------------------------
  * PBR renders: smooth normals, normal maps, a GGX light model and the material passes of the reference's
- * rendering/blender_render_pbr.py, on the raster stage above.  Parity with Blender is not claimed: directional lights, no shadows,
- * no ambient occlusion, no tone curve, texel values taken as they are (no sRGB decoding).
+ * rendering/blender_render_pbr.py, on the raster stage above.  Parity with Blender is not claimed: directional lights, shadows opt-in
+ * (s3d_pbr_shade_lit below), no ambient occlusion, no tone curve, texel values taken as they are (no sRGB decoding).
  * ------------------------------------------------------------------------------------------------ */
 #define S3D_RENDER_MAX_LIGHTS 4
 /* materials of one s3d_pbr_shade call: the PBR table is a host array and travels with the launch */
@@ -899,6 +899,52 @@ S3D_API int s3d_pbr_shade(const float* verts, const int32_t* xy_fixed, const flo
                                  const float* mat_kd, int n_mats, const uint8_t* images, int64_t image_bytes, const float* normals,
                                  const float* tangents, const int64_t* pbr_table, const float* pbr_factors, const float eye[3],
                                  const float* lights, int n_lights, float ambient, int pass, uint8_t* rgba, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Ray queries against a mesh and the shadows of the PBR renders (additions: no earlier entry point changed).
+ * The mesh and the grid are those of s3d_meshsdf_closest: tri9 [n_faces][9], origin [3] / cell / dims [3] (host), seg [cells + 1]
+ * and seg_tri [n_pairs] from s3d_meshsdf_bin_count / _bin_fill, whose `band` is here the slack that makes the lists conservative
+ * against the rounding of the walk (at least 2^-19 of the largest coordinate magnitude).  The grid box must hold
+ * the mesh: what lies outside it is not found.
+ *
+ * The ray-triangle test, fp32, no product fused into a sum, with a, b, c the triangle's corners, o the origin, d the direction:
+ *   e1 = b - a, e2 = c - a, p = d x e2, s = o - a, q = s x e1     (x x y = (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0))
+ *   det = e1 . p, u = s . p, v = d . q, w = e2 . q                (x . y = (x0 y0 + x1 y1) + x2 y2)
+ *   det < 0: det, u, v, w change sign
+ *   hit = det > 0 and u >= 0 and v >= 0 and u + v <= det and t_min <= w / det <= t_max
+ * Edges are inclusive; det == 0 or a value that is not finite is a miss.  The test is never clipped to a cell, and any hit ends
+ * the walk: `hit` does not depend on the grid, on the order of a cell's list or on a triangle standing in several cells.
+ * Not watertight: a ray through an edge two triangles share may miss both.  d need not have unit length: t counts in |d|.
+ * The walk: a 3-D DDA from the entry into the grid box (or t_min) to the exit (or t_max), every crossing computed from the border's
+ * index as (origin + i * cell - o) / d, a zero component never stepped, at most dims[0] + dims[1] + dims[2] + 1 cells.
+ * ------------------------------------------------------------------------------------------------ */
+/* origins, dirs [n_rays][3]; skip_face [n_rays] int32 (-1: none) or null; t_max may be +inf.  hit [n_rays] uint8: 1 when some
+ * triangle other than skip_face is crossed at a parameter in [t_min, t_max].  status [n_rays] uint8: 0 walked; 1 the ray does not
+ * meet the grid box within [t_min, t_max]; 2 an origin or direction that is not finite, or a zero direction (hit = 0 for 1 and 2).
+ * S3D_ERR_INVALID (nothing is launched): dims below 1, t_min negative or not finite, t_max < t_min or NaN, a null output. */
+S3D_API int s3d_mesh_ray_occluded(const float* origins, const float* dirs, const int32_t* skip_face, int64_t n_rays, float t_min, float t_max,
+                                  const float* tri9, int64_t n_faces, const float origin[3], float cell, const int dims[3], const int64_t* seg,
+                                  const int32_t* seg_tri, int64_t n_pairs, uint8_t* hit, uint8_t* status, void* stream);
+/* lit [hs][ws] uint8 from the raster buffers of a view (face_id, xy_fixed, inv_w as s3d_pbr_shade reads them; tri9 = verts[faces]):
+ * bit k is set when light k (lights HOST [n_lights][4], direction towards the light and intensity) reaches the sample; an
+ * uncovered sample gets 0.  Point = b0 P0 + b1 P1 + b2 P2 with the sample's barycentrics, as s3d_pbr_shade's view vector; N = the
+ * face's own normal cross(b - a, c - a) turned to the camera by the integer rule of the shaders.  N . L <= 0: bit 0, no ray.
+ * Otherwise one ray from the point along L with skip_face = the sample's face, [t_min, +inf): bit 1 when it is not occluded
+ * (status 1 or 2 included).  The terminator follows the faces, under smooth normals too.
+ * S3D_ERR_INVALID: more than S3D_RENDER_MAX_LIGHTS lights, dims below 1, t_min negative or not finite, a null output. */
+S3D_API int s3d_pbr_shadow_mask(const float* verts, const int32_t* xy_fixed, const float* inv_w, int64_t n_verts, const int32_t* faces,
+                                   int64_t n_faces, const int32_t* face_id, int ws, int hs, const float view_proj[16], const float* lights,
+                                   int n_lights, float t_min, const float* tri9, const float origin[3], float cell, const int dims[3],
+                                   const int64_t* seg, const int32_t* seg_tri, int64_t n_pairs, uint8_t* lit, void* stream);
+/* s3d_pbr_shade with lit [hs][ws] (s3d_pbr_shadow_mask): light k is skipped at a sample whose bit k is clear, the others are
+ * added in their order.  The albedo, metallic, roughness and normal passes do not read the mask; the geo pass does.  lit null:
+ * s3d_pbr_shade, its bits. */
+S3D_API int s3d_pbr_shade_lit(const float* verts, const int32_t* xy_fixed, const float* inv_w, int64_t n_verts, const int32_t* faces,
+                              int64_t n_faces, const int32_t* face_id, int ws, int hs, int supersample, const float view_proj[16],
+                              const float* vertex_colors, const float* uv, const int32_t* face_mat, const int64_t* mat_table,
+                              const float* mat_kd, int n_mats, const uint8_t* images, int64_t image_bytes, const float* normals,
+                              const float* tangents, const int64_t* pbr_table, const float* pbr_factors, const float eye[3],
+                              const float* lights, int n_lights, float ambient, int pass, const uint8_t* lit, uint8_t* rgba, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * torch's CPU noise stream on the device: the float32 values `torch.randn` / `torch.rand` draw from

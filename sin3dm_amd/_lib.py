@@ -246,6 +246,15 @@ SIGNATURES = {
     "s3d_pbr_shade": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                        c_fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
                                        C.c_void_p, C.c_void_p, c_i64p, c_fp, c_fp, c_fp, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p]),
+    # ray queries against a mesh, the shadow mask of a view, the PBR shade kernel with the mask
+    "s3d_mesh_ray_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p, C.c_int64, c_fp, C.c_float,
+                                        C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s3d_pbr_shadow_mask": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, c_fp,
+                                         c_fp, C.c_int, C.c_float, C.c_void_p, c_fp, C.c_float, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p]),
+    "s3d_pbr_shade_lit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    c_fp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64,
+                                    C.c_void_p, C.c_void_p, c_i64p, c_fp, c_fp, c_fp, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     # torch's CPU noise stream on the device
     "s3d_rng_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "s3d_rng_destroy": (None, [C.c_void_p]),

@@ -4,7 +4,7 @@
 // verts[tris] once), so no kernel follows a vertex index.  Sort, scan and compaction stay with the caller (torch), as for
 // s3d_tex.hip.  No float atomics; every output element is written by one thread that adds in a fixed order, so the results do not
 // depend on the launch geometry.
-#include "s3d_common.h"
+#include "s3d_cellgrid.h"
 
 namespace s3d {
 
@@ -13,12 +13,6 @@ constexpr int kWindTile = 256;                 // triangles staged in LDS per ro
 constexpr int kWindPts = 2;                    // points per lane of k_mesh_winding
 static inline unsigned mesh_blocks(long long n) { return (unsigned)((n + kMeshThreads - 1) / kMeshThreads); }
 
-struct CellGrid { float ox, oy, oz, cell; int nx, ny, nz; };
-
-// the cell of a coordinate along one axis, clamped to the grid: monotone in x, so a range of coordinates maps to a range of cells
-__device__ __forceinline__ int cell_of(float x, float o, float cell, int n) {
-    return min(n - 1, max(0, int(floorf(__fdiv_rn(x - o, cell)))));
-}
 // what a triangle's box is dilated by: a little more than the band, so that rounding in lo - band never excludes a cell that
 // holds a point nearer than the band
 __device__ __forceinline__ float dilation(float band) { return band * 1.001f + 1e-6f; }

@@ -156,8 +156,13 @@ static inline int check_mesh(const char* who, const void* xy, const void* inv_w,
     S3D_CHECK(n_verts == 0 || (xy && inv_w), S3D_ERR_INVALID, "%s: null vertex table", who);
     return 0;
 }
-// the arguments s3d_render_shade and s3d_pbr_shade share, checked and packed (front_sign: the handedness of the matrix, the
-// sign of the determinant of the x, y and w rows' linear parts)
+// the handedness of an object-to-clip matrix: the sign of the determinant of the x, y and w rows' linear parts
+static inline int matrix_front_sign(const float m[16]) {
+    const double det = double(m[0]) * (double(m[5]) * m[14] - double(m[6]) * m[13]) - double(m[1]) * (double(m[4]) * m[14] - double(m[6]) * m[12]) +
+                       double(m[2]) * (double(m[4]) * m[13] - double(m[5]) * m[12]);
+    return det < 0.0 ? -1 : 1;
+}
+// the arguments s3d_render_shade and s3d_pbr_shade share, checked and packed (front_sign: matrix_front_sign)
 static inline int pack_shade_args(const char* who, const float* verts, const int32_t* xy_fixed, const float* inv_w, int64_t n_verts,
                                   const int32_t* faces, int64_t n_faces, const int32_t* face_id, int ws, int hs, int supersample,
                                   const float view_proj[16], const float light[3], const float* vertex_colors, const float* uv,
@@ -174,13 +179,10 @@ static inline int pack_shade_args(const char* who, const float* verts, const int
     S3D_CHECK(n_mats == 0 || (mat_table && mat_kd), S3D_ERR_INVALID, "%s: null material table", who);
     S3D_CHECK(image_bytes == 0 || images, S3D_ERR_INVALID, "%s: null image buffer", who);
     S3D_CHECK(face_id && rgba && (n_verts == 0 || verts), S3D_ERR_INVALID, "%s: null argument", who);
-    const float* m = view_proj;
-    const double det = double(m[0]) * (double(m[5]) * m[14] - double(m[6]) * m[13]) - double(m[1]) * (double(m[4]) * m[14] - double(m[6]) * m[12]) +
-                       double(m[2]) * (double(m[4]) * m[13] - double(m[5]) * m[12]);
     a.verts = verts; a.xy = xy_fixed; a.inv_w = inv_w; a.V = n_verts; a.faces = faces; a.F = n_faces; a.face_id = face_id;
     a.ws = ws; a.hs = hs; a.ss = supersample; a.W = ws / supersample; a.H = hs / supersample;
     a.light[0] = light[0]; a.light[1] = light[1]; a.light[2] = light[2];
-    a.front_sign = det < 0.0 ? -1 : 1;
+    a.front_sign = matrix_front_sign(view_proj);
     a.vcol = vertex_colors; a.uv = uv; a.face_mat = face_mat; a.mat = reinterpret_cast<const long long*>(mat_table); a.kd = mat_kd; a.M = n_mats;
     a.img = images; a.img_bytes = image_bytes; a.rgba = rgba;
     return 0;

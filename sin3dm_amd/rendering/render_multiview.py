@@ -1,13 +1,15 @@
 """Multi-view renders of a mesh file with the flags of the reference's rendering/blender_render_multiview.py:
 
     python -m sin3dm_amd.rendering.render_multiview -s mesh.obj -o DIR [--image_resolution W H] [--supersample N]
-           [--shading flat|smooth|pbr]
+           [--shading flat|smooth|pbr] [--shadows]
 
 writes DIR/000.png ... 007.png (RGBA, transparent background): the eight views of the reference's rig, drawn by the device
-rasteriser (rasterizer.py; DESIGN.md §22 — not Blender: flat shading, one overhead light, no shadows).  Reads textured OBJs
+rasteriser (rasterizer.py; DESIGN.md §22 — not Blender: flat shading, one overhead light, shadows opt-in).  Reads textured OBJs
 (+ MTL, images) through data/obj_io.load_obj and the vertex-coloured OBJ of isosurface.export_obj (`v x y z r g b`).
 --shading smooth: the same colours under smooth normals and the three-light GGX model of DESIGN.md §24; pbr: also the MTL's
-metallic, roughness and normal maps (rendering/pbr.py).  The default, flat, is the shader of §22, bit for bit."""
+metallic, roughness and normal maps (rendering/pbr.py).  The default, flat, is the shader of §22, bit for bit.
+--shadows: hard shadows of the mesh on itself under the three lights of §24 (with --shading flat: that light model
+on flat normals)."""
 from __future__ import annotations
 
 import argparse
@@ -23,6 +25,7 @@ def build_parser():
     p.add_argument("--image_resolution", nargs=2, type=int, default=(512, 512), metavar=("W", "H"), help="size of every view in pixels")
     p.add_argument("--supersample", type=int, default=2, help="samples per pixel and axis (1 to 8)")
     p.add_argument("--shading", type=str, default="flat", choices=["flat", "smooth", "pbr"], help="flat: one light, flat normals (the default)")
+    p.add_argument("--shadows", action="store_true", help="shadow rays against the mesh itself (the light model of --shading smooth, on flat normals under flat)")
     return p
 
 
@@ -73,7 +76,7 @@ def write_views(images, out_dir):
     return paths
 
 
-def render_mesh_file(path, out_dir, resolution=(512, 512), supersample=2, shading="flat"):
+def render_mesh_file(path, out_dir, resolution=(512, 512), supersample=2, shading="flat", shadows=False):
     import torch
     from .rasterizer import render_views
     mesh = load_mesh(path)
@@ -91,13 +94,15 @@ def render_mesh_file(path, out_dir, resolution=(512, 512), supersample=2, shadin
                   materials=[m for _, m in mesh["materials"]])
     if shading != "flat":                                   # (the default call stays the one it always was)
         kw["shading"] = shading
+    if shadows:
+        kw["shadows"] = True
     images = render_views(verts, faces, resolution=resolution, supersample=supersample, **kw)
     return write_views(images.cpu().numpy(), out_dir)
 
 
 def main(argv=None):
     args = parse_args(argv)
-    paths = render_mesh_file(args.mesh_path, args.output_dir, args.image_resolution, args.supersample, args.shading)
+    paths = render_mesh_file(args.mesh_path, args.output_dir, args.image_resolution, args.supersample, args.shading, args.shadows)
     print(f"wrote {len(paths)} views under {args.output_dir}")
     return paths
 

@@ -1,13 +1,14 @@
 """One PBR render of a mesh file with the flags of the reference's rendering/blender_render_pbr.py:
 
     python -m sin3dm_amd.rendering.render_pbr -s object.obj [-o out.png] [-az 45] [-el 45] [--rot 0] [--scale 1]
-           [--image_resolution W H] [--shading smooth|flat] [--supersample 2]
+           [--image_resolution W H] [--shading smooth|flat] [--supersample 2] [--shadows]
 
 writes out.png (default: the mesh path with .png) and beside it out_albedo.png, out_metallic.png, out_roughness.png,
 out_normal.png — each only when a material of the mesh carries that map or factor, as the reference writes them — and
 out_geo.png (grey 134, no maps): one camera of the reference's rig at azimuth / elevation, its key / fill / rim lights as
-directional lights, drawn by the device rasteriser (rasterizer.py, pbr.py; DESIGN.md §24 — not Blender: no shadows, no ambient
-occlusion, no tone curve).  A vertex-coloured OBJ (`v x y z r g b`, isosurface.export_obj) without texture or PBR entries is
+directional lights, drawn by the device rasteriser (rasterizer.py, pbr.py; DESIGN.md §24 — not Blender: shadows opt-in, no ambient
+occlusion, no tone curve).  --shadows: hard shadows of the mesh on itself under the three lights in out.png and
+out_geo.png; the material passes do not change.  A vertex-coloured OBJ (`v x y z r g b`, isosurface.export_obj) without texture or PBR entries is
 drawn with its colours as the albedo (metallic 0, roughness 0.5): out.png, out_albedo.png, out_geo.png.
 
 -el defaults to 45: the reference's default 0 puts the eye on the rig's vertical axis, where its look-at with z up has no
@@ -36,6 +37,7 @@ def build_parser():
     p.add_argument("--image_resolution", nargs=2, type=int, default=(512, 512), metavar=("W", "H"), help="size of the images in pixels")
     p.add_argument("--shading", type=str, default="smooth", choices=["smooth", "flat"])
     p.add_argument("--supersample", type=int, default=2, help="samples per pixel and axis (1 to 8)")
+    p.add_argument("--shadows", action="store_true", help="shadow rays against the mesh itself for the three lights")
     return p
 
 
@@ -101,7 +103,8 @@ def render_pbr_file(args):
         kw = dict(uvs=torch.from_numpy(mesh["uvs"].astype(np.float32)).to(dev), face_mat=torch.from_numpy(mesh["face_mat"]).to(dev),
                   materials=materials)
     images = render_views(verts, faces, **kw, views=[view], resolution=args.image_resolution, supersample=args.supersample,
-                          shading="pbr" if args.shading == "smooth" else "pbr_flat", passes=tuple(names), lights=rig)
+                          shading="pbr" if args.shading == "smooth" else "pbr_flat", passes=tuple(names), lights=rig,
+                          **({"shadows": True} if args.shadows else {}))
     stem = args.output_path[:-4]
     suffix = dict(PASS_FILES, shaded="", geo="_geo")
     os.makedirs(os.path.dirname(os.path.abspath(args.output_path)), exist_ok=True)

@@ -34,6 +34,8 @@ reference's eight views, drawn on the device from the arrays the export holds (s
 S3D_RENDER_SHADING=smooth or pbr beside it draws them with smooth normals and the three-light GGX model of DESIGN.md §24 (pbr: the
 metallic, roughness and normal channels of an sdfpbr sample's bake included, and the map of S3D_MESH_NORMAL_MAP=field for either
 data type); unset: the flat shader, as before.
+S3D_RENDER_SHADOWS=1 beside S3D_RENDER=views draws them with the hard shadows of DESIGN.md §29 (render_views(shadows=True): the light
+model of §24, on flat normals unless S3D_RENDER_SHADING says otherwise); edit.py reads it as well.
 """
 from __future__ import annotations
 
@@ -163,16 +165,28 @@ def render_shading(mode=None):
     return name
 
 
-def render_sample(save_dir, mesh, shading=None):
+def render_shadows(value=None):
+    """False (the default) or True: the S3D_RENDER=views renders with shadows (render_views(shadows=True)).
+    value=None reads the environment variable S3D_RENDER_SHADOWS ("1" or "0" / unset)."""
+    raw = value if value is not None else (os.environ.get("S3D_RENDER_SHADOWS") or "0")
+    if raw in (True, False):
+        return bool(raw)
+    if str(raw) not in ("0", "1"):
+        raise ValueError(f"render shadows {raw!r}: expected '1' (or '0' / unset)")
+    return str(raw) == "1"
+
+
+def render_sample(save_dir, mesh, shading=None, shadows=None):
     """renderings/ beside a decoded mesh.  mesh: what decode_mesh (verts, tris, colours) or decode_texmesh (a dict, or None for an
     empty iso-surface) returned.  shading: see render_shading; with "pbr" the 8-channel bake of an sdfpbr sample is used as it
     lies on the device (albedo [..., :3], metallic [..., 3], roughness [..., 4], normal [..., 5:]); a baked "normal_map" in the dict
     (decode_texmesh normal_map="field") is the material's normal_image under "pbr", for an sdftex sample too.  Field normals in the mesh (a
-    dict's "normals", a fourth tuple entry) are passed on to render_views, which uses them under "smooth" and "pbr".  Returns the
-    paths written."""
+    dict's "normals", a fourth tuple entry) are passed on to render_views, which uses them under "smooth" and "pbr".  shadows: see
+    render_shadows.  Returns the paths written."""
     from .rendering.rasterizer import render_views
     from .rendering.render_multiview import write_views
     shading = render_shading(shading)
+    shadows = render_shadows(shadows)
     if mesh is None:
         return []
     if isinstance(mesh, dict):
@@ -198,6 +212,8 @@ def render_sample(save_dir, mesh, shading=None):
         kw["shading"] = shading
         if vn is not None:
             kw["normals"] = vn
+    if shadows:                                                 # (unset: no such argument in the call)
+        kw["shadows"] = True
     images = render_views(verts, tris, **kw)
     return write_views(images.cpu().numpy(), os.path.join(save_dir, "renderings"))
 
